@@ -88,7 +88,31 @@ def parse():
     ap.add_argument("--cpu-probes", type=int, default=8)
     ap.add_argument("--cpu-workers", type=int, default=-1,
                     help="processes of the all-cores CPU baseline line (-1: min(cores, 16); 0: skip)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float64, at most 64 MB in all): the per-probe estimates, the "
+                         "iteration counts, the reduced statistics of the timed steps and the trace "
+                         "estimate; the inputs are fixed by the arguments, so runs of two builds compare "
+                         "output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """Write each array as directory/<name>.npy in float64.  The outputs of a step are a few numbers
+    per probe (kilobytes), far inside the 64 MB budget; exceeding it is an error, not a silent cut."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (budget %d)" % (total, DUMP_BUDGET_BYTES))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def first_probe(step, world, rank, streams, stream, nb):
@@ -435,11 +459,14 @@ def run(args):
         engs[e].hutch_run(run_mode, 0, args.tol, maxiter)
         return engs[e].hutch_fetch()
 
+    fetched = [None]             # what the engines returned in the latest step: (ests, iters fine, iters coarse) each
+
     def step(s, generate=True, slot=0, prefetch=False):
         if ne == 1:
             res = [run_one(0, s, generate, slot, prefetch)]
         else:
             res = list(pool.map(lambda e: run_one(e, s, generate, slot, prefetch), range(ne)))
+        fetched[0] = res
         ests = np.concatenate([r[0] for r in res])
         itf = np.concatenate([r[1] for r in res])
         # this rank's {sum Re e, sum Im e, sum |e|^2, n}: accumulated over the steps and all-reduced ONCE
@@ -484,6 +511,21 @@ def run(args):
         # the one collective of the path: trace sum / variance statistics over the ranks (RCCL over xGMI)
         total[:] = comm.allreduce_stats(total)
     elapsed = timed(headline, ends_with_collective=True)
+
+    if args.dump_outputs:
+        # the last timed step as its caller receives it: this rank's per-probe estimates (engines in
+        # stream order) and iteration counts, and the statistics and trace reduced over all timed steps
+        # (trace_estimate: real part, imaginary part, population std of the estimates)
+        suffix = "" if world == 1 else "_rank%d" % rank
+        ests_last = np.concatenate([r[0] for r in fetched[0]])
+        dumped = {"estimates" + suffix: np.stack([ests_last.real, ests_last.imag], axis=1),
+                  "iterations_fine" + suffix: np.concatenate([r[1] for r in fetched[0]]),
+                  "iterations_coarse" + suffix: np.concatenate([r[2] for r in fetched[0]])}
+        if rank == 0:
+            mean_t, std_t = swdist.mean_and_population_std(total)
+            dumped["trace_statistics"] = total
+            dumped["trace_estimate"] = [np.real(mean_t + tr1), np.imag(mean_t + tr1), std_t]
+        dump_outputs(args.dump_outputs, dumped)
 
     # ---- the same K steps at the reference's own stopping point (stop_factor = 1: residual below tol, where
     # pyamg's fgmres stops; per-probe parity then holds to 1e-10 of max(|e|, a tenth of the batch median)) ----
