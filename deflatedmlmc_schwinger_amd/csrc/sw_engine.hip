@@ -334,6 +334,7 @@ struct sw_engine {
   cplx* eig_buf[3] = {nullptr, nullptr, nullptr};
   signed char* eig_sign = nullptr;
   cplx* eig_small = nullptr;     // [64*64] reduced Gram matrix / rotation
+  cplx* eig_cs[2] = {nullptr, nullptr};   // sw_eig_apply_diff: two [n_{l+1}][64] coarse blocks (first use)
   int eig_hid = -1, eig_level = -1, eig_n = 0;
   void* comm = nullptr;      // RCCL communicator (sw_comm_init), one rank per engine
   double* d_stats = nullptr; // [4] all-reduce buffer
@@ -3851,6 +3852,10 @@ int sw_eig_begin(sw_engine* h, int hid, int level, uint64_t seed) {
   const size_t cnt = (size_t)lv.n * 64;
   for (int q = 0; q < 3; ++q) SWCHK(dev_realloc(h, &h->eig_buf[q], cnt));
   SWCHK(dev_realloc(h, &h->eig_small, (size_t)4096));
+  for (int q = 0; q < 2; ++q) {     // sized for the level below this one on first use of sw_eig_apply_diff
+    if (h->eig_cs[q]) SWCHK(dev_free(h, h->eig_cs[q]));
+    h->eig_cs[q] = nullptr;
+  }
   // gamma_3 = +1 on the first half of the REFERENCE order, -1 on the second (multigrid.py:130-133)
   std::vector<signed char> sg(lv.n);
   for (int i = 0; i < lv.n; ++i) {
@@ -3881,6 +3886,10 @@ int sw_eig_end(sw_engine* h) {
   h->eig_sign = nullptr;
   if (h->eig_small) SWCHK(dev_free(h, h->eig_small));
   h->eig_small = nullptr;
+  for (int q = 0; q < 2; ++q) {
+    if (h->eig_cs[q]) SWCHK(dev_free(h, h->eig_cs[q]));
+    h->eig_cs[q] = nullptr;
+  }
   h->eig_n = 0;
   h->eig_hid = h->eig_level = -1;
   return 0;
@@ -3924,6 +3933,74 @@ int sw_eig_solve(sw_engine* h, int src, int dst, int mode, double tol, int maxit
   SWCHK(solve_dev(h, h->eig_hid, h->eig_level, rhs, h->eig_buf[dst], tol, maxiter, 64, &total));
   SWCHK(stream_sync(h));
   if (iters_max) *iters_max = total;
+  return 0;
+}
+
+// dst = (A_l^-1 - P A_c^-1 R) Gamma src on all 64 columns, l = the level of sw_eig_begin on hierarchy 0:
+// the MLMC difference operator of utils.py:141-143 / multigrid.py:461-549, built exactly as the probe body
+// of sw_hutch_run builds it (fine solve on the solver hierarchy at level 0 when it is ready, R / P of
+// hierarchy 0, coarse solve on hierarchy 0, direct or dense at the coarsest level).  Gamma = gamma_3 (g3 = 1)
+// or the identity (g3 = 0); skip = 1: A_0^-1 - P_0 P_1 A_2^-1 R_1 R_0.  The third eigen buffer and two
+// coarse blocks of the eigen state are the scratch; the probe workspace is not touched.
+int sw_eig_apply_diff(sw_engine* h, int src, int dst, int skip, int g3, double tol, int maxiter,
+                      int32_t* iters_max) {
+  SWCHK(eig_check(h, src));
+  SWCHK(eig_check(h, dst));
+  if (src == dst) return sw_fail(h, "source and destination buffers must differ");
+  if (g3 != 0 && g3 != 1) return sw_fail(h, "g3 must be 0 (identity) or 1 (gamma_3)");
+  if (skip != 0 && skip != 1) return sw_fail(h, "skip must be 0 or 1");
+  if (maxiter < 1) return sw_fail(h, "maxiter must be >= 1");
+  if (h->eig_hid != 0) return sw_fail(h, "the difference operator needs the eigen buffers on hierarchy 0");
+  HIPCHK(hipSetDevice(h->device));
+  Hier& H0 = h->hier[0];
+  const int level = h->eig_level;
+  if (skip && (level != 0 || H0.nlevels < 3))
+    return sw_fail(h, "level skipping is defined for level 0 of a hierarchy with at least three levels");
+  const int lcoarse = level + (skip ? 2 : 1);
+  if (lcoarse >= H0.nlevels) return sw_fail(h, "no coarse level %d", lcoarse);
+  Level& lv = H0.lv[level];
+  const int n = lv.n;
+  const int n1 = H0.lv[level + 1].n;
+  const int fine_hid = (level == 0 && h->hier[h->solver_hid].ready) ? h->solver_hid : 0;
+  if (fine_hid != 0 && h->hier[fine_hid].lv[0].n != n)
+    return sw_fail(h, "solver hierarchy level-0 size mismatch");
+  // two coarse blocks of the level below (with skip the level two below is smaller and fits in them)
+  for (int q = 0; q < 2; ++q)
+    if (!h->eig_cs[q]) SWCHK(dev_realloc(h, &h->eig_cs[q], (size_t)n1 * 64));
+  cplx* ca = h->eig_cs[0];
+  cplx* cb = h->eig_cs[1];
+  cplx* t = h->eig_buf[3 - src - dst];
+  // x = Gamma src (in dst: it is overwritten last)
+  const cplx* x = h->eig_buf[src];
+  if (g3) {
+    LaunchScope ls(h, T_OTHER);
+    hipLaunchKernelGGL(swk::k_row_sign, dim3((n + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK, 1),
+                       dim3(SW_BLOCK), 0, h->stream, x, (const signed char*)h->eig_sign, h->eig_buf[dst], n, 64);
+    KLAUNCH_CHECK();
+    x = h->eig_buf[dst];
+  }
+  // xc = R x (skip: R_1 R_0 x)
+  SWCHK(launch_ell(h, lv.R, 0, x, nullptr, ca, 64, T_R));
+  const cplx* xc = ca;
+  cplx* y = cb;
+  if (skip) {
+    SWCHK(launch_ell(h, H0.lv[1].R, 0, ca, nullptr, cb, 64, T_R));
+    xc = cb;
+    y = ca;
+  }
+  // t = A_l^-1 x
+  int total_f = 0, total_c = 0;
+  SWCHK(solve_dev(h, fine_hid, level, x, t, tol, maxiter, 64, &total_f));
+  // y = A_c^-1 xc
+  SWCHK(solve_dev(h, 0, lcoarse, xc, y, tol, maxiter, 64, &total_c));
+  // dst = t - P y (skip: t - P_0 P_1 y)
+  if (skip) {
+    SWCHK(launch_ell(h, H0.lv[1].P, 0, y, nullptr, cb, 64, T_P));
+    y = cb;
+  }
+  SWCHK(launch_ell(h, lv.P, 1, y, t, h->eig_buf[dst], 64, T_P));
+  SWCHK(stream_sync(h));
+  if (iters_max) *iters_max = total_f;
   return 0;
 }
 

@@ -104,6 +104,7 @@ def load_library():
     sig("sw_eig_begin", i32, vp, i32, i32, C.c_uint64)
     sig("sw_eig_load", i32, vp, i32, i32, vp)
     sig("sw_eig_solve", i32, vp, i32, i32, i32, dbl, i32, P(i32))
+    sig("sw_eig_apply_diff", i32, vp, i32, i32, i32, i32, dbl, i32, P(i32))
     sig("sw_eig_gram", i32, vp, i32, i32, vp)
     sig("sw_eig_rotate", i32, vp, i32, vp, i32, i32)
     sig("sw_eig_fetch", i32, vp, i32, i32, vp)
@@ -157,7 +158,7 @@ EXPORTED_SYMBOLS = (
     "sw_set_smoother", "sw_set_gmres_smoother", "sw_set_eo_smoother", "sw_set_eo_operator", "sw_setup_eo_operators", "sw_apply_eo_operator",
     "sw_get_level_bsr", "sw_setup_testvectors", "sw_setup_transfer",
     "sw_setup_galerkin", "sw_get_level_dense", "sw_setup_invert_coarsest", "sw_setup_direct_level", "sw_setup_level_inverse", "sw_setup_arnoldi", "sw_hier_end", "sw_set_deflation", "sw_set_level_deflation", "sw_set_perm", "sw_set_rhsmap", "sw_set_solver", "sw_set_option", "sw_get_option",
-    "sw_pool_trim", "sw_get_coarsest_inv", "sw_eig_begin", "sw_eig_load", "sw_eig_solve", "sw_eig_gram", "sw_eig_rotate", "sw_eig_fetch", "sw_eig_end",
+    "sw_pool_trim", "sw_get_coarsest_inv", "sw_eig_begin", "sw_eig_load", "sw_eig_solve", "sw_eig_apply_diff", "sw_eig_gram", "sw_eig_rotate", "sw_eig_fetch", "sw_eig_end",
     "sw_apply_dirac", "sw_restrict", "sw_prolong", "sw_coarsest", "sw_vcycle", "sw_solve",
     "sw_hutch_batch", "sw_probes_upload", "sw_probes_upload_slot", "sw_probes_select",
     "sw_kernel_stats", "sw_kernel_work", "sw_hutch_run", "sw_sync", "sw_hutch_fetch",
@@ -431,6 +432,14 @@ class Engine:
         its = C.c_int32(0)
         self._chk(self._lib.sw_eig_solve(self._h, src, dst, mode, float(tol), int(maxiter), C.byref(its)),
                   "sw_eig_solve")
+        return int(its.value)
+
+    def eig_apply_diff(self, src, dst, skip, g3, tol, maxiter=1000):
+        """buf_dst = (A_l^-1 - P A_c^-1 R) Gamma buf_src (Gamma = gamma_3 if g3, skip: the level-0 skip form);
+        returns the fine solve's iteration count"""
+        its = C.c_int32(0)
+        self._chk(self._lib.sw_eig_apply_diff(self._h, src, dst, int(bool(skip)), int(bool(g3)), float(tol),
+                                              int(maxiter), C.byref(its)), "sw_eig_apply_diff")
         return int(its.value)
 
     def eig_gram(self, a, b):

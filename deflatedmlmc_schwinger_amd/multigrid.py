@@ -208,6 +208,23 @@ class MG:
             raise EngineError("the device eigensolver needs the level-0 solver hierarchy")
         return setup_gpu.device_eigenpairs(self.engine, SOLVER_HID, 0, k, tol, hermitian_g3=hermitian, log=log)
 
+    def device_diff_eigenpairs(self, level_nr, k, tol, log=None, refine_to=None):
+        """k largest-magnitude eigenpairs of the MLMC difference operator (A_l^-1 - P A_c^-1 R) gamma_3 of
+        level `level_nr` (with self.skip_level at level 0: A_0^-1 - P_0 P_1 A_2^-1 R_1 R_0) on the GPU, the
+        solves at self.solve_tol (setup_gpu.device_diff_eigenpairs): what eigsh(lop, k, which='LM', tol)
+        returns at utils.py:141-143."""
+        from . import setup_gpu
+        if not 1 <= k <= 32:
+            raise Exception("device_diff_eigenpairs: k = %d outside 1..32 (the block is 64 vectors wide; "
+                            "mlmc_defl_setup = 'host' has no such limit)" % k)
+        eng = self._need_engine()
+        self._diff_op_checks(level_nr)
+        n = self.ml.levels[level_nr].A.shape[0]
+        return setup_gpu.device_diff_eigenpairs(eng, level_nr, k, tol, self.solve_tol,
+                                                skip=bool(self.skip_level and level_nr == 0),
+                                                maxiter=n if n < 1000 else self.maxiter_cap, log=log,
+                                                refine_to=refine_to)
+
     def _deferred_reference_hierarchy(self, dof, aggrs, max_levels, acc_eigvs, params, tv, ckey):
         """Device setup for flows that use level 0 only (stoch_trace.hutchinson): engines, solver hierarchy,
         level-0 test vectors and deflation vectors on the GPU as in _device_reference_hierarchy; the host part
@@ -724,6 +741,34 @@ class MG:
         if skip:
             t2 = eng.prolong(REF_HID, lvl + 1, t2)
         return t1 - eng.prolong(REF_HID, lvl, t2)
+
+    def _diff_op_checks(self, lvl):
+        nlev = len(self.ml.levels)
+        if not 0 <= lvl < nlev - 1:
+            raise Exception("no difference operator at level %d of %d levels" % (lvl, nlev))
+        if self.coarse_eo is not None and lvl != 0:
+            raise Exception("ref_coarsest = 'eo' keeps the coarse level in tile order on the GPU: the difference "
+                            "operator is available at level 0 only in that mode")
+
+    def diff_op_block(self, V, g3=False):
+        """diff_op on up to 64 columns of V ([n, m], reference row order in and out) in one engine call:
+        (A_f^-1 - P A_c^-1 R) V at self.level_for_diff_op and self.solve_tol, or that operator times gamma_3
+        (diff_op_Q without its in-place sign flip) when g3."""
+        eng = self._need_engine()
+        lvl = self.level_for_diff_op
+        self._diff_op_checks(lvl)
+        V = np.asarray(V, dtype=np.complex128)
+        n = self.ml.levels[lvl].A.shape[0]
+        if V.ndim != 2 or V.shape[0] != n or not 1 <= V.shape[1] <= 64:
+            raise Exception("diff_op_block: V must be [%d, m] with 1 <= m <= 64, got %s" % (n, V.shape))
+        eng.eig_begin(REF_HID, lvl)
+        try:
+            eng.eig_load(0, V.T)
+            eng.eig_apply_diff(0, 1, self.skip_level and lvl == 0, g3, self.solve_tol,
+                               n if n < 1000 else self.maxiter_cap)
+            return np.ascontiguousarray(eng.eig_fetch(1, V.shape[1]).T)
+        finally:
+            eng.eig_end()
 
     # ------------------------------------------------------------------------------------
     def sync_timer(self):

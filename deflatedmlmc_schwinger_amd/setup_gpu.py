@@ -394,13 +394,8 @@ def device_eigenpairs(eng, hid, level, k, tol, hermitian_g3=False, maxit=60, see
                       log=None):
     """The k eigenpairs nearest zero of A_level (hermitian_g3 = False: what eigs(A_l, k, sigma=0, tol)
     returns at multigrid.py:174) or of Q = gamma_3 A_level (True: eigsh(Q, k, sigma=0, tol), utils.py:140),
-    by block subspace iteration with Rayleigh-Ritz on the engine:
-
-        V orthonormal [n][64];  W = Op^-1 V (the engine's batched multigrid solve: the shift-invert
-        operator ARPACK gets from SuperLU);  T = V^H W (fp64 MFMA Gram kernel);  Ritz pairs (theta, y) of T;
-        block residual E = W - V T on the device, M = E^H E: |Op^-1 x - theta x|^2 = y^H M y for x = V y
-        (formed from the small residual vectors themselves -- the difference W^H W - T^H T of two O(theta^2)
-        matrices would lose everything below 1e-8);  V <- W R^-1 (Cholesky-QR, twice).
+    by block subspace iteration with Rayleigh-Ritz on the engine (block_eigenpairs), W = Op^-1 V being the
+    engine's batched multigrid solve: the shift-invert operator ARPACK gets from SuperLU.
 
     Stops when the k Ritz pairs of largest |theta| all satisfy ARPACK's own shift-invert criterion
     |Op^-1 x - theta x| <= tol |theta|.  The block width 64 (the engine's batch quantum: 64 solves cost what
@@ -408,71 +403,127 @@ def device_eigenpairs(eng, hid, level, k, tol, hermitian_g3=False, maxit=60, see
     schwinger128).  The solves start loose and tighten with the residual (inexact inverse iteration).
     Returns (lambda[k], X[n, k]) -- X columns of unit norm, orthonormal for the hermitian case --, and
     appends per-step records to `log`."""
+    mode = 1 if hermitian_g3 else 0
+
+    def apply(src, dst, res_prev):
+        # the shift-invert solve; its tolerance follows the residual of the wanted pairs (inexact inverse
+        # iteration: an error of tol_s in b - A x moves the wanted Ritz vectors by about
+        # tol_s |lambda_k / lambda_1|, so two orders below the current residual is ample)
+        tol_s = min(1e-3, max(5e-13, 1e-2 * res_prev))
+        return tol_s, eng.eig_solve(src, dst, mode, tol_s)
+
+    if not 1 <= k <= 32:
+        raise Exception("device_eigenpairs: k = %d outside 1..%d" % (k, 32))
+    eng.eig_begin(hid, level, seed)
+    try:
+        return block_eigenpairs(eng, k, tol, apply, inverse=True, hermitian=hermitian_g3, maxit=maxit,
+                                start=start, log=log, name="device_eigenpairs")
+    finally:
+        eng.eig_end()
+
+
+def device_diff_eigenpairs(eng, level, k, tol, solve_tol, skip=False, maxiter=1000, maxit=200, seed=11,
+                           log=None, refine_to=None):
+    """The k largest-magnitude eigenpairs of the MLMC difference operator Q_l = (A_l^-1 - P A_c^-1 R) gamma_3
+    of level `level` of hierarchy 0 (skip: A_0^-1 - P_0 P_1 A_2^-1 R_1 R_0), what eigsh(Q_l, k, which='LM',
+    tol) returns at utils.py:141-143: block subspace iteration with W = Q_l V (sw_eig_apply_diff, both solves
+    at the fixed tolerance `solve_tol`, as the reference fixes mg_solver.solve_tol for these mat-vecs).
+    Q_l is gamma_3-hermitian: Hermitian up to the inexactness of the solves, so T = V^H W is symmetrised.
+    The convergence factor per step is |lambda_65 / lambda_k| of Q_l.  `refine_to`: keep iterating below `tol`
+    while the residual still halves per step, down to `refine_to` (block_eigenpairs).  Returns (lambda[k] real,
+    X[n, k] orthonormal) and appends per-step records to `log`."""
+    if not 1 <= k <= 32:
+        raise Exception("device_diff_eigenpairs: k = %d outside 1..32 (the block is 64 vectors wide)" % k)
+
+    def apply(src, dst, res_prev):
+        return solve_tol, eng.eig_apply_diff(src, dst, skip, True, solve_tol, maxiter)
+
+    eng.eig_begin(0, level, seed)
+    try:
+        return block_eigenpairs(eng, k, tol, apply, inverse=False, hermitian=True, maxit=maxit, log=log,
+                                name="device_diff_eigenpairs", refine_to=refine_to)
+    finally:
+        eng.eig_end()
+
+
+def block_eigenpairs(eng, k, tol, apply, inverse, hermitian, maxit=60, start=None, log=None,
+                     name="block_eigenpairs", refine_to=None):
+    """Block subspace iteration with Rayleigh-Ritz on the engine's eigen buffers (sw_eig_begin done by the
+    caller):
+
+        V orthonormal [n][64];  W = Op V (`apply(src, dst, residual) -> (solve_tol, iterations)`: the
+        shift-invert solve when `inverse`, the operator itself otherwise);  T = V^H W (fp64 MFMA Gram kernel);
+        Ritz pairs (theta, y) of T;  block residual E = W - V T on the device, M = E^H E:
+        |Op x - theta x|^2 = y^H M y for x = V y (formed from the small residual vectors themselves -- the
+        difference W^H W - T^H T of two O(theta^2) matrices would lose everything below 1e-8);
+        V <- W R^-1 (Cholesky-QR, twice).
+
+    Keeps the k Ritz pairs of largest |theta| -- nearest zero of the operator when `inverse` (lambda =
+    1 / theta), largest in magnitude otherwise (lambda = theta, which='LM') -- and stops when they all satisfy
+    ARPACK's criterion |Op x - theta x| <= tol |theta|.  With `refine_to` < tol the iteration goes on past tol
+    while the residual at least halves per step, and stops at refine_to at the latest (or where it stalls: the
+    accuracy of an inexactly applied operator).  Returns (lambda[k], X[n, k])."""
     import scipy.linalg as sla
     m = 64
     if not 1 <= k <= m // 2:
-        raise Exception("device_eigenpairs: k = %d outside 1..%d" % (k, m // 2))
-    mode = 1 if hermitian_g3 else 0
-    eng.eig_begin(hid, level, seed)
-    try:
-        cur, nxt, tmp = 0, 1, 2
-        if start is not None:
-            eng.eig_load(cur, np.asarray(start))
+        raise Exception("%s: k = %d outside 1..%d" % (name, k, m // 2))
+    cur, nxt, tmp = 0, 1, 2
+    if start is not None:
+        eng.eig_load(cur, np.asarray(start))
 
-        def cholqr(src, dst):
-            """dst = src R^-1 with R^H R = src^H src"""
-            G = eng.eig_gram(src, src)
-            R = sla.cholesky(0.5 * (G + G.conj().T), lower=False)
-            eng.eig_rotate(src, sla.solve_triangular(R, np.eye(m, dtype=np.complex128), lower=False), dst)
+    def cholqr(src, dst):
+        """dst = src R^-1 with R^H R = src^H src"""
+        G = eng.eig_gram(src, src)
+        R = sla.cholesky(0.5 * (G + G.conj().T), lower=False)
+        eng.eig_rotate(src, sla.solve_triangular(R, np.eye(m, dtype=np.complex128), lower=False), dst)
 
-        # orthonormal start block
-        cholqr(cur, nxt)
-        cholqr(nxt, cur)
-        res_prev = 1.0
-        theta = Y = None
-        for it in range(maxit):
-            # the shift-invert solve; its tolerance follows the residual of the wanted pairs (inexact inverse
-            # iteration: an error of tol_s in b - A x moves the wanted Ritz vectors by about
-            # tol_s |lambda_k / lambda_1|, so two orders below the current residual is ample)
-            tol_s = min(1e-3, max(5e-13, 1e-2 * res_prev))
-            its = eng.eig_solve(cur, nxt, mode, tol_s)
-            T = eng.eig_gram(cur, nxt)
-            eng.eig_rotate(cur, T, tmp, sub=nxt)            # E = W - V T
-            M = eng.eig_gram(tmp, tmp)
-            if hermitian_g3:
-                theta, Y = np.linalg.eigh(0.5 * (T + T.conj().T))
-            else:
-                theta, Y = np.linalg.eig(T)
-                Y = Y / np.linalg.norm(Y, axis=0)[None, :]
-            # nearest zero = largest |theta|; of an (almost) degenerate modulus -- a complex-conjugate pair
-            # of A -- the member with the positive imaginary part first (ARPACK's choice is implementation-
-            # defined there, SURVEY section 3.4; this one is deterministic)
+    # orthonormal start block
+    cholqr(cur, nxt)
+    cholqr(nxt, cur)
+    res_prev = 1.0
+    res_last = np.inf
+    theta = Y = None
+    for it in range(maxit):
+        tol_s, its = apply(cur, nxt, res_prev)
+        T = eng.eig_gram(cur, nxt)
+        eng.eig_rotate(cur, T, tmp, sub=nxt)            # E = W - V T
+        M = eng.eig_gram(tmp, tmp)
+        if hermitian:
+            theta, Y = np.linalg.eigh(0.5 * (T + T.conj().T))
+        else:
+            theta, Y = np.linalg.eig(T)
+            Y = Y / np.linalg.norm(Y, axis=0)[None, :]
+        # largest |theta| first; of an (almost) degenerate modulus -- a complex-conjugate pair of A -- the
+        # member with the positive imaginary part first (ARPACK's choice is implementation-defined there,
+        # SURVEY section 3.4; this one is deterministic)
+        if inverse:
             lam_all = 1.0 / theta
             order = np.lexsort((-np.sign(np.round(lam_all.imag, 12)), np.round(np.abs(lam_all), 10)))
-            theta, Y = theta[order], Y[:, order]
-            yk = Y[:, :k]
-            r2 = np.einsum("ik,ij,jk->k", yk.conj(), M, yk).real
-            if not hermitian_g3:
-                # T y = theta y holds only to the accuracy of the dense eigensolver: add what it leaves
-                r2 = r2 + np.linalg.norm(T @ yk - yk * theta[None, :k], axis=0) ** 2
-            res = np.sqrt(np.maximum(r2, 0.0)) / np.abs(theta[:k])
-            res_prev = float(res.max())
-            if log is not None:
-                log.append({"step": it, "solve_tol": tol_s, "solve_iterations": its, "residual_max": res_prev})
-            if res_prev <= tol:
-                break
-            cholqr(nxt, tmp)
-            cholqr(tmp, cur)
         else:
-            raise Exception("device_eigenpairs: %d wanted pairs not converged to %g in %d steps (residual %.2e)"
-                            % (k, tol, maxit, res_prev))
-        Yfull = np.zeros((m, m), dtype=np.complex128)
-        Yfull[:, :k] = Y[:, :k]
-        eng.eig_rotate(cur, Yfull, tmp)
-        X = eng.eig_fetch(tmp, k).T
-        lam = 1.0 / theta[:k]
-        if hermitian_g3:
-            lam = lam.real
-        return lam, np.ascontiguousarray(X)
-    finally:
-        eng.eig_end()
+            order = np.lexsort((-np.sign(np.round(theta.imag, 12)), -np.round(np.abs(theta), 10)))
+        theta, Y = theta[order], Y[:, order]
+        yk = Y[:, :k]
+        r2 = np.einsum("ik,ij,jk->k", yk.conj(), M, yk).real
+        if not hermitian:
+            # T y = theta y holds only to the accuracy of the dense eigensolver: add what it leaves
+            r2 = r2 + np.linalg.norm(T @ yk - yk * theta[None, :k], axis=0) ** 2
+        res = np.sqrt(np.maximum(r2, 0.0)) / np.abs(theta[:k])
+        res_prev = float(res.max())
+        if log is not None:
+            log.append({"step": it, "solve_tol": tol_s, "solve_iterations": its, "residual_max": res_prev})
+        if res_prev <= tol and (refine_to is None or res_prev <= refine_to or res_prev > 0.5 * res_last):
+            break
+        res_last = res_prev
+        cholqr(nxt, tmp)
+        cholqr(tmp, cur)
+    else:
+        raise Exception("%s: %d wanted pairs not converged to %g in %d steps (residual %.2e)"
+                        % (name, k, tol, maxit, res_prev))
+    Yfull = np.zeros((m, m), dtype=np.complex128)
+    Yfull[:, :k] = Y[:, :k]
+    eng.eig_rotate(cur, Yfull, tmp)
+    X = eng.eig_fetch(tmp, k).T
+    lam = 1.0 / theta[:k] if inverse else theta[:k]
+    if hermitian:
+        lam = lam.real
+    return lam, np.ascontiguousarray(X)

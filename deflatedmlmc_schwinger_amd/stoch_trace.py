@@ -17,8 +17,8 @@ from scipy.sparse.linalg import LinearOperator
 from . import dist as _dist
 from .engine import ProbeStream
 from .multigrid import MG
-from .utils import (_engines, deflation_pre_computations, draw_probes, flopsV_manual, probe_batch,
-                    probe_batch_generated)
+from .utils import (_engines, deflation_pre_computations, draw_probes, flopsV_manual, mlmc_defl_setup_of,
+                    probe_batch, probe_batch_generated)
 
 DEFAULT_BATCH = 256
 NR_ROUGH_PROBES = 5
@@ -283,6 +283,7 @@ def hutchinson(A, params):
 
 # compute tr(A^{-1}) via multigrid multilevel Monte Carlo          stoch_trace.py:185-471
 def mlmc(A, params):
+    mlmc_defl_setup_of(params)
     skip_list = params['mlmc_levels_to_skip']
     if len(skip_list) > 1:
         raise Exception("Only allowed to skip one level for now")

@@ -62,7 +62,18 @@ _BUILD_KEYS = ('batch', 'device', 'engines', 'cache_dir', 'report_path', 'probe_
                'solver_testvectors', 'deflation_eigenpairs', 'ref_cycle_post', 'ref_cycle_k', 'ref_smoother',
                'solver_restart', 'stochastic_coarsest', 'stop_factor', 'ref_direct_max_n', 'ref_coarsest',
                'ref_coarse_dofs', 'setup_eigs', 'defer_coarse_levels',
-               'verbose', 'probe_rounds_max')
+               'verbose', 'probe_rounds_max', 'mlmc_defl_setup')
+# where the eigenpairs of the MLMC difference operators come from: host ARPACK (the reference's path) or
+# the block eigensolver on the GPU (setup_gpu.device_diff_eigenpairs)
+MLMC_DEFL_SETUPS = ("host", "device")
+
+
+def mlmc_defl_setup_of(params):
+    """The build-only key mlmc_defl_setup ("host" when absent); any other value raises."""
+    how = params.get('mlmc_defl_setup', "host") if hasattr(params, "get") else "host"
+    if how not in MLMC_DEFL_SETUPS:
+        raise Exception("mlmc_defl_setup = %r: expected one of %s" % (how, ", ".join(MLMC_DEFL_SETUPS)))
+    return how
 
 
 def trace_params_from_params(params, example):
@@ -184,9 +195,26 @@ def deflation_pre_computations(A, nr_deflat_vctrs, tolx, method, timer, params, 
             if hit is None and cdir:
                 _cache.save(cdir, "defl", ckey, {"S": Sy, "V": Vx})
     else:
+        how = mlmc_defl_setup_of(params)
         mg_solver.solve_tol = params['diff_lev_op_tol']                 # utils.py:142-143
-        Sy, Vx = _dist.default_comm().compute_on_root(
-            lambda: eigsh(lop, k=nr_deflat_vctrs, which='LM', tol=tolx))
+        t1 = time.time()
+        if how == "device":
+            # eigsh(Q_l, k, which='LM') by block subspace iteration on the GPU, 64 columns per operator
+            # application (the host path solves one right-hand side per ARPACK mat-vec).  The "exact" tr1 below
+            # is sum(lambda_i x_i^H gamma_3 x_i), off by -sum(x_i^H gamma_3 r_i) for residuals r_i.  Subspace
+            # iteration stops right at tol (3 steps at 0.1 on schwinger128) where ARPACK's Lanczos usually
+            # overshoots it, so the pairs are refined while the residual still halves per step, down to the
+            # accuracy of the operator's solves (7 steps there).
+            steps = []
+            Sy, Vx = _dist.default_comm().compute_on_root(
+                lambda: mg_solver.device_diff_eigenpairs(level_nr, nr_deflat_vctrs, tolx, log=steps,
+                                                         refine_to=params['diff_lev_op_tol']))
+            rec = {"method": "device", "seconds": round(time.time() - t1, 4), "steps": steps}
+        else:
+            Sy, Vx = _dist.default_comm().compute_on_root(
+                lambda: eigsh(lop, k=nr_deflat_vctrs, which='LM', tol=tolx))
+            rec = {"method": "host", "seconds": round(time.time() - t1, 4)}
+        mg_solver.setup_log.setdefault("mlmc_deflation", {})[level_nr] = rec
     sgn = np.where(Sy > 0, 1.0, -1.0)
     Sabs = Sy * sgn
     Ux = Vx * sgn[None, :]
@@ -217,10 +245,13 @@ def deflation_pre_computations(A, nr_deflat_vctrs, tolx, method, timer, params, 
     if defl_type == "exact":
         tr1 = np.sum(np.diag(overlap) * Sabs)                           # utils.py:176
     elif defl_type == "inexact_01":
-        Vbuff = np.zeros_like(Vx)
-        for i in range(nr_deflat_vctrs):
-            Vbuff[:, i] = mg_solver.diff_op(Vx[:, i].copy())
-            print('.', end='', flush=True)
+        if mlmc_defl_setup_of(params) == "device":
+            Vbuff = mg_solver.diff_op_block(Vx)                         # all k columns in one application
+        else:
+            Vbuff = np.zeros_like(Vx)
+            for i in range(nr_deflat_vctrs):
+                Vbuff[:, i] = mg_solver.diff_op(Vx[:, i].copy())
+                print('.', end='', flush=True)
         tr1 = np.trace(np.dot(Vx.transpose().conjugate(), Vbuff))
     elif defl_type == "inexact_02":
         raise Exception("deflation type inexact_02 under construction")

@@ -175,6 +175,12 @@ int sw_setup_arnoldi(sw_engine* h, int hid, int level, int which, int degree, ui
  *   sw_eig_load    first ncols columns of buffer dst <- host vectors (reference order)
  *   sw_eig_solve   buf_dst = Op^-1 buf_src, 64 right-hand sides to `tol`; mode 0: Op = A_level, mode 1:
  *                  Op = gamma_3 A_level (gamma_3 = +1 / -1 on the first / second half of the reference order)
+ *   sw_eig_apply_diff  buf_dst = (A_l^-1 - P A_c^-1 R) Gamma buf_src on all 64 columns, l = the level of
+ *                  sw_eig_begin, which must be on hierarchy 0: the MLMC difference operator of the probe body
+ *                  (SW_MODE_MLMC; skip = 1: A_0^-1 - P_0 P_1 A_2^-1 R_1 R_0 as SW_MODE_MLMC_SKIP, level 0 of
+ *                  at least three levels only).  Gamma = gamma_3 (g3 = 1) or the identity (g3 = 0).  Both
+ *                  solves run to `tol` with `maxiter`; *iters_max = the fine solve's iteration count.  Uses
+ *                  the third buffer and two coarse blocks of the eigen state as scratch (not the probe state)
  *   sw_eig_gram    out[64*64] = buf_a^H buf_b (fp64 MFMA, deterministic two-stage sum)
  *   sw_eig_rotate  buf_dst = buf_src Y (sub < 0) or buf_sub - buf_src Y (the block residual W - V T), Y[64*64]
  *                  row-major, dst != src
@@ -183,6 +189,8 @@ int sw_setup_arnoldi(sw_engine* h, int hid, int level, int which, int degree, ui
 int sw_eig_begin(sw_engine* h, int hid, int level, uint64_t seed);
 int sw_eig_load(sw_engine* h, int dst, int ncols, const double* X);
 int sw_eig_solve(sw_engine* h, int src, int dst, int mode, double tol, int maxiter, int32_t* iters_max);
+int sw_eig_apply_diff(sw_engine* h, int src, int dst, int skip, int g3, double tol, int maxiter,
+                      int32_t* iters_max);
 int sw_eig_gram(sw_engine* h, int a, int b, double* out);
 int sw_eig_rotate(sw_engine* h, int src, const double* Y, int dst, int sub);
 int sw_eig_fetch(sw_engine* h, int src, int k, double* out);
