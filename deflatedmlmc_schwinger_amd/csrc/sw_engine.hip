@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -810,26 +811,45 @@ static int stencil_spw(sw_engine* h, int tile_w) {
   return spw;
 }
 
+// Arguments of the stencil kernels of the lattice level (w = 0).  x-tile: whole rows while three of them
+// (2 KiB per site and 64-probe chunk; the even-odd kernels: five rows of half the sites) fit well inside a
+// 4-MiB L2, otherwise 256-site (or 64-site) tiles: 3.6 -> 4.6 TB/s on 1024^2; option stencil_tile where it
+// divides L.  eo: the even-odd kernels (k_schur_step, k_eo_hop), which need an even tile and store with
+// temporal stores.  C = complex64 (cplxf, or cplxf2: two probes per element): the complex64 links and
+// diagonal, rows of nbp / (probes per element) elements.
+template <class C>
+static swk::StencilArgsT<C> stencil_args(sw_engine* h, const Level& lv, int nbp, bool eo) {
+  using S = typename swk::scalar_of<C>::type;
+  swk::StencilArgsT<C> a;
+  a.L = lv.L;
+  a.Vh = lv.L * lv.L / 2;
+  a.diag = (typename swk::real_of<C>::type)(4.0 + lv.mass);
+  if constexpr (std::is_same<C, cplx>::value) {
+    a.U1 = lv.U1;
+    a.U2 = lv.U2;
+  } else {
+    a.U1 = lv.U1f;
+    a.U2 = lv.U2f;
+  }
+  a.nbp = nbp / (int)(sizeof(C) / sizeof(S));
+  a.w.x = 0;
+  a.w.y = 0;
+  a.nt_store = (!eo && h->stencil_nt) ? 1 : 0;
+  a.tile_w = lv.L;
+  if (lv.L > 256) a.tile_w = (lv.L % 256 == 0) ? 256 : ((lv.L % 64 == 0) ? 64 : lv.L);
+  if (h->stencil_tile > 0 && lv.L % h->stencil_tile == 0 && (!eo || h->stencil_tile % 2 == 0))
+    a.tile_w = h->stencil_tile;
+  return a;
+}
+
 // the Wilson stencil of the lattice level; CI = complex64: X is a direction stored by the
 // single-precision preconditioner (mode 0 only), widened on load
 template <class CI, class CO>
 static int launch_stencil(sw_engine* h, Level& lv, int mode, const CI* X, const cplx* B, CO* Y,
                           int nbp, cplx w) {
   {
-    swk::StencilArgs a;
-    a.L = lv.L;
-    a.Vh = lv.L * lv.L / 2;
-    a.diag = 4.0 + lv.mass;
-    a.U1 = lv.U1;
-    a.U2 = lv.U2;
-    a.nbp = nbp;
+    swk::StencilArgs a = stencil_args<cplx>(h, lv, nbp, false);
     a.w = w;
-    a.nt_store = h->stencil_nt ? 1 : 0;
-    // x-tile: whole rows while three of them (2 KiB per site and 64-probe chunk) fit well
-    // inside a 4-MiB L2, otherwise 256-site (or 64-site) tiles: 3.6 -> 4.6 TB/s on 1024^2
-    a.tile_w = lv.L;
-    if (lv.L > 256) a.tile_w = (lv.L % 256 == 0) ? 256 : ((lv.L % 64 == 0) ? 64 : lv.L);
-    if (h->stencil_tile > 0 && lv.L % h->stencil_tile == 0) a.tile_w = h->stencil_tile;
     const int spw = stencil_spw(h, a.tile_w);
     const int V = lv.L * lv.L;
     const int waves = V / spw;
@@ -1132,6 +1152,21 @@ static int fgmres(sw_engine* h, Hier& H, int level, const cplx* B, cplx* X, doub
                   int m, bool outer, KrylovWS& ws, int nbp, int* iters_total,
                   bool use_precond = true, const cplx* aug = nullptr);
 
+// The system a flexible GMRES iterates on (fgmres_loop, gram_cycle): the full system of a level
+// (full_system) or the even-odd reduced system of the stencil level (reduced_system)
+struct KrylovSys {
+  int n = 0;                                                        // vector length
+  std::function<int(int mode, const cplx* x, const cplx* b, cplx* y)> apply;   // y = A x (mode 0), b - A x (1)
+  std::function<int(const cplx* v, cplx* z)> precond;               // z = M v (empty: no preconditioner)
+  // complex64 directions (precond32 empty: none): z = M v, then w = A z into a complex64 basis (op32, option
+  // f32_krylov) or into the fp64 basis (op32w)
+  std::function<int(const cplxf* v, cplxf* z)> precond32;
+  std::function<int(const cplxf* z, cplxf* w)> op32;
+  std::function<int(const cplxf* z, cplx* w)> op32w;
+  bool normb_set = false;   // ||b|| of the stopping criterion was fixed by the caller (tail_begin)
+};
+static KrylovSys full_system(sw_engine* h, Hier& H, int level, int nbp, bool use_precond, bool outer);
+
 // nu MR steps on (X, R) with R = B - A X maintained
 static int mr_smooth(sw_engine* h, Level& lv, cplx* X, cplx* R, int nu, int nbp) {
   SWCHK(ensure_small(h, nbp));
@@ -1356,35 +1391,39 @@ static int ensure_even_orders(sw_engine* h, Hier& H) {
 static inline int* sink_slot(sw_engine* h);
 static bool f32_capable(const Hier& H, int level);
 
-// The K-cycle's inner iteration -- L steps of flexible GMRES from a zero guess, preconditioned by the cycle
-// of `level` -- in Gram-matrix form (see fgmres_eo_gram): directions without orthogonalisation, one pass for
-// all inner products, X = sum_j y_j z_j.  7 vector passes of BLAS-1 instead of 14 for L = 2.
-static int kcycle_gram(sw_engine* h, Hier& H, int level, const cplx* B, cplx* X, int L, KrylovWS& ws, int nbp) {
-  Level& lv = H.lv[level];
-  const size_t vec = (size_t)lv.n * nbp;
+// One restart cycle of L steps in Gram-matrix form (see fgmres_eo_gram) from the residual R: the directions
+// z_j = M v_j, w_j = A z_j (v_0 = R, v_j = w_{j-1}) without orthogonalisation, one multigram pass over
+// [R, w_0 .. w_{L-1}] whose SW_TAIL_GRAM tail `tg` (tolerances, iteration base, counter, first_cycle set by
+// the caller) solves for y, then X += sum_j y_j z_j
+static int gram_cycle(sw_engine* h, const KrylovSys& sys, const cplx* R, cplx* X, int L, KrylovWS& ws, int nbp,
+                      swk::FgTail tg) {
+  const size_t vec = (size_t)sys.n * nbp;
+  PtrList pu, pz;
+  pu.p[0] = R;
   for (int j = 0; j < L; ++j) {
-    const cplx* vin = (j == 0) ? B : ws.V + vec * (j - 1);
-    SWCHK(vcycle(h, H, level, vin, ws.Z + vec * j, nbp));
-    SWCHK(apply_op(h, lv, 0, ws.Z + vec * j, nullptr, ws.V + vec * j, nbp));
+    cplx* z = ws.Z + vec * j;
+    cplx* w = ws.V + vec * j;
+    SWCHK(sys.precond(pu.p[j], z));
+    SWCHK(sys.apply(0, z, nullptr, w));
+    pu.p[j + 1] = w;
+    pz.p[j] = z;
   }
-  PtrList pu;
-  pu.p[0] = B;
-  for (int j = 0; j < L; ++j) pu.p[j + 1] = ws.V + vec * j;
-  swk::FgTail tg{};
   tg.kind = SW_TAIL_GRAM;
   tg.s = ws.sc;
   tg.j = L;
   tg.h1 = ws.gram;
-  tg.tol = 0.0;
-  tg.tol_stop = 0.0;
-  tg.iter_base = 0;
+  SWCHK(multigram(h, pu, L + 1, sys.n, nbp, ws.gram, &tg));
+  return multiaxpy(h, pz, L, ws.sc.ys, 1.0, X, X, sys.n, nbp, nullptr);
+}
+
+// The K-cycle's inner iteration -- L steps of flexible GMRES from a zero guess, preconditioned by the cycle
+// of `level` -- as one Gram-matrix cycle: 7 vector passes of BLAS-1 instead of 14 for L = 2
+static int kcycle_gram(sw_engine* h, Hier& H, int level, const cplx* B, cplx* X, int L, KrylovWS& ws, int nbp) {
+  swk::FgTail tg{};      // (tol = 0: nothing to count; the counter is the sink)
   tg.first_cycle = 1;
   tg.notconv = sink_slot(h);
-  SWCHK(multigram(h, pu, L + 1, lv.n, nbp, ws.gram, &tg));
-  SWCHK(zero_vec(h, X, lv.n, nbp));
-  PtrList pz;
-  for (int q = 0; q < L; ++q) pz.p[q] = ws.Z + vec * q;
-  return multiaxpy(h, pz, L, ws.sc.ys, 1.0, X, X, lv.n, nbp, nullptr);
+  SWCHK(zero_vec(h, X, H.lv[level].n, nbp));
+  return gram_cycle(h, full_system(h, H, level, nbp, true, false), B, X, L, ws, nbp, tg);
 }
 
 static int coarse_correction(sw_engine* h, Hier& H, int l, int nbp) {
@@ -1403,7 +1442,21 @@ static int coarse_correction(sw_engine* h, Hier& H, int l, int nbp) {
   return vcycle(h, H, l + 1, lc.b, lc.x, nbp);
 }
 
-static swk::StencilArgs eo_stencil_args(sw_engine* h, Level& lv, int nbp);
+// Into and out of the even-odd reduced system of the stencil level (k_eo_hop):
+//   HOP 0:  out_e = b'_e = b_e + H_eo b_o / D   (src = B)
+//   HOP 1:  out_o = x_o  = (b_o + H_oe x_e) / D (src = out = the iterate, whose even half is x_e)
+template <int HOP>
+static int eo_hop(sw_engine* h, Level& lv, const cplx* B, const cplx* src, cplx* out, int nbp) {
+  const swk::StencilArgs a = stencil_args<cplx>(h, lv, nbp, true);
+  const int bpc = (a.Vh + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK;
+  const double di = 1.0 / a.diag;
+  LaunchScope ls(h, T_SCHUR);
+  if (h->profiling) h->twork[T_SCHUR] += (double)a.Vh * (96.0 * nbp + 64.0);
+  hipLaunchKernelGGL((swk::k_eo_hop<HOP>), dim3(bpc * (nbp / 64)), dim3(SW_BLOCK), 0, h->stream, B, src, out, a,
+                     HOP == 0 ? 1.0 : di, di, bpc);
+  KLAUNCH_CHECK();
+  return 0;
+}
 
 // One k_schur_step launch on the stencil level (fp64) on the lattice rows a.row0 .. a.row0 + a.nrows - 1
 // (a.nrows = 0: all)
@@ -1478,7 +1531,7 @@ static int skew_height(sw_engine* h, Level& lv, int nu, int nbp, int* width) {
 // A strip's working set is 3 (H + 4) rows: chosen to fit the cache, only the first and the last touch of a
 // strip reach HBM.  Same arithmetic per site in another order: results are bit-identical.
 static int schur_steps(sw_engine* h, Level& lv, cplx* cur, cplx* nxt, const cplx* bp, int nbp, cplx** result) {
-  swk::StencilArgs a = eo_stencil_args(h, lv, nbp);
+  swk::StencilArgs a = stencil_args<cplx>(h, lv, nbp, true);
   const int nu = (int)lv.w_eo.size();
   const int L = lv.L;
   int c0 = 0, cw = nbp;      // probe columns of the current launches
@@ -1529,7 +1582,7 @@ static int schur_steps(sw_engine* h, Level& lv, cplx* cur, cplx* nxt, const cplx
 // (launch k reads what launch k-1 wrote, two rows further out; x is read by launch 0 and written by the
 // last one, whose rows lie behind everything launch 0 still has to read).
 static int schur_product_steps(sw_engine* h, Level& lv, cplx* x, cplx* va, cplx* vb, const cplx* bp, int nbp) {
-  swk::StencilArgs a = eo_stencil_args(h, lv, nbp);
+  swk::StencilArgs a = stencil_args<cplx>(h, lv, nbp, true);
   const int nu = (int)lv.w_eo.size();
   const int L = lv.L;
   cplx* buf[2] = {va, vb};
@@ -1576,40 +1629,12 @@ static int schur_product_steps(sw_engine* h, Level& lv, cplx* x, cplx* va, cplx*
 // `start` and `other` are the ping-pong pair chosen by the caller so that the last step lands in Xout.
 static int eo_smooth(sw_engine* h, Level& lv, const cplx* Bin, cplx* start, cplx* other, cplx* Xout,
                      int nbp) {
-  swk::StencilArgs a;
-  a.L = lv.L;
-  a.Vh = lv.L * lv.L / 2;
-  a.diag = 4.0 + lv.mass;
-  a.U1 = lv.U1;
-  a.U2 = lv.U2;
-  a.nbp = nbp;
-  a.nt_store = 0;
-  a.tile_w = lv.L;
-  // five lattice rows (2 KiB per site and 64-probe chunk, half the sites) must fit an XCD's L2
-  if (lv.L > 256) a.tile_w = (lv.L % 256 == 0) ? 256 : ((lv.L % 64 == 0) ? 64 : lv.L);
-  if (h->stencil_tile > 0 && lv.L % h->stencil_tile == 0 && h->stencil_tile % 2 == 0) a.tile_w = h->stencil_tile;
-  a.w = cplx{0.0, 0.0};
-  const int bpc = (a.Vh + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK;
-  const double di = 1.0 / a.diag;
   cplx* bp = lv.r;   // b'_e lives in the even half of the level's residual buffer
-  const dim3 grid(bpc * (nbp / 64));
-  {
-    LaunchScope ls(h, T_SCHUR);
-    if (h->profiling) h->twork[T_SCHUR] += (double)a.Vh * (96.0 * nbp + 64.0);
-    hipLaunchKernelGGL((swk::k_eo_hop<0>), grid, dim3(SW_BLOCK), 0, h->stream, Bin, Bin, bp, a, 1.0, di, bpc);
-    KLAUNCH_CHECK();
-  }
+  SWCHK(eo_hop<0>(h, lv, Bin, Bin, bp, nbp));
   cplx* cur = nullptr;
   SWCHK(schur_steps(h, lv, start, other, bp, nbp, &cur));
-  {
-    LaunchScope ls(h, T_SCHUR);
-    if (h->profiling) h->twork[T_SCHUR] += (double)a.Vh * (96.0 * nbp + 64.0);
-    hipLaunchKernelGGL((swk::k_eo_hop<1>), grid, dim3(SW_BLOCK), 0, h->stream, Bin, (const cplx*)cur, cur, a,
-                       di, di, bpc);
-    KLAUNCH_CHECK();
-  }
-  cplx* last_out = cur;
-  if (last_out != Xout) return sw_fail(h, "internal: even-odd smoother ended in the wrong buffer");
+  SWCHK(eo_hop<1>(h, lv, Bin, cur, cur, nbp));
+  if (cur != Xout) return sw_fail(h, "internal: even-odd smoother ended in the wrong buffer");
   return 0;
 }
 
@@ -1869,24 +1894,11 @@ template <class C>
 // steps) and only the even half of the iterate is wanted (no hop after them); all arrays half-length
 static int eo_smooth32_t(sw_engine* h, Level& lv, const cplxf* Bin_, cplxf* start_, cplxf* other_,
                          cplxf* Xout_, int nbp, bool reduced) {
-  const int per = (int)(sizeof(C) / sizeof(cplxf));   // probes per lane
   const C* Bin = (const C*)Bin_;
   C* start = (C*)start_;
   C* other = (C*)other_;
   C* Xout = (C*)Xout_;
-  swk::StencilArgsT<C> a;
-  a.L = lv.L;
-  a.Vh = lv.L * lv.L / 2;
-  a.diag = (float)(4.0 + lv.mass);
-  a.U1 = lv.U1f;
-  a.U2 = lv.U2f;
-  a.nbp = nbp / per;
-  a.nt_store = 0;
-  a.tile_w = lv.L;
-  // five lattice rows (1 KiB per site and 64-lane chunk, half the sites) must fit an XCD's L2
-  if (lv.L > 256) a.tile_w = (lv.L % 256 == 0) ? 256 : ((lv.L % 64 == 0) ? 64 : lv.L);
-  if (h->stencil_tile > 0 && lv.L % h->stencil_tile == 0 && h->stencil_tile % 2 == 0) a.tile_w = h->stencil_tile;
-  a.w = cplxf{0.f, 0.f};
+  swk::StencilArgsT<C> a = stencil_args<C>(h, lv, nbp, true);
   const int bpc = (a.Vh + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK;
   const dim3 grid(bpc * (a.nbp / 64));
   const float di = (float)(1.0 / (4.0 + lv.mass));
@@ -1927,19 +1939,7 @@ static int eo_smooth32(sw_engine* h, Level& lv, const cplxf* Bin, cplxf* start, 
 // Y_e = S X_e on complex64 half vectors (operator of the even-odd reduced system, complex64 Krylov basis)
 template <class C>
 static int schur_apply32_t(sw_engine* h, Level& lv, const cplxf* X_, cplxf* Y_, int nbp) {
-  const int per = (int)(sizeof(C) / sizeof(cplxf));
-  swk::StencilArgsT<C> a;
-  a.L = lv.L;
-  a.Vh = lv.L * lv.L / 2;
-  a.diag = (float)(4.0 + lv.mass);
-  a.U1 = lv.U1f;
-  a.U2 = lv.U2f;
-  a.nbp = nbp / per;
-  a.nt_store = 0;
-  a.tile_w = lv.L;
-  if (lv.L > 256) a.tile_w = (lv.L % 256 == 0) ? 256 : ((lv.L % 64 == 0) ? 64 : lv.L);
-  if (h->stencil_tile > 0 && lv.L % h->stencil_tile == 0 && h->stencil_tile % 2 == 0) a.tile_w = h->stencil_tile;
-  a.w = cplxf{0.f, 0.f};
+  const swk::StencilArgsT<C> a = stencil_args<C>(h, lv, nbp, true);
   const int bpc = (a.Vh + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK;
   const dim3 grid(bpc * (a.nbp / 64));
   LaunchScope ls(h, T_SCHUR_OP);
@@ -2110,8 +2110,9 @@ static swk::FgTail tail_verify(const KrylovWS& ws, double tol, double tol_stop, 
 }
 
 // ---------------------------------------------------------------------------------------------
-// batched right-preconditioned flexible GMRES(m) (MG.solve -> fgmres, multigrid.py:347-366);
-// one classical Gram-Schmidt pass per step (two with option cgs2), true-residual verification
+// batched right-preconditioned flexible GMRES(m) (MG.solve -> fgmres, multigrid.py:347-366) on the system
+// `sys` with right-hand side B (of length sys.n); one classical Gram-Schmidt pass per step (two with option
+// cgs2), true-residual verification
 //  outer == true : restarted, converges every probe to stop_factor * tol (one host read-back per
 //                  iteration once the expected count is near)
 //  outer == false: exactly `maxiter` (= m, or m + 1 with `aug`) steps from a zero guess, no host
@@ -2121,44 +2122,45 @@ static swk::FgTail tail_verify(const KrylovWS& ws, double tol, double tol_stop, 
 //                  is `aug` instead of the next Krylov vector, so the cycle minimises the residual over
 //                  K_m(A, r) + span{aug}; ws must have room for m + 1 vectors
 // ---------------------------------------------------------------------------------------------
-static int fgmres(sw_engine* h, Hier& H, int level, const cplx* B, cplx* X, double tol, int maxiter,
-                  int m, bool outer, KrylovWS& ws, int nbp, int* iters_total, bool use_precond,
-                  const cplx* aug) {
-  Level& lv = H.lv[level];
+static int fgmres_loop(sw_engine* h, Hier& H, int level, const KrylovSys& sys, const cplx* B, cplx* X,
+                       double tol, int maxiter, int m, bool outer, KrylovWS& ws, int nbp, int* iters_total,
+                       const cplx* aug = nullptr) {
   const int hid_idx = (int)(&H - &h->hier[0]);
   const int check_from = (outer && h->lazy_sync) ? std::max(0, h->sync_hint[hid_idx][level] - 2) : 0;
-  const int n = lv.n;
+  const int n = sys.n;
   const size_t vec = (size_t)n * nbp;
-  const bool precond = use_precond && (level < H.nlevels - 1);
   const int tb = 256, tg = (nbp + tb - 1) / tb;
   const double tol_stop = outer ? tol * h->stop_factor : tol;
-  if (aug && (outer || precond || ws.m < m + 1)) return sw_fail(h, "internal: augmented cycle misused");
+  // complex64 directions: the input copy of each Krylov vector is written by its producer
+  const bool z32 = (bool)sys.precond32;
+  const bool k32 = z32 && h->f32_krylov;
+  if (aug && (outer || sys.precond || ws.m < m + 1)) return sw_fail(h, "internal: augmented cycle misused");
+  if (z32 && !(k32 ? (bool)sys.op32 : (bool)sys.op32w))
+    return sw_fail(h, "internal: complex64 operator of the Krylov system missing");
   int done = 0;
   bool first = true;
   bool converged = false;
   if (outer) SWCHK(reset_slots(h));
   SWCHK(zero_vec(h, X, n, nbp));
   const cplx* Rcur = B;
-  // single-precision preconditioner: on the lattice level its directions are kept complex64 and its
-  // input copy is written by the producer of each Krylov vector; elsewhere cast at the boundary
-  const bool pf32 = precond && h->precond_f32 && f32_capable(H, level);
-  const bool z32 = pf32 && outer && lv.stencil;
   if (z32) {
+    Level& lv = H.lv[level];
     SWCHK(ensure_f32(h, H));
     SWCHK(ensure_level_ws32(h, lv, nbp));
+    // full length of the level: its full and reduced systems share the workspace
+    const size_t full = (size_t)lv.n * nbp;
     if (!ws.Z32) {
-      SWCHK(dev_realloc(h, &ws.Z32, vec * m));
-      SWCHK(dev_realloc(h, &ws.v32, vec));
+      SWCHK(dev_realloc(h, &ws.Z32, full * m));
+      SWCHK(dev_realloc(h, &ws.v32, full));
     }
+    if (k32 && !ws.V32) SWCHK(dev_realloc(h, &ws.V32, full * m));
   }
-  const bool k32 = z32 && h->f32_krylov;
-  if (k32 && !ws.V32) SWCHK(dev_realloc(h, &ws.V32, vec * m));
   while (done < maxiter && !converged) {
     // beta = ||r||
     {
       PtrList pl;
       pl.p[0] = Rcur;
-      const swk::FgTail tbeg = tail_begin(ws, first ? 1 : 0);
+      const swk::FgTail tbeg = tail_begin(ws, (first && !sys.normb_set) ? 1 : 0);
       SWCHK(multidot(h, pl, 1, Rcur, n, nbp, ws.nrm, nullptr, nullptr, &tbeg));
     }
     // the basis is kept unnormalised (fg_hess_col): vtilde_0 is the residual where it lies,
@@ -2188,8 +2190,8 @@ static int fgmres(sw_engine* h, Hier& H, int level, const cplx* B, cplx* X, doub
         // complex64 cycle: vtilde_j -> z_j -> w = A z_j -> orthogonalised vtilde_{j+1}, all stored
         // complex64 (the arithmetic of A z and of the inner products is fp64 on widened operands)
         cplxf* w32 = ws.V32 + vec * j;
-        SWCHK(vcycle32(h, H, level, vt32(j), zj32, nbp));
-        SWCHK((launch_stencil<cplxf, cplxf>(h, lv, 0, zj32, nullptr, w32, nbp, cplx{0.0, 0.0})));
+        SWCHK(sys.precond32(vt32(j), zj32));
+        SWCHK(sys.op32(zj32, w32));
         swk::PtrListT<cplxf> pv32;
         for (int k = 0; k <= j; ++k) pv32.p[k] = vt32(k);
         pv32.p[j + 1] = w32;
@@ -2206,14 +2208,13 @@ static int fgmres(sw_engine* h, Hier& H, int level, const cplx* B, cplx* X, doub
         }
       } else {
       if (z32) {
-        SWCHK(vcycle32(h, H, level, ws.v32, zj32, nbp));
-        SWCHK((launch_stencil<cplxf, cplx>(h, lv, 0, zj32, nullptr, w, nbp, cplx{0.0, 0.0})));
+        SWCHK(sys.precond32(ws.v32, zj32));
+        SWCHK(sys.op32w(zj32, w));
       } else {
         if (aug_step) SWCHK(copy_vec(h, zj, aug, n, nbp));
-        else if (pf32) SWCHK(vcycle_f32_boundary(h, H, level, vj, zj, nbp));
-        else if (precond) SWCHK(vcycle(h, H, level, vj, zj, nbp));
+        else if (sys.precond) SWCHK(sys.precond(vj, zj));
         else SWCHK(copy_vec(h, zj, vj, n, nbp));
-        SWCHK(apply_op(h, lv, 0, zj, nullptr, w, nbp));
+        SWCHK(sys.apply(0, zj, nullptr, w));
       }
       PtrList pv;
       for (int k = 0; k <= j; ++k) pv.p[k] = vt(k);
@@ -2267,7 +2268,7 @@ static int fgmres(sw_engine* h, Hier& H, int level, const cplx* B, cplx* X, doub
       // (also at done == maxiter: a solve that is flagged converged on its last permitted
       // iteration is still checked, and reported as not converged when the check fails)
       // true residual of every probe; continue when the Arnoldi recurrence was optimistic
-      SWCHK(apply_op(h, lv, 1, X, B, ws.rres, nbp));
+      SWCHK(sys.apply(1, X, B, ws.rres));
       PtrList pr;
       pr.p[0] = ws.rres;
       int* slot = nullptr;
@@ -2282,13 +2283,48 @@ static int fgmres(sw_engine* h, Hier& H, int level, const cplx* B, cplx* X, doub
         continue;
       }
     } else if (!converged && done < maxiter) {
-      SWCHK(apply_op(h, lv, 1, X, B, ws.rres, nbp));
+      SWCHK(sys.apply(1, X, B, ws.rres));
       Rcur = ws.rres;
     }
   }
   if (iters_total) *iters_total = done;
   if (outer) h->sync_hint[hid_idx][level] = converged ? done : 0;
   return 0;
+}
+
+// A X = B at a level, preconditioned by its multigrid cycle (use_precond, above the coarsest level): fp64,
+// fp64 with the complex64 cycle cast at its boundary (precond_f32), or -- in the outer solve on the lattice
+// level -- with complex64 directions whose input copies are written by the producers of the Krylov vectors
+static KrylovSys full_system(sw_engine* h, Hier& H, int level, int nbp, bool use_precond, bool outer) {
+  Level& lv = H.lv[level];
+  const bool precond = use_precond && (level < H.nlevels - 1);
+  const bool pf32 = precond && h->precond_f32 && f32_capable(H, level);
+  KrylovSys s;
+  s.n = lv.n;
+  s.apply = [h, &lv, nbp](int mode, const cplx* x, const cplx* b, cplx* y) {
+    return apply_op(h, lv, mode, x, b, y, nbp);
+  };
+  if (pf32)
+    s.precond = [h, &H, level, nbp](const cplx* v, cplx* z) { return vcycle_f32_boundary(h, H, level, v, z, nbp); };
+  else if (precond)
+    s.precond = [h, &H, level, nbp](const cplx* v, cplx* z) { return vcycle(h, H, level, v, z, nbp); };
+  if (pf32 && outer && lv.stencil) {
+    s.precond32 = [h, &H, level, nbp](const cplxf* v, cplxf* z) { return vcycle32(h, H, level, v, z, nbp); };
+    s.op32 = [h, &lv, nbp](const cplxf* z, cplxf* w) {
+      return launch_stencil<cplxf, cplxf>(h, lv, 0, z, nullptr, w, nbp, cplx{0.0, 0.0});
+    };
+    s.op32w = [h, &lv, nbp](const cplxf* z, cplx* w) {
+      return launch_stencil<cplxf, cplx>(h, lv, 0, z, nullptr, w, nbp, cplx{0.0, 0.0});
+    };
+  }
+  return s;
+}
+
+static int fgmres(sw_engine* h, Hier& H, int level, const cplx* B, cplx* X, double tol, int maxiter,
+                  int m, bool outer, KrylovWS& ws, int nbp, int* iters_total, bool use_precond,
+                  const cplx* aug) {
+  return fgmres_loop(h, H, level, full_system(h, H, level, nbp, use_precond, outer), B, X, tol, maxiter, m,
+                     outer, ws, nbp, iters_total, aug);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4257,25 +4293,10 @@ int sw_vcycle(sw_engine* h, int hid, int level0, int nb, const double* B, double
 // stopping criterion is the reference's (multigrid.py:347-366).  Per iteration on the lattice level:
 // about 47 half-vector passes instead of 64.
 // ---------------------------------------------------------------------------------------------
-static swk::StencilArgs eo_stencil_args(sw_engine* h, Level& lv, int nbp) {
-  swk::StencilArgs a;
-  a.L = lv.L;
-  a.Vh = lv.L * lv.L / 2;
-  a.diag = 4.0 + lv.mass;
-  a.U1 = lv.U1;
-  a.U2 = lv.U2;
-  a.nbp = nbp;
-  a.nt_store = 0;
-  a.tile_w = lv.L;
-  if (lv.L > 256) a.tile_w = (lv.L % 256 == 0) ? 256 : ((lv.L % 64 == 0) ? 64 : lv.L);
-  if (h->stencil_tile > 0 && lv.L % h->stencil_tile == 0 && h->stencil_tile % 2 == 0) a.tile_w = h->stencil_tile;
-  a.w = cplx{0.0, 0.0};
-  return a;
-}
 
 // Y_e = S X_e (mode 0) or Bp_e - S X_e (mode 1); all three are half vectors
 static int schur_apply(sw_engine* h, Level& lv, int mode, const cplx* X, const cplx* Bp, cplx* Y, int nbp) {
-  swk::StencilArgs a = eo_stencil_args(h, lv, nbp);
+  swk::StencilArgs a = stencil_args<cplx>(h, lv, nbp, true);
   LaunchScope ls(h, T_SCHUR_OP);
   if (mode == 0) return launch_schur_step<0>(h, a, X, Bp, Y, nbp);
   return launch_schur_step<1>(h, a, X, Bp, Y, nbp);
@@ -4353,155 +4374,48 @@ static int vcycle32_even(sw_engine* h, Hier& H, const cplxf* Bin, cplxf* Xout, i
   return eo_smooth32(h, lv, Bin, start, other, Xout, nbp, true);
 }
 
-// batched flexible GMRES(m) on the even-odd reduced system of the stencil level (one Gram-Schmidt
-// pass, same scalar kernels, freezing, lazy read-back and true-residual verification as fgmres).
-// With the single-precision preconditioner (precond_f32 + f32_krylov) the restart cycle is complex64 as
-// in fgmres: basis, directions and w = S z in complex64 (S applied in single precision), inner products
-// accumulated in fp64; residual b' - S x, iterate and convergence check fp64, once per restart.
+// The even-odd reduced system S x_e = b'_e of the stencil level (half vectors), preconditioned by the even
+// block of the level-0 cycle.  With the single-precision preconditioner (precond_f32 + f32_krylov) the
+// restart cycle is complex64 as in the full system: basis, directions and w = S z in complex64 (S applied in
+// single precision), inner products accumulated in fp64; residual b' - S x, iterate and convergence check
+// fp64, once per restart.  ||b|| of the FULL system fixes normb (reduced_rhs).
+static KrylovSys reduced_system(sw_engine* h, Hier& H, int nbp) {
+  Level& lv = H.lv[0];
+  KrylovSys s;
+  s.n = lv.n / 2;
+  s.normb_set = true;
+  s.apply = [h, &lv, nbp](int mode, const cplx* x, const cplx* b, cplx* y) {
+    return schur_apply(h, lv, mode, x, b, y, nbp);
+  };
+  s.precond = [h, &H, nbp](const cplx* v, cplx* z) { return vcycle_even(h, H, v, z, nbp); };
+  if (h->precond_f32 && h->f32_krylov && f32_capable(H, 0)) {
+    s.precond32 = [h, &H, nbp](const cplxf* v, cplxf* z) { return vcycle32_even(h, H, v, z, nbp); };
+    s.op32 = [h, &lv, nbp](const cplxf* z, cplxf* w) { return schur_apply32(h, lv, z, w, nbp); };
+  }
+  return s;
+}
+
+// ||b|| of the FULL system fixes normb (the reference's stopping criterion); b'_e = b_e + H_eo b_o / D
+// into ws.xacc
+static int reduced_rhs(sw_engine* h, Level& lv, const cplx* B, KrylovWS& ws, int nbp) {
+  PtrList pl;
+  pl.p[0] = B;
+  const swk::FgTail tbeg = tail_begin(ws, 1);
+  SWCHK(multidot(h, pl, 1, B, lv.n, nbp, ws.nrm, nullptr, nullptr, &tbeg));
+  return eo_hop<0>(h, lv, B, B, ws.xacc, nbp);
+}
+
+// batched flexible GMRES(m) on the even-odd reduced system: the full system's restart loop on S, then
+// x_o = (b_o + H_oe x_e) / D
 static int fgmres_eo(sw_engine* h, Hier& H, const cplx* B, cplx* X, double tol, int maxiter, int m,
                      KrylovWS& ws, int nbp, int* iters_total) {
   Level& lv = H.lv[0];
-  const int hid_idx = (int)(&H - &h->hier[0]);
-  const int check_from = h->lazy_sync ? std::max(0, h->sync_hint[hid_idx][0] - 2) : 0;
-  const int n2 = lv.n / 2;
-  const size_t vec = (size_t)n2 * nbp;
-  const int tb = 256, tg = (nbp + tb - 1) / tb;
-  const double tol_stop = tol * h->stop_factor;
   SWCHK(ensure_level_ws(h, lv, nbp));
-  SWCHK(reset_slots(h));
-  swk::StencilArgs a = eo_stencil_args(h, lv, nbp);
-  const int bpc = (a.Vh + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK;
-  const dim3 grid(bpc * (nbp / 64));
-  const double di = 1.0 / a.diag;
-  cplx* bp = ws.xacc;               // b'_e
-  const bool k32 = h->precond_f32 && h->f32_krylov && f32_capable(H, 0);
-  if (k32) {
-    SWCHK(ensure_f32(h, H));
-    SWCHK(ensure_level_ws32(h, lv, nbp));
-    const size_t full = (size_t)lv.n * nbp;      // (sized as fgmres sizes them: both may run on this handle)
-    if (!ws.Z32) {
-      SWCHK(dev_realloc(h, &ws.Z32, full * m));
-      SWCHK(dev_realloc(h, &ws.v32, full));
-    }
-    if (!ws.V32) SWCHK(dev_realloc(h, &ws.V32, full * m));
-  }
-  {
-    // ||b|| of the FULL system fixes normb (the reference's stopping criterion); b'_e = b_e + H_eo b_o / D
-    PtrList pl;
-    pl.p[0] = B;
-    const swk::FgTail tbeg = tail_begin(ws, 1);
-    SWCHK(multidot(h, pl, 1, B, lv.n, nbp, ws.nrm, nullptr, nullptr, &tbeg));
-    LaunchScope ls(h, T_SCHUR);
-    if (h->profiling) h->twork[T_SCHUR] += (double)a.Vh * (96.0 * nbp + 64.0);
-    hipLaunchKernelGGL((swk::k_eo_hop<0>), grid, dim3(SW_BLOCK), 0, h->stream, B, B, bp, a, 1.0, di, bpc);
-    KLAUNCH_CHECK();
-  }
-  // the iterate lives in the even half of X; its odd half is set once at the end
-  {
-    LaunchScope ls(h, T_AXPY);
-    HIPCHK(hipMemsetAsync(X, 0, vec * sizeof(cplx), h->stream));
-  }
-  int done = 0;
-  bool converged = false;
-  const cplx* Rcur = bp;
-  while (done < maxiter && !converged) {
-    {
-      PtrList pl;
-      pl.p[0] = Rcur;
-      const swk::FgTail tbeg = tail_begin(ws, 0);
-      SWCHK(multidot(h, pl, 1, Rcur, n2, nbp, ws.nrm, nullptr, nullptr, &tbeg));
-    }
-    auto vt = [&](int k) -> const cplx* { return k == 0 ? Rcur : ws.V + vec * (k - 1); };
-    auto vt32 = [&](int k) -> const cplxf* { return k == 0 ? ws.v32 : ws.V32 + vec * (k - 1); };
-    if (k32) SWCHK(cast_vec(h, Rcur, ws.v32, vec, T_AXPY));
-    int j = 0;
-    const int jmax = std::min(m, maxiter - done);
-    for (; j < jmax; ++j) {
-      cplx* zj = ws.Z + vec * j;
-      cplx* w = ws.V + vec * j;          // becomes vtilde_{j+1}
-      const bool last = h->pyth_last && j == jmax - 1 && m <= 8;
-      int* slot = nullptr;
-      SWCHK(take_slot(h, &slot));
-      const swk::FgTail th = tail_hess(ws, j, false, last, tol, tol_stop, done, slot);
-      if (k32) {
-        cplxf* zj32 = ws.Z32 + vec * j;
-        cplxf* w32 = ws.V32 + vec * j;
-        SWCHK(vcycle32_even(h, H, vt32(j), zj32, nbp));
-        SWCHK(schur_apply32(h, lv, zj32, w32, nbp));
-        swk::PtrListT<cplxf> pv32;
-        for (int k = 0; k <= j; ++k) pv32.p[k] = vt32(k);
-        pv32.p[j + 1] = w32;
-        SWCHK(multidot(h, pv32, last ? j + 2 : j + 1, (const cplxf*)w32, n2, nbp, ws.h1, ws.sc.svec, ws.c1,
-                       last ? &th : nullptr));
-        if (!last)
-          SWCHK(multiaxpy(h, pv32, j + 1, ws.c1, -1.0, (const cplxf*)w32, w32, n2, nbp, ws.nrm, nullptr, &th));
-      } else {
-      SWCHK(vcycle_even(h, H, vt(j), zj, nbp));
-      SWCHK(schur_apply(h, lv, 0, zj, nullptr, w, nbp));
-      PtrList pv;
-      for (int k = 0; k <= j; ++k) pv.p[k] = vt(k);
-      pv.p[j + 1] = w;
-      SWCHK(multidot(h, pv, last ? j + 2 : j + 1, w, n2, nbp, ws.h1, ws.sc.svec, ws.c1, last ? &th : nullptr));
-      if (!last) SWCHK(multiaxpy(h, pv, j + 1, ws.c1, -1.0, w, w, n2, nbp, ws.nrm, nullptr, &th));
-      }
-      if (done + j + 1 >= check_from || done + j + 1 >= maxiter || ((done + j + 1) & 7) == 0) {
-        int left = 0;
-        SWCHK(read_slot(h, slot, &left));
-        if (left == 0) {
-          converged = true;
-          ++j;
-          break;
-        }
-      }
-    }
-    const int k = j;
-    {
-      LaunchScope ls(h, T_OTHER);
-      hipLaunchKernelGGL(swk::k_fg_solve, dim3(tg), dim3(tb), 0, h->stream, ws.sc, k);
-      KLAUNCH_CHECK();
-    }
-    if (k32) {
-      swk::PtrListT<cplxf> pz;
-      for (int q = 0; q < k; ++q) pz.p[q] = ws.Z32 + vec * q;
-      SWCHK(multiaxpy(h, pz, k, ws.sc.ys, 1.0, X, X, n2, nbp, nullptr));
-    } else {
-      PtrList pz;
-      for (int q = 0; q < k; ++q) pz.p[q] = ws.Z + vec * q;
-      SWCHK(multiaxpy(h, pz, k, ws.sc.ys, 1.0, X, X, n2, nbp, nullptr));
-    }
-    done += k;
-    if (converged && h->verify) {
-      // true residual of the reduced system = true residual of the full one
-      SWCHK(schur_apply(h, lv, 1, X, bp, ws.rres, nbp));
-      PtrList pr;
-      pr.p[0] = ws.rres;
-      int* slot = nullptr;
-      SWCHK(take_slot(h, &slot));
-      const swk::FgTail tv = tail_verify(ws, tol, tol_stop, slot);
-      SWCHK(multidot(h, pr, 1, ws.rres, n2, nbp, ws.nrm, nullptr, nullptr, &tv));
-      int left = 0;
-      SWCHK(read_slot(h, slot, &left));
-      if (left != 0) {
-        converged = false;
-        Rcur = ws.rres;
-        continue;
-      }
-    } else if (!converged && done < maxiter) {
-      SWCHK(schur_apply(h, lv, 1, X, bp, ws.rres, nbp));
-      Rcur = ws.rres;
-    }
-  }
-  {
-    // x_o = (b_o + H_oe x_e) / D
-    LaunchScope ls(h, T_SCHUR);
-    if (h->profiling) h->twork[T_SCHUR] += (double)a.Vh * (96.0 * nbp + 64.0);
-    hipLaunchKernelGGL((swk::k_eo_hop<1>), grid, dim3(SW_BLOCK), 0, h->stream, B, (const cplx*)X, X, a, di, di,
-                       bpc);
-    KLAUNCH_CHECK();
-  }
-  if (iters_total) *iters_total = done;
-  h->sync_hint[hid_idx][0] = converged ? done : 0;
-  return 0;
+  SWCHK(reduced_rhs(h, lv, B, ws, nbp));
+  // the iterate lives in the even half of X
+  SWCHK(fgmres_loop(h, H, 0, reduced_system(h, H, nbp), ws.xacc, X, tol, maxiter, m, true, ws, nbp,
+                    iters_total));
+  return eo_hop<1>(h, lv, B, X, X, nbp);
 }
 
 // The same solve with restart cycles in GRAM-MATRIX form (option gram_cycle, default).  A cycle of L <= m
@@ -4519,31 +4433,13 @@ static int fgmres_eo_gram(sw_engine* h, Hier& H, const cplx* B, cplx* X, double 
   Level& lv = H.lv[0];
   const int hid_idx = (int)(&H - &h->hier[0]);
   const int hint = h->lazy_sync ? h->sync_hint[hid_idx][0] : 0;
-  const int n2 = lv.n / 2;
-  const size_t vec = (size_t)n2 * nbp;
+  const KrylovSys sys = reduced_system(h, H, nbp);
   const double tol_stop = tol * h->stop_factor;
   SWCHK(ensure_level_ws(h, lv, nbp));
   SWCHK(reset_slots(h));
-  swk::StencilArgs a = eo_stencil_args(h, lv, nbp);
-  const int bpc = (a.Vh + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK;
-  const dim3 grid(bpc * (nbp / 64));
-  const double di = 1.0 / a.diag;
-  cplx* bp = ws.xacc;               // b'_e
-  {
-    // ||b|| of the FULL system fixes normb (the reference's stopping criterion); b'_e = b_e + H_eo b_o / D
-    PtrList pl;
-    pl.p[0] = B;
-    const swk::FgTail tbeg = tail_begin(ws, 1);
-    SWCHK(multidot(h, pl, 1, B, lv.n, nbp, ws.nrm, nullptr, nullptr, &tbeg));
-    LaunchScope ls(h, T_SCHUR);
-    if (h->profiling) h->twork[T_SCHUR] += (double)a.Vh * (96.0 * nbp + 64.0);
-    hipLaunchKernelGGL((swk::k_eo_hop<0>), grid, dim3(SW_BLOCK), 0, h->stream, B, B, bp, a, 1.0, di, bpc);
-    KLAUNCH_CHECK();
-  }
-  {
-    LaunchScope ls(h, T_AXPY);
-    HIPCHK(hipMemsetAsync(X, 0, vec * sizeof(cplx), h->stream));
-  }
+  SWCHK(reduced_rhs(h, lv, B, ws, nbp));
+  const cplx* bp = ws.xacc;
+  SWCHK(zero_vec(h, X, sys.n, nbp));
   std::vector<std::complex<double>> hrr(nbp), hrr0(nbp);
   int done = 0;
   bool converged = false;
@@ -4551,36 +4447,17 @@ static int fgmres_eo_gram(sw_engine* h, Hier& H, const cplx* B, cplx* X, double 
   int L = std::min(m, maxiter);
   while (done < maxiter && !converged) {
     L = std::max(1, std::min(L, std::min(m, maxiter - done)));
-    for (int j = 0; j < L; ++j) {
-      const cplx* vin = (j == 0) ? Rcur : ws.V + vec * (j - 1);
-      SWCHK(vcycle_even(h, H, vin, ws.Z + vec * j, nbp));
-      SWCHK(schur_apply(h, lv, 0, ws.Z + vec * j, nullptr, ws.V + vec * j, nbp));
-    }
     int* slot = nullptr;
     SWCHK(take_slot(h, &slot));
-    {
-      PtrList pu;
-      pu.p[0] = Rcur;
-      for (int j = 0; j < L; ++j) pu.p[j + 1] = ws.V + vec * j;
-      swk::FgTail tg{};
-      tg.kind = SW_TAIL_GRAM;
-      tg.s = ws.sc;
-      tg.j = L;
-      tg.h1 = ws.gram;
-      tg.tol = tol;
-      tg.tol_stop = tol_stop;
-      tg.iter_base = done;
-      tg.notconv = slot;
-      SWCHK(multigram(h, pu, L + 1, n2, nbp, ws.gram, &tg));
-    }
-    {
-      PtrList pz;
-      for (int q = 0; q < L; ++q) pz.p[q] = ws.Z + vec * q;
-      SWCHK(multiaxpy(h, pz, L, ws.sc.ys, 1.0, X, X, n2, nbp, nullptr));
-    }
+    swk::FgTail tg{};
+    tg.tol = tol;
+    tg.tol_stop = tol_stop;
+    tg.iter_base = done;
+    tg.notconv = slot;
+    SWCHK(gram_cycle(h, sys, Rcur, X, L, ws, nbp, tg));
     done += L;
     // the true residual: input of the next cycle and of the final check
-    SWCHK(schur_apply(h, lv, 1, X, bp, ws.rres, nbp));
+    SWCHK(sys.apply(1, X, bp, ws.rres));
     Rcur = ws.rres;
     // Observe?  Not while the previous batch's count says more than one further cycle is due.
     const bool observe = tol_stop > 0.0 && (hint <= 0 || done + m >= hint || done >= maxiter);
@@ -4611,7 +4488,7 @@ static int fgmres_eo_gram(sw_engine* h, Hier& H, const cplx* B, cplx* X, double 
       int* vslot = nullptr;
       SWCHK(take_slot(h, &vslot));
       const swk::FgTail tv = tail_verify(ws, tol, tol_stop, vslot);
-      SWCHK(multidot(h, pr, 1, ws.rres, n2, nbp, ws.nrm, nullptr, nullptr, &tv));
+      SWCHK(multidot(h, pr, 1, ws.rres, sys.n, nbp, ws.nrm, nullptr, nullptr, &tv));
       int left = 0;
       SWCHK(read_slot(h, vslot, &left));
       if (left != 0) {
@@ -4621,14 +4498,7 @@ static int fgmres_eo_gram(sw_engine* h, Hier& H, const cplx* B, cplx* X, double 
     }
     L = Lnext;
   }
-  {
-    // x_o = (b_o + H_oe x_e) / D
-    LaunchScope ls(h, T_SCHUR);
-    if (h->profiling) h->twork[T_SCHUR] += (double)a.Vh * (96.0 * nbp + 64.0);
-    hipLaunchKernelGGL((swk::k_eo_hop<1>), grid, dim3(SW_BLOCK), 0, h->stream, B, (const cplx*)X, X, a, di, di,
-                       bpc);
-    KLAUNCH_CHECK();
-  }
+  SWCHK(eo_hop<1>(h, lv, B, X, X, nbp));
   if (iters_total) *iters_total = done;
   h->sync_hint[hid_idx][0] = converged ? done : 0;
   return 0;
