@@ -259,8 +259,11 @@ struct sw_engine {
   bool precond_f32 = false;
   // deflation
   int kd = 0;
-  cplx* U = nullptr;  // [n0][kd] internal row order
-  // MLMC-level deflation vectors V_l (utils.py:260-266), [n_l][k_l] internal row order
+  cplx* U = nullptr;  // [n0][defl_ld(kd)] internal row order, zero beyond column kd
+  // deflation kernels: 0 = k_defl_dots / k_defl_apply up to kd = 64 and the MFMA kernels above it,
+  // 1 = the MFMA kernels (k_defl_gemm_*) at every kd
+  int defl_gemm = 0;
+  // MLMC-level deflation vectors V_l (utils.py:260-266), [n_l][defl_ld(k_l)] internal row order
   int lkd[SW_MAX_LEVELS] = {0};
   cplx* lV[SW_MAX_LEVELS] = {nullptr};
   // Pperm^T gathers and MLMC rhs maps (hid 0)
@@ -334,7 +337,8 @@ struct sw_engine {
   // in that level's row order, the partial sums of the block Gram kernel
   cplx* eig_buf[3] = {nullptr, nullptr, nullptr};
   signed char* eig_sign = nullptr;
-  cplx* eig_small = nullptr;     // [64*64] reduced Gram matrix / rotation
+  cplx* eig_small = nullptr;     // [w*w] reduced Gram matrix / rotation
+  int eig_w = 64;                // block width w: w/64 groups of [n][64] (sw_eig_begin_wide)
   cplx* eig_cs[2] = {nullptr, nullptr};   // sw_eig_apply_diff: two [n_{l+1}][64] coarse blocks (first use)
   int eig_hid = -1, eig_level = -1, eig_n = 0;
   void* comm = nullptr;      // RCCL communicator (sw_comm_init), one rank per engine
@@ -498,6 +502,8 @@ static int ensure_partial(sw_engine* h, size_t bytes) {
   return 0;
 }
 static inline int pad64(int nb) { return ((nb + 63) / 64) * 64; }
+// row stride of a registered deflation basis: kd rounded up to the 16-column MFMA tile
+static inline int defl_ld(int kd) { return ((kd + 15) / 16) * 16; }
 
 // ---------------------------------------------------------------------------------------------
 // launch bookkeeping (HIP-event buckets mirror CustomTimer, utils.py:366-445)
@@ -3663,6 +3669,11 @@ int sw_set_option(sw_engine* h, const char* name, double value) {
     h->use_mfma = value != 0.0;
     return 0;
   }
+  if (std::strcmp(name, "defl_gemm") == 0) {
+    if (value != 0.0 && value != 1.0) return sw_fail(h, "defl_gemm must be 0 or 1");
+    h->defl_gemm = (int)value;
+    return 0;
+  }
   if (std::strcmp(name, "bsr_map") == 0 || std::strcmp(name, "dense_map") == 0 ||
       std::strcmp(name, "bsr_sub") == 0) {
     const int v = (int)value;
@@ -3881,13 +3892,21 @@ static int eig_check(sw_engine* h, int a) {
 }
 
 int sw_eig_begin(sw_engine* h, int hid, int level, uint64_t seed) {
+  return sw_eig_begin_wide(h, hid, level, seed, 64);
+}
+
+// Blocks of `width` vectors (a multiple of 64, at most 512): width/64 groups, each an [n][64] array like
+// the buffers of width 64; the other sw_eig_* calls then act on all groups.
+int sw_eig_begin_wide(sw_engine* h, int hid, int level, uint64_t seed, int width) {
   SWCHK(check_hier(h, hid, level, true));
+  if (width < 64 || width > 512 || (width & 63)) return sw_fail(h, "block width %d: a multiple of 64 in 64..512", width);
   HIPCHK(hipSetDevice(h->device));
   Level& lv = h->hier[hid].lv[level];
   if (lv.n <= 0 || (lv.n & 3)) return sw_fail(h, "level %d has n = %d (a multiple of 4 is needed)", level, lv.n);
-  const size_t cnt = (size_t)lv.n * 64;
+  const size_t cnt = (size_t)lv.n * width;
   for (int q = 0; q < 3; ++q) SWCHK(dev_realloc(h, &h->eig_buf[q], cnt));
-  SWCHK(dev_realloc(h, &h->eig_small, (size_t)4096));
+  SWCHK(dev_realloc(h, &h->eig_small, (size_t)width * width));
+  h->eig_w = width;
   for (int q = 0; q < 2; ++q) {     // sized for the level below this one on first use of sw_eig_apply_diff
     if (h->eig_cs[q]) SWCHK(dev_free(h, h->eig_cs[q]));
     h->eig_cs[q] = nullptr;
@@ -3902,11 +3921,11 @@ int sw_eig_begin(sw_engine* h, int hid, int level, uint64_t seed) {
   h->eig_hid = hid;
   h->eig_level = level;
   h->eig_n = lv.n;
-  {
+  for (int g = 0; g < width / 64; ++g) {
     LaunchScope ls(h, T_OTHER);
     hipLaunchKernelGGL(swk::k_fill_random, dim3((lv.n + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK),
-                       dim3(SW_BLOCK), 0, h->stream, h->eig_buf[0], lv.n, 64, 64,
-                       (unsigned long long)(seed ? seed : 11));
+                       dim3(SW_BLOCK), 0, h->stream, h->eig_buf[0] + (size_t)g * lv.n * 64, lv.n, 64, 64,
+                       (unsigned long long)(seed ? seed : 11) + 0x632be59bd9b4e019ull * (unsigned long long)g);
     KLAUNCH_CHECK();
   }
   return stream_sync(h);
@@ -3927,6 +3946,7 @@ int sw_eig_end(sw_engine* h) {
     h->eig_cs[q] = nullptr;
   }
   h->eig_n = 0;
+  h->eig_w = 64;
   h->eig_hid = h->eig_level = -1;
   return 0;
 }
@@ -3935,18 +3955,22 @@ int sw_eig_end(sw_engine* h) {
 // contiguous vectors of length n), e.g. converged vectors of the level above as a start.
 int sw_eig_load(sw_engine* h, int dst, int ncols, const double* X) {
   SWCHK(eig_check(h, dst));
-  if (ncols < 1 || ncols > 64 || !X) return sw_fail(h, "bad arguments");
+  if (ncols < 1 || ncols > h->eig_w || !X) return sw_fail(h, "bad arguments");
   HIPCHK(hipSetDevice(h->device));
   Level& lv = h->hier[h->eig_hid].lv[h->eig_level];
   const int spare = dst == 2 ? 1 : 2;
-  // pack into a spare buffer (all 64 columns written, zero beyond ncols), then copy the columns over
-  SWCHK(pack_host(h, lv, ncols, X, h->eig_buf[spare], 64));
-  HIPCHK(hipMemcpy2DAsync(h->eig_buf[dst], 64 * sizeof(cplx), h->eig_buf[spare], 64 * sizeof(cplx),
-                          (size_t)ncols * sizeof(cplx), (size_t)lv.n, hipMemcpyDeviceToDevice, h->stream));
+  const size_t gs = (size_t)lv.n * 64;
+  // per group: pack into a spare buffer (all 64 columns written, zero beyond ncols), then copy the columns over
+  for (int g = 0; g * 64 < ncols; ++g) {
+    const int nc = std::min(64, ncols - g * 64);
+    SWCHK(pack_host(h, lv, nc, X + (size_t)g * 64 * lv.n * 2, h->eig_buf[spare], 64));
+    HIPCHK(hipMemcpy2DAsync(h->eig_buf[dst] + g * gs, 64 * sizeof(cplx), h->eig_buf[spare], 64 * sizeof(cplx),
+                            (size_t)nc * sizeof(cplx), (size_t)lv.n, hipMemcpyDeviceToDevice, h->stream));
+  }
   return stream_sync(h);
 }
 
-// dst = Op^-1 src on all 64 columns: mode 0 Op = A_level (multigrid.py:174), mode 1 Op = gamma_3 A_level
+// dst = Op^-1 src on all columns (one batched solve of 64 per group): mode 0 Op = A_level (multigrid.py:174), mode 1 Op = gamma_3 A_level
 // (utils.py:137-140; Q^-1 = A^-1 gamma_3).  Batched solve of the (hierarchy, level) to `tol`.
 int sw_eig_solve(sw_engine* h, int src, int dst, int mode, double tol, int maxiter, int32_t* iters_max) {
   SWCHK(eig_check(h, src));
@@ -3956,23 +3980,28 @@ int sw_eig_solve(sw_engine* h, int src, int dst, int mode, double tol, int maxit
   HIPCHK(hipSetDevice(h->device));
   Hier& H = h->hier[h->eig_hid];
   Level& lv = H.lv[h->eig_level];
-  const cplx* rhs = h->eig_buf[src];
-  if (mode == 1) {
-    cplx* tmp = h->eig_buf[3 - src - dst];
-    LaunchScope ls(h, T_OTHER);
-    hipLaunchKernelGGL(swk::k_row_sign, dim3((lv.n + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK, 1),
-                       dim3(SW_BLOCK), 0, h->stream, rhs, (const signed char*)h->eig_sign, tmp, lv.n, 64);
-    KLAUNCH_CHECK();
-    rhs = tmp;
+  const size_t gs = (size_t)lv.n * 64;
+  int worst = 0;
+  for (int g = 0; g < h->eig_w / 64; ++g) {
+    const cplx* rhs = h->eig_buf[src] + g * gs;
+    if (mode == 1) {
+      cplx* tmp = h->eig_buf[3 - src - dst] + g * gs;
+      LaunchScope ls(h, T_OTHER);
+      hipLaunchKernelGGL(swk::k_row_sign, dim3((lv.n + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK, 1),
+                         dim3(SW_BLOCK), 0, h->stream, rhs, (const signed char*)h->eig_sign, tmp, lv.n, 64);
+      KLAUNCH_CHECK();
+      rhs = tmp;
+    }
+    int total = 0;
+    SWCHK(solve_dev(h, h->eig_hid, h->eig_level, rhs, h->eig_buf[dst] + g * gs, tol, maxiter, 64, &total));
+    SWCHK(stream_sync(h));
+    worst = std::max(worst, total);
   }
-  int total = 0;
-  SWCHK(solve_dev(h, h->eig_hid, h->eig_level, rhs, h->eig_buf[dst], tol, maxiter, 64, &total));
-  SWCHK(stream_sync(h));
-  if (iters_max) *iters_max = total;
+  if (iters_max) *iters_max = worst;
   return 0;
 }
 
-// dst = (A_l^-1 - P A_c^-1 R) Gamma src on all 64 columns, l = the level of sw_eig_begin on hierarchy 0:
+// dst = (A_l^-1 - P A_c^-1 R) Gamma src on all columns (64 per pass), l = the level of sw_eig_begin on hierarchy 0:
 // the MLMC difference operator of utils.py:141-143 / multigrid.py:461-549, built exactly as the probe body
 // of sw_hutch_run builds it (fine solve on the solver hierarchy at level 0 when it is ready, R / P of
 // hierarchy 0, coarse solve on hierarchy 0, direct or dense at the coarsest level).  Gamma = gamma_3 (g3 = 1)
@@ -4003,50 +4032,79 @@ int sw_eig_apply_diff(sw_engine* h, int src, int dst, int skip, int g3, double t
   // two coarse blocks of the level below (with skip the level two below is smaller and fits in them)
   for (int q = 0; q < 2; ++q)
     if (!h->eig_cs[q]) SWCHK(dev_realloc(h, &h->eig_cs[q], (size_t)n1 * 64));
-  cplx* ca = h->eig_cs[0];
-  cplx* cb = h->eig_cs[1];
-  cplx* t = h->eig_buf[3 - src - dst];
-  // x = Gamma src (in dst: it is overwritten last)
-  const cplx* x = h->eig_buf[src];
-  if (g3) {
-    LaunchScope ls(h, T_OTHER);
-    hipLaunchKernelGGL(swk::k_row_sign, dim3((n + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK, 1),
-                       dim3(SW_BLOCK), 0, h->stream, x, (const signed char*)h->eig_sign, h->eig_buf[dst], n, 64);
-    KLAUNCH_CHECK();
-    x = h->eig_buf[dst];
+  int worst = 0;
+  for (int g = 0; g < h->eig_w / 64; ++g) {
+    cplx* ca = h->eig_cs[0];
+    cplx* cb = h->eig_cs[1];
+    const size_t go = (size_t)g * n * 64;   // this group of 64 columns
+    cplx* t = h->eig_buf[3 - src - dst] + go;
+    cplx* d = h->eig_buf[dst] + go;
+    // x = Gamma src (in dst: it is overwritten last)
+    const cplx* x = h->eig_buf[src] + go;
+    if (g3) {
+      LaunchScope ls(h, T_OTHER);
+      hipLaunchKernelGGL(swk::k_row_sign, dim3((n + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK, 1),
+                         dim3(SW_BLOCK), 0, h->stream, x, (const signed char*)h->eig_sign, d, n, 64);
+      KLAUNCH_CHECK();
+      x = d;
+    }
+    // xc = R x (skip: R_1 R_0 x)
+    SWCHK(launch_ell(h, lv.R, 0, x, nullptr, ca, 64, T_R));
+    const cplx* xc = ca;
+    cplx* y = cb;
+    if (skip) {
+      SWCHK(launch_ell(h, H0.lv[1].R, 0, ca, nullptr, cb, 64, T_R));
+      xc = cb;
+      y = ca;
+    }
+    // t = A_l^-1 x
+    int total_f = 0, total_c = 0;
+    SWCHK(solve_dev(h, fine_hid, level, x, t, tol, maxiter, 64, &total_f));
+    // y = A_c^-1 xc
+    SWCHK(solve_dev(h, 0, lcoarse, xc, y, tol, maxiter, 64, &total_c));
+    // dst = t - P y (skip: t - P_0 P_1 y)
+    if (skip) {
+      SWCHK(launch_ell(h, H0.lv[1].P, 0, y, nullptr, cb, 64, T_P));
+      y = cb;
+    }
+    SWCHK(launch_ell(h, lv.P, 1, y, t, d, 64, T_P));
+    SWCHK(stream_sync(h));
+    worst = std::max(worst, total_f);
   }
-  // xc = R x (skip: R_1 R_0 x)
-  SWCHK(launch_ell(h, lv.R, 0, x, nullptr, ca, 64, T_R));
-  const cplx* xc = ca;
-  cplx* y = cb;
-  if (skip) {
-    SWCHK(launch_ell(h, H0.lv[1].R, 0, ca, nullptr, cb, 64, T_R));
-    xc = cb;
-    y = ca;
-  }
-  // t = A_l^-1 x
-  int total_f = 0, total_c = 0;
-  SWCHK(solve_dev(h, fine_hid, level, x, t, tol, maxiter, 64, &total_f));
-  // y = A_c^-1 xc
-  SWCHK(solve_dev(h, 0, lcoarse, xc, y, tol, maxiter, 64, &total_c));
-  // dst = t - P y (skip: t - P_0 P_1 y)
-  if (skip) {
-    SWCHK(launch_ell(h, H0.lv[1].P, 0, y, nullptr, cb, 64, T_P));
-    y = cb;
-  }
-  SWCHK(launch_ell(h, lv.P, 1, y, t, h->eig_buf[dst], 64, T_P));
-  SWCHK(stream_sync(h));
-  if (iters_max) *iters_max = total_f;
+  if (iters_max) *iters_max = worst;
   return 0;
 }
 
-// out[64*64] (row-major complex128) = buf_a^H buf_b
+// out[w*w] (row-major complex128) = buf_a^H buf_b, w = the block width (64: k_block_gram)
 int sw_eig_gram(sw_engine* h, int a, int b, double* out) {
   SWCHK(eig_check(h, a));
   SWCHK(eig_check(h, b));
   if (!out) return sw_fail(h, "bad arguments");
   HIPCHK(hipSetDevice(h->device));
   const int n = h->eig_n;
+  const int w = h->eig_w;
+  if (w > 64) {
+    // ~1024 workgroups over (row slice, group pair), 8..256 slices of at least 64 rows
+    const int ng = w / 64;
+    const int pw = std::max(8, std::min(256, 1024 / (ng * ng)));
+    const int rpbw = std::max(64, (n + pw - 1) / pw);
+    const int Pw = (n + rpbw - 1) / rpbw;
+    SWCHK(ensure_partial(h, (size_t)Pw * w * w * sizeof(cplx)));
+    {
+      LaunchScope ls(h, T_DOTS);
+      hipLaunchKernelGGL(swk::k_block_gram_wide, dim3(Pw, ng, ng), dim3(SW_BLOCK), 0, h->stream,
+                         (const cplx*)h->eig_buf[a], (const cplx*)h->eig_buf[b], n, rpbw, w, h->partial);
+      KLAUNCH_CHECK();
+    }
+    {
+      LaunchScope ls(h, T_DOTS);
+      hipLaunchKernelGGL(swk::k_reduce_partials, dim3(w, ng), dim3(SW_BLOCK), 0, h->stream,
+                         (const cplx*)h->partial, Pw, w, w, h->eig_small, (const cplx*)nullptr, (cplx*)nullptr);
+      KLAUNCH_CHECK();
+    }
+    HIPCHK(hipMemcpyAsync(out, h->eig_small, (size_t)w * w * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
+    return stream_sync(h);
+  }
   int rpb = std::max(64, ((n + 255) / 256 + 3) & ~3);     // ~256 row blocks, multiples of 4 rows
   const int P = (n + rpb - 1) / rpb;
   SWCHK(ensure_partial(h, (size_t)P * 4096 * sizeof(cplx)));
@@ -4066,13 +4124,25 @@ int sw_eig_gram(sw_engine* h, int a, int b, double* out) {
   return stream_sync(h);
 }
 
-// buf_dst = buf_src Y (sub < 0) or buf_dst = buf_sub - buf_src Y, Y[64*64] row-major complex128 (dst != src)
+// buf_dst = buf_src Y (sub < 0) or buf_dst = buf_sub - buf_src Y, Y[w*w] row-major complex128 (dst != src)
 int sw_eig_rotate(sw_engine* h, int src, const double* Y, int dst, int sub) {
   SWCHK(eig_check(h, src));
   SWCHK(eig_check(h, dst));
   if (sub >= 0) SWCHK(eig_check(h, sub));
   if (src == dst || !Y) return sw_fail(h, "bad arguments");
   HIPCHK(hipSetDevice(h->device));
+  const int w = h->eig_w;
+  if (w > 64) {
+    HIPCHK(hipMemcpyAsync(h->eig_small, Y, (size_t)w * w * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
+    {
+      LaunchScope ls(h, T_AXPY);
+      hipLaunchKernelGGL(swk::k_block_rotate_wide, dim3((h->eig_n + 63) / 64, w / 64), dim3(SW_BLOCK), 0,
+                         h->stream, (const cplx*)h->eig_buf[src], (const cplx*)h->eig_small,
+                         (const cplx*)(sub >= 0 ? h->eig_buf[sub] : nullptr), h->eig_buf[dst], h->eig_n, w);
+      KLAUNCH_CHECK();
+    }
+    return stream_sync(h);
+  }
   HIPCHK(hipMemcpyAsync(h->eig_small, Y, 4096 * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
   {
     LaunchScope ls(h, T_AXPY);
@@ -4087,10 +4157,13 @@ int sw_eig_rotate(sw_engine* h, int src, const double* Y, int dst, int sub) {
 // The first k columns of buf_src as k host vectors of length n in the reference order.
 int sw_eig_fetch(sw_engine* h, int src, int k, double* out) {
   SWCHK(eig_check(h, src));
-  if (k < 1 || k > 64 || !out) return sw_fail(h, "bad arguments");
+  if (k < 1 || k > h->eig_w || !out) return sw_fail(h, "bad arguments");
   HIPCHK(hipSetDevice(h->device));
   Level& lv = h->hier[h->eig_hid].lv[h->eig_level];
-  return unpack_host(h, lv, k, h->eig_buf[src], out, 64);
+  for (int g = 0; g * 64 < k; ++g)
+    SWCHK(unpack_host(h, lv, std::min(64, k - g * 64), h->eig_buf[src] + (size_t)g * lv.n * 64,
+                      out + (size_t)g * 64 * lv.n * 2, 64));
+  return 0;
 }
 
 // Current value of an engine switch (the counterpart of sw_set_option: what a caller saves before an A/B run
@@ -4100,7 +4173,7 @@ int sw_get_option(sw_engine* h, const char* name, double* value) {
   if (!h || !name || !value) return 1;
   struct Ent { const char* name; double v; };
   const Ent tab[] = {
-      {"use_mfma", (double)h->use_mfma}, {"bsr_map", (double)h->bsr_map}, {"dense_map", (double)h->dense_map},
+      {"use_mfma", (double)h->use_mfma}, {"defl_gemm", (double)h->defl_gemm}, {"bsr_map", (double)h->bsr_map}, {"dense_map", (double)h->dense_map},
       {"bsr_sub", (double)h->bsr_sub}, {"bsr_stages", (double)h->bsr_stages},
       {"dense_stages", (double)h->dense_stages}, {"bsr_nt", (double)h->bsr_nt}, {"bsr_xreg", (double)h->bsr_xreg},
       {"p_even", (double)h->p_even}, {"ell_order", (double)h->ell_order}, {"bench_what", (double)h->bench_what},
@@ -4141,10 +4214,11 @@ int sw_set_deflation(sw_engine* h, int k, const double* U) {
   if (!U) return sw_fail(h, "null deflation vectors");
   if (lv.n <= 0) return sw_fail(h, "level 0 undefined");
   const std::complex<double>* Uh = (const std::complex<double>*)U;
-  std::vector<std::complex<double>> Ui((size_t)lv.n * k);
+  const int ld = defl_ld(k);
+  std::vector<std::complex<double>> Ui((size_t)lv.n * ld);
   for (int i = 0; i < lv.n; ++i) {
     const int r = lv.h_rowmap.empty() ? i : lv.h_rowmap[i];
-    for (int q = 0; q < k; ++q) Ui[(size_t)r * k + q] = Uh[(size_t)i * k + q];
+    for (int q = 0; q < k; ++q) Ui[(size_t)r * ld + q] = Uh[(size_t)i * k + q];
   }
   SWCHK(upload(h, (std::complex<double>**)&h->U, Ui.data(), Ui.size()));
   h->kd = k;
@@ -4161,10 +4235,11 @@ int sw_set_level_deflation(sw_engine* h, int level, int k, const double* V) {
   if (!V) return sw_fail(h, "null deflation vectors");
   if (lv.n <= 0) return sw_fail(h, "level %d undefined", level);
   const std::complex<double>* Vh = (const std::complex<double>*)V;
-  std::vector<std::complex<double>> Vi((size_t)lv.n * k);
+  const int ld = defl_ld(k);
+  std::vector<std::complex<double>> Vi((size_t)lv.n * ld);
   for (int i = 0; i < lv.n; ++i) {
     const int r = lv.h_rowmap.empty() ? i : lv.h_rowmap[i];
-    for (int q = 0; q < k; ++q) Vi[(size_t)r * k + q] = Vh[(size_t)i * k + q];
+    for (int q = 0; q < k; ++q) Vi[(size_t)r * ld + q] = Vh[(size_t)i * k + q];
   }
   SWCHK(upload(h, (std::complex<double>**)&h->lV[level], Vi.data(), Vi.size()));
   h->lkd[level] = k;
@@ -4828,11 +4903,51 @@ static int record_iters(sw_engine* h, KrylovWS* ws, int total_or_const, std::vec
 }
 
 // out[r] = X[s] - sum_k U[s][k] (U^H X)[k],  s = srcrow[r] (NULL: identity)   (utils.py:221-225)
+// U is [n][defl_ld(kd)].  Up to kd = 64 (and defl_gemm = 0): k_defl_dots in chunks of 32 vectors, then
+// k_defl_apply; above, or with defl_gemm = 1: the matrix-core pair k_defl_gemm_dots / k_defl_gemm_apply,
+// which read the probe block once for all kd vectors.
 static int deflate(sw_engine* h, const cplx* U, int kd, const int* srcrow, const cplx* X, cplx* out,
                    int n, int nbp) {
+  const int ld = defl_ld(kd);
+  cplx* cbuf = h->small + 8 * nbp;  // [ld][nbp], ld <= SW_MAX_DEFL
+  if (h->defl_gemm || kd > 64) {
+    // ~2048 workgroups of 16 probes, at least 64 rows per slice
+    const int nchunks = nbp / 16;
+    const int pmax = std::max(1, (n + 63) / 64);
+    int P = std::max(1, std::min(pmax, 2048 / nchunks));
+    const int rpb = (n + P - 1) / P;
+    P = (n + rpb - 1) / rpb;
+    SWCHK(ensure_partial(h, (size_t)P * ld * nbp * sizeof(cplx)));
+    {
+      LaunchScope ls(h, T_DEFL);
+      dim3 grid(P, nchunks);
+      if (ld <= 64)
+        hipLaunchKernelGGL((swk::k_defl_gemm_dots<1>), grid, dim3(SW_BLOCK), 0, h->stream, U, ld, X, n,
+                           nbp, rpb, h->partial);
+      else if (ld <= 128)
+        hipLaunchKernelGGL((swk::k_defl_gemm_dots<2>), grid, dim3(SW_BLOCK), 0, h->stream, U, ld, X, n,
+                           nbp, rpb, h->partial);
+      else
+        hipLaunchKernelGGL((swk::k_defl_gemm_dots<4>), grid, dim3(SW_BLOCK), 0, h->stream, U, ld, X, n,
+                           nbp, rpb, h->partial);
+      KLAUNCH_CHECK();
+    }
+    {
+      LaunchScope ls(h, T_DEFL);
+      hipLaunchKernelGGL(swk::k_reduce_partials, dim3(ld, nbp / 64), dim3(SW_BLOCK), 0, h->stream,
+                         h->partial, P, ld, nbp, cbuf, (const cplx*)nullptr, (cplx*)nullptr);
+      KLAUNCH_CHECK();
+    }
+    {
+      LaunchScope ls(h, T_DEFL);
+      hipLaunchKernelGGL(swk::k_defl_gemm_apply, dim3((n + 63) / 64, nbp / 64), dim3(SW_BLOCK), 0, h->stream,
+                         U, ld, (const cplx*)cbuf, srcrow, X, out, n, nbp);
+      KLAUNCH_CHECK();
+    }
+    return 0;
+  }
   int P, rpb;
   row_blocking(n, nbp, true, &P, &rpb);
-  cplx* cbuf = h->small + 8 * nbp;  // [kd][nbp], kd <= SW_MAX_DEFL
   for (int k0 = 0; k0 < kd; k0 += 32) {
     const int kc = std::min(32, kd - k0);
     SWCHK(ensure_partial(h, (size_t)P * kc * nbp * sizeof(cplx)));
@@ -4841,13 +4956,13 @@ static int deflate(sw_engine* h, const cplx* U, int kd, const int* srcrow, const
       dim3 grid(P, nbp / 64);
       if (kc <= 8)
         hipLaunchKernelGGL((swk::k_defl_dots<8>), grid, dim3(SW_BLOCK), 0, h->stream,
-                           (const cplx*)(U + k0), kd, kc, X, n, nbp, rpb, h->partial);
+                           (const cplx*)(U + k0), ld, kc, X, n, nbp, rpb, h->partial);
       else if (kc <= 16)
         hipLaunchKernelGGL((swk::k_defl_dots<16>), grid, dim3(SW_BLOCK), 0, h->stream,
-                           (const cplx*)(U + k0), kd, kc, X, n, nbp, rpb, h->partial);
+                           (const cplx*)(U + k0), ld, kc, X, n, nbp, rpb, h->partial);
       else
         hipLaunchKernelGGL((swk::k_defl_dots<32>), grid, dim3(SW_BLOCK), 0, h->stream,
-                           (const cplx*)(U + k0), kd, kc, X, n, nbp, rpb, h->partial);
+                           (const cplx*)(U + k0), ld, kc, X, n, nbp, rpb, h->partial);
       KLAUNCH_CHECK();
     }
     {
@@ -4861,11 +4976,34 @@ static int deflate(sw_engine* h, const cplx* U, int kd, const int* srcrow, const
   {
     LaunchScope ls(h, T_DEFL);
     dim3 grid((n + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK, nbp / 64);
-    hipLaunchKernelGGL(swk::k_defl_apply, grid, dim3(SW_BLOCK), 0, h->stream, U, kd, cbuf, srcrow, X,
+    hipLaunchKernelGGL(swk::k_defl_apply, grid, dim3(SW_BLOCK), 0, h->stream, U, ld, kd, cbuf, srcrow, X,
                        out, n, nbp);
     KLAUNCH_CHECK();
   }
   return 0;
+}
+
+// Y = the registered deflation projection of the host vectors X (reference order, nb contiguous vectors):
+// which = 0: Pperm^T (I - U U^H) X at level 0 (Hutchinson, sw_set_deflation / sw_set_perm), which = 1:
+// (I - V_l V_l^H) X at `level` (sw_set_level_deflation).  The kernels and the launch sequence of
+// sw_hutch_run's deflation step.
+int sw_apply_deflation(sw_engine* h, int which, int level, int nb, const double* X, double* Y) {
+  SWCHK(check_hier(h, 0, level, false));
+  if (which != 0 && which != 1) return sw_fail(h, "which must be 0 (Hutchinson) or 1 (MLMC level)");
+  if (which == 0 && level != 0) return sw_fail(h, "the Hutchinson deflation acts at level 0");
+  if (nb <= 0 || !X || !Y) return sw_fail(h, "bad arguments");
+  const int kd = which == 0 ? h->kd : h->lkd[level];
+  const cplx* U = which == 0 ? h->U : h->lV[level];
+  if (kd <= 0 || !U) return sw_fail(h, "no deflation vectors registered at level %d", level);
+  HIPCHK(hipSetDevice(h->device));
+  Level& lv = h->hier[0].lv[level];
+  const int nbp = pad64(nb);
+  cplx *a, *b;
+  SWCHK(io_vectors(h, lv, nbp, &a, &b));
+  SWCHK(ensure_small(h, nbp));
+  SWCHK(pack_host(h, lv, nb, X, a, nbp));
+  SWCHK(deflate(h, U, kd, which == 0 ? (const int*)h->perm_src[0] : nullptr, a, b, lv.n, nbp));
+  return unpack_host(h, lv, nb, b, Y, nbp);
 }
 
 int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {

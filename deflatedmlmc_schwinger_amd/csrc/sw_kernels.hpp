@@ -2727,7 +2727,7 @@ __global__ __launch_bounds__(SW_BLOCK) void k_defl_dots(const cplx* __restrict__
   }
 }
 
-__global__ __launch_bounds__(SW_BLOCK) void k_defl_apply(const cplx* __restrict__ U, int kd,
+__global__ __launch_bounds__(SW_BLOCK) void k_defl_apply(const cplx* __restrict__ U, int ldu, int kd,
                                                          const cplx* __restrict__ c,
                                                          const int* __restrict__ srcrow,
                                                          const cplx* __restrict__ X,
@@ -2738,13 +2738,123 @@ __global__ __launch_bounds__(SW_BLOCK) void k_defl_apply(const cplx* __restrict_
   if (r >= n) return;
   const int s = srcrow ? srcrow[r] : r;
   cplx x = X[(size_t)s * nbp + col];
-  const cplx* u = U + (size_t)s * kd;
+  const cplx* u = U + (size_t)s * ldu;
 #pragma unroll 4
   for (int k = 0; k < kd; ++k) {
     const cplx ck = c[(size_t)k * nbp + col];
     cfma(x, cmake(-u[k].x, -u[k].y), ck);
   }
   out[(size_t)r * nbp + col] = x;
+}
+
+// ------------------------------------------------------------------------------------------
+// Deflation on the fp64 matrix cores (kd > 64, or option defl_gemm): the same two products as
+// k_defl_dots / k_defl_apply, as tall-skinny GEMMs on v_mfma_f64_16x16x4_f64 (operand layout as
+// k_block_gram: lane l holds A[l&15][l>>4], B[l>>4][l&15], D[(l>>4)+4r][l&15]).  U is [n][ldu] with
+// ldu = kd rounded up to a multiple of 16, the padding columns zero, so C = U^H X has ldu rows of
+// which the last ldu - kd are zero.
+//   k_defl_gemm_dots:  partial[(p*ldu + i)*nbp + j] = sum_{rows of slice p} conj(U[row][i]) X[row][j].
+//     grid = (P, nbp/16), block = 4 waves on the same 16 probes; wave w owns the C rows
+//     [64 KT w, 64 KT (w+1)) (KT tiles of 16), so one block covers every C row of its probes and each
+//     probe element is read once per launch.  Then k_reduce_partials(P, K = ldu).
+//   k_defl_gemm_apply: out[r][j] = X[s][j] - sum_k U[s][k] C[k][j], s = srcrow[r] (NULL: r), the fused
+//     Pperm^T gather of k_defl_apply.  grid = (ceil(n/64), nbp/64), wave = 16 rows x 64 probes with
+//     U rows as the A operand; C goes through LDS SW_DG_KC rows at a time (all of C is 1 MiB at
+//     kd = nbp = 256).
+// Four real products per complex product; accumulators stay in registers (2 KT or 8 sw_double4).
+// ------------------------------------------------------------------------------------------
+template <int KT>
+__global__ __launch_bounds__(SW_BLOCK) void k_defl_gemm_dots(const cplx* __restrict__ U, int ldu,
+                                                             const cplx* __restrict__ X, int n, int nbp,
+                                                             int rows_per_block,
+                                                             cplx* __restrict__ partial) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int k = lane >> 4, c = lane & 15;
+  const int t0 = wave * KT;                       // first 16-column tile of U for this wave
+  const int nt = min(KT, ldu / 16 - t0);          // tiles of this wave inside [0, ldu)
+  if (nt <= 0) return;
+  const int r0 = blockIdx.x * rows_per_block;
+  const int r1 = min(n, r0 + rows_per_block);
+  const size_t j = (size_t)blockIdx.y * 16 + c;
+  sw_double4 cr[KT], ci[KT];
+#pragma unroll
+  for (int t = 0; t < KT; ++t) cr[t] = ci[t] = sw_double4{0.0, 0.0, 0.0, 0.0};
+  for (int row = r0 + k; row < r1 + k; row += 4) {
+    const bool in = row < r1;
+    const cplx x = in ? X[(size_t)row * nbp + j] : cmake(0.0, 0.0);
+    const cplx* up = U + (size_t)row * ldu + t0 * 16 + c;
+#pragma unroll
+    for (int t = 0; t < KT; ++t) {
+      if (t < nt) {
+        const cplx u = in ? up[t * 16] : cmake(0.0, 0.0);
+        // conj(u) x = (ur xr + ui xi) + i (ur xi - ui xr)
+        cr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(u.x, x.x, cr[t], 0, 0, 0);
+        cr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(u.y, x.y, cr[t], 0, 0, 0);
+        ci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(u.x, x.y, ci[t], 0, 0, 0);
+        ci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(-u.y, x.x, ci[t], 0, 0, 0);
+      }
+    }
+  }
+  cplx* out = partial + (size_t)blockIdx.x * ldu * nbp + j;
+#pragma unroll
+  for (int t = 0; t < KT; ++t) {
+    if (t < nt) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        out[(size_t)((t0 + t) * 16 + k + 4 * r) * nbp] = cmake(cr[t][r], ci[t][r]);
+    }
+  }
+}
+
+#define SW_DG_KC 32
+__global__ __launch_bounds__(SW_BLOCK) void k_defl_gemm_apply(const cplx* __restrict__ U, int ldu,
+                                                              const cplx* __restrict__ C,
+                                                              const int* __restrict__ srcrow,
+                                                              const cplx* __restrict__ X,
+                                                              cplx* __restrict__ out, int n, int nbp) {
+  __shared__ cplx Cs[SW_DG_KC][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int k = lane >> 4, c = lane & 15;
+  const int rb = blockIdx.x * 64 + wave * 16;     // first row of this wave's tile
+  const size_t j0 = (size_t)blockIdx.y * 64;
+  // A operand: row rb + c of the output, i.e. row s(rb + c) of U
+  const int ra = rb + c;
+  const cplx* up = nullptr;
+  if (ra < n) up = U + (size_t)(srcrow ? srcrow[ra] : ra) * ldu + k;
+  sw_double4 re[4], im[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) re[t] = im[t] = sw_double4{0.0, 0.0, 0.0, 0.0};
+  for (int k0 = 0; k0 < ldu; k0 += SW_DG_KC) {
+    const int kc = min(SW_DG_KC, ldu - k0);       // a multiple of 16
+    __syncthreads();
+    for (int e = threadIdx.x; e < kc * 64; e += SW_BLOCK)
+      Cs[e >> 6][e & 63] = C[(size_t)(k0 + (e >> 6)) * nbp + j0 + (e & 63)];
+    __syncthreads();
+    for (int kk = 0; kk < kc; kk += 4) {
+      const cplx u = up ? up[k0 + kk] : cmake(0.0, 0.0);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const cplx b = Cs[kk + k][t * 16 + c];
+        // u b = (ur br - ui bi) + i (ur bi + ui br)
+        re[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(u.x, b.x, re[t], 0, 0, 0);
+        re[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(-u.y, b.y, re[t], 0, 0, 0);
+        im[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(u.x, b.y, im[t], 0, 0, 0);
+        im[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(u.y, b.x, im[t], 0, 0, 0);
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = rb + k + 4 * r;
+    if (row >= n) continue;
+    const size_t s = (size_t)(srcrow ? srcrow[row] : row);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const size_t j = j0 + t * 16 + c;
+      const cplx x = X[s * nbp + j];
+      out[(size_t)row * nbp + j] = cmake(x.x - re[t][r], x.y - im[t][r]);
+    }
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3057,6 +3167,100 @@ __global__ __launch_bounds__(SW_BLOCK) void k_block_rotate(const cplx* __restric
     // Cm given: out = Cm - W Y (the block residual W - V T of the Rayleigh-Ritz step)
     out[(size_t)row * 64 + lane] = Cm ? csub(Cm[(size_t)row * 64 + lane], acc) : acc;
     __syncthreads();
+  }
+}
+
+// Blocks wider than 64 vectors (sw_eig_begin_wide): a block of width W is W/64 groups, group g an [n][64]
+// array at offset g*n*64 (column g*64 + c of the block = column c of group g).
+//   k_block_gram_wide:   partial[(p*W + i)*W + j] = sum_{rows of slice p} conj(V[row][i]) Wm[row][j];
+//                        grid = (P, W/64, W/64) = (row slice, V group, Wm group), wave = one 16-column
+//                        tile of the V group against the four tiles of the Wm group (8 accumulators);
+//                        k_reduce_partials(K = W, nbp = W) adds the slices in a fixed order.
+//   k_block_rotate_wide: out_g = sum_h Wm_h Y[h][g]  or  Cm_g - that,  Y[W][W] row-major;
+//                        grid = (ceil(n/64), W/64), wave = 16 rows x the 64 columns of group g, Y passes
+//                        through LDS SW_DG_KC rows of one 64x64 block at a time (all of Y is 4 MiB at W = 512).
+// Operand layout as k_block_gram (four real products per complex product).
+__global__ __launch_bounds__(SW_BLOCK) void k_block_gram_wide(const cplx* __restrict__ V,
+                                                              const cplx* __restrict__ Wm, int n,
+                                                              int rows_per_block, int width,
+                                                              cplx* __restrict__ partial) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int k = lane >> 4, c = lane & 15;
+  const size_t gs = (size_t)n * 64;
+  const cplx* vp = V + blockIdx.y * gs + wave * 16 + c;
+  const cplx* wp = Wm + blockIdx.z * gs + c;
+  const int r0 = blockIdx.x * rows_per_block;
+  const int r1 = min(n, r0 + rows_per_block);
+  sw_double4 cr[4], ci[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) cr[t] = ci[t] = sw_double4{0.0, 0.0, 0.0, 0.0};
+  for (int row = r0 + k; row < r1 + k; row += 4) {
+    const bool in = row < r1;
+    const cplx v = in ? vp[(size_t)row * 64] : cmake(0.0, 0.0);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const cplx w = in ? wp[(size_t)row * 64 + t * 16] : cmake(0.0, 0.0);
+      cr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(v.x, w.x, cr[t], 0, 0, 0);
+      cr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(v.y, w.y, cr[t], 0, 0, 0);
+      ci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(v.x, w.y, ci[t], 0, 0, 0);
+      ci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(-v.y, w.x, ci[t], 0, 0, 0);
+    }
+  }
+  cplx* out = partial + (size_t)blockIdx.x * width * width;
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      out[(size_t)(blockIdx.y * 64 + wave * 16 + k + 4 * r) * width + blockIdx.z * 64 + t * 16 + c] =
+          cmake(cr[t][r], ci[t][r]);
+}
+
+__global__ __launch_bounds__(SW_BLOCK) void k_block_rotate_wide(const cplx* __restrict__ Wm,
+                                                                const cplx* __restrict__ Y,
+                                                                const cplx* Cm, cplx* out, int n,
+                                                                int width) {
+  __shared__ cplx Ys[SW_DG_KC][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int k = lane >> 4, c = lane & 15;
+  const int g = blockIdx.y;
+  const size_t gs = (size_t)n * 64;
+  const int rb = blockIdx.x * 64 + wave * 16;     // first row of this wave's tile
+  const int ra = rb + c;                          // A-operand row of this lane
+  sw_double4 re[4], im[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) re[t] = im[t] = sw_double4{0.0, 0.0, 0.0, 0.0};
+  for (int hg = 0; hg < width / 64; ++hg) {
+    const cplx* wp = ra < n ? Wm + hg * gs + (size_t)ra * 64 + k : nullptr;
+    for (int k0 = 0; k0 < 64; k0 += SW_DG_KC) {
+      __syncthreads();
+      for (int e = threadIdx.x; e < SW_DG_KC * 64; e += SW_BLOCK)
+        Ys[e >> 6][e & 63] = Y[(size_t)(hg * 64 + k0 + (e >> 6)) * width + g * 64 + (e & 63)];
+      __syncthreads();
+#pragma unroll 2
+      for (int kk = 0; kk < SW_DG_KC; kk += 4) {
+        const cplx u = wp ? wp[k0 + kk] : cmake(0.0, 0.0);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const cplx b = Ys[kk + k][t * 16 + c];
+          re[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(u.x, b.x, re[t], 0, 0, 0);
+          re[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(-u.y, b.y, re[t], 0, 0, 0);
+          im[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(u.x, b.y, im[t], 0, 0, 0);
+          im[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(u.y, b.x, im[t], 0, 0, 0);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = rb + k + 4 * r;
+    if (row >= n) continue;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const size_t o = g * gs + (size_t)row * 64 + t * 16 + c;
+      const cplx acc = cmake(re[t][r], im[t][r]);
+      // Cm given: out = Cm - W Y (the block residual W - V T of the Rayleigh-Ritz step)
+      out[o] = Cm ? csub(Cm[o], acc) : acc;
+    }
   }
 }
 

@@ -102,6 +102,7 @@ def load_library():
     sig("sw_pool_trim", i32)
     sig("sw_get_coarsest_inv", i32, vp, i32, vp)
     sig("sw_eig_begin", i32, vp, i32, i32, C.c_uint64)
+    sig("sw_eig_begin_wide", i32, vp, i32, i32, C.c_uint64, i32)
     sig("sw_eig_load", i32, vp, i32, i32, vp)
     sig("sw_eig_solve", i32, vp, i32, i32, i32, dbl, i32, P(i32))
     sig("sw_eig_apply_diff", i32, vp, i32, i32, i32, i32, dbl, i32, P(i32))
@@ -113,6 +114,7 @@ def load_library():
     sig("sw_restrict", i32, vp, i32, i32, i32, vp, vp)
     sig("sw_prolong", i32, vp, i32, i32, i32, vp, vp)
     sig("sw_coarsest", i32, vp, i32, i32, vp, vp)
+    sig("sw_apply_deflation", i32, vp, i32, i32, i32, vp, vp)
     sig("sw_vcycle", i32, vp, i32, i32, i32, vp, vp)
     sig("sw_solve", i32, vp, i32, i32, i32, vp, vp, dbl, i32, vp, vp)
     sig("sw_hutch_batch", i32, vp, i32, i32, i32, vp, dbl, i32, vp, vp)
@@ -158,8 +160,8 @@ EXPORTED_SYMBOLS = (
     "sw_set_smoother", "sw_set_gmres_smoother", "sw_set_eo_smoother", "sw_set_eo_operator", "sw_setup_eo_operators", "sw_apply_eo_operator",
     "sw_get_level_bsr", "sw_setup_testvectors", "sw_setup_transfer",
     "sw_setup_galerkin", "sw_get_level_dense", "sw_setup_invert_coarsest", "sw_setup_direct_level", "sw_setup_level_inverse", "sw_setup_arnoldi", "sw_hier_end", "sw_set_deflation", "sw_set_level_deflation", "sw_set_perm", "sw_set_rhsmap", "sw_set_solver", "sw_set_option", "sw_get_option",
-    "sw_pool_trim", "sw_get_coarsest_inv", "sw_eig_begin", "sw_eig_load", "sw_eig_solve", "sw_eig_apply_diff", "sw_eig_gram", "sw_eig_rotate", "sw_eig_fetch", "sw_eig_end",
-    "sw_apply_dirac", "sw_restrict", "sw_prolong", "sw_coarsest", "sw_vcycle", "sw_solve",
+    "sw_pool_trim", "sw_get_coarsest_inv", "sw_eig_begin", "sw_eig_begin_wide", "sw_eig_load", "sw_eig_solve", "sw_eig_apply_diff", "sw_eig_gram", "sw_eig_rotate", "sw_eig_fetch", "sw_eig_end",
+    "sw_apply_dirac", "sw_restrict", "sw_prolong", "sw_coarsest", "sw_apply_deflation", "sw_vcycle", "sw_solve",
     "sw_hutch_batch", "sw_probes_upload", "sw_probes_upload_slot", "sw_probes_select",
     "sw_kernel_stats", "sw_kernel_work", "sw_hutch_run", "sw_sync", "sw_hutch_fetch",
     "sw_comm_unique_id", "sw_comm_init", "sw_allreduce_stats", "sw_comm_destroy",
@@ -420,9 +422,15 @@ class Engine:
         return float(v.value)
 
     # -- device eigensolver (block subspace iteration; driver: setup_gpu.device_eigenpairs) ------
-    def eig_begin(self, hid, level, seed=11):
-        self._chk(self._lib.sw_eig_begin(self._h, hid, level, int(seed)), "sw_eig_begin")
+    def eig_begin(self, hid, level, seed=11, width=64):
+        """Block buffers of `width` vectors (a multiple of 64, at most 512) on (hid, level)."""
+        if width == 64:
+            self._chk(self._lib.sw_eig_begin(self._h, hid, level, int(seed)), "sw_eig_begin")
+        else:
+            self._chk(self._lib.sw_eig_begin_wide(self._h, hid, level, int(seed), int(width)),
+                      "sw_eig_begin_wide")
         self._eig_n = self._n(hid, level)
+        self._eig_w = int(width)
 
     def eig_load(self, dst, X):
         X = np.ascontiguousarray(np.atleast_2d(X), dtype=np.complex128)
@@ -443,15 +451,17 @@ class Engine:
         return int(its.value)
 
     def eig_gram(self, a, b):
-        out = np.empty((64, 64), dtype=np.complex128)
+        w = self._eig_w
+        out = np.empty((w, w), dtype=np.complex128)
         self._chk(self._lib.sw_eig_gram(self._h, a, b, _ptr(out)), "sw_eig_gram")
         return out
 
     def eig_rotate(self, src, Y, dst, sub=-1):
         """buf_dst = buf_src Y, or (sub >= 0) buf_dst = buf_sub - buf_src Y"""
         Y = np.ascontiguousarray(Y, dtype=np.complex128)
-        if Y.shape != (64, 64):
-            raise EngineError("rotation matrix must be 64 x 64")
+        w = self._eig_w
+        if Y.shape != (w, w):
+            raise EngineError("rotation matrix must be %d x %d" % (w, w))
         self._chk(self._lib.sw_eig_rotate(self._h, src, _ptr(Y), dst, sub), "sw_eig_rotate")
 
     def eig_fetch(self, src, k):
@@ -500,6 +510,15 @@ class Engine:
         Y = np.empty_like(X2)
         self._chk(self._lib.sw_coarsest(self._h, hid, X2.shape[0], _ptr(X2), _ptr(Y)),
                   "sw_coarsest")
+        return Y[0] if single else Y
+
+    def apply_deflation(self, which, level, X):
+        """The registered deflation projection: which = 0, Pperm^T (I - U U^H) X at level 0 (Hutchinson);
+        which = 1, (I - V_l V_l^H) X at `level` (MLMC)."""
+        X2, single = self._io(X, self._n(0, level))
+        Y = np.empty_like(X2)
+        self._chk(self._lib.sw_apply_deflation(self._h, int(which), int(level), X2.shape[0], _ptr(X2),
+                                               _ptr(Y)), "sw_apply_deflation")
         return Y[0] if single else Y
 
     def vcycle(self, hid, level0, B):

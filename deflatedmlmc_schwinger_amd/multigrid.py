@@ -16,7 +16,8 @@ from . import dist as _dist
 from . import hierarchy as _hier
 from .engine import Engine, EngineError
 from .hierarchy import LevelML, SimpleML  # noqa: F401  (re-exported, multigrid.py:26-48)
-from .utils import CustomTimer
+from .setup_gpu import eig_width_for
+from .utils import CustomTimer, defl_setup_of
 
 REF_HID = 0      # reference hierarchy (MLMC level operators)
 SOLVER_HID = 1   # level-0 preconditioner hierarchy
@@ -200,30 +201,41 @@ class MG:
         self.upload_solver_hierarchy(cfg, params.get("solver_testvectors"))
         self._solver_cfg_built = dict(cfg)
 
-    def device_eigenpairs(self, k, tol, hermitian=False, log=None):
+    @staticmethod
+    def _setup_defl_wanted(kd, params):
+        """Whether the setup computes the Hutchinson deflation pairs on the GPU ahead of the estimator: up to
+        32 pairs under defl_setup = "auto", up to 256 under "device", never under "host"."""
+        if kd <= 0 or params.get("deflation_eigenpairs") is not None:
+            return False
+        how = defl_setup_of(params)
+        return kd <= 32 if how == "auto" else (how == "device" and kd <= 256)
+
+    def device_eigenpairs(self, k, tol, hermitian=False, log=None, width=None):
         """k eigenpairs nearest zero of A (level 0) -- or of gamma_3 A (hermitian) -- on the GPU, the level-0
-        solver hierarchy's solves as the shift-invert (setup_gpu.device_eigenpairs)."""
+        solver hierarchy's solves as the shift-invert (setup_gpu.device_eigenpairs; width None: 64)."""
         from . import setup_gpu
         if not self._have_solver_hier:
             raise EngineError("the device eigensolver needs the level-0 solver hierarchy")
-        return setup_gpu.device_eigenpairs(self.engine, SOLVER_HID, 0, k, tol, hermitian_g3=hermitian, log=log)
+        return setup_gpu.device_eigenpairs(self.engine, SOLVER_HID, 0, k, tol, hermitian_g3=hermitian, log=log,
+                                           width=width)
 
-    def device_diff_eigenpairs(self, level_nr, k, tol, log=None, refine_to=None):
+    def device_diff_eigenpairs(self, level_nr, k, tol, log=None, refine_to=None, width=None):
         """k largest-magnitude eigenpairs of the MLMC difference operator (A_l^-1 - P A_c^-1 R) gamma_3 of
         level `level_nr` (with self.skip_level at level 0: A_0^-1 - P_0 P_1 A_2^-1 R_1 R_0) on the GPU, the
         solves at self.solve_tol (setup_gpu.device_diff_eigenpairs): what eigsh(lop, k, which='LM', tol)
-        returns at utils.py:141-143."""
+        returns at utils.py:141-143.  width: the block width (None: 64, at most 32 pairs)."""
         from . import setup_gpu
-        if not 1 <= k <= 32:
-            raise Exception("device_diff_eigenpairs: k = %d outside 1..32 (the block is 64 vectors wide; "
-                            "mlmc_defl_setup = 'host' has no such limit)" % k)
+        wmax = 64 if width is None else width
+        if not 1 <= k <= wmax // 2:
+            raise Exception("device_diff_eigenpairs: k = %d outside 1..%d (the block is %d vectors wide; "
+                            "mlmc_defl_setup = 'host' has no such limit)" % (k, wmax // 2, wmax))
         eng = self._need_engine()
         self._diff_op_checks(level_nr)
         n = self.ml.levels[level_nr].A.shape[0]
         return setup_gpu.device_diff_eigenpairs(eng, level_nr, k, tol, self.solve_tol,
                                                 skip=bool(self.skip_level and level_nr == 0),
                                                 maxiter=n if n < 1000 else self.maxiter_cap, log=log,
-                                                refine_to=refine_to)
+                                                refine_to=refine_to, width=width)
 
     def _deferred_reference_hierarchy(self, dof, aggrs, max_levels, acc_eigvs, params, tv, ckey):
         """Device setup for flows that use level 0 only (stoch_trace.hutchinson): engines, solver hierarchy,
@@ -239,8 +251,8 @@ class MG:
         tolx = 1.0e-3 if acc_eigvs == "low" else 1.0e-9
         kd = int(params.get("nr_deflat_vctrs", 0) or 0)
         tol_d = params.get("defl_eigvs_tol_Hutch", 1.0e-9)
-        want_defl = kd > 0 and params.get("deflation_eigenpairs") is None and kd <= 32
-        if want_defl and self._cache_dir:
+        want_defl = self._setup_defl_wanted(kd, params)
+        if want_defl and self._cache_dir and defl_setup_of(params) == "auto":
             dkey = _cache.matrix_key(self._A0, {"k": kd, "tol": tol_d})
             want_defl = _cache.load(self._cache_dir, "defl", dkey) is None
 
@@ -261,7 +273,8 @@ class MG:
         if want_defl:
             dlog = []
             t1 = time.time()
-            defl = comm.compute_on_root(lambda: self.device_eigenpairs(kd, tol_d, hermitian=True, log=dlog))
+            defl = comm.compute_on_root(lambda: self.device_eigenpairs(kd, tol_d, hermitian=True, log=dlog,
+                                                                        width=eig_width_for(kd)))
             self.setup_log["eigsh_deflation"] = {"seconds": round(time.time() - t1, 4), "steps": dlog}
             self._device_defl[(kd, float(tol_d))] = defl
         # level 0 as the estimators read it (multigrid.py:130-155), the rest arrives with finish_setup()
@@ -320,8 +333,8 @@ class MG:
         tolx = 1.0e-3 if acc_eigvs == "low" else 1.0e-9
         kd = int(params.get("nr_deflat_vctrs", 0) or 0)
         tol_d = params.get("defl_eigvs_tol_Hutch", 1.0e-9)
-        want_defl = kd > 0 and params.get("deflation_eigenpairs") is None and kd <= 32
-        if want_defl and self._cache_dir:
+        want_defl = self._setup_defl_wanted(kd, params)
+        if want_defl and self._cache_dir and defl_setup_of(params) == "auto":
             dkey = _cache.matrix_key(self._A0, {"k": kd, "tol": tol_d})
             want_defl = _cache.load(self._cache_dir, "defl", dkey) is None
         built = None
@@ -343,7 +356,7 @@ class MG:
                 if want_defl:
                     dlog = []
                     t1 = time.time()
-                    defl = self.device_eigenpairs(kd, tol_d, hermitian=True, log=dlog)
+                    defl = self.device_eigenpairs(kd, tol_d, hermitian=True, log=dlog, width=eig_width_for(kd))
                     self.setup_log["eigsh_deflation"] = {"seconds": round(time.time() - t1, 4), "steps": dlog}
                 t1 = time.time()
                 built = fut.result()
@@ -751,7 +764,7 @@ class MG:
                             "operator is available at level 0 only in that mode")
 
     def diff_op_block(self, V, g3=False):
-        """diff_op on up to 64 columns of V ([n, m], reference row order in and out) in one engine call:
+        """diff_op on up to 512 columns of V ([n, m], reference row order in and out) in one engine call:
         (A_f^-1 - P A_c^-1 R) V at self.level_for_diff_op and self.solve_tol, or that operator times gamma_3
         (diff_op_Q without its in-place sign flip) when g3."""
         eng = self._need_engine()
@@ -759,9 +772,13 @@ class MG:
         self._diff_op_checks(lvl)
         V = np.asarray(V, dtype=np.complex128)
         n = self.ml.levels[lvl].A.shape[0]
-        if V.ndim != 2 or V.shape[0] != n or not 1 <= V.shape[1] <= 64:
-            raise Exception("diff_op_block: V must be [%d, m] with 1 <= m <= 64, got %s" % (n, V.shape))
-        eng.eig_begin(REF_HID, lvl)
+        if V.ndim != 2 or V.shape[0] != n or not 1 <= V.shape[1] <= 512:
+            raise Exception("diff_op_block: V must be [%d, m] with 1 <= m <= 512, got %s" % (n, V.shape))
+        width = 64 * -(-V.shape[1] // 64)
+        if width == 64:
+            eng.eig_begin(REF_HID, lvl)
+        else:
+            eng.eig_begin(REF_HID, lvl, width=width)
         try:
             eng.eig_load(0, V.T)
             eng.eig_apply_diff(0, 1, self.skip_level and lvl == 0, g3, self.solve_tol,

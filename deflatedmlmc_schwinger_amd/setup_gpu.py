@@ -390,8 +390,32 @@ def device_solver_hierarchy(eng, lat, cfg, hid):
 # ----------------------------------------------------------------------------------------------
 # device eigensolver: the host ARPACK + SuperLU calls of the setup, on the GPU
 # ----------------------------------------------------------------------------------------------
+def _eig_width(name, k, width):
+    """The block width of a device eigensolve: None = 64 (at most 32 pairs); otherwise a multiple of 64 in
+    64..512 that holds 2 k vectors."""
+    if width is None:
+        width = 64
+    elif width % 64 or not 64 <= width <= 512:
+        raise Exception("%s: block width %d is not a multiple of 64 in 64..512" % (name, width))
+    if not 1 <= k <= width // 2:
+        raise Exception("%s: k = %d outside 1..%d (the block is %d vectors wide)" % (name, k, width // 2, width))
+    return width
+
+
+def eig_width_for(k):
+    """The narrowest block that holds 2 k vectors: 64 * ceil(2 k / 64)."""
+    return 64 * max(1, -(-2 * int(k) // 64))
+
+
+def _eig_begin(eng, hid, level, seed, width):
+    if width == 64:
+        eng.eig_begin(hid, level, seed)
+    else:
+        eng.eig_begin(hid, level, seed, width=width)
+
+
 def device_eigenpairs(eng, hid, level, k, tol, hermitian_g3=False, maxit=60, seed=11, start=None,
-                      log=None):
+                      log=None, width=None):
     """The k eigenpairs nearest zero of A_level (hermitian_g3 = False: what eigs(A_l, k, sigma=0, tol)
     returns at multigrid.py:174) or of Q = gamma_3 A_level (True: eigsh(Q, k, sigma=0, tol), utils.py:140),
     by block subspace iteration with Rayleigh-Ritz on the engine (block_eigenpairs), W = Op^-1 V being the
@@ -401,9 +425,11 @@ def device_eigenpairs(eng, hid, level, k, tol, hermitian_g3=False, maxit=60, see
     |Op^-1 x - theta x| <= tol |theta|.  The block width 64 (the engine's batch quantum: 64 solves cost what
     one costs) makes the convergence factor |lambda_k / lambda_65| per step (0.13 for A, 0.16 for Q on
     schwinger128).  The solves start loose and tighten with the residual (inexact inverse iteration).
+    `width` (None: 64): the block width, a multiple of 64 up to 512, at least 2 k (eig_width_for).
     Returns (lambda[k], X[n, k]) -- X columns of unit norm, orthonormal for the hermitian case --, and
     appends per-step records to `log`."""
     mode = 1 if hermitian_g3 else 0
+    width = _eig_width("device_eigenpairs", k, width)
 
     def apply(src, dst, res_prev):
         # the shift-invert solve; its tolerance follows the residual of the wanted pairs (inexact inverse
@@ -412,46 +438,43 @@ def device_eigenpairs(eng, hid, level, k, tol, hermitian_g3=False, maxit=60, see
         tol_s = min(1e-3, max(5e-13, 1e-2 * res_prev))
         return tol_s, eng.eig_solve(src, dst, mode, tol_s)
 
-    if not 1 <= k <= 32:
-        raise Exception("device_eigenpairs: k = %d outside 1..%d" % (k, 32))
-    eng.eig_begin(hid, level, seed)
+    _eig_begin(eng, hid, level, seed, width)
     try:
         return block_eigenpairs(eng, k, tol, apply, inverse=True, hermitian=hermitian_g3, maxit=maxit,
-                                start=start, log=log, name="device_eigenpairs")
+                                start=start, log=log, name="device_eigenpairs", width=width)
     finally:
         eng.eig_end()
 
 
 def device_diff_eigenpairs(eng, level, k, tol, solve_tol, skip=False, maxiter=1000, maxit=200, seed=11,
-                           log=None, refine_to=None):
+                           log=None, refine_to=None, width=None):
     """The k largest-magnitude eigenpairs of the MLMC difference operator Q_l = (A_l^-1 - P A_c^-1 R) gamma_3
     of level `level` of hierarchy 0 (skip: A_0^-1 - P_0 P_1 A_2^-1 R_1 R_0), what eigsh(Q_l, k, which='LM',
     tol) returns at utils.py:141-143: block subspace iteration with W = Q_l V (sw_eig_apply_diff, both solves
     at the fixed tolerance `solve_tol`, as the reference fixes mg_solver.solve_tol for these mat-vecs).
     Q_l is gamma_3-hermitian: Hermitian up to the inexactness of the solves, so T = V^H W is symmetrised.
     The convergence factor per step is |lambda_65 / lambda_k| of Q_l.  `refine_to`: keep iterating below `tol`
-    while the residual still halves per step, down to `refine_to` (block_eigenpairs).  Returns (lambda[k] real,
-    X[n, k] orthonormal) and appends per-step records to `log`."""
-    if not 1 <= k <= 32:
-        raise Exception("device_diff_eigenpairs: k = %d outside 1..32 (the block is 64 vectors wide)" % k)
+    while the residual still halves per step, down to `refine_to` (block_eigenpairs).  `width` as for
+    device_eigenpairs.  Returns (lambda[k] real, X[n, k] orthonormal) and appends per-step records to `log`."""
+    width = _eig_width("device_diff_eigenpairs", k, width)
 
     def apply(src, dst, res_prev):
         return solve_tol, eng.eig_apply_diff(src, dst, skip, True, solve_tol, maxiter)
 
-    eng.eig_begin(0, level, seed)
+    _eig_begin(eng, 0, level, seed, width)
     try:
         return block_eigenpairs(eng, k, tol, apply, inverse=False, hermitian=True, maxit=maxit, log=log,
-                                name="device_diff_eigenpairs", refine_to=refine_to)
+                                name="device_diff_eigenpairs", refine_to=refine_to, width=width)
     finally:
         eng.eig_end()
 
 
 def block_eigenpairs(eng, k, tol, apply, inverse, hermitian, maxit=60, start=None, log=None,
-                     name="block_eigenpairs", refine_to=None):
+                     name="block_eigenpairs", refine_to=None, width=64):
     """Block subspace iteration with Rayleigh-Ritz on the engine's eigen buffers (sw_eig_begin done by the
     caller):
 
-        V orthonormal [n][64];  W = Op V (`apply(src, dst, residual) -> (solve_tol, iterations)`: the
+        V orthonormal [n][width];  W = Op V (`apply(src, dst, residual) -> (solve_tol, iterations)`: the
         shift-invert solve when `inverse`, the operator itself otherwise);  T = V^H W (fp64 MFMA Gram kernel);
         Ritz pairs (theta, y) of T;  block residual E = W - V T on the device, M = E^H E:
         |Op x - theta x|^2 = y^H M y for x = V y (formed from the small residual vectors themselves -- the
@@ -462,9 +485,10 @@ def block_eigenpairs(eng, k, tol, apply, inverse, hermitian, maxit=60, start=Non
     1 / theta), largest in magnitude otherwise (lambda = theta, which='LM') -- and stops when they all satisfy
     ARPACK's criterion |Op x - theta x| <= tol |theta|.  With `refine_to` < tol the iteration goes on past tol
     while the residual at least halves per step, and stops at refine_to at the latest (or where it stalls: the
-    accuracy of an inexactly applied operator).  Returns (lambda[k], X[n, k])."""
+    accuracy of an inexactly applied operator).  `width`: the block width of the caller's eig_begin (k <=
+    width / 2; the Rayleigh-Ritz step is width x width).  Returns (lambda[k], X[n, k])."""
     import scipy.linalg as sla
-    m = 64
+    m = width
     if not 1 <= k <= m // 2:
         raise Exception("%s: k = %d outside 1..%d" % (name, k, m // 2))
     cur, nxt, tmp = 0, 1, 2

@@ -62,7 +62,7 @@ _BUILD_KEYS = ('batch', 'device', 'engines', 'cache_dir', 'report_path', 'probe_
                'solver_testvectors', 'deflation_eigenpairs', 'ref_cycle_post', 'ref_cycle_k', 'ref_smoother',
                'solver_restart', 'stochastic_coarsest', 'stop_factor', 'ref_direct_max_n', 'ref_coarsest',
                'ref_coarse_dofs', 'setup_eigs', 'defer_coarse_levels',
-               'verbose', 'probe_rounds_max', 'mlmc_defl_setup')
+               'verbose', 'probe_rounds_max', 'mlmc_defl_setup', 'defl_setup')
 # where the eigenpairs of the MLMC difference operators come from: host ARPACK (the reference's path) or
 # the block eigensolver on the GPU (setup_gpu.device_diff_eigenpairs)
 MLMC_DEFL_SETUPS = ("host", "device")
@@ -73,6 +73,20 @@ def mlmc_defl_setup_of(params):
     how = params.get('mlmc_defl_setup', "host") if hasattr(params, "get") else "host"
     if how not in MLMC_DEFL_SETUPS:
         raise Exception("mlmc_defl_setup = %r: expected one of %s" % (how, ", ".join(MLMC_DEFL_SETUPS)))
+    return how
+
+
+# where the Hutchinson deflation eigenpairs come from: "auto" (the device block eigensolver for k <= 32 when
+# the solver hierarchy was set up on the device, host ARPACK otherwise), "device" (the block eigensolver for
+# 1 <= k <= 256, block width 64 ceil(2 k / 64)) or "host" (ARPACK always)
+DEFL_SETUPS = ("auto", "device", "host")
+
+
+def defl_setup_of(params):
+    """The build-only key defl_setup ("auto" when absent); any other value raises."""
+    how = params.get('defl_setup', "auto") if hasattr(params, "get") else "auto"
+    if how not in DEFL_SETUPS:
+        raise Exception("defl_setup = %r: expected one of %s" % (how, ", ".join(DEFL_SETUPS)))
     return how
 
 
@@ -149,6 +163,25 @@ def _engines(mg_solver):
 # ----------------------------------------------------------------------------------------
 # deflation (setup-time, host)                                          utils.py:130-201
 # ----------------------------------------------------------------------------------------
+def _explicit_deflation_pairs(how, A, k, tolx, mg_solver, lev0):
+    """eigsh(gamma_3 A, k, sigma=0) as defl_setup = "device" (block eigensolver, k <= 256; the pairs the setup
+    already computed on the GPU when it had them) or "host" (ARPACK) asks."""
+    if how == "host":
+        Q = (lev0.g3 * A).tocsc()
+        return _dist.default_comm().compute_on_root(lambda: eigsh(Q, k=k, which='LM', tol=tolx, sigma=0.0))
+    if not 1 <= k <= 256:
+        raise Exception("defl_setup = 'device': nr_deflat_vctrs = %d outside 1..256" % k)
+    if not getattr(mg_solver, "_have_solver_hier", False):
+        raise Exception("defl_setup = 'device' needs the level-0 solver hierarchy on the GPU "
+                        "(the device eigensolver's shift-invert solves)")
+    found = getattr(mg_solver, "_device_defl", {}).get((int(k), float(tolx)))
+    if found is not None:
+        return found
+    from .setup_gpu import eig_width_for
+    return _dist.default_comm().compute_on_root(
+        lambda: mg_solver.device_eigenpairs(k, tolx, hermitian=True, width=eig_width_for(k)))
+
+
 def deflation_pre_computations(A, nr_deflat_vctrs, tolx, method, timer, params, mg_solver,
                                lop=None, level_nr=0):
     if method not in ("hutchinson", "mlmc"):
@@ -165,8 +198,11 @@ def deflation_pre_computations(A, nr_deflat_vctrs, tolx, method, timer, params, 
     lev0 = mg_solver.ml.levels[0]
     if method == "hutchinson":
         pre = params.get("deflation_eigenpairs") if hasattr(params, "get") else None
+        how = defl_setup_of(params)
         if pre is not None:
             Sy, Vx = np.array(pre[0], dtype=float), np.array(pre[1], dtype=np.complex128)
+        elif how != "auto":
+            Sy, Vx = _explicit_deflation_pairs(how, A, nr_deflat_vctrs, tolx, mg_solver, lev0)
         else:
             from . import cache as _cache
             cdir = _cache.cache_dir(params)
@@ -206,9 +242,11 @@ def deflation_pre_computations(A, nr_deflat_vctrs, tolx, method, timer, params, 
             # overshoots it, so the pairs are refined while the residual still halves per step, down to the
             # accuracy of the operator's solves (7 steps there).
             steps = []
+            from .setup_gpu import eig_width_for
             Sy, Vx = _dist.default_comm().compute_on_root(
                 lambda: mg_solver.device_diff_eigenpairs(level_nr, nr_deflat_vctrs, tolx, log=steps,
-                                                         refine_to=params['diff_lev_op_tol']))
+                                                         refine_to=params['diff_lev_op_tol'],
+                                                         width=eig_width_for(nr_deflat_vctrs)))
             rec = {"method": "device", "seconds": round(time.time() - t1, 4), "steps": steps}
         else:
             Sy, Vx = _dist.default_comm().compute_on_root(

@@ -31,7 +31,7 @@ extern "C" {
 #define SW_MAX_HIER 2
 #define SW_MAX_LEVELS 8
 #define SW_MAX_KRYLOV 32
-#define SW_MAX_DEFL 64
+#define SW_MAX_DEFL 256
 
 typedef struct sw_engine sw_engine;
 
@@ -172,6 +172,9 @@ int sw_setup_arnoldi(sw_engine* h, int hid, int level, int which, int degree, ui
  * (index 0..2) on one finished (hid, level); the caller does the 64 x 64 dense algebra in between
  * (Rayleigh-Ritz on V^H Op^-1 V, Cholesky-QR), see setup_gpu.device_eigenpairs.
  *   sw_eig_begin   buffers on (hid, level), buffer 0 <- pseudo-random block
+ *   sw_eig_begin_wide  the same with blocks of `width` vectors (a multiple of 64, at most 512): width/64
+ *                  groups of 64 columns; load / fetch then take up to `width` columns, gram returns and
+ *                  rotate takes width x width, solve and apply_diff act on every group (64 at a time)
  *   sw_eig_load    first ncols columns of buffer dst <- host vectors (reference order)
  *   sw_eig_solve   buf_dst = Op^-1 buf_src, 64 right-hand sides to `tol`; mode 0: Op = A_level, mode 1:
  *                  Op = gamma_3 A_level (gamma_3 = +1 / -1 on the first / second half of the reference order)
@@ -187,6 +190,7 @@ int sw_setup_arnoldi(sw_engine* h, int hid, int level, int which, int degree, ui
  *   sw_eig_fetch   first k columns of buf_src as k host vectors in the reference order
  *   sw_eig_end     release the buffers */
 int sw_eig_begin(sw_engine* h, int hid, int level, uint64_t seed);
+int sw_eig_begin_wide(sw_engine* h, int hid, int level, uint64_t seed, int width);
 int sw_eig_load(sw_engine* h, int dst, int ncols, const double* X);
 int sw_eig_solve(sw_engine* h, int src, int dst, int mode, double tol, int maxiter, int32_t* iters_max);
 int sw_eig_apply_diff(sw_engine* h, int src, int dst, int skip, int g3, double tol, int maxiter,
@@ -198,7 +202,7 @@ int sw_eig_end(sw_engine* h);
 /* Mark the hierarchy complete (allocates level workspaces lazily). */
 int sw_hier_end(sw_engine* h, int hid);
 
-/* Deflation vectors U (utils.py:145-155), row-major complex128[n0*k], reference ordering. */
+/* Deflation vectors U (utils.py:145-155), row-major complex128[n0*k], reference ordering, k <= SW_MAX_DEFL. */
 int sw_set_deflation(sw_engine* h, int k, const double* U);
 /* MLMC-level deflation vectors V_l of the difference operator at `level` of hid 0
  * (utils.py:141-157,260-266), row-major complex128[n_l*k]; k = 0 clears. */
@@ -255,6 +259,8 @@ int sw_set_solver(sw_engine* h, int restart, int solver_hid);
  *                  level, direct inverse of a small level) through k_dense_mfma3_lds: operands shared through LDS
  *                  (register-staged, double-buffered), 2 or 4 row tiles x 2 probe tiles per workgroup (0: k_bsr_mfma3)
  *   setup:         "gj_block" (32) panel width of the blocked Gauss-Jordan inverse (0: unblocked)
+ *   deflation:     "defl_gemm" (0) 0: k_defl_dots / k_defl_apply up to 64 vectors, the fp64-MFMA pair
+ *                  k_defl_gemm_dots / k_defl_gemm_apply above; 1: the MFMA pair at every rank
  *   sw_bench_dirac: "bench_mode" (0 Y=AX, 1 residual, 2 smoother step), "bench_what" (operator / R / P /
  *                  coarsest) */
 int sw_set_option(sw_engine* h, const char* name, double value);
@@ -273,6 +279,10 @@ int sw_restrict(sw_engine* h, int hid, int level, int nb, const double* X, doubl
 int sw_prolong(sw_engine* h, int hid, int level, int nb, const double* X, double* Y);
 /* Y = coarsest_inv X (multigrid.py:413-416; utils.py:309-310,321-322). */
 int sw_coarsest(sw_engine* h, int hid, int nb, const double* X, double* Y);
+/* Y = the registered deflation projection of X with the kernels of sw_hutch_run.  which = 0: the
+ * Hutchinson form Pperm_0^T (I - U U^H) X at level 0 (sw_set_deflation, sw_set_perm); which = 1: the MLMC
+ * form (I - V_l V_l^H) X at `level` (sw_set_level_deflation).  X,Y: complex128[nb*n_level]. */
+int sw_apply_deflation(sw_engine* h, int which, int level, int nb, const double* X, double* Y);
 /* X = one multigrid cycle applied to B starting at level0 (MG.one_mg_step, multigrid.py:369-447). */
 int sw_vcycle(sw_engine* h, int hid, int level0, int nb, const double* B, double* X);
 /* Solve A_level0 X = B to ||r|| < tol*||b|| per right-hand side (MG.solve -> pyamg fgmres,
