@@ -45,9 +45,9 @@ static int sw_fail(sw_engine* h, const char* fmt, ...);
       return sw_fail(h, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__,  \
                      __LINE__);                                                           \
   } while (0)
-#define SWCHK(call)             \
+#define SWCHK(...)              \
   do {                          \
-    int rc_ = (call);           \
+    int rc_ = (__VA_ARGS__);    \
     if (rc_ != 0) return rc_;   \
   } while (0)
 
@@ -345,6 +345,139 @@ struct sw_engine {
   double* d_stats = nullptr; // [4] all-reduce buffer
 };
 
+// ---------------------------------------------------------------------------------------------
+// engine options (sw_set_option / sw_get_option): one entry per name.  Bool fields take value != 0, int
+// fields (int)value; a validator rejects a value with its message before anything is stored.
+// ---------------------------------------------------------------------------------------------
+static int g_dot_blocks = 1024, g_dot_pmax = 1024;   // process-wide (row_blocking has no engine)
+
+struct EngineOption {
+  const char* name;
+  double (*get)(const sw_engine*);
+  void (*set)(sw_engine*, double);   // nullptr: a read-only statistic
+  bool (*ok)(double) = nullptr;      // the values sw_set_option accepts (nullptr: all)
+  const char* msg = nullptr;         // its message for the others
+};
+template <auto F>
+static double get_field(const sw_engine* h) { return (double)(h->*F); }
+template <auto F>
+static void set_field(sw_engine* h, double v) { h->*F = static_cast<std::remove_reference_t<decltype(h->*F)>>(v); }
+template <auto F>
+static constexpr EngineOption field(const char* name, bool (*ok)(double) = nullptr, const char* msg = nullptr) {
+  return {name, get_field<F>, set_field<F>, ok, msg};
+}
+
+static constexpr EngineOption kOptions[] = {
+    // kernel choices
+    field<&sw_engine::use_mfma>("use_mfma"),   // MFMA block-row kernels where an operator has that form
+    field<&sw_engine::mfma_ops>("mfma_ops"),   // ... also for the block-structured level operators
+    field<&sw_engine::mfma_3m>("mfma_3m"),     // k_bsr_mfma3 (three real products) instead of k_bsr_mfma
+    // k_bsr_mfma probe tiles per wave, and on operators too small to fill the chip (0: off)
+    field<&sw_engine::mfma_tiles>("mfma_tiles", [](double v) { return v == 2.0 || v == 4.0; },
+                                  "mfma_tiles must be 2 or 4"),
+    field<&sw_engine::mfma_small_tiles>("mfma_small_tiles",
+                                        [](double v) { return v == 0.0 || v == 2.0 || v == 4.0; },
+                                        "mfma_small_tiles must be 0, 2 or 4"),
+    // k_bsr_mfma3 probe tiles per wave (0: by the operator's size)
+    field<&sw_engine::mfma3_tiles>("mfma3_tiles",
+                                   [](double v) { const int t = (int)v; return t == 0 || t == 1 || t == 2 || t == 4; },
+                                   "mfma3_tiles must be 0, 1, 2 or 4"),
+    // block orderings of k_bsr_mfma on level operators and on the dense coarsest inverse, and their grouping
+    field<&sw_engine::bsr_map>("bsr_map", [](double v) { return (int)v >= 0 && (int)v <= 3; },
+                               "bsr_map must be 0..3"),
+    field<&sw_engine::dense_map>("dense_map", [](double v) { return (int)v >= 0 && (int)v <= 3; },
+                                 "dense_map must be 0..3"),
+    field<&sw_engine::bsr_sub>("bsr_sub", [](double v) { return (int)v >= 1; }, "bsr_sub must be >= 1"),
+    // k-steps in flight in k_bsr_mfma on level operators and on dense ones
+    field<&sw_engine::bsr_stages>("bsr_stages", [](double v) { return v == 2.0 || v == 4.0 || v == 8.0; },
+                                  "bsr_stages must be 2, 4 or 8 (dense_stages: or 16)"),
+    field<&sw_engine::dense_stages>("dense_stages",
+                                    [](double v) { return v == 2.0 || v == 4.0 || v == 8.0 || v == 16.0; },
+                                    "dense_stages must be 2, 4 or 8 (dense_stages: or 16)"),
+    field<&sw_engine::bsr_nt>("bsr_nt"),       // non-temporal loads / stores on level operators
+    field<&sw_engine::bsr_xreg>("bsr_xreg"),   // own X rows from the operand registers
+    // k_dense_mfma3_lds row tiles per workgroup (1 is stored as 2; 0: k_bsr_mfma3)
+    {"dense_lds", get_field<&sw_engine::dense_lds>,
+     [](sw_engine* h, double v) { h->dense_lds = v == 1.0 ? 2 : (int)v; },
+     [](double v) { return v == 0.0 || v == 1.0 || v == 2.0 || v == 4.0; }, "dense_lds must be 0, 2 or 4"},
+    // k_defl_gemm_* at every deflation rank
+    field<&sw_engine::defl_gemm>("defl_gemm", [](double v) { return v == 0.0 || v == 1.0; },
+                                 "defl_gemm must be 0 or 1"),
+    field<&sw_engine::fused_reduce>("fused_reduce"),   // cross-workgroup sums inside the reducing launch
+    // row blocks of the reducing BLAS-1 launches (process-wide, at least 64)
+    {"dot_blocks", [](const sw_engine*) { return (double)g_dot_blocks; },
+     [](sw_engine*, double v) { g_dot_blocks = g_dot_pmax = std::max(64, (int)v); }},
+    // panel width of the blocked Gauss-Jordan inverse (0: unblocked)
+    field<&sw_engine::gj_block>("gj_block",
+                                [](double v) {
+                                  const int b = (int)v;
+                                  return b == 0 || (b >= 8 && b <= 256 && b % 8 == 0);
+                                },
+                                "gj_block must be 0 or a multiple of 8 in 8..256"),
+    // lattice level: stencil stores, x-tile and x-sites per wave (0: automatic)
+    field<&sw_engine::stencil_nt>("stencil_nt"),
+    field<&sw_engine::stencil_tile>("stencil_tile"),
+    field<&sw_engine::stencil_spw>("stencil_spw",
+                                   [](double v) {
+                                     const int t = (int)v;
+                                     return t == 0 || t == 1 || t == 2 || t == 4 || t == 8;
+                                   },
+                                   "stencil_spw must be 0,1,2,4,8"),
+    // k_schur_tile waves per workgroup (0: off), and its timing diagnostics (two bits)
+    field<&sw_engine::eo_tile>("eo_tile", [](double v) { return v == 0.0 || v == 4.0 || v == 8.0; },
+                               "eo_tile must be 0 (off), 4 or 8 waves"),
+    {"eo_tile_dbg", get_field<&sw_engine::eo_tile_dbg>, [](sw_engine* h, double v) { h->eo_tile_dbg = (int)v & 3; }},
+    // time-skewed Schur steps: strip height (-1 automatic, 0 off), walked 64 probes at a time
+    field<&sw_engine::eo_skew>("eo_skew", [](double v) { return !(v < -1.0 || v > 65536.0); },
+                               "eo_skew must be -1 (automatic), 0 (off) or a strip height"),
+    field<&sw_engine::eo_skew_chunk>("eo_skew_chunk"),
+    field<&sw_engine::eo_product>("eo_product"),   // even-odd smoother in product form
+    // transfers and cycle
+    field<&sw_engine::p_even>("p_even"),           // prolongate onto the even sites ahead of an even-odd smoother
+    // prolongator row groups in column order (the even-site group lists are rebuilt)
+    {"ell_order", get_field<&sw_engine::ell_order>, [](sw_engine* h, double v) {
+       h->ell_order = v != 0.0;
+       for (Hier& H : h->hier) H.even_valid = false;
+     }},
+    field<&sw_engine::direct_small>("direct_small"),   // solve levels with a dense inverse directly
+    field<&sw_engine::eo_direct>("eo_direct"),         // ... and block levels with a dense Schur inverse
+    field<&sw_engine::lgmres_aug>("lgmres_aug"),       // LGMRES augmentation in the GMRES smoother
+    // outer solve
+    field<&sw_engine::cgs2>("cgs2"),                   // two Gram-Schmidt passes per Arnoldi step
+    field<&sw_engine::inner_cgs2>("inner_cgs2"),       // ... in the inner Krylov cycles
+    field<&sw_engine::pyth_last>("pyth_last"),         // last Arnoldi step of a cycle without its pass
+    field<&sw_engine::verify>("verify"),               // true-residual check of a converged solve
+    field<&sw_engine::lazy_sync>("lazy_sync"),         // convergence read back late (sync_hint)
+    field<&sw_engine::eo_solve>("eo_solve"),           // outer solve on the even-odd reduced system
+    field<&sw_engine::gram_cycle>("gram_cycle"),       // ... in Gram-matrix restart cycles
+    field<&sw_engine::stop_factor>("stop_factor", [](double v) { return v > 0.0 && v <= 1.0; },
+                                   "stop_factor must be in (0, 1]"),   // iterate to stop_factor * tol
+    // single-precision preconditioner
+    field<&sw_engine::precond_f32>("precond_f32"),     // complex64 multigrid cycle
+    field<&sw_engine::f32_krylov>("f32_krylov"),       // complex64 Krylov basis per restart cycle
+    field<&sw_engine::f32_pairs>("f32_pairs"),         // two probes per lane
+    // k_bsr_mfma_f32 probe tiles per wave (0: automatic), k-steps in flight, split-K kernel (0 off, 1 dense
+    // coarsest inverse, 2 every small operator)
+    field<&sw_engine::f32_tiles>("f32_tiles",
+                                 [](double v) { const int t = (int)v; return t == 0 || t == 1 || t == 2 || t == 4; },
+                                 "f32_tiles must be 0, 1, 2 or 4"),
+    field<&sw_engine::f32_stages>("f32_stages"),
+    field<&sw_engine::f32_dense_stages>("f32_dense_stages"),
+    field<&sw_engine::f32_splitk>("f32_splitk"),
+    // what sw_bench_dirac times (0 operator, 1 restrict, 2 prolong, 3 coarsest inverse), in which operator mode
+    field<&sw_engine::bench_what>("bench_what", [](double v) { return !(v < 0.0 || v > 3.0); },
+                                  "bench_what must be 0..3"),
+    field<&sw_engine::bench_mode>("bench_mode", [](double v) { return v == 0.0 || v == 1.0 || v == 2.0; },
+                                  "bench_mode must be 0, 1 or 2"),
+    // read-only statistics: direct solves that fell back to the iterative path, allocator time, calls, volume,
+    // and allocations served from parked blocks
+    {"direct_fallbacks", get_field<&sw_engine::direct_fallbacks>, nullptr},
+    {"alloc_seconds", get_field<&sw_engine::alloc_s>, nullptr},
+    {"alloc_calls", get_field<&sw_engine::alloc_calls>, nullptr},
+    {"alloc_gbytes", [](const sw_engine* h) { return h->alloc_bytes * 1e-9; }, nullptr},
+    {"pool_hits", get_field<&sw_engine::pool_hits>, nullptr},
+};
+
 static int sw_fail(sw_engine* h, const char* fmt, ...) {
   char buf[1024];
   va_list ap;
@@ -556,6 +689,34 @@ static int stream_sync(sw_engine* h) {
 }
 #define KLAUNCH_CHECK() HIPCHK(hipGetLastError())
 
+// One kernel launch on the engine's stream, counted and (while profiling) timed in class `cat`
+template <class... P, class... A>
+static int launch(sw_engine* h, int cat, void (*k)(P...), dim3 grid, dim3 block, A&&... a) {
+  LaunchScope ls(h, cat);
+  k<<<grid, block, 0, h->stream>>>(a...);
+  KLAUNCH_CHECK();
+  return 0;
+}
+
+// Runtime value -> template argument: f(IntC<V>{}) for one V of the list.
+// pick: the V equal to v, or the last V when none is.  pick_ge: the first V >= v, or the last V.
+template <int V>
+using IntC = std::integral_constant<int, V>;
+template <int... Vs, class F>
+static int pick(int v, F&& f) {
+  constexpr int last[] = {Vs...};
+  int rc = 0;
+  (void)(((v == Vs || Vs == last[sizeof...(Vs) - 1]) && (rc = f(IntC<Vs>{}), true)) || ...);
+  return rc;
+}
+template <int... Vs, class F>
+static int pick_ge(int v, F&& f) {
+  constexpr int last[] = {Vs...};
+  int rc = 0;
+  (void)(((v <= Vs || Vs == last[sizeof...(Vs) - 1]) && (rc = f(IntC<Vs>{}), true)) || ...);
+  return rc;
+}
+
 // ---------------------------------------------------------------------------------------------
 // CSR -> grouped ELL / MFMA block-row form: packed on the host (sw_pack.hpp), uploaded here
 // ---------------------------------------------------------------------------------------------
@@ -648,7 +809,6 @@ static int launch_bsr(sw_engine* h, const EllOp& op, int mode, const cplx* X, co
   const int cls = cat == T_COARSEST ? T_MFMA_DENSE
                                     : (cat == T_MVM ? (op.nrows == n1 || n1 == 0 ? T_MFMA_OP : T_MFMA_OP2)
                                                     : cat);
-  LaunchScope ls(h, cls);
   // 16 rows x 4 columns x nbp probes x 8 flops per complex multiply-add, per (tile, k-step)
   if (h->profiling) h->twork[cls] += 512.0 * (double)RT * (double)op.bsr_KS * (double)nbp;
   const int dl_kb = 4;     // k-steps per LDS stage (8 measured 135.1 us against 136.4: barriers are not the bound)
@@ -658,15 +818,11 @@ static int launch_bsr(sw_engine* h, const EllOp& op, int mode, const cplx* X, co
     // dense operator: operands shared through LDS (register-staged, double-buffered), one workgroup per
     // (16 dense_lds)-row x 32-probe block -- 1 KiB (0.75 KiB) per wave and k-step through the L2 -> CU path
     // instead of 2
-#define DL_LAUNCH(RTW_, KB_)                                                                                \
-  hipLaunchKernelGGL((swk::k_dense_mfma3_lds<RTW_, KB_>), dim3((RT / RTW_) * (nbp / 32)), dim3(128 * RTW_), 0, \
-                     h->stream, (const cplx*)op.bsr_vals, (const int*)op.bsr_kcol, op.bsr_KS, RT, X, Y, nbp,  \
-                     (const int*)op.bsr_tmap)
-    if (h->dense_lds == 4) DL_LAUNCH(4, 4);
-    else DL_LAUNCH(2, 4);
-#undef DL_LAUNCH
-    KLAUNCH_CHECK();
-    return 0;
+    return pick<4, 2>(h->dense_lds, [&](auto RTW) {
+      return launch(h, cls, swk::k_dense_mfma3_lds<RTW, dl_kb>, dim3((RT / RTW) * (nbp / 32)), dim3(128 * RTW),
+                    (const cplx*)op.bsr_vals, (const int*)op.bsr_kcol, op.bsr_KS, RT, X, Y, nbp,
+                    (const int*)op.bsr_tmap);
+    });
   }
   if (h->mfma_3m) {
     // three real products per complex one (k_bsr_mfma3): tiles of 16 probes per wave
@@ -684,64 +840,54 @@ static int launch_bsr(sw_engine* h, const EllOp& op, int mode, const cplx* X, co
     const bool ntio3 = h->bsr_nt && cat != T_COARSEST;
     const int xr = (op.bsr_diag_last && h->bsr_xreg) ? 1 : 0;
     const int bm3 = (bmap == 0) ? 0 : bmap;
-#define B3_LAUNCH(MD, NTT, NTB, SG)                                                              \
-  hipLaunchKernelGGL((swk::k_bsr_mfma3<MD, NTT, NTB, SG>), grid3, dim3(SW_BLOCK), 0, h->stream,   \
-                     (const cplx*)op.bsr_vals, (const int*)op.bsr_kcol, op.bsr_KS, RT, X, B, Y, nbp, \
-                     w, bm3, msub, (const int*)op.bsr_tmap, xr)
-#define B3_NT(MD, NTB, SG)                        \
-  do {                                            \
-    if (NT3 == 4) B3_LAUNCH(MD, 4, NTB, SG);      \
-    else if (NT3 == 2) B3_LAUNCH(MD, 2, NTB, SG); \
-    else B3_LAUNCH(MD, 1, NTB, SG);               \
-  } while (0)
-    if (!ntio3 && mode == 0 && want >= 16 && NT3 == 1 && op.bsr_KS % 16 == 0) B3_LAUNCH(0, 1, false, 16);
-    else if (!ntio3 && mode == 0 && want >= 8) B3_NT(0, false, 8);
-    else if (mode == 0) { if (ntio3) B3_NT(0, true, 4); else B3_NT(0, false, 4); }
-    else if (mode == 1) { if (ntio3) B3_NT(1, true, 4); else B3_NT(1, false, 4); }
-    else { if (ntio3) B3_NT(3, true, 4); else B3_NT(3, false, 4); }
-#undef B3_NT
-#undef B3_LAUNCH
-    KLAUNCH_CHECK();
-    return 0;
+    auto b3 = [&](auto MD, auto NTT, auto NTB, auto SG) {
+      return launch(h, cls, swk::k_bsr_mfma3<MD, NTT, NTB, SG>, grid3, dim3(SW_BLOCK), (const cplx*)op.bsr_vals,
+                    (const int*)op.bsr_kcol, op.bsr_KS, RT, X, B, Y, nbp, w, bm3, msub, (const int*)op.bsr_tmap, xr);
+    };
+    if (!ntio3 && mode == 0 && want >= 16 && NT3 == 1 && op.bsr_KS % 16 == 0)
+      return b3(IntC<0>{}, IntC<1>{}, IntC<0>{}, IntC<16>{});
+    if (!ntio3 && mode == 0 && want >= 8)
+      return pick<4, 2, 1>(NT3, [&](auto NTT) { return b3(IntC<0>{}, NTT, IntC<0>{}, IntC<8>{}); });
+    return pick<0, 1, 3>(mode, [&](auto MD) {
+      return pick<4, 2, 1>(NT3, [&](auto NTT) {
+        return pick<0, 1>(ntio3, [&](auto NTB) { return b3(MD, NTT, NTB, IntC<4>{}); });
+      });
+    });
   }
-  const double* Xr = (const double*)X;
-  const double* Br = (const double*)B;
-  double* Yr = (double*)Y;
-#define BSR_LAUNCH_S(MD, NTT, NTB, SG)                                                           \
-  hipLaunchKernelGGL((swk::k_bsr_mfma<MD, NTT, NTB, SG>), grid, dim3(SW_BLOCK), 0, h->stream,   \
-                     (const cplx*)op.bsr_vals, (const int*)op.bsr_kcol, op.bsr_KS, RT, Xr, Br,   \
-                     Yr, 2 * nbp, nbp, w, bmap, msub, (const int*)op.bsr_tmap,                  \
-                     (op.bsr_diag_last && h->bsr_xreg) ? 1 : 0)
-#define BSR_LAUNCH(MD, NTT)                                                                     \
-  do {                                                                                          \
-    const bool ntio_ = h->bsr_nt && cat != T_COARSEST;                                          \
-    if (stages == 8) {                                                                          \
-      if (ntio_) BSR_LAUNCH_S(MD, NTT, true, 8);                                                \
-      else BSR_LAUNCH_S(MD, NTT, false, 8);                                                     \
-    } else if (stages == 4) {                                                                   \
-      if (ntio_) BSR_LAUNCH_S(MD, NTT, true, 4);                                                \
-      else BSR_LAUNCH_S(MD, NTT, false, 4);                                                     \
-    } else {                                                                                    \
-      if (ntio_) BSR_LAUNCH_S(MD, NTT, true, 2);                                                \
-      else BSR_LAUNCH_S(MD, NTT, false, 2);                                                     \
-    }                                                                                           \
-  } while (0)
-  if (NT == 2) {
-    if (mode == 0) BSR_LAUNCH(0, 2);
-    else if (mode == 1) BSR_LAUNCH(1, 2);
-    else BSR_LAUNCH(3, 2);
-  } else {
-    if (mode == 0) BSR_LAUNCH(0, 4);
-    else if (mode == 1) BSR_LAUNCH(1, 4);
-    else BSR_LAUNCH(3, 4);
-  }
-#undef BSR_LAUNCH
-#undef BSR_LAUNCH_S
-  KLAUNCH_CHECK();
-  return 0;
+  const bool ntio = h->bsr_nt && cat != T_COARSEST;
+  const int xr = (op.bsr_diag_last && h->bsr_xreg) ? 1 : 0;
+  return pick<0, 1, 3>(mode, [&](auto MD) {
+    return pick<2, 4>(NT, [&](auto NTT) {
+      return pick<0, 1>(ntio, [&](auto NTB) {
+        return pick<8, 4, 2>(stages, [&](auto SG) {
+          return launch(h, cls, swk::k_bsr_mfma<MD, NTT, NTB, SG>, grid, dim3(SW_BLOCK), (const cplx*)op.bsr_vals,
+                        (const int*)op.bsr_kcol, op.bsr_KS, RT, (const double*)X, (const double*)B, (double*)Y,
+                        2 * nbp, nbp, w, bmap, msub, (const int*)op.bsr_tmap, xr);
+        });
+      });
+    });
+  });
 }
 
-// even_only: write the rows of the even sites only (prolongation before an even-odd smoother)
+// The grouped-ELL kernel of an operator (T = cplx: fp64 values, cplxf: their complex64 mirror).  even_only:
+// write the rows of the even sites only (prolongation before an even-odd smoother)
+template <class T>
+static int launch_ell_groups(sw_engine* h, const EllOp& op, const T* vals, int mode, const T* X, const T* B, T* Y,
+                             int nbp, int cat, T w, bool even_only) {
+  const bool ev = even_only && op.order_even && h->p_even;
+  const int ng = ev ? op.ngroups_even : op.ngroups;
+  const int* ord = ev ? op.order_even : (h->ell_order ? op.order : nullptr);
+  const dim3 grid((ng + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK, nbp / 64);
+  if (op.G != 1 && op.G != 2 && op.G != 4 && op.G != 8 && op.G != 16)
+    return sw_fail(h, "unsupported ELL group size %d", op.G);
+  return pick<1, 2, 4, 8, 16>(op.G, [&](auto G) {
+    return pick<0, 1, 2, 3>(mode, [&](auto MODE) {
+      return launch(h, cat, swk::k_ell<G, MODE, T>, grid, dim3(SW_BLOCK), (const int*)op.cols, vals, op.K, ng, ord,
+                    X, B, Y, nbp, w);
+    });
+  });
+}
+
 static int launch_ell(sw_engine* h, const EllOp& op, int mode, const cplx* X, const cplx* B,
                       cplx* Y, int nbp, int cat, cplx w = cplx{0.0, 0.0}, bool even_only = false) {
   if (!op.set) return sw_fail(h, "operator not set");
@@ -751,38 +897,7 @@ static int launch_ell(sw_engine* h, const EllOp& op, int mode, const cplx* X, co
   if (!op.cols || !op.vals)
     return sw_fail(h, "operator exists in MFMA block-row form only (built on the device): it needs "
                       "use_mfma = mfma_ops = 1");
-  const bool ev = even_only && op.order_even && h->p_even;
-  const int ng = ev ? op.ngroups_even : op.ngroups;
-  const int* ord = ev ? op.order_even : (h->ell_order ? op.order : nullptr);
-  dim3 grid((ng + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK, nbp / 64);
-  LaunchScope ls(h, cat);
-#define ELL_CASE(GG)                                                                            \
-  case GG:                                                                                      \
-    if (mode == 0)                                                                              \
-      hipLaunchKernelGGL((swk::k_ell<GG, 0>), grid, dim3(SW_BLOCK), 0, h->stream, op.cols,      \
-                         op.vals, op.K, ng, ord, X, B, Y, nbp, w);      \
-    else if (mode == 1)                                                                         \
-      hipLaunchKernelGGL((swk::k_ell<GG, 1>), grid, dim3(SW_BLOCK), 0, h->stream, op.cols,      \
-                         op.vals, op.K, ng, ord, X, B, Y, nbp, w);      \
-    else if (mode == 2)                                                                         \
-      hipLaunchKernelGGL((swk::k_ell<GG, 2>), grid, dim3(SW_BLOCK), 0, h->stream, op.cols,      \
-                         op.vals, op.K, ng, ord, X, B, Y, nbp, w);      \
-    else                                                                                        \
-      hipLaunchKernelGGL((swk::k_ell<GG, 3>), grid, dim3(SW_BLOCK), 0, h->stream, op.cols,      \
-                         op.vals, op.K, ng, ord, X, B, Y, nbp, w);      \
-    break;
-  switch (op.G) {
-    ELL_CASE(1)
-    ELL_CASE(2)
-    ELL_CASE(4)
-    ELL_CASE(8)
-    ELL_CASE(16)
-    default:
-      return sw_fail(h, "unsupported ELL group size %d", op.G);
-  }
-#undef ELL_CASE
-  KLAUNCH_CHECK();
-  return 0;
+  return launch_ell_groups<cplx>(h, op, op.vals, mode, X, B, Y, nbp, cat, w, even_only);
 }
 
 static int launch_bsr(sw_engine* h, const EllOp& op, int mode, const cplx* X, const cplx* B, cplx* Y,
@@ -853,35 +968,24 @@ static swk::StencilArgsT<C> stencil_args(sw_engine* h, const Level& lv, int nbp,
 template <class CI, class CO>
 static int launch_stencil(sw_engine* h, Level& lv, int mode, const CI* X, const cplx* B, CO* Y,
                           int nbp, cplx w) {
-  {
-    swk::StencilArgs a = stencil_args<cplx>(h, lv, nbp, false);
-    a.w = w;
-    const int spw = stencil_spw(h, a.tile_w);
-    const int V = lv.L * lv.L;
-    const int waves = V / spw;
-    const int bpc = (waves + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK;
-    const int nchunks = nbp / 64;
-    LaunchScope ls(h, mode == 0 ? T_STENCIL : (mode == 1 ? T_STENCIL_RES : T_STENCIL_SM));
-#define ST_LAUNCH(MD, SP)                                                                       \
-  hipLaunchKernelGGL((swk::k_stencil<MD, SP, CI, CO>), dim3(bpc * nchunks), dim3(SW_BLOCK), 0, h->stream, \
-                     X, B, Y, a, bpc)
-#define ST_MODE(SP)                                                  \
-  do {                                                               \
-    if (mode == 0) ST_LAUNCH(0, SP);                                 \
-    else if constexpr (std::is_same<CI, cplx>::value && std::is_same<CO, cplx>::value) { \
-      if (mode == 1) ST_LAUNCH(1, SP);                               \
-      else ST_LAUNCH(2, SP);                                         \
-    } else return sw_fail(h, "internal: complex64 stencil input supports Y = A X only"); \
-  } while (0)
-    if (spw == 8) ST_MODE(8);
-    else if (spw == 4) ST_MODE(4);
-    else if (spw == 2) ST_MODE(2);
-    else ST_MODE(1);
-#undef ST_MODE
-#undef ST_LAUNCH
-    KLAUNCH_CHECK();
-    return 0;
-  }
+  swk::StencilArgs a = stencil_args<cplx>(h, lv, nbp, false);
+  a.w = w;
+  const int spw = stencil_spw(h, a.tile_w);
+  const int V = lv.L * lv.L;
+  const int waves = V / spw;
+  const int bpc = (waves + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK;
+  const int nchunks = nbp / 64;
+  const int cat = mode == 0 ? T_STENCIL : (mode == 1 ? T_STENCIL_RES : T_STENCIL_SM);
+  return pick<8, 4, 2, 1>(spw, [&](auto SP) {
+    auto go = [&](auto MD) {
+      return launch(h, cat, swk::k_stencil<MD, SP, CI, CO>, dim3(bpc * nchunks), dim3(SW_BLOCK), X, B, Y, a, bpc);
+    };
+    if (mode == 0) return go(IntC<0>{});
+    if constexpr (std::is_same<CI, cplx>::value && std::is_same<CO, cplx>::value)
+      return pick<1, 2>(mode, go);
+    else
+      return sw_fail(h, "internal: complex64 stencil input supports Y = A X only");
+  });
 }
 
 // Y = A X (mode 0), Y = B - A X (mode 1) or Y = X + w (B - A X) (mode 2) at a level
@@ -897,7 +1001,6 @@ static int apply_op(sw_engine* h, Level& lv, int mode, const cplx* X, const cplx
 // (165 -> 214 probe-samples/s); beyond ~1500 the second reduction stage grows faster than the first shrinks.
 // With four or more probe chunks 128 row blocks already make 512+ workgroups, and the second stage
 // (k_reduce_partials: 5 us at 128 partials, 17 us at 256) would eat what the first gains.
-static int g_dot_blocks = 1024, g_dot_pmax = 1024;
 static void row_blocking(int n, int nbp, bool reduce, int* P, int* rpb) {
   const int nchunks = nbp / 64;
   int p;
@@ -937,11 +1040,8 @@ static swk::RedArgs red_args(sw_engine* h, bool fused, int P, int K, int nbp, cp
   return ra;
 }
 static int launch_tail(sw_engine* h, const swk::FgTail& tail) {
-  LaunchScope ls(h, T_OTHER);
   const int nbp = tail.s.nbp, tb = 256;
-  hipLaunchKernelGGL(swk::k_fg_tail, dim3((nbp + tb - 1) / tb), dim3(tb), 0, h->stream, tail);
-  KLAUNCH_CHECK();
-  return 0;
+  return launch(h, T_OTHER, swk::k_fg_tail, dim3((nbp + tb - 1) / tb), dim3(tb), tail);
 }
 
 // out[k][col] = sum_r conj(V_k[r]) W[r],  k < K
@@ -958,27 +1058,13 @@ static int multidot(sw_engine* h, const swk::PtrListT<CV>& V, int K, const CV* W
   const swk::RedArgs ra = red_args(h, fused, P, K, nbp, out, svec, coef);
   const swk::FgTail tl = (fused && tail) ? *tail : kNoTail;
   dim3 grid(P, nbp / 64);
-  {
-    LaunchScope ls(h, T_DOTS);
-#define MD_CASE(KT)                                                                             \
-  hipLaunchKernelGGL((swk::k_multidot<KT, CV>), grid, dim3(SW_BLOCK), 0, h->stream, V, K, W, n, nbp, \
-                     rpb, h->partial, ra, tl)
-    if (K <= 2) MD_CASE(2);
-    else if (K <= 4) MD_CASE(4);
-    else if (K <= 8) MD_CASE(8);
-    else if (K <= 16) MD_CASE(16);
-    else if (K <= 24) MD_CASE(24);
-    else MD_CASE(34);
-#undef MD_CASE
-    KLAUNCH_CHECK();
-  }
+  SWCHK(pick_ge<2, 4, 8, 16, 24, 34>(K, [&](auto KT) {
+    return launch(h, T_DOTS, swk::k_multidot<KT, CV>, grid, dim3(SW_BLOCK), V, K, W, n, nbp, rpb, h->partial, ra,
+                  tl);
+  }));
   if (fused) return 0;
-  {
-    LaunchScope ls(h, T_DOTS);
-    hipLaunchKernelGGL(swk::k_reduce_partials, dim3(K, nbp / 64), dim3(SW_BLOCK), 0, h->stream,
-                       h->partial, P, K, nbp, out, svec, coef);
-    KLAUNCH_CHECK();
-  }
+  SWCHK(launch(h, T_DOTS, swk::k_reduce_partials, dim3(K, nbp / 64), dim3(SW_BLOCK), h->partial, P, K, nbp, out,
+               svec, coef));
   if (tail) SWCHK(launch_tail(h, *tail));
   return 0;
 }
@@ -996,16 +1082,9 @@ static int multigram(sw_engine* h, const PtrList& U, int NV, int n, int nbp, cpl
   const swk::RedArgs ra = red_args(h, true, P, K, nbp, out, nullptr, nullptr);
   const swk::FgTail tl = tail ? *tail : kNoTail;
   dim3 grid(P, nbp / 64);
-  LaunchScope ls(h, T_DOTS);
-#define GR_CASE(NN) hipLaunchKernelGGL((swk::k_gram<NN>), grid, dim3(SW_BLOCK), 0, h->stream, U, n, nbp, rpb, \
-                                       h->partial, ra, tl)
-  if (NV == 2) GR_CASE(2);
-  else if (NV == 3) GR_CASE(3);
-  else if (NV == 4) GR_CASE(4);
-  else GR_CASE(5);
-#undef GR_CASE
-  KLAUNCH_CHECK();
-  return 0;
+  return pick<2, 3, 4, 5>(NV, [&](auto NN) {
+    return launch(h, T_DOTS, swk::k_gram<NN>, grid, dim3(SW_BLOCK), U, n, nbp, rpb, h->partial, ra, tl);
+  });
 }
 
 // Wout = Win + sign * sum_k coef[k] V_k ; optional nrm[col].x = ||Wout||^2
@@ -1023,31 +1102,16 @@ static int multiaxpy(sw_engine* h, const swk::PtrListT<CV>& V, int K, const cplx
   const swk::RedArgs ra = red_args(h, fused, P, 1, nbp, nrm_out, nullptr, nullptr);
   const swk::FgTail tl = (fused && tail) ? *tail : kNoTail;
   dim3 grid(P, nbp / 64);
-  {
-    LaunchScope ls(h, T_AXPY);
-#define MA_CASE(KT)                                                                              \
-  do {                                                                                           \
-    if (nrm_out)                                                                                 \
-      hipLaunchKernelGGL((swk::k_multiaxpy<KT, true, CV, CW>), grid, dim3(SW_BLOCK), 0, h->stream, V, K, \
-                         coef, sign, Win, Wout, n, nbp, rpb, h->partial, w32, ra, tl);           \
-    else                                                                                         \
-      hipLaunchKernelGGL((swk::k_multiaxpy<KT, false, CV, CW>), grid, dim3(SW_BLOCK), 0, h->stream, V, \
-                         K, coef, sign, Win, Wout, n, nbp, rpb, h->partial, w32, ra, tl);        \
-  } while (0)
-    if (K <= 2) MA_CASE(2);
-    else if (K <= 4) MA_CASE(4);
-    else if (K <= 8) MA_CASE(8);
-    else if (K <= 16) MA_CASE(16);
-    else if (K <= 24) MA_CASE(24);
-    else MA_CASE(34);
-#undef MA_CASE
-    KLAUNCH_CHECK();
-  }
+  SWCHK(pick_ge<2, 4, 8, 16, 24, 34>(K, [&](auto KT) {
+    if (nrm_out)
+      return launch(h, T_AXPY, swk::k_multiaxpy<KT, true, CV, CW>, grid, dim3(SW_BLOCK), V, K, coef, sign, Win, Wout,
+                    n, nbp, rpb, h->partial, w32, ra, tl);
+    return launch(h, T_AXPY, swk::k_multiaxpy<KT, false, CV, CW>, grid, dim3(SW_BLOCK), V, K, coef, sign, Win, Wout,
+                  n, nbp, rpb, h->partial, w32, ra, tl);
+  }));
   if (nrm_out && !fused) {
-    LaunchScope ls(h, T_DOTS);
-    hipLaunchKernelGGL(swk::k_reduce_partials, dim3(1, nbp / 64), dim3(SW_BLOCK), 0, h->stream,
-                       h->partial, P, 1, nbp, nrm_out, (const cplx*)nullptr, (cplx*)nullptr);
-    KLAUNCH_CHECK();
+    SWCHK(launch(h, T_DOTS, swk::k_reduce_partials, dim3(1, nbp / 64), dim3(SW_BLOCK), h->partial, P, 1, nbp,
+                 nrm_out, (const cplx*)nullptr, (cplx*)nullptr));
   }
   if (tail && !fused) SWCHK(launch_tail(h, *tail));
   return 0;
@@ -1184,20 +1248,11 @@ static int mr_smooth(sw_engine* h, Level& lv, cplx* X, cplx* R, int nu, int nbp)
     pl.p[0] = R;
     pl.p[1] = lv.t;
     SWCHK(multidot(h, pl, 2, lv.t, lv.n, nbp, d));
-    {
-      LaunchScope ls(h, T_DOTS);
-      hipLaunchKernelGGL(swk::k_mr_alpha, dim3((nbp + 255) / 256), dim3(256), 0, h->stream, d, nbp,
-                         alpha);
-      KLAUNCH_CHECK();
-    }
+    SWCHK(launch(h, T_DOTS, swk::k_mr_alpha, dim3((nbp + 255) / 256), dim3(256), d, nbp, alpha));
     int P, rpb;
     row_blocking(lv.n, nbp, false, &P, &rpb);
-    {
-      LaunchScope ls(h, T_AXPY);
-      hipLaunchKernelGGL(swk::k_mr_update, dim3(P, nbp / 64), dim3(SW_BLOCK), 0, h->stream, alpha,
-                         X, R, lv.t, lv.n, nbp, rpb);
-      KLAUNCH_CHECK();
-    }
+    SWCHK(launch(h, T_AXPY, swk::k_mr_update, dim3(P, nbp / 64), dim3(SW_BLOCK), alpha, X, R, lv.t, lv.n, nbp,
+                 rpb));
   }
   return 0;
 }
@@ -1209,11 +1264,9 @@ static int rich_steps(sw_engine* h, Level& lv, const cplx* Bin, cplx* cur, cplx*
                       cplx** result) {
   size_t k = 0;
   if (from_zero && !w.empty()) {
-    LaunchScope ls(h, T_AXPY);
     const size_t count = (size_t)lv.n * nbp;
-    hipLaunchKernelGGL(swk::k_cscale, dim3(2048), dim3(SW_BLOCK), 0, h->stream,
-                       cplx{w[0].real(), w[0].imag()}, Bin, cur, count);
-    KLAUNCH_CHECK();
+    SWCHK(launch(h, T_AXPY, swk::k_cscale, dim3(2048), dim3(SW_BLOCK), cplx{w[0].real(), w[0].imag()}, Bin, cur,
+                 count));
     k = 1;
   }
   for (; k < w.size(); ++k) {
@@ -1227,11 +1280,7 @@ static int rich_steps(sw_engine* h, Level& lv, const cplx* Bin, cplx* cur, cplx*
 static int vcycle_rich(sw_engine* h, Hier& H, int l, const cplx* Bin, cplx* Xout, int nbp);
 
 static int vec_add(sw_engine* h, const cplx* a, const cplx* b, cplx* dst, int n, int nbp) {
-  LaunchScope ls(h, T_AXPY);
-  hipLaunchKernelGGL(swk::k_add, dim3(2048), dim3(SW_BLOCK), 0, h->stream, a, b, dst,
-                     (size_t)n * nbp);
-  KLAUNCH_CHECK();
-  return 0;
+  return launch(h, T_AXPY, swk::k_add, dim3(2048), dim3(SW_BLOCK), a, b, dst, (size_t)n * nbp);
 }
 
 // E = gm_cycles x GMRES(gm_m) applied to A_l e = R from a zero guess (unpreconditioned).  With two cycles
@@ -1456,18 +1505,15 @@ static int eo_hop(sw_engine* h, Level& lv, const cplx* B, const cplx* src, cplx*
   const swk::StencilArgs a = stencil_args<cplx>(h, lv, nbp, true);
   const int bpc = (a.Vh + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK;
   const double di = 1.0 / a.diag;
-  LaunchScope ls(h, T_SCHUR);
   if (h->profiling) h->twork[T_SCHUR] += (double)a.Vh * (96.0 * nbp + 64.0);
-  hipLaunchKernelGGL((swk::k_eo_hop<HOP>), dim3(bpc * (nbp / 64)), dim3(SW_BLOCK), 0, h->stream, B, src, out, a,
-                     HOP == 0 ? 1.0 : di, di, bpc);
-  KLAUNCH_CHECK();
-  return 0;
+  return launch(h, T_SCHUR, swk::k_eo_hop<HOP, cplx>, dim3(bpc * (nbp / 64)), dim3(SW_BLOCK), B, src, out, a,
+                HOP == 0 ? 1.0 : di, di, bpc);
 }
 
-// One k_schur_step launch on the stencil level (fp64) on the lattice rows a.row0 .. a.row0 + a.nrows - 1
+// One k_schur_step launch (class cat) on the stencil level (fp64) on the lattice rows a.row0 .. a.row0 + a.nrows - 1
 // (a.nrows = 0: all)
 template <int MODE>
-static int launch_schur_step(sw_engine* h, swk::StencilArgs& a, const cplx* src, const cplx* bp, cplx* dst,
+static int launch_schur_step(sw_engine* h, int cat, swk::StencilArgs& a, const cplx* src, const cplx* bp, cplx* dst,
                              int nbp) {
   const int items = (a.nrows > 0 ? a.nrows : a.L) * (a.L / 2);
   if (h->eo_tile > 0 && (MODE == 0 || MODE == 3) && a.nrows == 0 && a.L % 8 == 0) {
@@ -1480,19 +1526,11 @@ static int launch_schur_step(sw_engine* h, swk::StencilArgs& a, const cplx* src,
     int grid = std::min(h->num_cus, njobs);
     grid = std::max(8, (grid + 7) & ~7);
     if (h->eo_tile == 8)
-      hipLaunchKernelGGL((swk::k_schur_tile<TM, 8>), dim3(grid), dim3(512), 0, h->stream, src, dst, at, tiles_v,
-                         ntiles, njobs);
-    else
-      hipLaunchKernelGGL((swk::k_schur_tile<TM, 4>), dim3(grid), dim3(256), 0, h->stream, src, dst, at, tiles_v,
-                         ntiles, njobs);
-    KLAUNCH_CHECK();
-    return 0;
+      return launch(h, cat, swk::k_schur_tile<TM, 8>, dim3(grid), dim3(512), src, dst, at, tiles_v, ntiles, njobs);
+    return launch(h, cat, swk::k_schur_tile<TM, 4>, dim3(grid), dim3(256), src, dst, at, tiles_v, ntiles, njobs);
   }
   const int bpc = (items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK;
-  hipLaunchKernelGGL((swk::k_schur_step<cplx, MODE>), dim3(bpc * (nbp / 64)), dim3(SW_BLOCK), 0, h->stream, src,
-                     bp, dst, a, bpc);
-  KLAUNCH_CHECK();
-  return 0;
+  return launch(h, cat, swk::k_schur_step<cplx, MODE>, dim3(bpc * (nbp / 64)), dim3(SW_BLOCK), src, bp, dst, a, bpc);
 }
 
 // strip height of the time-skewed order for nu launches that each reach two lattice rows (0: plain order),
@@ -1546,10 +1584,9 @@ static int schur_steps(sw_engine* h, Level& lv, cplx* cur, cplx* nxt, const cplx
     a.row0 = row0;
     a.nrows = nrows;
     const int items = (nrows > 0 ? nrows : L) * (L / 2);
-    LaunchScope ls(h, T_SCHUR);
     // algorithmic bytes: three half-vector rows per even site and spin (x_e, b'_e in, x_e out) + links
     if (h->profiling) h->twork[T_SCHUR] += (double)items * (96.0 * cw + 64.0);
-    return launch_schur_step<2>(h, a, src + c0, bp + c0, dst + c0, cw);
+    return launch_schur_step<2>(h, T_SCHUR, a, src + c0, bp + c0, dst + c0, cw);
   };
   const int H = skew_height(h, lv, nu, nbp, &cw);      // 0 = no skewing
   if (H == 0) {
@@ -1597,20 +1634,19 @@ static int schur_product_steps(sw_engine* h, Level& lv, cplx* x, cplx* va, cplx*
     a.row0 = row0;
     a.nrows = nrows;
     const int items = (nrows > 0 ? nrows : L) * (L / 2);
-    LaunchScope ls(h, T_SCHUR);
     if (k == 0) {
       if (h->profiling) h->twork[T_SCHUR] += (double)items * (96.0 * cw + 64.0);
-      return launch_schur_step<1>(h, a, x + c0, bp + c0, buf[0] + c0, cw);
+      return launch_schur_step<1>(h, T_SCHUR, a, x + c0, bp + c0, buf[0] + c0, cw);
     }
     const std::complex<double> u = lv.q_w[k - 1];
     a.w = cplx{u.real(), u.imag()};
     if (k < nu - 1) {
       if (h->profiling) h->twork[T_SCHUR] += (double)items * (64.0 * cw + 64.0);
-      return launch_schur_step<3>(h, a, buf[(k + 1) & 1] + c0, nullptr, buf[k & 1] + c0, cw);
+      return launch_schur_step<3>(h, T_SCHUR, a, buf[(k + 1) & 1] + c0, nullptr, buf[k & 1] + c0, cw);
     }
     a.w2 = cplx{lv.q_beta.real(), lv.q_beta.imag()};
     if (h->profiling) h->twork[T_SCHUR] += (double)items * (96.0 * cw + 64.0);
-    return launch_schur_step<4>(h, a, buf[(k + 1) & 1] + c0, x + c0, x + c0, cw);
+    return launch_schur_step<4>(h, T_SCHUR, a, buf[(k + 1) & 1] + c0, x + c0, x + c0, cw);
   };
   const int H = skew_height(h, lv, nu, nbp, &cw);
   if (H == 0) {
@@ -1718,11 +1754,8 @@ static int vcycle_rich(sw_engine* h, Hier& H, int l, const cplx* Bin, cplx* Xout
 // ---------------------------------------------------------------------------------------------
 template <class CI, class CO>
 static int cast_vec(sw_engine* h, const CI* src, CO* dst, size_t count, int cat = T_OTHER) {
-  LaunchScope ls(h, cat);
-  hipLaunchKernelGGL((swk::k_cast<CI, CO>), dim3((unsigned)((count + SW_BLOCK - 1) / SW_BLOCK)),
-                     dim3(SW_BLOCK), 0, h->stream, src, dst, count);
-  KLAUNCH_CHECK();
-  return 0;
+  return launch(h, cat, swk::k_cast<CI, CO>, dim3((unsigned)((count + SW_BLOCK - 1) / SW_BLOCK)), dim3(SW_BLOCK),
+                src, dst, count);
 }
 
 static int mirror_op32(sw_engine* h, EllOp& op) {
@@ -1800,56 +1833,29 @@ static int launch_bsr32(sw_engine* h, const EllOp& op, int mode, const cplxf* X,
   const int cls = cat == T_COARSEST ? T_MFMA_DENSE
                                     : (cat == T_MVM ? (op.nrows == n1 || n1 == 0 ? T_MFMA_OP : T_MFMA_OP2)
                                                     : cat);
-  LaunchScope ls(h, cls);
   if (h->profiling) h->twork[cls] += 512.0 * (double)RT * (double)op.bsr_KS * (double)nbp;
   if ((h->f32_splitk == 1 && cat == T_COARSEST) ||
       (h->f32_splitk == 2 && (long long)RT * (nbp / 64) < 4096 && op.bsr_KS >= 16)) {
     // few (tile, chunk) pairs: four waves per pair, each a quarter of the k-steps
     const int NTs = (h->f32_tiles == 1) ? 1 : 2;
     const dim3 gsk(RT * (nbp / (16 * NTs)));
-#define SKF_LAUNCH(MD, NTT)                                                                       \
-  hipLaunchKernelGGL((swk::k_bsr_mfma_f32_sk<MD, NTT>), gsk, dim3(SW_BLOCK), 0, h->stream,         \
-                     (const cplxf*)op.bsr_vals32, (const int*)op.bsr_kcol, op.bsr_KS, RT, X, B, Y, \
-                     nbp, w, (const int*)op.bsr_tmap)
-#define SKF_MODE(NTT)                      \
-  do {                                     \
-    if (mode == 0) SKF_LAUNCH(0, NTT);     \
-    else if (mode == 1) SKF_LAUNCH(1, NTT); \
-    else SKF_LAUNCH(3, NTT);               \
-  } while (0)
-    if (NTs == 1) SKF_MODE(1);
-    else SKF_MODE(2);
-#undef SKF_MODE
-#undef SKF_LAUNCH
-    KLAUNCH_CHECK();
-    return 0;
+    return pick<1, 2>(NTs, [&](auto NTT) {
+      return pick<0, 1, 3>(mode, [&](auto MD) {
+        return launch(h, cls, swk::k_bsr_mfma_f32_sk<MD, NTT>, gsk, dim3(SW_BLOCK), (const cplxf*)op.bsr_vals32,
+                      (const int*)op.bsr_kcol, op.bsr_KS, RT, X, B, Y, nbp, w, (const int*)op.bsr_tmap);
+      });
+    });
   }
   const dim3 grid(RBn * NCn);
   const int stg = (cat == T_COARSEST) ? h->f32_dense_stages : h->f32_stages;
-#define BSRF_LAUNCH(MD, NTT, SG)                                                                  \
-  hipLaunchKernelGGL((swk::k_bsr_mfma_f32<MD, NTT, SG>), grid, dim3(SW_BLOCK), 0, h->stream,      \
-                     (const cplxf*)op.bsr_vals32, (const int*)op.bsr_kcol, op.bsr_KS, RT, X, B, Y, \
-                     nbp, w, bmap, (const int*)op.bsr_tmap)
-#define BSRF_STG(MD, NTT)                      \
-  do {                                         \
-    if (stg >= 8) BSRF_LAUNCH(MD, NTT, 8);     \
-    else if (stg >= 4) BSRF_LAUNCH(MD, NTT, 4); \
-    else BSRF_LAUNCH(MD, NTT, 2);              \
-  } while (0)
-#define BSRF_MODE(NTT)                         \
-  do {                                         \
-    if (mode == 0) BSRF_STG(0, NTT);           \
-    else if (mode == 1) BSRF_STG(1, NTT);      \
-    else BSRF_STG(3, NTT);                     \
-  } while (0)
-  if (NT == 4) BSRF_MODE(4);
-  else if (NT == 2) BSRF_MODE(2);
-  else BSRF_MODE(1);
-#undef BSRF_MODE
-#undef BSRF_STG
-#undef BSRF_LAUNCH
-  KLAUNCH_CHECK();
-  return 0;
+  return pick<4, 2, 1>(NT, [&](auto NTT) {
+    return pick<0, 1, 3>(mode, [&](auto MD) {
+      return pick<8, 4, 2>(stg >= 8 ? 8 : (stg >= 4 ? 4 : 2), [&](auto SG) {
+        return launch(h, cls, swk::k_bsr_mfma_f32<MD, NTT, SG>, grid, dim3(SW_BLOCK), (const cplxf*)op.bsr_vals32,
+                      (const int*)op.bsr_kcol, op.bsr_KS, RT, X, B, Y, nbp, w, bmap, (const int*)op.bsr_tmap);
+      });
+    });
+  });
 }
 
 static int launch_ell32(sw_engine* h, const EllOp& op, int mode, const cplxf* X, const cplxf* B,
@@ -1859,38 +1865,7 @@ static int launch_ell32(sw_engine* h, const EllOp& op, int mode, const cplxf* X,
     return launch_bsr32(h, op, mode, X, B, Y, nbp, cat, w);
   if (!op.cols || !op.vals32)
     return sw_fail(h, "internal: complex64 mirror of a grouped-ELL operator missing");
-  const bool ev = even_only && op.order_even && h->p_even;
-  const int ng = ev ? op.ngroups_even : op.ngroups;
-  const int* ord = ev ? op.order_even : (h->ell_order ? op.order : nullptr);
-  dim3 grid((ng + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK, nbp / 64);
-  LaunchScope ls(h, cat);
-#define ELLF_CASE(GG)                                                                            \
-  case GG:                                                                                       \
-    if (mode == 0)                                                                               \
-      hipLaunchKernelGGL((swk::k_ell<GG, 0, cplxf>), grid, dim3(SW_BLOCK), 0, h->stream,         \
-                         (const int*)op.cols, (const cplxf*)op.vals32, op.K, ng, ord, X, B, Y, nbp, w); \
-    else if (mode == 1)                                                                          \
-      hipLaunchKernelGGL((swk::k_ell<GG, 1, cplxf>), grid, dim3(SW_BLOCK), 0, h->stream,         \
-                         (const int*)op.cols, (const cplxf*)op.vals32, op.K, ng, ord, X, B, Y, nbp, w); \
-    else if (mode == 2)                                                                          \
-      hipLaunchKernelGGL((swk::k_ell<GG, 2, cplxf>), grid, dim3(SW_BLOCK), 0, h->stream,         \
-                         (const int*)op.cols, (const cplxf*)op.vals32, op.K, ng, ord, X, B, Y, nbp, w); \
-    else                                                                                         \
-      hipLaunchKernelGGL((swk::k_ell<GG, 3, cplxf>), grid, dim3(SW_BLOCK), 0, h->stream,         \
-                         (const int*)op.cols, (const cplxf*)op.vals32, op.K, ng, ord, X, B, Y, nbp, w); \
-    break;
-  switch (op.G) {
-    ELLF_CASE(1)
-    ELLF_CASE(2)
-    ELLF_CASE(4)
-    ELLF_CASE(8)
-    ELLF_CASE(16)
-    default:
-      return sw_fail(h, "unsupported ELL group size %d", op.G);
-  }
-#undef ELLF_CASE
-  KLAUNCH_CHECK();
-  return 0;
+  return launch_ell_groups<cplxf>(h, op, op.vals32, mode, X, B, Y, nbp, cat, w, even_only);
 }
 
 // even-odd post-smoothing of the stencil level in complex64 (eo_smooth's twin).  C = cplxf2: two probes
@@ -1910,27 +1885,18 @@ static int eo_smooth32_t(sw_engine* h, Level& lv, const cplxf* Bin_, cplxf* star
   const float di = (float)(1.0 / (4.0 + lv.mass));
   const C* bp = reduced ? Bin : (const C*)lv.r32;
   if (!reduced) {
-    LaunchScope ls(h, T_SCHUR);
-    hipLaunchKernelGGL((swk::k_eo_hop<0, C>), grid, dim3(SW_BLOCK), 0, h->stream, Bin, Bin, (C*)lv.r32, a,
-                       1.0f, di, bpc);
-    KLAUNCH_CHECK();
+    SWCHK(launch(h, T_SCHUR, swk::k_eo_hop<0, C>, grid, dim3(SW_BLOCK), Bin, Bin, (C*)lv.r32, a, 1.0f, di, bpc));
   }
   C* cur = start;
   C* nxt = other;
   for (size_t k = 0; k < lv.w_eo.size(); ++k) {
     a.w = cplxf{(float)lv.w_eo[k].real(), (float)lv.w_eo[k].imag()};
-    LaunchScope ls(h, T_SCHUR);
-    hipLaunchKernelGGL((swk::k_schur_step<C>), grid, dim3(SW_BLOCK), 0, h->stream, (const C*)cur,
-                       (const C*)bp, nxt, a, bpc);
-    KLAUNCH_CHECK();
+    SWCHK(launch(h, T_SCHUR, swk::k_schur_step<C>, grid, dim3(SW_BLOCK), (const C*)cur, (const C*)bp, nxt, a, bpc));
     std::swap(cur, nxt);
   }
   if (cur != Xout) return sw_fail(h, "internal: even-odd smoother ended in the wrong buffer");
   if (!reduced) {
-    LaunchScope ls(h, T_SCHUR);
-    hipLaunchKernelGGL((swk::k_eo_hop<1, C>), grid, dim3(SW_BLOCK), 0, h->stream, Bin,
-                       (const C*)Xout, Xout, a, di, di, bpc);
-    KLAUNCH_CHECK();
+    SWCHK(launch(h, T_SCHUR, swk::k_eo_hop<1, C>, grid, dim3(SW_BLOCK), Bin, (const C*)Xout, Xout, a, di, di, bpc));
   }
   return 0;
 }
@@ -1948,11 +1914,8 @@ static int schur_apply32_t(sw_engine* h, Level& lv, const cplxf* X_, cplxf* Y_, 
   const swk::StencilArgsT<C> a = stencil_args<C>(h, lv, nbp, true);
   const int bpc = (a.Vh + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK;
   const dim3 grid(bpc * (a.nbp / 64));
-  LaunchScope ls(h, T_SCHUR_OP);
-  hipLaunchKernelGGL((swk::k_schur_step<C, 0>), grid, dim3(SW_BLOCK), 0, h->stream, (const C*)X_,
-                     (const C*)nullptr, (C*)Y_, a, bpc);
-  KLAUNCH_CHECK();
-  return 0;
+  return launch(h, T_SCHUR_OP, swk::k_schur_step<C, 0>, grid, dim3(SW_BLOCK), (const C*)X_, (const C*)nullptr,
+                (C*)Y_, a, bpc);
 }
 static int schur_apply32(sw_engine* h, Level& lv, const cplxf* X, cplxf* Y, int nbp) {
   if (nbp % 128 == 0 && h->f32_pairs) return schur_apply32_t<swk::cplxf2>(h, lv, X, Y, nbp);
@@ -2253,11 +2216,7 @@ static int fgmres_loop(sw_engine* h, Hier& H, int level, const KrylovSys& sys, c
       }
     }
     const int k = j;  // columns built in this cycle
-    {
-      LaunchScope ls(h, T_OTHER);
-      hipLaunchKernelGGL(swk::k_fg_solve, dim3(tg), dim3(tb), 0, h->stream, ws.sc, k);
-      KLAUNCH_CHECK();
-    }
+    SWCHK(launch(h, T_OTHER, swk::k_fg_solve, dim3(tg), dim3(tb), ws.sc, k));
     if (z32) {
       swk::PtrListT<cplxf> pz;
       for (int q = 0; q < k; ++q) pz.p[q] = ws.Z32 + vec * q;
@@ -2340,21 +2299,14 @@ static int pack_host(sw_engine* h, Level& lv, int nb, const double* Xhost, cplx*
   const size_t bytes = (size_t)nb * lv.n * sizeof(cplx);
   SWCHK(ensure_stage(h, bytes));
   HIPCHK(hipMemcpyAsync(h->stage, Xhost, bytes, hipMemcpyHostToDevice, h->stream));
-  LaunchScope ls(h, T_OTHER);
-  hipLaunchKernelGGL(swk::k_pack_c, dim3((lv.n + 63) / 64, nbp / 64), dim3(SW_BLOCK), 0, h->stream,
-                     (const cplx*)h->stage, nb, lv.n, (const int*)lv.rowmap, dst, nbp);
-  KLAUNCH_CHECK();
-  return 0;
+  return launch(h, T_OTHER, swk::k_pack_c, dim3((lv.n + 63) / 64, nbp / 64), dim3(SW_BLOCK), (const cplx*)h->stage,
+                nb, lv.n, (const int*)lv.rowmap, dst, nbp);
 }
 static int unpack_host(sw_engine* h, Level& lv, int nb, const cplx* src, double* Yhost, int nbp) {
   const size_t bytes = (size_t)nb * lv.n * sizeof(cplx);
   SWCHK(ensure_stage(h, bytes));
-  {
-    LaunchScope ls(h, T_OTHER);
-    hipLaunchKernelGGL(swk::k_unpack_c, dim3((lv.n + 63) / 64, nbp / 64), dim3(SW_BLOCK), 0,
-                       h->stream, src, nbp, lv.n, (const int*)lv.rowmap, (cplx*)h->stage, nb);
-    KLAUNCH_CHECK();
-  }
+  SWCHK(launch(h, T_OTHER, swk::k_unpack_c, dim3((lv.n + 63) / 64, nbp / 64), dim3(SW_BLOCK), src, nbp, lv.n,
+               (const int*)lv.rowmap, (cplx*)h->stage, nb));
   HIPCHK(hipMemcpyAsync(Yhost, h->stage, bytes, hipMemcpyDeviceToHost, h->stream));
   SWCHK(stream_sync(h));
   return 0;
@@ -2718,11 +2670,8 @@ int sw_setup_testvectors(sw_engine* h, int hid, int level, int nvec, uint64_t se
   if (!lv.tv2) SWCHK(dev_realloc(h, &lv.tv2, cnt));
   if (!lv.tv || seed != 0) {
     if (!lv.tv) SWCHK(dev_realloc(h, &lv.tv, cnt));
-    LaunchScope ls(h, T_OTHER);
-    hipLaunchKernelGGL(swk::k_fill_random, dim3((lv.n + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK),
-                       dim3(SW_BLOCK), 0, h->stream, lv.tv, lv.n, nbp, nvec,
-                       (unsigned long long)(seed ? seed : 7));
-    KLAUNCH_CHECK();
+    SWCHK(launch(h, T_OTHER, swk::k_fill_random, dim3((lv.n + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK),
+                 dim3(SW_BLOCK), lv.tv, lv.n, nbp, nvec, (unsigned long long)(seed ? seed : 7)));
   }
   // the solver's own restart in both modes: ONE Krylov workspace (2 m + 2 vectors of 64 columns, tens
   // of GB on a 1024^2 lattice) serves the setup and the solves that follow
@@ -2779,19 +2728,12 @@ int sw_setup_transfer(sw_engine* h, int hid, int level, int nblocks, int rpb, co
   SWCHK(dev_realloc(h, &R.vals, (size_t)qcount));
   cplx* Q = nullptr;
   SWCHK(dev_realloc(h, &Q, (size_t)qcount));
-  {
-    LaunchScope ls(h, T_OTHER);
-    dim3 grid((nblocks + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK);
-#define QR_LAUNCH(RPL)                                                                           \
-  hipLaunchKernelGGL((swk::k_block_qr<RPL>), grid, dim3(SW_BLOCK), 0, h->stream,                 \
-                     (const cplx*)lf.tv, 64, (const int*)R.cols, nblocks, rpb, Q, R.vals)
-    if (rpb <= 64) QR_LAUNCH(1);
-    else if (rpb <= 128) QR_LAUNCH(2);
-    else if (rpb <= 256) QR_LAUNCH(4);
-    else QR_LAUNCH(8);      // 8 x 8 aggregates of a block level (BASELINE config 5's 3-level hierarchy)
-#undef QR_LAUNCH
-    KLAUNCH_CHECK();
-  }
+  // rows per lane 1, 2, 4 or 8 (8 x 8 aggregates of a block level: BASELINE config 5's 3-level hierarchy)
+  SWCHK(pick_ge<64, 128, 256, 512>(rpb, [&](auto RPB) {
+    return launch(h, T_OTHER, swk::k_block_qr<RPB / 64>,
+                  dim3((nblocks + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK), dim3(SW_BLOCK), (const cplx*)lf.tv,
+                  64, (const int*)R.cols, nblocks, rpb, Q, R.vals);
+  }));
   R.set = true;
   // P: structure from the host (geometry), values gathered from Q
   EllOp& P = lf.P;
@@ -2813,12 +2755,8 @@ int sw_setup_transfer(sw_engine* h, int hid, int level, int nblocks, int rpb, co
   SWCHK(dev_realloc(h, &P.vals, pv));
   long long* dmap = nullptr;
   SWCHK(upload(h, &dmap, (const long long*)pmap, pv));
-  {
-    LaunchScope ls(h, T_OTHER);
-    hipLaunchKernelGGL(swk::k_fill_from_map, dim3(4096), dim3(SW_BLOCK), 0, h->stream,
-                       (const long long*)dmap, (const cplx*)Q, P.vals, pv);
-    KLAUNCH_CHECK();
-  }
+  SWCHK(launch(h, T_OTHER, swk::k_fill_from_map, dim3(4096), dim3(SW_BLOCK), (const long long*)dmap,
+               (const cplx*)Q, P.vals, pv));
   P.set = true;
   // the coarse image of the test vectors is the starting guess one level down
   if (!lc.tv) SWCHK(dev_realloc(h, &lc.tv, (size_t)n_c * 64));
@@ -2853,12 +2791,8 @@ int sw_setup_galerkin(sw_engine* h, int hid, int level, int Lc, const int32_t* n
   SWCHK(dev_realloc(h, &E, (size_t)n_c * nbp));
   SWCHK(dev_realloc(h, &X, (size_t)n_f * nbp));
   SWCHK(dev_realloc(h, &Y, (size_t)n_f * nbp));
-  {
-    LaunchScope ls(h, T_OTHER);
-    hipLaunchKernelGGL(swk::k_probe_unit, dim3((n_c + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK),
-                       dim3(SW_BLOCK), 0, h->stream, E, Lc, nbp);
-    KLAUNCH_CHECK();
-  }
+  SWCHK(launch(h, T_OTHER, swk::k_probe_unit, dim3((n_c + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK),
+               dim3(SW_BLOCK), E, Lc, nbp));
   SWCHK(launch_ell(h, lf.P, 0, E, nullptr, X, nbp, T_P));          // X = P E
   SWCHK(apply_op(h, lf, 0, X, nullptr, Y, nbp));                   // Y = A X
   SWCHK(launch_ell(h, lf.R, 0, Y, nullptr, E, nbp, T_R));          // Z = R Y  (over E)
@@ -2870,13 +2804,8 @@ int sw_setup_galerkin(sw_engine* h, int hid, int level, int Lc, const int32_t* n
   A.bsr_KS = 20;
   SWCHK(dev_realloc(h, &A.bsr_vals, (size_t)ncs * 20 * 64));
   SWCHK(dev_realloc(h, &A.bsr_kcol, (size_t)ncs * 20));
-  {
-    LaunchScope ls(h, T_OTHER);
-    hipLaunchKernelGGL(swk::k_bsr_from_probe, dim3((ncs * 20 + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK),
-                       dim3(SW_BLOCK), 0, h->stream, (const cplx*)E, nbp, (const int*)dnbr, Lc,
-                       A.bsr_vals, A.bsr_kcol);
-    KLAUNCH_CHECK();
-  }
+  SWCHK(launch(h, T_OTHER, swk::k_bsr_from_probe, dim3((ncs * 20 + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK),
+               dim3(SW_BLOCK), (const cplx*)E, nbp, (const int*)dnbr, Lc, A.bsr_vals, A.bsr_kcol));
   A.set = true;
   SWCHK(stream_sync(h));
   {
@@ -2994,19 +2923,15 @@ int sw_setup_invert_coarsest(sw_engine* h, int hid) {
   SWCHK(dev_realloc(h, &D, (size_t)n * n));
   HIPCHK(hipMemsetAsync(D, 0, (size_t)n * n * sizeof(cplx), h->stream));
   if (A.bsr_KS > 0 && !A.bsr_tmap) {
-    LaunchScope ls(h, T_OTHER);
     const int items = (n / 16) * A.bsr_KS;
-    hipLaunchKernelGGL(swk::k_bsr_to_dense, dim3((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK),
-                       dim3(SW_BLOCK), 0, h->stream, (const cplx*)A.bsr_vals, (const int*)A.bsr_kcol,
-                       n / 16, A.bsr_KS, n, D, (const int*)nullptr, (const int*)nullptr);
-    KLAUNCH_CHECK();
+    SWCHK(launch(h, T_OTHER, swk::k_bsr_to_dense, dim3((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK),
+                 dim3(SW_BLOCK), (const cplx*)A.bsr_vals, (const int*)A.bsr_kcol, n / 16, A.bsr_KS, n, D,
+                 (const int*)nullptr, (const int*)nullptr));
   } else if (A.cols && A.vals) {
     // a coarsest operator handed over as CSR (sw_set_csr: the reference hierarchy's R A P)
-    LaunchScope ls(h, T_OTHER);
     const size_t total = (size_t)A.ngroups * A.K * A.G;
-    hipLaunchKernelGGL(swk::k_ell_to_dense, dim3((unsigned)((total + SW_BLOCK - 1) / SW_BLOCK)), dim3(SW_BLOCK), 0,
-                       h->stream, (const int*)A.cols, (const cplx*)A.vals, A.K, A.G, A.ngroups, n, D);
-    KLAUNCH_CHECK();
+    SWCHK(launch(h, T_OTHER, swk::k_ell_to_dense, dim3((unsigned)((total + SW_BLOCK - 1) / SW_BLOCK)),
+                 dim3(SW_BLOCK), (const int*)A.cols, (const cplx*)A.vals, A.K, A.G, A.ngroups, n, D));
   } else {
     (void)dev_free(h, D);
     return sw_fail(h, "coarsest operator in neither grouped-ELL nor full block-row form");
@@ -3022,12 +2947,10 @@ int sw_setup_invert_coarsest(sw_engine* h, int hid) {
   SWCHK(dev_realloc(h, &op.bsr_vals, (size_t)RT * KS * 64));
   SWCHK(dev_realloc(h, &op.bsr_kcol, (size_t)RT * KS));
   {
-    LaunchScope ls(h, T_OTHER);
     const size_t items = (size_t)RT * KS;
-    hipLaunchKernelGGL(swk::k_dense_to_bsr, dim3((unsigned)((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK)),
-                       dim3(SW_BLOCK), 0, h->stream, (const cplx*)D, n, op.bsr_vals, op.bsr_kcol,
-                       (const int*)nullptr);
-    KLAUNCH_CHECK();
+    SWCHK(launch(h, T_OTHER, swk::k_dense_to_bsr,
+                 dim3((unsigned)((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK)), dim3(SW_BLOCK),
+                 (const cplx*)D, n, op.bsr_vals, op.bsr_kcol, (const int*)nullptr));
   }
   op.bsr_KS = KS;
   op.set = true;
@@ -3052,18 +2975,15 @@ int sw_get_coarsest_inv(sw_engine* h, int hid, double* dense) {
   SWCHK(dev_realloc(h, &D, (size_t)n * n));
   HIPCHK(hipMemsetAsync(D, 0, (size_t)n * n * sizeof(cplx), h->stream));
   if (op.bsr_KS > 0 && !op.bsr_tmap) {
-    LaunchScope ls(h, T_OTHER);
     const size_t items = (size_t)(n / 16) * op.bsr_KS;
-    hipLaunchKernelGGL(swk::k_bsr_to_dense, dim3((unsigned)((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK)),
-                       dim3(SW_BLOCK), 0, h->stream, (const cplx*)op.bsr_vals, (const int*)op.bsr_kcol, n / 16,
-                       op.bsr_KS, n, D, (const int*)nullptr, (const int*)nullptr);
-    KLAUNCH_CHECK();
+    SWCHK(launch(h, T_OTHER, swk::k_bsr_to_dense,
+                 dim3((unsigned)((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK)), dim3(SW_BLOCK),
+                 (const cplx*)op.bsr_vals, (const int*)op.bsr_kcol, n / 16, op.bsr_KS, n, D, (const int*)nullptr,
+                 (const int*)nullptr));
   } else if (op.cols && op.vals) {
-    LaunchScope ls(h, T_OTHER);
     const size_t total = (size_t)op.ngroups * op.K * op.G;
-    hipLaunchKernelGGL(swk::k_ell_to_dense, dim3((unsigned)((total + SW_BLOCK - 1) / SW_BLOCK)), dim3(SW_BLOCK), 0,
-                       h->stream, (const int*)op.cols, (const cplx*)op.vals, op.K, op.G, op.ngroups, n, D);
-    KLAUNCH_CHECK();
+    SWCHK(launch(h, T_OTHER, swk::k_ell_to_dense, dim3((unsigned)((total + SW_BLOCK - 1) / SW_BLOCK)),
+                 dim3(SW_BLOCK), (const int*)op.cols, (const cplx*)op.vals, op.K, op.G, op.ngroups, n, D));
   } else {
     (void)dev_free(h, D);
     return sw_fail(h, "coarsest inverse in an unknown form");
@@ -3111,12 +3031,10 @@ int sw_setup_direct_level(sw_engine* h, int hid, int level) {
   SWCHK(dev_realloc(h, &D, (size_t)n * n));
   HIPCHK(hipMemsetAsync(D, 0, (size_t)n * n * sizeof(cplx), h->stream));
   {
-    LaunchScope ls(h, T_OTHER);
     const int items = ne * S.bsr_KS;
-    hipLaunchKernelGGL(swk::k_bsr_to_dense, dim3((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK),
-                       dim3(SW_BLOCK), 0, h->stream, (const cplx*)S.bsr_vals, (const int*)S.bsr_kcol, ne,
-                       S.bsr_KS, n, D, (const int*)d_rank, (const int*)nullptr);
-    KLAUNCH_CHECK();
+    SWCHK(launch(h, T_OTHER, swk::k_bsr_to_dense, dim3((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK),
+                 dim3(SW_BLOCK), (const cplx*)S.bsr_vals, (const int*)S.bsr_kcol, ne, S.bsr_KS, n, D,
+                 (const int*)d_rank, (const int*)nullptr));
   }
   if (gj_invert(h, D, n) != 0) {
     (void)dev_free(h, D);
@@ -3133,12 +3051,10 @@ int sw_setup_direct_level(sw_engine* h, int hid, int level) {
   SWCHK(dev_realloc(h, &op.bsr_vals, (size_t)ne * op.bsr_KS * 64));
   SWCHK(dev_realloc(h, &op.bsr_kcol, (size_t)ne * op.bsr_KS));
   {
-    LaunchScope ls(h, T_OTHER);
     const size_t items = (size_t)ne * op.bsr_KS;
-    hipLaunchKernelGGL(swk::k_dense_to_bsr, dim3((unsigned)((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK)),
-                       dim3(SW_BLOCK), 0, h->stream, (const cplx*)D, n, op.bsr_vals, op.bsr_kcol,
-                       (const int*)d_E);
-    KLAUNCH_CHECK();
+    SWCHK(launch(h, T_OTHER, swk::k_dense_to_bsr,
+                 dim3((unsigned)((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK)), dim3(SW_BLOCK),
+                 (const cplx*)D, n, op.bsr_vals, op.bsr_kcol, (const int*)d_E));
   }
   op.set = true;
   op.dense_uniform = true;     // k_dense_to_bsr: the column list depends on the k-step only
@@ -3171,18 +3087,14 @@ int sw_setup_level_inverse(sw_engine* h, int hid, int level) {
   SWCHK(dev_realloc(h, &D, (size_t)n * n));
   HIPCHK(hipMemsetAsync(D, 0, (size_t)n * n * sizeof(cplx), h->stream));
   if (A.cols && A.vals) {
-    LaunchScope ls(h, T_OTHER);
     const size_t total = (size_t)A.ngroups * A.K * A.G;
-    hipLaunchKernelGGL(swk::k_ell_to_dense, dim3((unsigned)((total + SW_BLOCK - 1) / SW_BLOCK)), dim3(SW_BLOCK), 0,
-                       h->stream, (const int*)A.cols, (const cplx*)A.vals, A.K, A.G, A.ngroups, n, D);
-    KLAUNCH_CHECK();
+    SWCHK(launch(h, T_OTHER, swk::k_ell_to_dense, dim3((unsigned)((total + SW_BLOCK - 1) / SW_BLOCK)),
+                 dim3(SW_BLOCK), (const int*)A.cols, (const cplx*)A.vals, A.K, A.G, A.ngroups, n, D));
   } else if (A.bsr_KS > 0 && !A.bsr_tmap) {
-    LaunchScope ls(h, T_OTHER);
     const int items = (n / 16) * A.bsr_KS;
-    hipLaunchKernelGGL(swk::k_bsr_to_dense, dim3((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK),
-                       dim3(SW_BLOCK), 0, h->stream, (const cplx*)A.bsr_vals, (const int*)A.bsr_kcol, n / 16,
-                       A.bsr_KS, n, D, (const int*)nullptr, (const int*)nullptr);
-    KLAUNCH_CHECK();
+    SWCHK(launch(h, T_OTHER, swk::k_bsr_to_dense, dim3((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK),
+                 dim3(SW_BLOCK), (const cplx*)A.bsr_vals, (const int*)A.bsr_kcol, n / 16, A.bsr_KS, n, D,
+                 (const int*)nullptr, (const int*)nullptr));
   } else {
     (void)dev_free(h, D);
     return sw_fail(h, "level %d: operator in neither grouped-ELL nor full block-row form", level);
@@ -3198,12 +3110,10 @@ int sw_setup_level_inverse(sw_engine* h, int hid, int level) {
   SWCHK(dev_realloc(h, &op.bsr_vals, (size_t)RT * KS * 64));
   SWCHK(dev_realloc(h, &op.bsr_kcol, (size_t)RT * KS));
   {
-    LaunchScope ls(h, T_OTHER);
     const size_t items = (size_t)RT * KS;
-    hipLaunchKernelGGL(swk::k_dense_to_bsr, dim3((unsigned)((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK)),
-                       dim3(SW_BLOCK), 0, h->stream, (const cplx*)D, n, op.bsr_vals, op.bsr_kcol,
-                       (const int*)nullptr);
-    KLAUNCH_CHECK();
+    SWCHK(launch(h, T_OTHER, swk::k_dense_to_bsr,
+                 dim3((unsigned)((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK)), dim3(SW_BLOCK),
+                 (const cplx*)D, n, op.bsr_vals, op.bsr_kcol, (const int*)nullptr));
   }
   op.bsr_KS = KS;
   op.set = true;
@@ -3243,11 +3153,9 @@ int sw_setup_arnoldi(sw_engine* h, int hid, int level, int which, int degree, ui
   cplx* d2 = d + (size_t)(degree + 1) * nbp;
   cplx* nr = d + (size_t)2 * (degree + 1) * nbp;
   auto normalise = [&](cplx* w) -> int {
-    LaunchScope ls(h, T_AXPY);
-    hipLaunchKernelGGL(swk::k_colscale, dim3(std::min(4096, (n + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK), 1),
-                       dim3(SW_BLOCK), 0, h->stream, w, (const cplx*)nr, n, nbp);
-    KLAUNCH_CHECK();
-    return 0;
+    return launch(h, T_AXPY, swk::k_colscale,
+                  dim3(std::min(4096, (n + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK), 1), dim3(SW_BLOCK), w,
+                  (const cplx*)nr, n, nbp);
   };
   auto apply = [&](const cplx* x, cplx* y) -> int {
     if (!schur) return apply_op(h, lv, 0, x, nullptr, y, nbp);
@@ -3258,20 +3166,13 @@ int sw_setup_arnoldi(sw_engine* h, int hid, int level, int which, int degree, ui
   // start vector: one pseudo-random column (the other 63 stay zero), on the rows the operator acts on
   {
     cplx* tmp = (schur && !lv.stencil) ? V + vec : V;
-    {
-      LaunchScope ls(h, T_OTHER);
-      hipLaunchKernelGGL(swk::k_fill_random, dim3((n + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK), dim3(SW_BLOCK),
-                         0, h->stream, tmp, n, nbp, 1, (unsigned long long)(seed ? seed : 2024));
-      KLAUNCH_CHECK();
-    }
+    SWCHK(launch(h, T_OTHER, swk::k_fill_random, dim3((n + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK),
+                 dim3(SW_BLOCK), tmp, n, nbp, 1, (unsigned long long)(seed ? seed : 2024)));
     if (schur && !lv.stencil) {
       SWCHK(zero_vec(h, V, n, nbp));
-      LaunchScope ls(h, T_OTHER);
       const int items = lv.eo_op[0].bsr_RT * 16;
-      hipLaunchKernelGGL(swk::k_copy_tiles, dim3((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK),
-                         dim3(SW_BLOCK), 0, h->stream, (const cplx*)tmp, (const int*)lv.eo_op[0].bsr_tmap,
-                         lv.eo_op[0].bsr_RT, nbp, V);
-      KLAUNCH_CHECK();
+      SWCHK(launch(h, T_OTHER, swk::k_copy_tiles, dim3((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK),
+                   dim3(SW_BLOCK), (const cplx*)tmp, (const int*)lv.eo_op[0].bsr_tmap, lv.eo_op[0].bsr_RT, nbp, V));
     }
     SWCHK(dot_into(h, V, V, n, nbp, nr));
     SWCHK(normalise(V));
@@ -3488,12 +3389,8 @@ int sw_setup_eo_operators(sw_engine* h, int hid, int level, int Lc) {
     long long *dso = nullptr, *ddo = nullptr;
     SWCHK(upload(h, &dso, so.data(), so.size()));
     SWCHK(upload(h, &ddo, dof.data(), dof.size()));
-    {
-      LaunchScope ls(h, T_OTHER);
-      hipLaunchKernelGGL(swk::k_block_inverse, dim3(no), dim3(256), 0, h->stream, Av, (const long long*)dso,
-                         lv.eo_op[2].bsr_vals, (const long long*)ddo, info);
-      KLAUNCH_CHECK();
-    }
+    SWCHK(launch(h, T_OTHER, swk::k_block_inverse, dim3(no), dim3(256), Av, (const long long*)dso,
+                 lv.eo_op[2].bsr_vals, (const long long*)ddo, info));
     SWCHK(stream_sync(h));
     SWCHK(dev_free(h, dso));
     SWCHK(dev_free(h, ddo));
@@ -3509,13 +3406,9 @@ int sw_setup_eo_operators(sw_engine* h, int hid, int level, int Lc) {
     SWCHK(upload(h, &dbo, bo.data(), bo.size()));
     SWCHK(upload(h, &dio, io.data(), io.size()));
     SWCHK(upload(h, &doo, oo.data(), oo.size()));
-    {
-      LaunchScope ls(h, T_OTHER);
-      hipLaunchKernelGGL(swk::k_block_products, dim3((unsigned)oo.size()), dim3(256), 0, h->stream,
-                         (const int*)dptr, (const long long*)dao, (const long long*)dbo, Ab, Bb,
-                         (const long long*)dio, Av, sign, out, (const long long*)doo);
-      KLAUNCH_CHECK();
-    }
+    SWCHK(launch(h, T_OTHER, swk::k_block_products, dim3((unsigned)oo.size()), dim3(256), (const int*)dptr,
+                 (const long long*)dao, (const long long*)dbo, Ab, Bb, (const long long*)dio, Av, sign, out,
+                 (const long long*)doo));
     SWCHK(stream_sync(h));
     SWCHK(dev_free(h, dptr));
     SWCHK(dev_free(h, dao));
@@ -3665,216 +3558,12 @@ int sw_set_solver(sw_engine* h, int restart, int solver_hid) {
 
 int sw_set_option(sw_engine* h, const char* name, double value) {
   if (!h || !name) return 1;
-  if (std::strcmp(name, "use_mfma") == 0) {
-    h->use_mfma = value != 0.0;
-    return 0;
-  }
-  if (std::strcmp(name, "defl_gemm") == 0) {
-    if (value != 0.0 && value != 1.0) return sw_fail(h, "defl_gemm must be 0 or 1");
-    h->defl_gemm = (int)value;
-    return 0;
-  }
-  if (std::strcmp(name, "bsr_map") == 0 || std::strcmp(name, "dense_map") == 0 ||
-      std::strcmp(name, "bsr_sub") == 0) {
-    const int v = (int)value;
-    if (name[4] == 's') {
-      if (v < 1) return sw_fail(h, "bsr_sub must be >= 1");
-      h->bsr_sub = v;
-    } else {
-      if (v < 0 || v > 3) return sw_fail(h, "%s must be 0..3", name);
-      (name[0] == 'd' ? h->dense_map : h->bsr_map) = v;
+  for (const EngineOption& o : kOptions)
+    if (o.set && std::strcmp(name, o.name) == 0) {
+      if (o.ok && !o.ok(value)) return sw_fail(h, "%s", o.msg);
+      o.set(h, value);
+      return 0;
     }
-    return 0;
-  }
-  if (std::strcmp(name, "bsr_stages") == 0 || std::strcmp(name, "dense_stages") == 0) {
-    if (value != 2.0 && value != 4.0 && value != 8.0 && !(value == 16.0 && name[0] == 'd'))
-      return sw_fail(h, "%s must be 2, 4 or 8 (dense_stages: or 16)", name);
-    (name[0] == 'd' ? h->dense_stages : h->bsr_stages) = (int)value;
-    return 0;
-  }
-  if (std::strcmp(name, "bsr_nt") == 0) {
-    h->bsr_nt = value != 0.0;
-    return 0;
-  }
-  if (std::strcmp(name, "bsr_xreg") == 0) {
-    h->bsr_xreg = value != 0.0;
-    return 0;
-  }
-  if (std::strcmp(name, "p_even") == 0) {
-    h->p_even = value != 0.0;
-    return 0;
-  }
-  if (std::strcmp(name, "ell_order") == 0) {
-    h->ell_order = value != 0.0;
-    for (int i = 0; i < SW_MAX_HIER; ++i) h->hier[i].even_valid = false;
-    return 0;
-  }
-  if (std::strcmp(name, "bench_what") == 0) {
-    if (value < 0.0 || value > 3.0) return sw_fail(h, "bench_what must be 0..3");
-    h->bench_what = (int)value;
-    return 0;
-  }
-  if (std::strcmp(name, "bench_mode") == 0) {
-    if (value != 0.0 && value != 1.0 && value != 2.0) return sw_fail(h, "bench_mode must be 0, 1 or 2");
-    h->bench_mode = (int)value;
-    return 0;
-  }
-  if (std::strcmp(name, "stencil_nt") == 0) {
-    h->stencil_nt = value != 0.0;
-    return 0;
-  }
-  if (std::strcmp(name, "stencil_spw") == 0) {
-    const int v = (int)value;
-    if (v != 0 && v != 1 && v != 2 && v != 4 && v != 8) return sw_fail(h, "stencil_spw must be 0,1,2,4,8");
-    h->stencil_spw = v;
-    return 0;
-  }
-  if (std::strcmp(name, "stencil_tile") == 0) {
-    h->stencil_tile = (int)value;
-    return 0;
-  }
-  if (std::strcmp(name, "cgs2") == 0) {
-    h->cgs2 = value != 0.0;
-    return 0;
-  }
-  if (std::strcmp(name, "inner_cgs2") == 0) {
-    h->inner_cgs2 = value != 0.0;
-    return 0;
-  }
-  if (std::strcmp(name, "eo_direct") == 0) {
-    h->eo_direct = value != 0.0;
-    return 0;
-  }
-  if (std::strcmp(name, "eo_solve") == 0) {
-    h->eo_solve = value != 0.0;
-    return 0;
-  }
-  if (std::strcmp(name, "pyth_last") == 0) {
-    h->pyth_last = value != 0.0;
-    return 0;
-  }
-  if (std::strcmp(name, "precond_f32") == 0) {
-    h->precond_f32 = value != 0.0;
-    return 0;
-  }
-  if (std::strcmp(name, "f32_tiles") == 0) {
-    const int v = (int)value;
-    if (v != 0 && v != 1 && v != 2 && v != 4) return sw_fail(h, "f32_tiles must be 0, 1, 2 or 4");
-    h->f32_tiles = v;
-    return 0;
-  }
-  if (std::strcmp(name, "f32_splitk") == 0) {
-    h->f32_splitk = (int)value;
-    return 0;
-  }
-  if (std::strcmp(name, "dot_blocks") == 0) {
-    g_dot_blocks = std::max(64, (int)value);
-    g_dot_pmax = g_dot_blocks;
-    return 0;
-  }
-  if (std::strcmp(name, "f32_krylov") == 0) {
-    h->f32_krylov = value != 0.0;
-    return 0;
-  }
-  if (std::strcmp(name, "f32_pairs") == 0) {
-    h->f32_pairs = value != 0.0;
-    return 0;
-  }
-  if (std::strcmp(name, "f32_stages") == 0) {
-    h->f32_stages = (int)value;
-    return 0;
-  }
-  if (std::strcmp(name, "f32_dense_stages") == 0) {
-    h->f32_dense_stages = (int)value;
-    return 0;
-  }
-  if (std::strcmp(name, "stop_factor") == 0) {
-    if (!(value > 0.0 && value <= 1.0)) return sw_fail(h, "stop_factor must be in (0, 1]");
-    h->stop_factor = value;
-    return 0;
-  }
-  if (std::strcmp(name, "fused_reduce") == 0) {
-    h->fused_reduce = value != 0.0;
-    return 0;
-  }
-  if (std::strcmp(name, "eo_skew") == 0) {
-    if (value < -1.0 || value > 65536.0) return sw_fail(h, "eo_skew must be -1 (automatic), 0 (off) or a strip height");
-    h->eo_skew = (int)value;
-    return 0;
-  }
-  if (std::strcmp(name, "direct_small") == 0) {
-    h->direct_small = value != 0.0;
-    return 0;
-  }
-  if (std::strcmp(name, "gram_cycle") == 0) {
-    h->gram_cycle = value != 0.0;
-    return 0;
-  }
-  if (std::strcmp(name, "lgmres_aug") == 0) {
-    h->lgmres_aug = value != 0.0;
-    return 0;
-  }
-  if (std::strcmp(name, "verify") == 0) {
-    h->verify = value != 0.0;
-    return 0;
-  }
-  if (std::strcmp(name, "lazy_sync") == 0) {
-    h->lazy_sync = value != 0.0;
-    return 0;
-  }
-  if (std::strcmp(name, "mfma_3m") == 0) {
-    h->mfma_3m = value != 0.0;
-    return 0;
-  }
-  if (std::strcmp(name, "eo_skew_chunk") == 0) {
-    h->eo_skew_chunk = value != 0.0;
-    return 0;
-  }
-  if (std::strcmp(name, "gj_block") == 0) {
-    const int v = (int)value;
-    if (v != 0 && (v < 8 || v > 256 || v % 8)) return sw_fail(h, "gj_block must be 0 or a multiple of 8 in 8..256");
-    h->gj_block = v;
-    return 0;
-  }
-  if (std::strcmp(name, "dense_lds") == 0) {
-    if (value != 0.0 && value != 1.0 && value != 2.0 && value != 4.0) return sw_fail(h, "dense_lds must be 0, 2 or 4");
-    h->dense_lds = value == 1.0 ? 2 : (int)value;
-    return 0;
-  }
-  if (std::strcmp(name, "eo_tile_dbg") == 0) {
-    h->eo_tile_dbg = (int)value & 3;
-    return 0;
-  }
-  if (std::strcmp(name, "eo_tile") == 0) {
-    if (value != 0.0 && value != 4.0 && value != 8.0) return sw_fail(h, "eo_tile must be 0 (off), 4 or 8 waves");
-    h->eo_tile = (int)value;
-    return 0;
-  }
-  if (std::strcmp(name, "eo_product") == 0) {
-    h->eo_product = value != 0.0;
-    return 0;
-  }
-  if (std::strcmp(name, "mfma3_tiles") == 0) {
-    const int v = (int)value;
-    if (v != 0 && v != 1 && v != 2 && v != 4) return sw_fail(h, "mfma3_tiles must be 0, 1, 2 or 4");
-    h->mfma3_tiles = v;
-    return 0;
-  }
-  if (std::strcmp(name, "mfma_ops") == 0) {
-    h->mfma_ops = value != 0.0;
-    return 0;
-  }
-  if (std::strcmp(name, "mfma_small_tiles") == 0) {
-    if (value != 0.0 && value != 2.0 && value != 4.0)
-      return sw_fail(h, "mfma_small_tiles must be 0, 2 or 4");
-    h->mfma_small_tiles = (int)value;
-    return 0;
-  }
-  if (std::strcmp(name, "mfma_tiles") == 0) {
-    if (value != 2.0 && value != 4.0) return sw_fail(h, "mfma_tiles must be 2 or 4");
-    h->mfma_tiles = (int)value;
-    return 0;
-  }
   return sw_fail(h, "unknown option %s", name);
 }
 
@@ -3922,11 +3611,9 @@ int sw_eig_begin_wide(sw_engine* h, int hid, int level, uint64_t seed, int width
   h->eig_level = level;
   h->eig_n = lv.n;
   for (int g = 0; g < width / 64; ++g) {
-    LaunchScope ls(h, T_OTHER);
-    hipLaunchKernelGGL(swk::k_fill_random, dim3((lv.n + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK),
-                       dim3(SW_BLOCK), 0, h->stream, h->eig_buf[0] + (size_t)g * lv.n * 64, lv.n, 64, 64,
-                       (unsigned long long)(seed ? seed : 11) + 0x632be59bd9b4e019ull * (unsigned long long)g);
-    KLAUNCH_CHECK();
+    SWCHK(launch(h, T_OTHER, swk::k_fill_random, dim3((lv.n + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK),
+                 dim3(SW_BLOCK), h->eig_buf[0] + (size_t)g * lv.n * 64, lv.n, 64, 64,
+                 (unsigned long long)(seed ? seed : 11) + 0x632be59bd9b4e019ull * (unsigned long long)g));
   }
   return stream_sync(h);
 }
@@ -3986,10 +3673,8 @@ int sw_eig_solve(sw_engine* h, int src, int dst, int mode, double tol, int maxit
     const cplx* rhs = h->eig_buf[src] + g * gs;
     if (mode == 1) {
       cplx* tmp = h->eig_buf[3 - src - dst] + g * gs;
-      LaunchScope ls(h, T_OTHER);
-      hipLaunchKernelGGL(swk::k_row_sign, dim3((lv.n + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK, 1),
-                         dim3(SW_BLOCK), 0, h->stream, rhs, (const signed char*)h->eig_sign, tmp, lv.n, 64);
-      KLAUNCH_CHECK();
+      SWCHK(launch(h, T_OTHER, swk::k_row_sign, dim3((lv.n + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK, 1),
+                   dim3(SW_BLOCK), rhs, (const signed char*)h->eig_sign, tmp, lv.n, 64));
       rhs = tmp;
     }
     int total = 0;
@@ -4042,10 +3727,8 @@ int sw_eig_apply_diff(sw_engine* h, int src, int dst, int skip, int g3, double t
     // x = Gamma src (in dst: it is overwritten last)
     const cplx* x = h->eig_buf[src] + go;
     if (g3) {
-      LaunchScope ls(h, T_OTHER);
-      hipLaunchKernelGGL(swk::k_row_sign, dim3((n + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK, 1),
-                         dim3(SW_BLOCK), 0, h->stream, x, (const signed char*)h->eig_sign, d, n, 64);
-      KLAUNCH_CHECK();
+      SWCHK(launch(h, T_OTHER, swk::k_row_sign, dim3((n + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK, 1),
+                   dim3(SW_BLOCK), x, (const signed char*)h->eig_sign, d, n, 64));
       x = d;
     }
     // xc = R x (skip: R_1 R_0 x)
@@ -4090,36 +3773,20 @@ int sw_eig_gram(sw_engine* h, int a, int b, double* out) {
     const int rpbw = std::max(64, (n + pw - 1) / pw);
     const int Pw = (n + rpbw - 1) / rpbw;
     SWCHK(ensure_partial(h, (size_t)Pw * w * w * sizeof(cplx)));
-    {
-      LaunchScope ls(h, T_DOTS);
-      hipLaunchKernelGGL(swk::k_block_gram_wide, dim3(Pw, ng, ng), dim3(SW_BLOCK), 0, h->stream,
-                         (const cplx*)h->eig_buf[a], (const cplx*)h->eig_buf[b], n, rpbw, w, h->partial);
-      KLAUNCH_CHECK();
-    }
-    {
-      LaunchScope ls(h, T_DOTS);
-      hipLaunchKernelGGL(swk::k_reduce_partials, dim3(w, ng), dim3(SW_BLOCK), 0, h->stream,
-                         (const cplx*)h->partial, Pw, w, w, h->eig_small, (const cplx*)nullptr, (cplx*)nullptr);
-      KLAUNCH_CHECK();
-    }
+    SWCHK(launch(h, T_DOTS, swk::k_block_gram_wide, dim3(Pw, ng, ng), dim3(SW_BLOCK), (const cplx*)h->eig_buf[a],
+                 (const cplx*)h->eig_buf[b], n, rpbw, w, h->partial));
+    SWCHK(launch(h, T_DOTS, swk::k_reduce_partials, dim3(w, ng), dim3(SW_BLOCK), (const cplx*)h->partial, Pw, w,
+                 w, h->eig_small, (const cplx*)nullptr, (cplx*)nullptr));
     HIPCHK(hipMemcpyAsync(out, h->eig_small, (size_t)w * w * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
     return stream_sync(h);
   }
   int rpb = std::max(64, ((n + 255) / 256 + 3) & ~3);     // ~256 row blocks, multiples of 4 rows
   const int P = (n + rpb - 1) / rpb;
   SWCHK(ensure_partial(h, (size_t)P * 4096 * sizeof(cplx)));
-  {
-    LaunchScope ls(h, T_DOTS);
-    hipLaunchKernelGGL(swk::k_block_gram, dim3(P, 4), dim3(SW_BLOCK), 0, h->stream,
-                       (const cplx*)h->eig_buf[a], (const cplx*)h->eig_buf[b], n, rpb, h->partial);
-    KLAUNCH_CHECK();
-  }
-  {
-    LaunchScope ls(h, T_DOTS);
-    hipLaunchKernelGGL(swk::k_block_gram_reduce, dim3(64), dim3(64), 0, h->stream,
-                       (const cplx*)h->partial, P, h->eig_small);
-    KLAUNCH_CHECK();
-  }
+  SWCHK(launch(h, T_DOTS, swk::k_block_gram, dim3(P, 4), dim3(SW_BLOCK), (const cplx*)h->eig_buf[a],
+               (const cplx*)h->eig_buf[b], n, rpb, h->partial));
+  SWCHK(launch(h, T_DOTS, swk::k_block_gram_reduce, dim3(64), dim3(64), (const cplx*)h->partial, P,
+               h->eig_small));
   HIPCHK(hipMemcpyAsync(out, h->eig_small, 4096 * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
   return stream_sync(h);
 }
@@ -4134,23 +3801,15 @@ int sw_eig_rotate(sw_engine* h, int src, const double* Y, int dst, int sub) {
   const int w = h->eig_w;
   if (w > 64) {
     HIPCHK(hipMemcpyAsync(h->eig_small, Y, (size_t)w * w * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
-    {
-      LaunchScope ls(h, T_AXPY);
-      hipLaunchKernelGGL(swk::k_block_rotate_wide, dim3((h->eig_n + 63) / 64, w / 64), dim3(SW_BLOCK), 0,
-                         h->stream, (const cplx*)h->eig_buf[src], (const cplx*)h->eig_small,
-                         (const cplx*)(sub >= 0 ? h->eig_buf[sub] : nullptr), h->eig_buf[dst], h->eig_n, w);
-      KLAUNCH_CHECK();
-    }
+    SWCHK(launch(h, T_AXPY, swk::k_block_rotate_wide, dim3((h->eig_n + 63) / 64, w / 64), dim3(SW_BLOCK),
+                 (const cplx*)h->eig_buf[src], (const cplx*)h->eig_small,
+                 (const cplx*)(sub >= 0 ? h->eig_buf[sub] : nullptr), h->eig_buf[dst], h->eig_n, w));
     return stream_sync(h);
   }
   HIPCHK(hipMemcpyAsync(h->eig_small, Y, 4096 * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
-  {
-    LaunchScope ls(h, T_AXPY);
-    hipLaunchKernelGGL(swk::k_block_rotate, dim3(std::min(2048, h->eig_n / SW_WAVES_PER_BLOCK)), dim3(SW_BLOCK),
-                       0, h->stream, (const cplx*)h->eig_buf[src], (const cplx*)h->eig_small,
-                       (const cplx*)(sub >= 0 ? h->eig_buf[sub] : nullptr), h->eig_buf[dst], h->eig_n);
-    KLAUNCH_CHECK();
-  }
+  SWCHK(launch(h, T_AXPY, swk::k_block_rotate, dim3(std::min(2048, h->eig_n / SW_WAVES_PER_BLOCK)),
+               dim3(SW_BLOCK), (const cplx*)h->eig_buf[src], (const cplx*)h->eig_small,
+               (const cplx*)(sub >= 0 ? h->eig_buf[sub] : nullptr), h->eig_buf[dst], h->eig_n));
   return stream_sync(h);
 }
 
@@ -4166,39 +3825,13 @@ int sw_eig_fetch(sw_engine* h, int src, int k, double* out) {
   return 0;
 }
 
-// Current value of an engine switch (the counterpart of sw_set_option: what a caller saves before an A/B run
-// and restores afterwards); "direct_fallbacks": how often a directly solved level missed the tolerance
-// and the iterative path took over (read-only).
+// Current value of an engine option (what a caller saves before an A/B run and restores afterwards), or of
+// one of the read-only statistics of kOptions.
 int sw_get_option(sw_engine* h, const char* name, double* value) {
   if (!h || !name || !value) return 1;
-  struct Ent { const char* name; double v; };
-  const Ent tab[] = {
-      {"use_mfma", (double)h->use_mfma}, {"defl_gemm", (double)h->defl_gemm}, {"bsr_map", (double)h->bsr_map}, {"dense_map", (double)h->dense_map},
-      {"bsr_sub", (double)h->bsr_sub}, {"bsr_stages", (double)h->bsr_stages},
-      {"dense_stages", (double)h->dense_stages}, {"bsr_nt", (double)h->bsr_nt}, {"bsr_xreg", (double)h->bsr_xreg},
-      {"p_even", (double)h->p_even}, {"ell_order", (double)h->ell_order}, {"bench_what", (double)h->bench_what},
-      {"bench_mode", (double)h->bench_mode}, {"stencil_nt", (double)h->stencil_nt},
-      {"stencil_spw", (double)h->stencil_spw}, {"stencil_tile", (double)h->stencil_tile}, {"cgs2", (double)h->cgs2},
-      {"inner_cgs2", (double)h->inner_cgs2}, {"eo_direct", (double)h->eo_direct}, {"eo_solve", (double)h->eo_solve},
-      {"pyth_last", (double)h->pyth_last}, {"precond_f32", (double)h->precond_f32},
-      {"f32_tiles", (double)h->f32_tiles}, {"f32_splitk", (double)h->f32_splitk},
-      {"dot_blocks", (double)g_dot_blocks}, {"f32_krylov", (double)h->f32_krylov},
-      {"f32_pairs", (double)h->f32_pairs}, {"f32_stages", (double)h->f32_stages},
-      {"f32_dense_stages", (double)h->f32_dense_stages}, {"stop_factor", h->stop_factor},
-      {"fused_reduce", (double)h->fused_reduce}, {"eo_skew", (double)h->eo_skew},
-      {"direct_small", (double)h->direct_small}, {"gram_cycle", (double)h->gram_cycle},
-      {"lgmres_aug", (double)h->lgmres_aug}, {"verify", (double)h->verify}, {"lazy_sync", (double)h->lazy_sync},
-      {"mfma_3m", (double)h->mfma_3m}, {"eo_skew_chunk", (double)h->eo_skew_chunk},
-      {"gj_block", (double)h->gj_block}, {"eo_product", (double)h->eo_product},       {"eo_tile", (double)h->eo_tile}, {"dense_lds", (double)h->dense_lds},
-      {"mfma3_tiles", (double)h->mfma3_tiles}, {"mfma_ops", (double)h->mfma_ops},
-      {"mfma_small_tiles", (double)h->mfma_small_tiles}, {"mfma_tiles", (double)h->mfma_tiles},
-      {"direct_fallbacks", (double)h->direct_fallbacks}, {"alloc_seconds", h->alloc_s},
-      {"alloc_calls", (double)h->alloc_calls}, {"alloc_gbytes", h->alloc_bytes * 1e-9},
-      {"pool_hits", (double)h->pool_hits},
-      {"eo_tile_dbg", (double)h->eo_tile_dbg}};
-  for (const Ent& e : tab)
-    if (std::strcmp(name, e.name) == 0) {
-      *value = e.v;
+  for (const EngineOption& o : kOptions)
+    if (std::strcmp(name, o.name) == 0) {
+      *value = o.get(h);
       return 0;
     }
   return sw_fail(h, "unknown option %s", name);
@@ -4372,9 +4005,8 @@ int sw_vcycle(sw_engine* h, int hid, int level0, int nb, const double* B, double
 // Y_e = S X_e (mode 0) or Bp_e - S X_e (mode 1); all three are half vectors
 static int schur_apply(sw_engine* h, Level& lv, int mode, const cplx* X, const cplx* Bp, cplx* Y, int nbp) {
   swk::StencilArgs a = stencil_args<cplx>(h, lv, nbp, true);
-  LaunchScope ls(h, T_SCHUR_OP);
-  if (mode == 0) return launch_schur_step<0>(h, a, X, Bp, Y, nbp);
-  return launch_schur_step<1>(h, a, X, Bp, Y, nbp);
+  if (mode == 0) return launch_schur_step<0>(h, T_SCHUR_OP, a, X, Bp, Y, nbp);
+  return launch_schur_step<1>(h, T_SCHUR_OP, a, X, Bp, Y, nbp);
 }
 
 static bool eo_solve_eligible(sw_engine* h, Hier& H, int level) {
@@ -4918,67 +4550,31 @@ static int deflate(sw_engine* h, const cplx* U, int kd, const int* srcrow, const
     const int rpb = (n + P - 1) / P;
     P = (n + rpb - 1) / rpb;
     SWCHK(ensure_partial(h, (size_t)P * ld * nbp * sizeof(cplx)));
-    {
-      LaunchScope ls(h, T_DEFL);
-      dim3 grid(P, nchunks);
-      if (ld <= 64)
-        hipLaunchKernelGGL((swk::k_defl_gemm_dots<1>), grid, dim3(SW_BLOCK), 0, h->stream, U, ld, X, n,
-                           nbp, rpb, h->partial);
-      else if (ld <= 128)
-        hipLaunchKernelGGL((swk::k_defl_gemm_dots<2>), grid, dim3(SW_BLOCK), 0, h->stream, U, ld, X, n,
-                           nbp, rpb, h->partial);
-      else
-        hipLaunchKernelGGL((swk::k_defl_gemm_dots<4>), grid, dim3(SW_BLOCK), 0, h->stream, U, ld, X, n,
-                           nbp, rpb, h->partial);
-      KLAUNCH_CHECK();
-    }
-    {
-      LaunchScope ls(h, T_DEFL);
-      hipLaunchKernelGGL(swk::k_reduce_partials, dim3(ld, nbp / 64), dim3(SW_BLOCK), 0, h->stream,
-                         h->partial, P, ld, nbp, cbuf, (const cplx*)nullptr, (cplx*)nullptr);
-      KLAUNCH_CHECK();
-    }
-    {
-      LaunchScope ls(h, T_DEFL);
-      hipLaunchKernelGGL(swk::k_defl_gemm_apply, dim3((n + 63) / 64, nbp / 64), dim3(SW_BLOCK), 0, h->stream,
-                         U, ld, (const cplx*)cbuf, srcrow, X, out, n, nbp);
-      KLAUNCH_CHECK();
-    }
-    return 0;
+    // 64-column groups of U per workgroup: 1, 2 or 4
+    SWCHK(pick_ge<64, 128, 256>(ld, [&](auto LD) {
+      return launch(h, T_DEFL, swk::k_defl_gemm_dots<LD / 64>, dim3(P, nchunks), dim3(SW_BLOCK), U, ld, X, n, nbp,
+                    rpb, h->partial);
+    }));
+    SWCHK(launch(h, T_DEFL, swk::k_reduce_partials, dim3(ld, nbp / 64), dim3(SW_BLOCK), h->partial, P, ld, nbp,
+                 cbuf, (const cplx*)nullptr, (cplx*)nullptr));
+    return launch(h, T_DEFL, swk::k_defl_gemm_apply, dim3((n + 63) / 64, nbp / 64), dim3(SW_BLOCK), U, ld,
+                  (const cplx*)cbuf, srcrow, X, out, n, nbp);
   }
   int P, rpb;
   row_blocking(n, nbp, true, &P, &rpb);
   for (int k0 = 0; k0 < kd; k0 += 32) {
     const int kc = std::min(32, kd - k0);
     SWCHK(ensure_partial(h, (size_t)P * kc * nbp * sizeof(cplx)));
-    {
-      LaunchScope ls(h, T_DEFL);
-      dim3 grid(P, nbp / 64);
-      if (kc <= 8)
-        hipLaunchKernelGGL((swk::k_defl_dots<8>), grid, dim3(SW_BLOCK), 0, h->stream,
-                           (const cplx*)(U + k0), ld, kc, X, n, nbp, rpb, h->partial);
-      else if (kc <= 16)
-        hipLaunchKernelGGL((swk::k_defl_dots<16>), grid, dim3(SW_BLOCK), 0, h->stream,
-                           (const cplx*)(U + k0), ld, kc, X, n, nbp, rpb, h->partial);
-      else
-        hipLaunchKernelGGL((swk::k_defl_dots<32>), grid, dim3(SW_BLOCK), 0, h->stream,
-                           (const cplx*)(U + k0), ld, kc, X, n, nbp, rpb, h->partial);
-      KLAUNCH_CHECK();
-    }
-    {
-      LaunchScope ls(h, T_DEFL);
-      hipLaunchKernelGGL(swk::k_reduce_partials, dim3(kc, nbp / 64), dim3(SW_BLOCK), 0, h->stream,
-                         h->partial, P, kc, nbp, cbuf + (size_t)k0 * nbp, (const cplx*)nullptr,
-                         (cplx*)nullptr);
-      KLAUNCH_CHECK();
-    }
+    SWCHK(pick_ge<8, 16, 32>(kc, [&](auto KC) {
+      return launch(h, T_DEFL, swk::k_defl_dots<KC>, dim3(P, nbp / 64), dim3(SW_BLOCK), (const cplx*)(U + k0), ld,
+                    kc, X, n, nbp, rpb, h->partial);
+    }));
+    SWCHK(launch(h, T_DEFL, swk::k_reduce_partials, dim3(kc, nbp / 64), dim3(SW_BLOCK), h->partial, P, kc, nbp,
+                 cbuf + (size_t)k0 * nbp, (const cplx*)nullptr, (cplx*)nullptr));
   }
   {
-    LaunchScope ls(h, T_DEFL);
     dim3 grid((n + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK, nbp / 64);
-    hipLaunchKernelGGL(swk::k_defl_apply, grid, dim3(SW_BLOCK), 0, h->stream, U, ld, kd, cbuf, srcrow, X,
-                       out, n, nbp);
-    KLAUNCH_CHECK();
+    SWCHK(launch(h, T_DEFL, swk::k_defl_apply, grid, dim3(SW_BLOCK), U, ld, kd, cbuf, srcrow, X, out, n, nbp));
   }
   return 0;
 }
@@ -5023,12 +4619,8 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
     h->slots[h->pb_slot].pending = false;
   }
   // x0 <- probes
-  {
-    LaunchScope ls(h, T_OTHER);
-    hipLaunchKernelGGL(swk::k_pack_i8, dim3((n + 63) / 64, nbp / 64), dim3(SW_BLOCK), 0, h->stream,
-                       h->pb_probes, nb, n, (const int*)lv.rowmap, h->pb_x0, nbp);
-    KLAUNCH_CHECK();
-  }
+  SWCHK(launch(h, T_OTHER, swk::k_pack_i8, dim3((n + 63) / 64, nbp / 64), dim3(SW_BLOCK), h->pb_probes, nb, n,
+               (const int*)lv.rowmap, h->pb_x0, nbp));
   const int fine_hid = (level == 0 && h->hier[h->solver_hid].ready) ? h->solver_hid : 0;
   if (fine_hid != 0 && h->hier[fine_hid].lv[0].n != n)
     return sw_fail(h, "solver hierarchy level-0 size mismatch");
@@ -5039,11 +4631,9 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
     if (kd > 0) {
       SWCHK(deflate(h, h->U, kd, (const int*)h->perm_src[0], h->pb_x0, h->pb_rhs, n, nbp));
     } else {
-      LaunchScope ls(h, T_DEFL);
       dim3 grid((n + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK, nbp / 64);
-      hipLaunchKernelGGL(swk::k_gather_rows, grid, dim3(SW_BLOCK), 0, h->stream,
-                         (const int*)h->perm_src[0], h->pb_x0, h->pb_rhs, n, nbp);
-      KLAUNCH_CHECK();
+      SWCHK(launch(h, T_DEFL, swk::k_gather_rows, grid, dim3(SW_BLOCK), (const int*)h->perm_src[0], h->pb_x0,
+                   h->pb_rhs, n, nbp));
     }
     int total = 0;
     SWCHK(solve_dev(h, fine_hid, 0, h->pb_rhs, h->pb_z, tol, maxiter, nbp, &total));
@@ -5116,13 +4706,8 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
   // e = x0^H z - x0^H w                      utils.py:336,353-355
   SWCHK(dot_into(h, h->pb_x0, h->pb_z, n, nbp, h->pb_est + nbp));
   SWCHK(dot_into(h, h->pb_x0, w, n, nbp, h->pb_est + 2 * nbp));
-  {
-    LaunchScope ls(h, T_OTHER);
-    hipLaunchKernelGGL(swk::k_est_combine, dim3((nbp + 255) / 256), dim3(256), 0, h->stream,
-                       (const cplx*)(h->pb_est + nbp), (const cplx*)(h->pb_est + 2 * nbp), nbp,
-                       h->pb_est);
-    KLAUNCH_CHECK();
-  }
+  SWCHK(launch(h, T_OTHER, swk::k_est_combine, dim3((nbp + 255) / 256), dim3(256), (const cplx*)(h->pb_est + nbp),
+               (const cplx*)(h->pb_est + 2 * nbp), nbp, h->pb_est));
   SWCHK(stream_sync(h));
   return 0;
 }

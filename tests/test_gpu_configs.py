@@ -12,6 +12,8 @@
 
 Tolerances: floating point complex128; per-probe estimates 1e-10 relative (north star), differences of
 two O(100) numbers relative to the minuend, operator applications 1e-12."""
+import re
+
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -20,7 +22,7 @@ pytestmark = pytest.mark.gpu
 
 from deflatedmlmc_schwinger_amd import gateway, hierarchy, matrix, utils  # noqa: E402
 from deflatedmlmc_schwinger_amd.engine import (MODE_HUTCHINSON, MODE_MLMC, MODE_MLMC_SKIP,  # noqa: E402
-                                               ProbeStream)
+                                               Engine, EngineError, ProbeStream)
 from deflatedmlmc_schwinger_amd.multigrid import MG, REF_HID, SOLVER_HID  # noqa: E402
 from oracle import ref_path as rp  # noqa: E402
 
@@ -686,4 +688,73 @@ def test_small_reference_levels_solved_directly_match_the_iterative_solves():
     scale = np.maximum(np.abs(out[(0, "e")][0]), 1.0)
     assert np.max(np.abs(out[(1, "e")][0] - out[(0, "e")][0]) / scale) < 1e-9
     assert np.max(np.abs(out[(1, "e")][1] - out[(0, "e")][1]) / np.maximum(np.abs(out[(0, "e")][1]), 1.0)) < 1e-9
+    eng.close()
+
+
+# Every option sw_set_option accepts.  sw_get_option knows these and the read-only statistics below.
+_SETTABLE_OPTIONS = [
+    "use_mfma", "defl_gemm", "bsr_map", "dense_map", "bsr_sub", "bsr_stages", "dense_stages", "bsr_nt",
+    "bsr_xreg", "p_even", "ell_order", "bench_what", "bench_mode", "stencil_nt", "stencil_spw", "stencil_tile",
+    "cgs2", "inner_cgs2", "eo_direct", "eo_solve", "pyth_last", "precond_f32", "f32_tiles", "f32_splitk",
+    "dot_blocks", "f32_krylov", "f32_pairs", "f32_stages", "f32_dense_stages", "stop_factor", "fused_reduce",
+    "eo_skew", "direct_small", "gram_cycle", "lgmres_aug", "verify", "lazy_sync", "mfma_3m", "eo_skew_chunk",
+    "gj_block", "eo_product", "eo_tile", "dense_lds", "mfma3_tiles", "mfma_ops", "mfma_small_tiles",
+    "mfma_tiles", "eo_tile_dbg"]
+_READ_ONLY_OPTIONS = ["direct_fallbacks", "alloc_seconds", "alloc_calls", "alloc_gbytes", "pool_hits"]
+# validated options: (a valid non-default value, the value read back, an invalid value, the refusal's message)
+_VALIDATED_OPTIONS = {
+    "defl_gemm": (1, 1, 2, "defl_gemm must be 0 or 1"),
+    "bsr_map": (2, 2, 4, "bsr_map must be 0..3"),
+    "dense_map": (3, 3, -1, "dense_map must be 0..3"),
+    "bsr_sub": (4, 4, 0, "bsr_sub must be >= 1"),
+    "bsr_stages": (8, 8, 16, "bsr_stages must be 2, 4 or 8 (dense_stages: or 16)"),
+    "dense_stages": (16, 16, 6, "dense_stages must be 2, 4 or 8 (dense_stages: or 16)"),
+    "bench_what": (3, 3, 4, "bench_what must be 0..3"),
+    "bench_mode": (2, 2, 3, "bench_mode must be 0, 1 or 2"),
+    "stencil_spw": (4, 4, 3, "stencil_spw must be 0,1,2,4,8"),
+    "f32_tiles": (2, 2, 8, "f32_tiles must be 0, 1, 2 or 4"),
+    "stop_factor": (0.5, 0.5, 0.0, "stop_factor must be in (0, 1]"),
+    "eo_skew": (16, 16, -2, "eo_skew must be -1 (automatic), 0 (off) or a strip height"),
+    "gj_block": (64, 64, 12, "gj_block must be 0 or a multiple of 8 in 8..256"),
+    "dense_lds": (1, 2, 3, "dense_lds must be 0, 2 or 4"),
+    "eo_tile": (8, 8, 2, "eo_tile must be 0 (off), 4 or 8 waves"),
+    "mfma3_tiles": (2, 2, 3, "mfma3_tiles must be 0, 1, 2 or 4"),
+    "mfma_small_tiles": (4, 4, 1, "mfma_small_tiles must be 0, 2 or 4"),
+    "mfma_tiles": (2, 2, 8, "mfma_tiles must be 2 or 4"),
+}
+
+
+def test_engine_option_table_round_trips_validates_and_rejects():
+    """sw_set_option / sw_get_option: every settable option reads back what is set; each validated option
+    accepts a valid value and refuses an invalid one with its message, leaving the value alone; the
+    conversions of dense_lds (1 means 2), eo_tile_dbg (two bits) and dot_blocks (at least 64) hold; the
+    read-only statistics are readable only; unknown names are refused.  Every value is restored (dot_blocks
+    is process-wide)."""
+    eng = Engine(0)
+    saved = {name: eng.get_option(name) for name in _SETTABLE_OPTIONS}
+    try:
+        for name in _SETTABLE_OPTIONS:
+            eng.set_option(name, saved[name])
+            assert eng.get_option(name) == saved[name], name
+        for name, (good, back, bad, msg) in _VALIDATED_OPTIONS.items():
+            eng.set_option(name, good)
+            assert eng.get_option(name) == back, name
+            with pytest.raises(EngineError, match=r"sw_set_option failed: %s$" % re.escape(msg)):
+                eng.set_option(name, bad)
+            assert eng.get_option(name) == back, name
+            eng.set_option(name, saved[name])
+        for name, value, back in (("eo_tile_dbg", 6, 2), ("dot_blocks", 10, 64), ("dot_blocks", 512, 512)):
+            eng.set_option(name, value)
+            assert eng.get_option(name) == back, name
+        for name in _READ_ONLY_OPTIONS:
+            eng.get_option(name)
+            with pytest.raises(EngineError, match="unknown option %s$" % name):
+                eng.set_option(name, 0)
+        for call in (lambda: eng.set_option("no_such_option", 0), lambda: eng.get_option("no_such_option")):
+            with pytest.raises(EngineError, match="unknown option no_such_option$"):
+                call()
+    finally:
+        for name in _SETTABLE_OPTIONS:
+            eng.set_option(name, saved[name])
+    assert {name: eng.get_option(name) for name in _SETTABLE_OPTIONS} == saved
     eng.close()
