@@ -580,9 +580,17 @@ static int dev_free(sw_engine* h, void* p) {
     }
   const auto t0 = std::chrono::steady_clock::now();
   if (bytes >= kPoolMinBlock && pool_cap() > 0) {
-    // nothing of this engine may still be using the block when another stream gets it
-    if (h->stream) HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->gen_stream) HIPCHK(hipStreamSynchronize(h->gen_stream));
+    // nothing of this engine may still be using the block when another stream gets it; a block whose streams
+    // cannot be drained goes back to the driver instead
+    auto drain = [&]() -> int {
+      if (h->stream) HIPCHK(hipStreamSynchronize(h->stream));
+      if (h->gen_stream) HIPCHK(hipStreamSynchronize(h->gen_stream));
+      return 0;
+    };
+    if (drain() != 0) {
+      (void)hipFree(p);
+      return 1;
+    }
     std::vector<void*> evict;
     {
       std::lock_guard<std::mutex> lk(g_pool_mu);
@@ -616,6 +624,26 @@ static int upload(sw_engine* h, T** dst, const T* src, size_t count) {
   if (count) HIPCHK(hipMemcpy(*dst, src, count * sizeof(T), hipMemcpyHostToDevice));
   return 0;
 }
+// Owner of a function-local device buffer: allocated through dev_realloc / upload on `p`, released through
+// dev_free when it goes out of scope, error returns included.  That release keeps the message already in
+// h->err: the first failure is what the caller reports.
+template <class T>
+struct DevBuf {
+  sw_engine* h;
+  T* p = nullptr;
+  explicit DevBuf(sw_engine* h_) : h(h_) {}
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : h(o.h), p(o.p) { o.p = nullptr; }
+  ~DevBuf() {
+    if (!p) return;
+    std::string first;
+    first.swap(h->err);
+    (void)dev_free(h, p);
+    h->err.swap(first);
+  }
+  operator T*() const { return p; }
+};
 static int ensure_stage(sw_engine* h, size_t bytes) {
   if (h->stage_bytes >= bytes) return 0;
   if (h->stage) SWCHK(dev_free(h, h->stage));
@@ -2726,8 +2754,8 @@ int sw_setup_transfer(sw_engine* h, int hid, int level, int nblocks, int rpb, co
   R.ngroups = nblocks;
   SWCHK(upload(h, &R.cols, (const int*)blk_rows, (size_t)nblocks * rpb));
   SWCHK(dev_realloc(h, &R.vals, (size_t)qcount));
-  cplx* Q = nullptr;
-  SWCHK(dev_realloc(h, &Q, (size_t)qcount));
+  DevBuf<cplx> Q(h);
+  SWCHK(dev_realloc(h, &Q.p, (size_t)qcount));
   // rows per lane 1, 2, 4 or 8 (8 x 8 aggregates of a block level: BASELINE config 5's 3-level hierarchy)
   SWCHK(pick_ge<64, 128, 256, 512>(rpb, [&](auto RPB) {
     return launch(h, T_OTHER, swk::k_block_qr<RPB / 64>,
@@ -2753,18 +2781,15 @@ int sw_setup_transfer(sw_engine* h, int hid, int level, int nblocks, int rpb, co
   }
   const size_t pv = (size_t)ng * K * G;
   SWCHK(dev_realloc(h, &P.vals, pv));
-  long long* dmap = nullptr;
-  SWCHK(upload(h, &dmap, (const long long*)pmap, pv));
+  DevBuf<long long> dmap(h);
+  SWCHK(upload(h, &dmap.p, (const long long*)pmap, pv));
   SWCHK(launch(h, T_OTHER, swk::k_fill_from_map, dim3(4096), dim3(SW_BLOCK), (const long long*)dmap,
                (const cplx*)Q, P.vals, pv));
   P.set = true;
   // the coarse image of the test vectors is the starting guess one level down
   if (!lc.tv) SWCHK(dev_realloc(h, &lc.tv, (size_t)n_c * 64));
   SWCHK(launch_ell(h, R, 0, lf.tv, nullptr, lc.tv, 64, T_R));
-  SWCHK(stream_sync(h));
-  SWCHK(dev_free(h, dmap));
-  SWCHK(dev_free(h, Q));
-  return 0;
+  return stream_sync(h);
 }
 
 int sw_setup_galerkin(sw_engine* h, int hid, int level, int Lc, const int32_t* nbr) {
@@ -2787,17 +2812,17 @@ int sw_setup_galerkin(sw_engine* h, int hid, int level, int Lc, const int32_t* n
       for (int b = 0; b < a; ++b)
         if (nbr[I * 5 + a] == nbr[I * 5 + b]) return sw_fail(h, "neighbour lists must hold five distinct sites");
   const int nbp = 256;
-  cplx *E = nullptr, *X = nullptr, *Y = nullptr;
-  SWCHK(dev_realloc(h, &E, (size_t)n_c * nbp));
-  SWCHK(dev_realloc(h, &X, (size_t)n_f * nbp));
-  SWCHK(dev_realloc(h, &Y, (size_t)n_f * nbp));
+  DevBuf<cplx> Y(h), X(h), E(h);     // released E, X, Y: the block pool hands X's block out first
+  SWCHK(dev_realloc(h, &E.p, (size_t)n_c * nbp));
+  SWCHK(dev_realloc(h, &X.p, (size_t)n_f * nbp));
+  SWCHK(dev_realloc(h, &Y.p, (size_t)n_f * nbp));
   SWCHK(launch(h, T_OTHER, swk::k_probe_unit, dim3((n_c + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK),
                dim3(SW_BLOCK), E, Lc, nbp));
   SWCHK(launch_ell(h, lf.P, 0, E, nullptr, X, nbp, T_P));          // X = P E
   SWCHK(apply_op(h, lf, 0, X, nullptr, Y, nbp));                   // Y = A X
   SWCHK(launch_ell(h, lf.R, 0, Y, nullptr, E, nbp, T_R));          // Z = R Y  (over E)
-  int* dnbr = nullptr;
-  SWCHK(upload(h, &dnbr, (const int*)nbr, (size_t)ncs * 5));
+  DevBuf<int> dnbr(h);
+  SWCHK(upload(h, &dnbr.p, (const int*)nbr, (size_t)ncs * 5));
   SWCHK(free_op(h, lc.A));
   EllOp& A = lc.A;
   A.nrows = A.ncols = n_c;
@@ -2814,10 +2839,6 @@ int sw_setup_galerkin(sw_engine* h, int hid, int level, int Lc, const int32_t* n
     for (int I = 0; I < ncs && last; ++I) last = nbr[I * 5 + 4] == I;
     A.bsr_diag_last = last;
   }
-  SWCHK(dev_free(h, dnbr));
-  SWCHK(dev_free(h, E));
-  SWCHK(dev_free(h, X));
-  SWCHK(dev_free(h, Y));
   return 0;
 }
 
@@ -2831,12 +2852,11 @@ int sw_setup_galerkin(sw_engine* h, int hid, int level, int Lc, const int32_t* n
 // update on the fp64 matrix cores (k_bsr_mfma3 in residual mode on the negated panel, the matrix as nbp = n
 // "probes").  n = 4096: 0.355 s -> see profiles/r03_ab_sessions.txt (r03ab).
 static int gj_invert(sw_engine* h, cplx* D, int n) {
-  cplx* colk = nullptr;
-  cplx* pvinv = nullptr;
-  int* pivs = nullptr;
-  SWCHK(dev_realloc(h, &colk, (size_t)n));
-  SWCHK(dev_realloc(h, &pvinv, (size_t)1));
-  SWCHK(dev_realloc(h, &pivs, (size_t)n + 1));
+  DevBuf<cplx> colk(h), pvinv(h);
+  DevBuf<int> pivs(h);
+  SWCHK(dev_realloc(h, &colk.p, (size_t)n));
+  SWCHK(dev_realloc(h, &pvinv.p, (size_t)1));
+  SWCHK(dev_realloc(h, &pivs.p, (size_t)n + 1));
   int* info = pivs + n;
   HIPCHK(hipMemsetAsync(info, 0, sizeof(int), h->stream));
   const int nb = (h->gj_block >= 8 && h->gj_block % 8 == 0 && n % 64 == 0 && n % h->gj_block == 0 &&
@@ -2862,15 +2882,18 @@ static int gj_invert(sw_engine* h, cplx* D, int n) {
       if ((k & 255) == 255) HIPCHK(hipStreamSynchronize(h->stream));
     }
   } else {
-    cplx* T = nullptr;
+    DevBuf<cplx> T(h), pvals(h);
+    DevBuf<int> pkcol(h);
+    SWCHK(dev_realloc(h, &T.p, (size_t)nb * n));
+    SWCHK(dev_realloc(h, &pvals.p, (size_t)(n / 16) * (nb / 4) * 64));
+    SWCHK(dev_realloc(h, &pkcol.p, (size_t)(n / 16) * (nb / 4)));
     EllOp pn;                       // -N of the current panel in block-row form
     pn.nrows = n;
     pn.ncols = nb;
     pn.bsr_KS = nb / 4;
+    pn.bsr_vals = pvals;
+    pn.bsr_kcol = pkcol;
     pn.set = true;
-    SWCHK(dev_realloc(h, &T, (size_t)nb * n));
-    SWCHK(dev_realloc(h, &pn.bsr_vals, (size_t)(n / 16) * pn.bsr_KS * 64));
-    SWCHK(dev_realloc(h, &pn.bsr_kcol, (size_t)(n / 16) * pn.bsr_KS));
     const size_t items = (size_t)(n / 16) * pn.bsr_KS;
     for (int k0 = 0; k0 < n; k0 += nb) {
       if (nb <= 64) {
@@ -2892,8 +2915,6 @@ static int gj_invert(sw_engine* h, cplx* D, int n) {
       if (((k0 / nb) & 7) == 7) HIPCHK(hipStreamSynchronize(h->stream));      // (shallow queue, as above)
     }
     SWCHK(stream_sync(h));
-    SWCHK(dev_free(h, T));
-    SWCHK(free_op(h, pn));
   }
   hipLaunchKernelGGL(swk::k_gj_unpermute, g1, dim3(SW_BLOCK), 0, h->stream, D, n, (const int*)pivs);
   KLAUNCH_CHECK();
@@ -2901,10 +2922,46 @@ static int gj_invert(sw_engine* h, cplx* D, int n) {
   int hinfo = 0;
   HIPCHK(hipMemcpyAsync(&hinfo, info, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   SWCHK(stream_sync(h));
-  SWCHK(dev_free(h, colk));
-  SWCHK(dev_free(h, pvinv));
-  SWCHK(dev_free(h, pivs));
   if (hinfo != 0) return sw_fail(h, "Gauss-Jordan inverse: the matrix is singular");
+  return 0;
+}
+
+// Zero the dense row-major [n][n] matrix D and expand op into it: its block-row form over all n / 16 row tiles, or
+// over a subset of them (bsr_tmap) with colrank[site tile] the dense tile of each column, where it has one; else
+// its grouped-ELL form (sw_set_csr builds both from one CSR: each kernel writes every non-zero once and skips zeros).
+static int op_to_dense(sw_engine* h, const EllOp& op, int n, cplx* D, const int* colrank) {
+  HIPCHK(hipMemsetAsync(D, 0, (size_t)n * n * sizeof(cplx), h->stream));
+  if (op.bsr_KS > 0 && (!op.bsr_tmap || colrank)) {
+    const int items = (n / 16) * op.bsr_KS;
+    return launch(h, T_OTHER, swk::k_bsr_to_dense, dim3((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK),
+                  dim3(SW_BLOCK), (const cplx*)op.bsr_vals, (const int*)op.bsr_kcol, n / 16, op.bsr_KS, n, D, colrank,
+                  (const int*)nullptr);
+  }
+  if (op.cols && op.vals) {
+    const size_t total = (size_t)op.ngroups * op.K * op.G;
+    return launch(h, T_OTHER, swk::k_ell_to_dense, dim3((unsigned)((total + SW_BLOCK - 1) / SW_BLOCK)),
+                  dim3(SW_BLOCK), (const int*)op.cols, (const cplx*)op.vals, op.K, op.G, op.ngroups, n, D);
+  }
+  return sw_fail(h, "operator in neither grouped-ELL nor block-row form");
+}
+
+// op <- the block-row form of the dense row-major [n][n] matrix D, as an operator of `rows` rows: every 4-column
+// group of each of its n / 16 row tiles.  tmap (optional, with its device copy d_tmap): dense tile t is the
+// level's site tile tmap[t], for rows and columns.
+static int dense_to_bsr(sw_engine* h, EllOp& op, int rows, const cplx* D, int n, const std::vector<int>* tmap,
+                        const int* d_tmap) {
+  SWCHK(free_op(h, op));
+  op.nrows = op.ncols = rows;
+  op.bsr_RT = n / 16;
+  op.bsr_KS = n / 4;
+  if (tmap) SWCHK(upload(h, &op.bsr_tmap, tmap->data(), tmap->size()));
+  const size_t items = (size_t)op.bsr_RT * op.bsr_KS;
+  SWCHK(dev_realloc(h, &op.bsr_vals, items * 64));
+  SWCHK(dev_realloc(h, &op.bsr_kcol, items));
+  SWCHK(launch(h, T_OTHER, swk::k_dense_to_bsr, dim3((unsigned)((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK)),
+               dim3(SW_BLOCK), D, n, op.bsr_vals, op.bsr_kcol, d_tmap));
+  op.set = true;
+  op.dense_uniform = true;     // k_dense_to_bsr: the column list depends on the k-step only
   return 0;
 }
 
@@ -2914,50 +2971,16 @@ int sw_setup_invert_coarsest(sw_engine* h, int hid) {
   Hier& H = h->hier[hid];
   H.f32_valid = H.even_valid = false;
   Level& lv = H.lv[H.nlevels - 1];
-  const EllOp& A = lv.A;
-  if (H.nlevels < 2 || !A.set) return sw_fail(h, "coarsest level has no operator");
+  if (H.nlevels < 2 || !lv.A.set) return sw_fail(h, "coarsest level has no operator");
   const int n = lv.n;
   if (n % 16) return sw_fail(h, "coarsest size %d is not a multiple of 16", n);
   if (n > 8192) return sw_fail(h, "coarsest size %d too large for the in-engine dense inverse", n);
-  cplx* D = nullptr;
-  SWCHK(dev_realloc(h, &D, (size_t)n * n));
-  HIPCHK(hipMemsetAsync(D, 0, (size_t)n * n * sizeof(cplx), h->stream));
-  if (A.bsr_KS > 0 && !A.bsr_tmap) {
-    const int items = (n / 16) * A.bsr_KS;
-    SWCHK(launch(h, T_OTHER, swk::k_bsr_to_dense, dim3((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK),
-                 dim3(SW_BLOCK), (const cplx*)A.bsr_vals, (const int*)A.bsr_kcol, n / 16, A.bsr_KS, n, D,
-                 (const int*)nullptr, (const int*)nullptr));
-  } else if (A.cols && A.vals) {
-    // a coarsest operator handed over as CSR (sw_set_csr: the reference hierarchy's R A P)
-    const size_t total = (size_t)A.ngroups * A.K * A.G;
-    SWCHK(launch(h, T_OTHER, swk::k_ell_to_dense, dim3((unsigned)((total + SW_BLOCK - 1) / SW_BLOCK)),
-                 dim3(SW_BLOCK), (const int*)A.cols, (const cplx*)A.vals, A.K, A.G, A.ngroups, n, D));
-  } else {
-    (void)dev_free(h, D);
-    return sw_fail(h, "coarsest operator in neither grouped-ELL nor full block-row form");
-  }
-  if (gj_invert(h, D, n) != 0) {
-    (void)dev_free(h, D);
-    return 1;
-  }
-  SWCHK(free_op(h, H.cinv));
-  EllOp& op = H.cinv;
-  op.nrows = op.ncols = n;
-  const int KS = n / 4, RT = n / 16;
-  SWCHK(dev_realloc(h, &op.bsr_vals, (size_t)RT * KS * 64));
-  SWCHK(dev_realloc(h, &op.bsr_kcol, (size_t)RT * KS));
-  {
-    const size_t items = (size_t)RT * KS;
-    SWCHK(launch(h, T_OTHER, swk::k_dense_to_bsr,
-                 dim3((unsigned)((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK)), dim3(SW_BLOCK),
-                 (const cplx*)D, n, op.bsr_vals, op.bsr_kcol, (const int*)nullptr));
-  }
-  op.bsr_KS = KS;
-  op.set = true;
-  op.dense_uniform = true;     // k_dense_to_bsr: the column list depends on the k-step only
-  SWCHK(stream_sync(h));
-  SWCHK(dev_free(h, D));
-  return 0;
+  DevBuf<cplx> D(h);
+  SWCHK(dev_realloc(h, &D.p, (size_t)n * n));
+  SWCHK(op_to_dense(h, lv.A, n, D, nullptr));
+  SWCHK(gj_invert(h, D, n));
+  SWCHK(dense_to_bsr(h, H.cinv, n, D, n, nullptr, nullptr));
+  return stream_sync(h);
 }
 
 // The dense coarsest inverse the engine holds (set by the caller or formed on the device) as a row-major
@@ -2967,31 +2990,14 @@ int sw_get_coarsest_inv(sw_engine* h, int hid, double* dense) {
   SWCHK(check_hier(h, hid, 0, false));
   if (!dense) return sw_fail(h, "bad arguments");
   HIPCHK(hipSetDevice(h->device));
-  Hier& H = h->hier[hid];
-  const EllOp& op = H.cinv;
+  const EllOp& op = h->hier[hid].cinv;
   if (!op.set) return sw_fail(h, "coarsest inverse missing");
   const int n = op.nrows;
-  cplx* D = nullptr;
-  SWCHK(dev_realloc(h, &D, (size_t)n * n));
-  HIPCHK(hipMemsetAsync(D, 0, (size_t)n * n * sizeof(cplx), h->stream));
-  if (op.bsr_KS > 0 && !op.bsr_tmap) {
-    const size_t items = (size_t)(n / 16) * op.bsr_KS;
-    SWCHK(launch(h, T_OTHER, swk::k_bsr_to_dense,
-                 dim3((unsigned)((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK)), dim3(SW_BLOCK),
-                 (const cplx*)op.bsr_vals, (const int*)op.bsr_kcol, n / 16, op.bsr_KS, n, D, (const int*)nullptr,
-                 (const int*)nullptr));
-  } else if (op.cols && op.vals) {
-    const size_t total = (size_t)op.ngroups * op.K * op.G;
-    SWCHK(launch(h, T_OTHER, swk::k_ell_to_dense, dim3((unsigned)((total + SW_BLOCK - 1) / SW_BLOCK)),
-                 dim3(SW_BLOCK), (const int*)op.cols, (const cplx*)op.vals, op.K, op.G, op.ngroups, n, D));
-  } else {
-    (void)dev_free(h, D);
-    return sw_fail(h, "coarsest inverse in an unknown form");
-  }
+  DevBuf<cplx> D(h);
+  SWCHK(dev_realloc(h, &D.p, (size_t)n * n));
+  SWCHK(op_to_dense(h, op, n, D, nullptr));
   HIPCHK(hipMemcpyAsync(dense, D, (size_t)n * n * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
-  SWCHK(stream_sync(h));
-  SWCHK(dev_free(h, D));
-  return 0;
+  return stream_sync(h);
 }
 
 static int schur_apply(sw_engine* h, Level& lv, int mode, const cplx* X, const cplx* Bp, cplx* Y, int nbp);
@@ -3024,45 +3030,15 @@ int sw_setup_direct_level(sw_engine* h, int hid, int level) {
   HIPCHK(hipMemcpy(kc.data(), S.bsr_kcol, kc.size() * sizeof(int), hipMemcpyDeviceToHost));
   for (int c : kc)
     if (erank[c >> 4] < 0) return sw_fail(h, "level %d: the Schur operator reaches an odd site", level);
-  int *d_rank = nullptr, *d_E = nullptr;
-  SWCHK(upload(h, &d_rank, erank.data(), erank.size()));
-  SWCHK(upload(h, &d_E, E.data(), E.size()));
-  cplx* D = nullptr;
-  SWCHK(dev_realloc(h, &D, (size_t)n * n));
-  HIPCHK(hipMemsetAsync(D, 0, (size_t)n * n * sizeof(cplx), h->stream));
-  {
-    const int items = ne * S.bsr_KS;
-    SWCHK(launch(h, T_OTHER, swk::k_bsr_to_dense, dim3((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK),
-                 dim3(SW_BLOCK), (const cplx*)S.bsr_vals, (const int*)S.bsr_kcol, ne, S.bsr_KS, n, D,
-                 (const int*)d_rank, (const int*)nullptr));
-  }
-  if (gj_invert(h, D, n) != 0) {
-    (void)dev_free(h, D);
-    (void)dev_free(h, d_rank);
-    (void)dev_free(h, d_E);
-    return 1;
-  }
-  EllOp& op = lv.eo_op[4];
-  SWCHK(free_op(h, op));
-  op.nrows = op.ncols = lv.n;
-  op.bsr_RT = ne;
-  op.bsr_KS = n / 4;
-  SWCHK(upload(h, &op.bsr_tmap, E.data(), E.size()));
-  SWCHK(dev_realloc(h, &op.bsr_vals, (size_t)ne * op.bsr_KS * 64));
-  SWCHK(dev_realloc(h, &op.bsr_kcol, (size_t)ne * op.bsr_KS));
-  {
-    const size_t items = (size_t)ne * op.bsr_KS;
-    SWCHK(launch(h, T_OTHER, swk::k_dense_to_bsr,
-                 dim3((unsigned)((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK)), dim3(SW_BLOCK),
-                 (const cplx*)D, n, op.bsr_vals, op.bsr_kcol, (const int*)d_E));
-  }
-  op.set = true;
-  op.dense_uniform = true;     // k_dense_to_bsr: the column list depends on the k-step only
-  SWCHK(stream_sync(h));
-  SWCHK(dev_free(h, D));
-  SWCHK(dev_free(h, d_rank));
-  SWCHK(dev_free(h, d_E));
-  return 0;
+  DevBuf<int> d_rank(h), d_E(h);
+  SWCHK(upload(h, &d_rank.p, erank.data(), erank.size()));
+  SWCHK(upload(h, &d_E.p, E.data(), E.size()));
+  DevBuf<cplx> D(h);
+  SWCHK(dev_realloc(h, &D.p, (size_t)n * n));
+  SWCHK(op_to_dense(h, S, n, D, d_rank));
+  SWCHK(gj_invert(h, D, n));
+  SWCHK(dense_to_bsr(h, lv.eo_op[4], lv.n, D, n, &E, d_E));
+  return stream_sync(h);
 }
 
 // Dense inverse of a small level's operator (n <= 8192, n % 16 == 0; grouped-ELL operator from sw_set_csr, or the
@@ -3081,47 +3057,14 @@ int sw_setup_level_inverse(sw_engine* h, int hid, int level) {
   const int n = lv.n;
   if (lv.stencil) return sw_fail(h, "level %d is the lattice level", level);
   if (n <= 0 || n % 16 || n > 8192) return sw_fail(h, "level %d: size %d not a multiple of 16 or above 8192", level, n);
-  const EllOp& A = lv.A;
-  if (!A.set) return sw_fail(h, "level %d has no operator", level);
-  cplx* D = nullptr;
-  SWCHK(dev_realloc(h, &D, (size_t)n * n));
-  HIPCHK(hipMemsetAsync(D, 0, (size_t)n * n * sizeof(cplx), h->stream));
-  if (A.cols && A.vals) {
-    const size_t total = (size_t)A.ngroups * A.K * A.G;
-    SWCHK(launch(h, T_OTHER, swk::k_ell_to_dense, dim3((unsigned)((total + SW_BLOCK - 1) / SW_BLOCK)),
-                 dim3(SW_BLOCK), (const int*)A.cols, (const cplx*)A.vals, A.K, A.G, A.ngroups, n, D));
-  } else if (A.bsr_KS > 0 && !A.bsr_tmap) {
-    const int items = (n / 16) * A.bsr_KS;
-    SWCHK(launch(h, T_OTHER, swk::k_bsr_to_dense, dim3((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK),
-                 dim3(SW_BLOCK), (const cplx*)A.bsr_vals, (const int*)A.bsr_kcol, n / 16, A.bsr_KS, n, D,
-                 (const int*)nullptr, (const int*)nullptr));
-  } else {
-    (void)dev_free(h, D);
-    return sw_fail(h, "level %d: operator in neither grouped-ELL nor full block-row form", level);
-  }
-  if (gj_invert(h, D, n) != 0) {
-    (void)dev_free(h, D);
-    return 1;
-  }
-  EllOp& op = lv.dinv;
-  SWCHK(free_op(h, op));
-  op.nrows = op.ncols = n;
-  const int KS = n / 4, RT = n / 16;
-  SWCHK(dev_realloc(h, &op.bsr_vals, (size_t)RT * KS * 64));
-  SWCHK(dev_realloc(h, &op.bsr_kcol, (size_t)RT * KS));
-  {
-    const size_t items = (size_t)RT * KS;
-    SWCHK(launch(h, T_OTHER, swk::k_dense_to_bsr,
-                 dim3((unsigned)((items + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK)), dim3(SW_BLOCK),
-                 (const cplx*)D, n, op.bsr_vals, op.bsr_kcol, (const int*)nullptr));
-  }
-  op.bsr_KS = KS;
-  op.set = true;
-  op.dense_uniform = true;     // k_dense_to_bsr: the column list depends on the k-step only
+  if (!lv.A.set) return sw_fail(h, "level %d has no operator", level);
+  DevBuf<cplx> D(h);
+  SWCHK(dev_realloc(h, &D.p, (size_t)n * n));
+  SWCHK(op_to_dense(h, lv.A, n, D, nullptr));
+  SWCHK(gj_invert(h, D, n));
+  SWCHK(dense_to_bsr(h, lv.dinv, n, D, n, nullptr, nullptr));
   H.f32_valid = false;
-  SWCHK(stream_sync(h));
-  SWCHK(dev_free(h, D));
-  return 0;
+  return stream_sync(h);
 }
 
 // Arnoldi relation of a level's operator for the smoother polynomial (hierarchy.smoother_weights fits
@@ -3145,10 +3088,10 @@ int sw_setup_arnoldi(sw_engine* h, int hid, int level, int which, int degree, ui
   const int nbp = 64;
   const int n = (schur && lv.stencil) ? lv.n / 2 : lv.n;     // rows of the vectors the operator acts on
   const size_t vec = (size_t)n * nbp;
-  cplx* V = nullptr;      // degree + 1 basis vectors
-  cplx* d = nullptr;      // [2][degree + 1][nbp] dots of the two passes, + [nbp] norm
-  SWCHK(dev_realloc(h, &V, vec * (degree + 1)));
-  SWCHK(dev_realloc(h, &d, (size_t)(2 * (degree + 1) + 1) * nbp));
+  DevBuf<cplx> V(h);      // degree + 1 basis vectors
+  DevBuf<cplx> d(h);      // [2][degree + 1][nbp] dots of the two passes, + [nbp] norm
+  SWCHK(dev_realloc(h, &V.p, vec * (degree + 1)));
+  SWCHK(dev_realloc(h, &d.p, (size_t)(2 * (degree + 1) + 1) * nbp));
   cplx* d1 = d;
   cplx* d2 = d + (size_t)(degree + 1) * nbp;
   cplx* nr = d + (size_t)2 * (degree + 1) * nbp;
@@ -3199,8 +3142,6 @@ int sw_setup_arnoldi(sw_engine* h, int hid, int level, int which, int degree, ui
   }
   SWCHK(stream_sync(h));
   std::memcpy(Hout, Hm.data(), Hm.size() * sizeof(std::complex<double>));
-  SWCHK(dev_free(h, V));
-  SWCHK(dev_free(h, d));
   return 0;
 }
 
@@ -3376,8 +3317,8 @@ int sw_setup_eo_operators(sw_engine* h, int hid, int level, int Lc) {
   const cplx* Av = A.bsr_vals;
   auto ablk = [](int s, int j) { return ((long long)s * 20 + 4 * j) * 64; };          // block j of row site s in A
   auto oblk = [](int r, int nblk, int q) { return ((long long)r * nblk + q) * 256; };   // block q of row r
-  int* info = nullptr;
-  SWCHK(dev_realloc(h, &info, (size_t)1));
+  DevBuf<int> info(h);
+  SWCHK(dev_realloc(h, &info.p, (size_t)1));
   HIPCHK(hipMemsetAsync(info, 0, sizeof(int), h->stream));
   // G
   {
@@ -3386,36 +3327,28 @@ int sw_setup_eo_operators(sw_engine* h, int hid, int level, int Lc) {
       so[r] = ablk(O[r], 4);
       dof[r] = oblk(r, 1, 0);
     }
-    long long *dso = nullptr, *ddo = nullptr;
-    SWCHK(upload(h, &dso, so.data(), so.size()));
-    SWCHK(upload(h, &ddo, dof.data(), dof.size()));
+    DevBuf<long long> dso(h), ddo(h);
+    SWCHK(upload(h, &dso.p, so.data(), so.size()));
+    SWCHK(upload(h, &ddo.p, dof.data(), dof.size()));
     SWCHK(launch(h, T_OTHER, swk::k_block_inverse, dim3(no), dim3(256), Av, (const long long*)dso,
                  lv.eo_op[2].bsr_vals, (const long long*)ddo, info));
     SWCHK(stream_sync(h));
-    SWCHK(dev_free(h, dso));
-    SWCHK(dev_free(h, ddo));
   }
   auto products = [&](const std::vector<int>& ptr, const std::vector<long long>& ao,
                       const std::vector<long long>& bo, const cplx* Ab, const cplx* Bb,
                       const std::vector<long long>& io, double sign, cplx* out,
                       const std::vector<long long>& oo) -> int {
-    int* dptr = nullptr;
-    long long *dao = nullptr, *dbo = nullptr, *dio = nullptr, *doo = nullptr;
-    SWCHK(upload(h, &dptr, ptr.data(), ptr.size()));
-    SWCHK(upload(h, &dao, ao.data(), ao.size()));
-    SWCHK(upload(h, &dbo, bo.data(), bo.size()));
-    SWCHK(upload(h, &dio, io.data(), io.size()));
-    SWCHK(upload(h, &doo, oo.data(), oo.size()));
+    DevBuf<int> dptr(h);
+    DevBuf<long long> dao(h), dbo(h), dio(h), doo(h);
+    SWCHK(upload(h, &dptr.p, ptr.data(), ptr.size()));
+    SWCHK(upload(h, &dao.p, ao.data(), ao.size()));
+    SWCHK(upload(h, &dbo.p, bo.data(), bo.size()));
+    SWCHK(upload(h, &dio.p, io.data(), io.size()));
+    SWCHK(upload(h, &doo.p, oo.data(), oo.size()));
     SWCHK(launch(h, T_OTHER, swk::k_block_products, dim3((unsigned)oo.size()), dim3(256), (const int*)dptr,
                  (const long long*)dao, (const long long*)dbo, Ab, Bb, (const long long*)dio, Av, sign, out,
                  (const long long*)doo));
-    SWCHK(stream_sync(h));
-    SWCHK(dev_free(h, dptr));
-    SWCHK(dev_free(h, dao));
-    SWCHK(dev_free(h, dbo));
-    SWCHK(dev_free(h, dio));
-    SWCHK(dev_free(h, doo));
-    return 0;
+    return stream_sync(h);
   };
   const cplx* Gv = lv.eo_op[2].bsr_vals;
   // F(e, j) = A(e, j) G(o_j);  Hb(o, j) = G(o) A(o, j)
@@ -3476,7 +3409,6 @@ int sw_setup_eo_operators(sw_engine* h, int hid, int level, int Lc) {
   }
   int hinfo = 0;
   HIPCHK(hipMemcpy(&hinfo, info, sizeof(int), hipMemcpyDeviceToHost));
-  SWCHK(dev_free(h, info));
   if (hinfo != 0) return sw_fail(h, "level %d: a diagonal block of an odd site is singular", level);
   return 0;
 }

@@ -402,6 +402,32 @@ def test_blocked_gauss_jordan_inverse_matches_the_unblocked_one():
     eng.close()
 
 
+def test_singular_coarsest_operator_is_refused_and_the_engine_then_inverts_a_regular_one():
+    """sw_setup_invert_coarsest on a singular operator fails with the Gauss-Jordan inverse's own reason (an
+    all-zero pivot column): the device scratch released on the way out must not replace that message.  The same
+    engine then inverts a regular operator, applied through sw_coarsest against NumPy.  Two-level hierarchy of
+    16 rows per level on a fresh engine: level 0 from CSR, identity transfer, coarsest operator from CSR (the
+    singular one grouped-ELL only, the dense regular one also in block-row form)."""
+    n, hid = 16, 1
+    eng = Engine(0)
+    try:
+        eng.hier_begin(hid, 2)
+        eng.set_csr(hid, 0, sp.csr_matrix(np.diag(np.full(n, 2.0 + 0j))))
+        eng.set_transfer(hid, 0, sp.identity(n, dtype=complex, format="csr"))
+        keep = np.arange(n) != 5                       # the identity without its diagonal entry 5
+        eng.set_csr(hid, 1, sp.csr_matrix((np.ones(n - 1, dtype=complex), (np.nonzero(keep)[0],) * 2), shape=(n, n)))
+        with pytest.raises(EngineError, match=r"the matrix is singular$"):
+            eng.setup_invert_coarsest(hid)
+        M = _rand((n, n), 93) + 8.0 * np.eye(n)
+        eng.set_csr(hid, 1, sp.csr_matrix(M))
+        eng.setup_invert_coarsest(hid)
+        eng.hier_end(hid)
+        X = _rand((3, n), 94)
+        assert _relerr(eng.coarsest(hid, X), np.linalg.solve(M, X.T).T) < 1e-12
+    finally:
+        eng.close()
+
+
 def test_three_product_block_row_kernel_matches_the_four_product_one():
     """engine option mfma_3m: the block-row operator with three real matrix products per complex one
     (k_bsr_mfma3: T1 = Ar Xr, T2 = Ai Xi, T3 = (Ar + Ai)(Xr + Xi)) against the four-product kernel and
