@@ -5,8 +5,9 @@ One step = one batch of NB (default 256) deflated-Hutchinson probes per engine s
 the probes are GENERATED on the GPU inside the timed region (the reference's MT19937 stream,
 bit-exact, k_mt_generate) and solved as one multi-RHS batch in fp64 to a relative residual of
 1e-12 (config 2 of BASELINE.json; with --gpus N the probe stream is sharded in contiguous
-blocks over N ranks, config 4, every rank jumping straight to its stream positions).  The line
-printed by rank 0 also carries
+blocks over N ranks, config 4, every rank jumping straight to its stream positions).  A plain run
+sets up, warms up, times the steps, writes --dump-outputs and prints the line.  With ``--full``
+the run goes on after the timed region, and the line printed by rank 0 also carries
 
 * ``value_probes_resident``: the same steps with the probes already resident in HBM (round 1's
   headline), and ``value_pcie_inclusive_this_rank``: with host-made probes uploaded per step;
@@ -74,20 +75,27 @@ def parse():
     ap.add_argument("--synthetic-levels", type=int, default=0,
                     help="--workload synthetic: 0 the tuned hierarchy (five levels at 1024^2), 3 BASELINE config 5 as "
                          "written (2097152 -> 262144 -> 4096)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything that takes runs of its own and add it "
+                         "to the result line: the steps at the reference's stopping point, with resident and "
+                         "with uploaded probes, with the single-precision preconditioner, probe generation "
+                         "alone, the instrumented step behind the per-kernel rooflines, the 1024^2 stencil "
+                         "point, the CPU baseline and the other BASELINE configurations (minutes).  Without "
+                         "it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-f32-line", action="store_true",
-                    help="skip the secondary measurement with the single-precision preconditioner")
+                    help="--full: skip the secondary measurement with the single-precision preconditioner")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the compact driver-run records of the other BASELINE configurations "
+                    help="--full: skip the compact records of the other BASELINE configurations "
                          "(config 2 as written, config 3's MLMC difference, config 5's 1024^2 lattice, the "
                          "strict parity mode, the drop-in G102 / G202 flows)")
     ap.add_argument("--no-large-stencil", action="store_true",
-                    help="skip the synthetic 1024^2 stencil roofline point")
+                    help="--full: skip the synthetic 1024^2 stencil roofline point")
     ap.add_argument("--engine-opts", type=str, default=os.environ.get("SW_ENGINE_OPTS", ""),
                     help="comma-separated name=value engine switches (sw_set_option) for A/B runs")
-    ap.add_argument("--cpu-probes", type=int, default=8)
+    ap.add_argument("--cpu-probes", type=int, default=8, help="--full: probes of the one-core CPU baseline")
     ap.add_argument("--cpu-workers", type=int, default=-1,
-                    help="processes of the all-cores CPU baseline line (-1: min(cores, 16); 0: skip)")
+                    help="--full: processes of the all-cores CPU baseline line (-1: min(cores, 16); 0: skip)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned to its caller as "
                          "DIR/<name>.npy (float64, at most 64 MB in all): the per-probe estimates, the "
@@ -527,119 +535,153 @@ def run(args):
             dumped["trace_estimate"] = [np.real(mean_t + tr1), np.imag(mean_t + tr1), std_t]
         dump_outputs(args.dump_outputs, dumped)
 
-    # ---- the same K steps at the reference's own stopping point (stop_factor = 1: residual below tol, where
-    # pyamg's fgmres stops; per-probe parity then holds to 1e-10 of max(|e|, a tenth of the batch median)) ----
-    elapsed_refstop = None
-    if args.stop_factor != 1.0:
-        for e_ in engs:
-            e_.set_option("stop_factor", 1.0)
-        for e in range(ne):
-            gen_ready[e] = None
-        step(max(0, args.warmup - 1))      # one untimed step in the other mode
+    levels = mg.solver_info["levels"] if mg.solver_info else [lev.A.shape[0] for lev in mg.ml.levels]
 
-        def refstop():
-            acc = np.zeros(4)
-            last = args.warmup + args.steps - 1
-            for s in range(args.warmup, last + 1):
-                acc += step(s, prefetch=(s < last))[2]
-            comm.allreduce_stats(acc)
-        for e in range(ne):
-            gen_ready[e] = None
-        elapsed_refstop = timed(refstop, ends_with_collective=True)
-        for e_ in engs:
-            e_.set_option("stop_factor", args.stop_factor)
-        for e in range(ne):
-            gen_ready[e] = None
+    def full_records():
+        """--full: every measurement that takes runs of its own after the timed region, and the keys of the
+        result line they fill (on rank 0; the other ranks take part in the steps and return nothing)."""
+        # ---- the same K steps at the reference's own stopping point (stop_factor = 1: residual below tol, where
+        # pyamg's fgmres stops; per-probe parity then holds to 1e-10 of max(|e|, a tenth of the batch median)) ----
+        elapsed_refstop = None
+        if args.stop_factor != 1.0:
+            for e_ in engs:
+                e_.set_option("stop_factor", 1.0)
+            for e in range(ne):
+                gen_ready[e] = None
+            step(max(0, args.warmup - 1))      # one untimed step in the other mode
 
-    # ---- secondary: the same steps with the probes resident in HBM before the clock starts
-    # (round 1's definition), and with host-made probes uploaded per step (PCIe-inclusive) -------
-    nres = min(args.steps, 8)
-    for i in range(nres):
-        for e in range(ne):
-            engs[e].probes_generate(2 + i, 0, nb, block_start(args.warmup + i, e) * n)
-    for e in range(ne):
-        engs[e].sync()
-    elapsed_resident = timed(lambda: [step(args.warmup + i, False, 2 + i) for i in range(nres)])
-    host_batches = [ProbeStream(7 + e).rademacher(nb, n) for e in range(ne)]
+            def refstop():
+                acc = np.zeros(4)
+                last = args.warmup + args.steps - 1
+                for s in range(args.warmup, last + 1):
+                    acc += step(s, prefetch=(s < last))[2]
+                comm.allreduce_stats(acc)
+            for e in range(ne):
+                gen_ready[e] = None
+            elapsed_refstop = timed(refstop, ends_with_collective=True)
+            for e_ in engs:
+                e_.set_option("stop_factor", args.stop_factor)
+            for e in range(ne):
+                gen_ready[e] = None
 
-    def pcie():
+        # ---- secondary: the same steps with the probes resident in HBM before the clock starts
+        # (round 1's definition), and with host-made probes uploaded per step (PCIe-inclusive) -------
+        nres = min(args.steps, 8)
         for i in range(nres):
             for e in range(ne):
-                engs[e].probes_upload_slot(2 + i, 0, host_batches[e])
-            step(args.warmup + i, False, 2 + i)
-    elapsed_pcie = timed(pcie)
+                engs[e].probes_generate(2 + i, 0, nb, block_start(args.warmup + i, e) * n)
+        for e in range(ne):
+            engs[e].sync()
+        elapsed_resident = timed(lambda: [step(args.warmup + i, False, 2 + i) for i in range(nres)])
+        host_batches = [ProbeStream(7 + e).rademacher(nb, n) for e in range(ne)]
 
-    # ---- secondary: the same K steps with the multigrid cycle in single precision (complex64 on the
-    # f32 matrix cores) INSIDE the fp64 flexible GMRES -- residuals, orthogonalisation and the
-    # true-residual verification stay fp64, every probe converges to the same tol.  Reported next
-    # to `value`, never as `value` (which is the all-fp64 path).
-    f32_line = None
-    scfg_used = (mg.solver_info or {}).get("cfg") if mg.solver_info else None
-    if scfg_used and swhier.f32_capable(scfg_used) and not args.no_f32_line:
-        for e_ in engs:
-            e_.set_option("precond_f32", 1)
-        step(args.warmup + args.steps)                      # builds the complex64 mirrors
-        its32 = []
-        ref_chk = []
+        def pcie():
+            for i in range(nres):
+                for e in range(ne):
+                    engs[e].probes_upload_slot(2 + i, 0, host_batches[e])
+                step(args.warmup + i, False, 2 + i)
+        elapsed_pcie = timed(pcie)
 
-        def f32_steps():
-            acc = np.zeros(4)
-            for s in range(args.warmup, args.warmup + args.steps):
-                ests, itf, stats = step(s)
-                its32.append(int(itf.max()))
-                acc += stats
-            ref_chk.append(comm.allreduce_stats(acc))
-        elapsed_f32 = timed(f32_steps)
-        for e_ in engs:
-            e_.set_option("precond_f32", 0)
-        tot32 = np.sum(ref_chk, axis=0)
-        f32_line = {"value": world * ne * args.steps * nb / elapsed_f32,
-                    "ms_per_step": 1e3 * elapsed_f32 / args.steps,
-                    "outer_iterations_max": max(its32),
-                    # same probes as the fp64 steps: the sums of the per-probe estimates agree to
-                    # the solver tolerance
-                    "rel_diff_of_estimate_sum_vs_fp64": float(abs(tot32[0] - total[0]) / abs(total[0]))
-                    if total[0] != 0 else None,
-                    "note": "multigrid preconditioner in complex64 (k_bsr_mfma_f32, k_schur_step<float2>) "
-                            "inside the fp64 FGMRES; tol %.0e reached by every probe in fp64" % args.tol}
+        # ---- secondary: the same K steps with the multigrid cycle in single precision (complex64 on the
+        # f32 matrix cores) INSIDE the fp64 flexible GMRES -- residuals, orthogonalisation and the
+        # true-residual verification stay fp64, every probe converges to the same tol.  Reported next
+        # to `value`, never as `value` (which is the all-fp64 path).
+        f32_line = None
+        scfg_used = (mg.solver_info or {}).get("cfg") if mg.solver_info else None
+        if scfg_used and swhier.f32_capable(scfg_used) and not args.no_f32_line:
+            for e_ in engs:
+                e_.set_option("precond_f32", 1)
+            step(args.warmup + args.steps)                      # builds the complex64 mirrors
+            its32 = []
+            ref_chk = []
 
-    # ---- generation alone (device time of k_mt_jump + k_mt_generate per batch) ------------------
-    def gen_only():
-        for i in range(nres):
-            engs[0].probes_generate(0, 0, nb, block_start(args.warmup + i, 0) * n)
-        engs[0].sync()
-    gen_ms = 1e3 * timed(gen_only) / nres
+            def f32_steps():
+                acc = np.zeros(4)
+                for s in range(args.warmup, args.warmup + args.steps):
+                    ests, itf, stats = step(s)
+                    its32.append(int(itf.max()))
+                    acc += stats
+                ref_chk.append(comm.allreduce_stats(acc))
+            elapsed_f32 = timed(f32_steps)
+            for e_ in engs:
+                e_.set_option("precond_f32", 0)
+            tot32 = np.sum(ref_chk, axis=0)
+            f32_line = {"value": world * ne * args.steps * nb / elapsed_f32,
+                        "ms_per_step": 1e3 * elapsed_f32 / args.steps,
+                        "outer_iterations_max": max(its32),
+                        # same probes as the fp64 steps: the sums of the per-probe estimates agree to
+                        # the solver tolerance
+                        "rel_diff_of_estimate_sum_vs_fp64": float(abs(tot32[0] - total[0]) / abs(total[0]))
+                        if total[0] != 0 else None,
+                        "note": "multigrid preconditioner in complex64 (k_bsr_mfma_f32, k_schur_step<float2>) "
+                                "inside the fp64 FGMRES; tol %.0e reached by every probe in fp64" % args.tol}
 
-    # ---- instrumented step: HIP events around every launch, on the engine stream ----------
-    eng.set_profiling(True)
-    eng.timers_reset()
-    run_one(0, args.warmup + args.steps)      # one stream alone: clean per-kernel durations
-    levels = mg.solver_info["levels"] if mg.solver_info else [lev.A.shape[0] for lev in mg.ml.levels]
-    pmc_all = {}
-    try:
-        pmc_all = json.load(open(os.path.join(ROOT, "profiles", "kernel_pmc.json")))
-    except Exception:
+        # ---- generation alone (device time of k_mt_jump + k_mt_generate per batch) ------------------
+        def gen_only():
+            for i in range(nres):
+                engs[0].probes_generate(0, 0, nb, block_start(args.warmup + i, 0) * n)
+            engs[0].sync()
+        gen_ms = 1e3 * timed(gen_only) / nres
+
+        # ---- instrumented step: HIP events around every launch, on the engine stream ----------
+        eng.set_profiling(True)
+        eng.timers_reset()
+        run_one(0, args.warmup + args.steps)      # one stream alone: clean per-kernel durations
         pmc_all = {}
-    if synthetic:
-        pmc_all = {}
-    elif args.workload != "hutchinson":
-        pmc_all = {k: v for k, v in pmc_all.items() if k.startswith(("k_stencil", "k_schur"))}
-    kroofs = kernel_rooflines(eng, levels, V, nbp, pmc_all,
-                              skip=("k_bsr_mfma(level-1 operator)", "k_bsr_mfma(level-2 operator)")
-                              if synthetic else (), three_products="mfma_3m=0" not in args.engine_opts)
-    buckets = eng.timers()
-    launches = eng.launch_count()
-    eng.set_profiling(False)
-    # back-to-back stencil launches (no other kernels in between), same buffers
-    dirac_ms = eng.bench_dirac(REF_HID, 0, nb, 50)
+        try:
+            pmc_all = json.load(open(os.path.join(ROOT, "profiles", "kernel_pmc.json")))
+        except Exception:
+            pmc_all = {}
+        if synthetic:
+            pmc_all = {}
+        elif args.workload != "hutchinson":
+            pmc_all = {k: v for k, v in pmc_all.items() if k.startswith(("k_stencil", "k_schur"))}
+        kroofs = kernel_rooflines(eng, levels, V, nbp, pmc_all,
+                                  skip=("k_bsr_mfma(level-1 operator)", "k_bsr_mfma(level-2 operator)")
+                                  if synthetic else (), three_products="mfma_3m=0" not in args.engine_opts)
+        buckets = eng.timers()
+        launches = eng.launch_count()
+        eng.set_profiling(False)
+        # back-to-back stencil launches (no other kernels in between), same buffers
+        dirac_ms = eng.bench_dirac(REF_HID, 0, nb, 50)
+        if rank != 0:
+            return {}
 
-    if rank == 0:
-        mean, std = swdist.mean_and_population_std(total)
         rooflines = kroofs
         dominant = rooflines[0] if rooflines else None
         stencil = max((r for r in rooflines if r["kernel"].startswith(("k_stencil", "k_schur"))),
                       key=lambda r: r["step_ms"], default=None)
         bytes0 = V * (64.0 * nbp + 32.0)      # SURVEY 8d: Y = A X, one launch
+        rec = {
+            # the same K steps stopped where the reference's solver stops (stop_factor = 1)
+            "value_reference_stopping_point": (world * ne * args.steps * nb / elapsed_refstop)
+            if elapsed_refstop else None,
+            "value_probes_resident": world * ne * nres * nb / elapsed_resident,
+            "value_pcie_inclusive_this_rank": ne * nres * nb / elapsed_pcie,
+            "probe_generation_ms_per_batch": gen_ms,
+            "f32_preconditioner": f32_line,
+            # dominant kernel of the step (by device time)
+            "roofline": dominant,
+            # the north star's named target: the batched Dirac stencil against the HBM roofline
+            "stencil_roofline": dict(stencil or {}, back_to_back_ms=dirac_ms,
+                                     back_to_back_GBs=bytes0 / (dirac_ms * 1e-3) / 1e9,
+                                     back_to_back_frac=bytes0 / (dirac_ms * 1e-3) / 1e9 / HBM_PEAK_GBS),
+            "kernel_rooflines": rooflines,
+            "step_breakdown_ms": dict(buckets, kernel_launches=launches),
+        }
+        if not args.no_large_stencil and not synthetic:
+            rec["stencil_roofline_1024"] = large_stencil_point()
+        if world == 1 and not args.no_cpu_baseline and args.workload == "hutchinson":  # 128^2 only
+            rec["cpu_baseline"] = cpu_baseline(A, tp, mg, args.cpu_probes, args.cpu_workers)
+        if world == 1 and args.workload == "hutchinson" and not args.no_other_configs:
+            rec["other_configs"] = other_configs(args, mg, n, device_index)
+        return rec
+
+    # a plain run ends its measurements here: only --full goes on to the runs of their own
+    extra = full_records() if args.full else {}
+
+    if rank == 0:
+        mean, std = swdist.mean_and_population_std(total)
         parity_txt = ("[STRICT per-probe parity: stop_factor %.2g, every true residual below %.2g x tol] "
                       % (args.stop_factor, args.stop_factor) if args.stop_factor < 1.0 else
                       "[stopped at the reference's own point: residual below tol] ")
@@ -656,17 +698,11 @@ def run(args):
             if args.stop_factor < 1.0 else
             "reference stopping point: residual below tol (1e-10 relative to max(|e|, 0.1 median|e|))",
             "stop_factor": args.stop_factor,
-            # the same K steps stopped where the reference's solver stops (stop_factor = 1)
-            "value_reference_stopping_point": (world * ne * args.steps * nb / elapsed_refstop)
-            if elapsed_refstop else None,
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": 1e3 * elapsed / args.steps,
-            "value_probes_resident": world * ne * nres * nb / elapsed_resident,
-            "value_pcie_inclusive_this_rank": ne * nres * nb / elapsed_pcie,
-            "probe_generation_ms_per_batch": gen_ms,
-            "f32_preconditioner": f32_line,
+            "full": args.full,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -713,21 +749,8 @@ def run(args):
                 "std_dev": std,
                 "setup_s": t_setup,
             },
-            # dominant kernel of the step (by device time)
-            "roofline": dominant,
-            # the north star's named target: the batched Dirac stencil against the HBM roofline
-            "stencil_roofline": dict(stencil or {}, back_to_back_ms=dirac_ms,
-                                     back_to_back_GBs=bytes0 / (dirac_ms * 1e-3) / 1e9,
-                                     back_to_back_frac=bytes0 / (dirac_ms * 1e-3) / 1e9 / HBM_PEAK_GBS),
-            "kernel_rooflines": rooflines,
-            "step_breakdown_ms": dict(buckets, kernel_launches=launches),
         }
-        if not args.no_large_stencil and not synthetic:
-            out["stencil_roofline_1024"] = large_stencil_point()
-        if world == 1 and not args.no_cpu_baseline and args.workload == "hutchinson":  # 128^2 only
-            out["cpu_baseline"] = cpu_baseline(A, tp, mg, args.cpu_probes, args.cpu_workers)
-        if world == 1 and args.workload == "hutchinson" and not args.no_other_configs:
-            out["other_configs"] = other_configs(args, mg, n, device_index)
+        out.update(extra)
         line_out = json.dumps(out)
     if td.is_initialized():
         comm.barrier()

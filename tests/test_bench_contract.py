@@ -68,3 +68,21 @@ def test_dump_outputs_writes_float64_arrays_within_the_budget(tmp_path):
     with pytest.raises(SystemExit):
         bench.dump_outputs(str(tmp_path / "big"), {"x": big})
     assert not os.path.exists(tmp_path / "big")
+
+
+def test_full_is_an_option_and_off_by_default(monkeypatch):
+    """--full gates everything beyond the headline (bench.run: full_records); a plain command line leaves
+    it off, and the switches that trim a --full run stay accepted without it."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--no-cpu-baseline", "--no-f32-line", "--no-other-configs",
+                                      "--no-large-stencil"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--steps", "3"])
+    args = bench.parse()
+    assert args.full is True and args.steps == 3
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"],
+                         capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "--full" in out.stdout

@@ -4,7 +4,7 @@
 OUT=gpurun_out/r02_schur
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-ARGS="--steps 1 --warmup 0 --streams 1 --no-large-stencil --no-cpu-baseline --no-f32-line"
+ARGS="--full --steps 1 --warmup 0 --streams 1 --no-large-stencil --no-cpu-baseline --no-f32-line"
 i=0
 for grp in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVES" \
            "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU" \

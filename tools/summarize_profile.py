@@ -20,7 +20,7 @@ def main(out, extra=""):
     if stats:
         rows = list(csv.DictReader(open(stats[0])))
         tot = sum(float(r["TotalDurationNs"]) for r in rows)
-        lines.append("rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 4 --warmup 1 "
+        lines.append("rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 4 --warmup 1 "
                      "--no-large-stencil --no-cpu-baseline --no-f32-line --no-other-configs" + extra)
         lines.append("%-72s %7s %12s %10s %6s" % ("kernel", "calls", "total_ms", "avg_us", "%"))
         for r in rows[:24]:
