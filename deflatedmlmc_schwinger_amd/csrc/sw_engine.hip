@@ -304,6 +304,15 @@ struct sw_engine {
   int pb_ws_nbp = 0;
   cplx* pb_est = nullptr;
   int* pb_iters = nullptr;
+  // shifted probe dots (sw_set_shifts, SW_MODE_HUTCHINSON_SHIFTS): the registered flat shifts, their ring
+  // displacements d_j = s_j / 2L on the device (padded to a multiple of 16 with d_0), the ring -> internal row
+  // table of the lattice level, the probes' int8 codes in the engine layout and the estimates [shift][probe]
+  std::vector<int64_t> shifts;
+  int* shift_disp = nullptr;
+  int* ringrow = nullptr;
+  int8_t* pb_codes = nullptr;
+  cplx* pb_sest = nullptr;
+  int shift_nb = 0;   // probes of the last shifted batch (0: sw_hutch_fetch_shifts has nothing to return)
   std::vector<int32_t> last_iters_f, last_iters_c;
   // profiling
   bool profiling = false;
@@ -2511,6 +2520,8 @@ int sw_hier_begin(sw_engine* h, int hid, int nlevels) {
     h->pb_level = -1;
     h->pb_nb = h->pb_nbp = 0;
     h->pb_ws_nbp = 0;
+    h->shifts.clear();
+    h->shift_nb = 0;
   }
   return 0;
 }
@@ -4274,6 +4285,10 @@ static int ensure_probe_ws(sw_engine* h, int nbp) {
   SWCHK(dev_realloc(h, &h->pb_xd, cnt));
   SWCHK(dev_realloc(h, &h->pb_est, (size_t)4 * nbp));
   SWCHK(dev_realloc(h, &h->pb_iters, (size_t)2 * nbp));
+  // shifted probe dots: the probes' int8 codes and the estimates [shift][probe]
+  SWCHK(dev_realloc(h, &h->pb_codes, cnt));
+  SWCHK(dev_realloc(h, &h->pb_sest, (size_t)SW_MAX_SHIFTS * nbp));
+  h->shift_nb = 0;
   h->pb_ws_nbp = nbp;
   return 0;
 }
@@ -4534,10 +4549,115 @@ int sw_apply_deflation(sw_engine* h, int which, int level, int nb, const double*
   return unpack_host(h, lv, nb, b, Y, nbp);
 }
 
+// ---- shifted probe dots: Tr(A^-1 D_s) at many flat shifts s = 2 L d from one solve per probe ----------
+int sw_set_shifts(sw_engine* h, int nshifts, const int64_t* shifts) {
+  SWCHK(check_hier(h, 0, 0, false));
+  if (nshifts < 0 || nshifts > SW_MAX_SHIFTS)
+    return sw_fail(h, "%d shifts: at most %d per registration", nshifts, SW_MAX_SHIFTS);
+  h->shift_nb = 0;
+  if (nshifts == 0) {
+    h->shifts.clear();
+    return 0;
+  }
+  if (!shifts) return sw_fail(h, "null shift list");
+  Level& lv = h->hier[0].lv[0];
+  if (!lv.stencil || lv.h_rowmap.empty())
+    return sw_fail(h, "shifted traces need a lattice level 0 (sw_set_lattice)");
+  const int L = lv.L, n = lv.n;
+  if (L > SW_SHIFT_MAX_L) return sw_fail(h, "shifted traces: L=%d above %d", L, SW_SHIFT_MAX_L);
+  std::vector<int> disp;
+  for (int j = 0; j < nshifts; ++j) {
+    const int64_t sft = shifts[j];
+    if (sft < 0 || sft >= n) return sw_fail(h, "shift %lld outside [0,%d)", (long long)sft, n);
+    if (sft % (2 * L)) return sw_fail(h, "shift %lld is not a multiple of 2L = %d", (long long)sft, 2 * L);
+    for (int i = 0; i < j; ++i)
+      if (shifts[i] == sft) return sw_fail(h, "shift %lld listed twice", (long long)sft);
+    disp.push_back((int)(sft / (2 * L)));
+  }
+  HIPCHK(hipSetDevice(h->device));
+  SWCHK(stream_sync(h));
+  disp.resize((size_t)((nshifts + 15) / 16) * 16, disp[0]);
+  SWCHK(upload(h, &h->shift_disp, disp.data(), disp.size()));
+  // reference index i = q * 2L + r: ring r in [0, 2L), position q in [0, L)
+  std::vector<int> rr((size_t)n);
+  for (int r = 0; r < 2 * L; ++r)
+    for (int q = 0; q < L; ++q) rr[(size_t)r * L + q] = lv.h_rowmap[(size_t)q * 2 * L + r];
+  SWCHK(upload(h, &h->ringrow, rr.data(), rr.size()));
+  h->shifts.assign(shifts, shifts + nshifts);
+  return 0;
+}
+
+// pb_sest[j][col] = sum_i conj(x_col[(i + s_j) mod n]) z_col[i] for the registered shifts: the probes' codes
+// from their int8 form (reference order), then k_shift_dots over the rings and the sum over its ring blocks
+static int shift_dots(sw_engine* h, Level& lv, const int8_t* probes, int nb, const cplx* Z, int nbp) {
+  const int S = (int)h->shifts.size();
+  const int L = lv.L, n = lv.n, nrings = 2 * L;
+  h->shift_nb = 0;   // pb_sest is rewritten: only a completed shifted batch sets it again
+  SWCHK(ensure_probe_ws(h, nbp));
+  SWCHK(launch(h, T_OTHER, swk::k_probe_codes, dim3((n + 63) / 64, nbp / 64), dim3(SW_BLOCK), probes, nb, n,
+               (const int*)lv.rowmap, h->pb_codes, nbp));
+  // shifts per pass over z: the smallest group that holds them all, 16 beyond that (S = 5..8 would otherwise
+  // pay for 16 accumulators, most of them on padded copies of the first shift)
+  return pick_ge<1, 4, 8, 16>(S, [&](auto SGc) {
+    constexpr int SG = decltype(SGc)::value;
+    const int Sp = (S + SG - 1) / SG * SG;           // <= the padded length of shift_disp
+    const int other = (nbp / 64) * (Sp / SG);
+    // ~2048 workgroups
+    int rpb = std::max(1, std::min(nrings, (nrings * other + 2047) / 2048));
+    const int P = (nrings + rpb - 1) / rpb;
+    SWCHK(ensure_partial(h, (size_t)P * Sp * nbp * sizeof(cplx)));
+    const dim3 grid(P, nbp / 64, Sp / SG);
+    SWCHK(pick_ge<SW_SHIFT_SMALL_L, SW_SHIFT_MID_L, SW_SHIFT_MAX_L>(L, [&](auto LC) {
+      return launch(h, T_DOTS, swk::k_shift_dots<SG, decltype(LC)::value>, grid, dim3(SW_BLOCK),
+                    (const int8_t*)h->pb_codes, Z, (const int*)h->ringrow, (const int*)h->shift_disp, L, nrings,
+                    rpb, nbp, Sp, h->partial);
+    }));
+    // the first S of the Sp sums
+    return launch(h, T_DOTS, swk::k_reduce_partials, dim3(S, nbp / 64), dim3(SW_BLOCK), h->partial, P, Sp, nbp,
+                  h->pb_sest, (const cplx*)nullptr, (cplx*)nullptr);
+  });
+}
+
+// The kernel alone on host inputs (reference ordering): out[j][k] = vdot(roll(x_k, -s_j), Z_k).
+int sw_apply_shift_dots(sw_engine* h, int nb, const int8_t* probes, const double* Z, double* out) {
+  SWCHK(check_hier(h, 0, 0, false));
+  if (nb <= 0 || !probes || !Z || !out) return sw_fail(h, "bad arguments");
+  if (h->shifts.empty()) return sw_fail(h, "no shifts registered (sw_set_shifts)");
+  HIPCHK(hipSetDevice(h->device));
+  Level& lv = h->hier[0].lv[0];
+  const int nbp = pad64(nb), S = (int)h->shifts.size();
+  cplx *a, *b;
+  SWCHK(io_vectors(h, lv, nbp, &a, &b));
+  SWCHK(pack_host(h, lv, nb, Z, a, nbp));
+  DevBuf<int8_t> pr(h);
+  SWCHK(upload(h, &pr.p, probes, (size_t)nb * lv.n));
+  SWCHK(shift_dots(h, lv, pr, nb, a, nbp));
+  SWCHK(stream_sync(h));
+  HIPCHK(hipMemcpy2D(out, sizeof(cplx) * nb, h->pb_sest, sizeof(cplx) * nbp, sizeof(cplx) * nb, S,
+                     hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int sw_hutch_fetch_shifts(sw_engine* h, double* ests) {
+  if (!h) return 1;
+  if (!ests) return sw_fail(h, "null output");
+  if (h->shift_nb <= 0 || !h->pb_sest) return sw_fail(h, "no shifted batch to fetch");
+  HIPCHK(hipSetDevice(h->device));
+  SWCHK(stream_sync(h));
+  const int nb = h->shift_nb, nbp = h->pb_ws_nbp;
+  HIPCHK(hipMemcpy2D(ests, sizeof(cplx) * nb, h->pb_sest, sizeof(cplx) * nbp, sizeof(cplx) * nb,
+                     h->shifts.size(), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
   SWCHK(check_hier(h, 0, level, true));
   if (h->pb_level != level || h->pb_nb <= 0) return sw_fail(h, "no probes uploaded for level %d", level);
   if (maxiter < 1) return sw_fail(h, "maxiter must be >= 1");
+  if (mode == SW_MODE_HUTCHINSON_SHIFTS) {
+    if (level != 0) return sw_fail(h, "shifted Hutchinson mode runs at level 0");
+    if (h->shifts.empty()) return sw_fail(h, "no shifts registered (sw_set_shifts)");
+  }
   HIPCHK(hipSetDevice(h->device));
   Hier& H0 = h->hier[0];
   const int nb = h->pb_nb, nbp = h->pb_nbp;
@@ -4571,6 +4691,24 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
     SWCHK(solve_dev(h, fine_hid, 0, h->pb_rhs, h->pb_z, tol, maxiter, nbp, &total));
     SWCHK(dot_into(h, h->pb_x0, h->pb_z, n, nbp, h->pb_est));   // e = x^H z   utils.py:249
     SWCHK(stream_sync(h));
+    SWCHK(record_iters(h, &h->hier[fine_hid].lv[0].sws, total, h->last_iters_f, nb));
+    h->last_iters_c.assign(nb, 0);
+    return 0;
+  }
+  if (mode == SW_MODE_HUTCHINSON_SHIFTS) {
+    // z = A^-1 (x - U U^H x) once, then e_j = (D_{s_j}^T x)^H z for every registered shift; U as registered
+    // (the caller's W = gamma_3 V sgn(lambda) without Pperm), no perm_src gather
+    const cplx* rhs = h->pb_x0;
+    if (h->kd > 0) {
+      SWCHK(deflate(h, h->U, h->kd, nullptr, h->pb_x0, h->pb_rhs, n, nbp));
+      rhs = h->pb_rhs;
+    }
+    int total = 0;
+    SWCHK(solve_dev(h, fine_hid, 0, rhs, h->pb_z, tol, maxiter, nbp, &total));
+    SWCHK(shift_dots(h, lv, h->pb_probes, nb, h->pb_z, nbp));
+    HIPCHK(hipMemcpyAsync(h->pb_est, h->pb_sest, sizeof(cplx) * nbp, hipMemcpyDeviceToDevice, h->stream));
+    SWCHK(stream_sync(h));
+    h->shift_nb = nb;
     SWCHK(record_iters(h, &h->hier[fine_hid].lv[0].sws, total, h->last_iters_f, nb));
     h->last_iters_c.assign(nb, 0);
     return 0;

@@ -18,6 +18,10 @@ typedef double2 cplx;
 #define SW_WAVE 64
 #define SW_BLOCK 256
 #define SW_WAVES_PER_BLOCK 4
+// k_shift_dots: ring lengths (lattice extents L) its three LDS sizes hold, 64 code bytes per ring position
+#define SW_SHIFT_SMALL_L 256
+#define SW_SHIFT_MID_L 768
+#define SW_SHIFT_MAX_L 1024
 
 __device__ __forceinline__ cplx cmake(double a, double b) { cplx r; r.x = a; r.y = b; return r; }
 __device__ __forceinline__ cplx cadd(cplx a, cplx b) { return cmake(a.x + b.x, a.y + b.y); }
@@ -3273,6 +3277,107 @@ __global__ __launch_bounds__(SW_BLOCK) void k_row_sign(const cplx* __restrict__ 
   const double sg = (double)sign[row];
   const cplx v = src[o];
   dst[o] = cmake(sg * v.x, sg * v.y);
+}
+
+// ------------------------------------------------------------------------------------------
+// Shifted probe dots (SW_MODE_HUTCHINSON_SHIFTS): e[j][k] = sum_i conj(x_k[(i + s_j) mod n]) z_k[i] for
+// flat shifts s_j = 2 L d_j of the lattice level.  Such a shift moves the reference index i = q * 2L + r
+// within its residue class r: the rows fall into 2L independent rings of length L, and per ring and probe the
+// work is a circular cross-correlation sum_q conj(x[r][(q + d) mod L]) z[r][q].  ringrow[r * L + q] is the
+// internal row of ring r, position q (built from the level's row map: the kernel does not know the layout).
+// ------------------------------------------------------------------------------------------
+// The probes' int8 codes (+-1, +-2 = +-i) in the engine layout [internal row][probe]: what k_pack_i8 widens
+// to complex numbers, kept as the bytes the ring staging below reads.
+__global__ __launch_bounds__(SW_BLOCK) void k_probe_codes(const int8_t* __restrict__ src, int nb, int n,
+                                                          const int* __restrict__ rowmap,
+                                                          int8_t* __restrict__ dst, int nbp) {
+  __shared__ int8_t tile[64][65];
+  const int i0 = blockIdx.x * 64;
+  const int j0 = blockIdx.y * 64;
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  for (int jj = ty; jj < 64; jj += 4) {
+    const int j = j0 + jj, i = i0 + tx;
+    tile[jj][tx] = (j < nb && i < n) ? src[(size_t)j * n + i] : (int8_t)0;
+  }
+  __syncthreads();
+  for (int ii = ty; ii < 64; ii += 4) {
+    const int i = i0 + ii;
+    if (i < n) {
+      const size_t row = rowmap ? (size_t)rowmap[i] : (size_t)i;
+      dst[row * nbp + j0 + tx] = tile[tx][ii];
+    }
+  }
+}
+
+// grid = (ring blocks, nbp / 64, shift groups of SG); lane = probe.  A workgroup walks `rings_per_block` rings:
+// it stages the ring's codes in LDS ([q][probe] bytes: L * 64 <= LCAP * 64), then its four waves take the
+// positions q = wave, wave + 4, ...: one 16-byte read of z per lane serves all SG shifts of the group, whose
+// accumulators stay in registers.  The waves combine through LDS in a fixed order and the workgroup writes
+// partial[(ring block * S + shift) * nbp + col]; k_reduce_partials sums the ring blocks (deterministic).
+// conj(code) * z: code 1 -> z, -1 -> -z, 2 (= i) -> -i z = (z.y, -z.x), -2 -> i z.  A padded probe column (code 0) only
+// ever touches its own lane's sums, which nobody reads.
+template <int SG, int LCAP>
+__global__ __launch_bounds__(SW_BLOCK) void k_shift_dots(const int8_t* __restrict__ codes,
+                                                         const cplx* __restrict__ Z,
+                                                         const int* __restrict__ ringrow,
+                                                         const int* __restrict__ disp, int L, int nrings,
+                                                         int rings_per_block, int nbp, int S,
+                                                         cplx* __restrict__ partial) {
+  constexpr int CODE_BYTES = LCAP * 64;
+  constexpr int RED_BYTES = 3 * SG * 64 * (int)sizeof(cplx);
+  constexpr int LDS_BYTES = CODE_BYTES > RED_BYTES ? CODE_BYTES : RED_BYTES;
+  __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_BYTES];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const size_t col = (size_t)blockIdx.y * 64 + lane;
+  int d[SG];
+#pragma unroll
+  for (int j = 0; j < SG; ++j) d[j] = disp[blockIdx.z * SG + j];
+  double ar[SG], ai[SG];
+#pragma unroll
+  for (int j = 0; j < SG; ++j) ar[j] = ai[j] = 0.0;
+  const int r0 = blockIdx.x * rings_per_block;
+  const int r1 = min(r0 + rings_per_block, nrings);
+  for (int r = r0; r < r1; ++r) {
+    const int* __restrict__ rr = ringrow + (size_t)r * L;
+    __syncthreads();   // the previous ring's codes are no longer read
+    for (int q = threadIdx.x >> 4; q < L; q += SW_BLOCK / 16) {
+      const uint32_t* srcw = (const uint32_t*)(codes + (size_t)rr[q] * nbp + (size_t)blockIdx.y * 64);
+      ((uint32_t*)smem)[q * 16 + (threadIdx.x & 15)] = srcw[threadIdx.x & 15];
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int q = wave; q < L; q += SW_WAVES_PER_BLOCK) {
+      const cplx z = Z[(size_t)rr[q] * nbp + col];
+#pragma unroll
+      for (int j = 0; j < SG; ++j) {
+        int qq = q + d[j];
+        qq = qq >= L ? qq - L : qq;
+        const int c = (int)(signed char)smem[qq * 64 + lane];
+        const bool rot = (c & 1) == 0;            // +-2: multiply by -+i
+        double ur = rot ? z.y : z.x;
+        double ui = rot ? -z.x : z.y;
+        ar[j] += c < 0 ? -ur : ur;
+        ai[j] += c < 0 ? -ui : ui;
+      }
+    }
+  }
+  __syncthreads();
+  cplx* red = (cplx*)smem;   // [3][SG][64]
+  if (wave > 0) {
+#pragma unroll
+    for (int j = 0; j < SG; ++j) red[((wave - 1) * SG + j) * 64 + lane] = cmake(ar[j], ai[j]);
+  }
+  __syncthreads();
+  if (wave == 0) {
+#pragma unroll
+    for (int j = 0; j < SG; ++j) {
+      cplx s = cmake(ar[j], ai[j]);
+      s = cadd(s, red[(0 * SG + j) * 64 + lane]);
+      s = cadd(s, red[(1 * SG + j) * 64 + lane]);
+      s = cadd(s, red[(2 * SG + j) * 64 + lane]);
+      partial[((size_t)blockIdx.x * S + (size_t)blockIdx.z * SG + j) * nbp + col] = s;
+    }
+  }
 }
 
 }  // namespace swk

@@ -19,6 +19,8 @@ MODE_HUTCHINSON = 0
 MODE_MLMC = 1
 MODE_MLMC_SKIP = 2
 MODE_LEVEL = 3
+MODE_HUTCHINSON_SHIFTS = 4
+MAX_SHIFTS = 128
 PROBES_Z2 = 1
 PROBES_Z4 = 2
 PROBE_KINDS = {"z2": PROBES_Z2, "z4": PROBES_Z4}
@@ -150,6 +152,9 @@ def load_library():
     sig("sw_probes_stream_set", i32, vp, vp)
     sig("sw_probes_generate", i32, vp, i32, i32, i32, i32, C.c_uint64)
     sig("sw_probes_fetch", i32, vp, i32, vp)
+    sig("sw_set_shifts", i32, vp, i32, vp)
+    sig("sw_hutch_fetch_shifts", i32, vp, vp)
+    sig("sw_apply_shift_dots", i32, vp, i32, vp, vp, vp)
     _lib = lib
     return lib
 
@@ -170,6 +175,7 @@ EXPORTED_SYMBOLS = (
     "sw_mt_z4", "sw_mt_from_state", "sw_mt_get_state", "sw_mt_window", "sw_mt_jump",
     "sw_mt_jump_poly", "sw_mt_window_jump",
     "sw_probes_stream_set", "sw_probes_generate", "sw_probes_fetch",
+    "sw_set_shifts", "sw_hutch_fetch_shifts", "sw_apply_shift_dots",
 )
 
 
@@ -235,6 +241,8 @@ class Engine:
     def hier_begin(self, hid, nlevels):
         self._chk(self._lib.sw_hier_begin(self._h, hid, nlevels), "sw_hier_begin")
         self.level_sizes[hid] = [0] * nlevels
+        if hid == 0:
+            self._nshifts = 0          # the engine drops its shift registration with hierarchy 0
 
     def set_lattice(self, hid, L, mass, U1, U2):
         U1, U2 = _c128(U1), _c128(U2)
@@ -404,6 +412,13 @@ class Engine:
     def set_perm(self, level, shift):
         self._chk(self._lib.sw_set_perm(self._h, level, int(shift)), "sw_set_perm")
 
+    def set_shifts(self, shifts):
+        """Register the flat-index shifts of MODE_HUTCHINSON_SHIFTS (multiples of 2L in [0, n), no
+        duplicates, at most MAX_SHIFTS); None or an empty list clears the registration."""
+        s = np.ascontiguousarray([] if shifts is None else shifts, dtype=np.int64).ravel()
+        self._chk(self._lib.sw_set_shifts(self._h, s.size, _ptr(s) if s.size else None), "sw_set_shifts")
+        self._nshifts = int(s.size)
+
     def set_rhsmap(self, level, Cmat):
         (n, m), indptr, indices, data = _csr_parts(Cmat)
         self._chk(self._lib.sw_set_rhsmap(self._h, level, n, _ptr(indptr), _ptr(indices),
@@ -557,6 +572,31 @@ class Engine:
                                            int(maxiter), _ptr(ests), _ptr(iters)),
                   "sw_hutch_batch")
         return ests, iters[:nb].copy(), iters[nb:].copy()
+
+    def hutch_batch_shifts(self, level, probes, tol, maxiter=1000):
+        """One MODE_HUTCHINSON_SHIFTS batch: (ests[nb, S], iters_fine[nb], iters_coarse[nb]) with one
+        column per registered shift."""
+        _, itf, itc = self.hutch_batch(MODE_HUTCHINSON_SHIFTS, level, probes, tol, maxiter)
+        self._nb_uploaded = itf.size
+        return self.hutch_fetch_shifts(), itf, itc
+
+    def hutch_fetch_shifts(self):
+        """Estimates of the last MODE_HUTCHINSON_SHIFTS batch at every registered shift, shape (nb, S)."""
+        out = np.zeros((getattr(self, "_nshifts", 0), self._nb_uploaded), dtype=np.complex128)
+        self._chk(self._lib.sw_hutch_fetch_shifts(self._h, _ptr(out)), "sw_hutch_fetch_shifts")
+        return np.ascontiguousarray(out.T)
+
+    def apply_shift_dots(self, probes, Z):
+        """The shifted-dot kernel alone: out[k, j] = np.vdot(np.roll(x_k, -s_j), Z[k]) for the registered
+        shifts; probes int8 (nb, n) codes, Z complex (nb, n), both in the reference ordering."""
+        p = self._probes(probes)
+        Z2, _ = self._io(Z, self._n(0, 0))
+        if p.shape != Z2.shape:
+            raise EngineError("probes %s and Z %s differ in shape" % (p.shape, Z2.shape))
+        out = np.zeros((getattr(self, "_nshifts", 0), p.shape[0]), dtype=np.complex128)
+        self._chk(self._lib.sw_apply_shift_dots(self._h, p.shape[0], _ptr(p), _ptr(Z2), _ptr(out)),
+                  "sw_apply_shift_dots")
+        return np.ascontiguousarray(out.T)
 
     def probes_upload(self, level, probes):
         p = self._probes(probes)

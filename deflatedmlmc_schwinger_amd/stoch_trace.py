@@ -17,8 +17,9 @@ from scipy.sparse.linalg import LinearOperator
 from . import dist as _dist
 from .engine import ProbeStream
 from .multigrid import MG
-from .utils import (_engines, deflation_pre_computations, draw_probes, flopsV_manual, mlmc_defl_setup_of,
-                    probe_batch, probe_batch_generated)
+from .utils import (_engines, deflation_pre_computations, displacements_of, draw_probes, flopsV_manual,
+                    mlmc_defl_setup_of, probe_batch, probe_batch_generated, probe_batch_shifts,
+                    probe_batch_shifts_generated, register_shifts)
 
 DEFAULT_BATCH = 256
 NR_ROUGH_PROBES = 5
@@ -177,6 +178,72 @@ def run_probe_loop(evaluate, n, level_tol, max_nr_ests, batch, comm=None, min_in
             "solved": int(ests.size)}
 
 
+class DeviceShiftProbes:
+    """Probe source of the displaced-trace loop: as :class:`DeviceProbes`, each probe evaluated at every
+    registered shift (one row of S estimates per probe)."""
+
+    def __init__(self, mg_solver, params, kind="z2"):
+        self.mg_solver = mg_solver
+        self.params = params
+        self.kind = kind
+
+    def begin(self, entry_stream):
+        window = entry_stream.window()
+        for eng in _engines(self.mg_solver):
+            eng.stream_set(window)
+
+    def __call__(self, first_probe, count):
+        return probe_batch_shifts_generated(self.mg_solver, self.params, first_probe, count, self.kind)
+
+
+def run_probe_loop_displaced(evaluate, n, level_tols, control, max_nr_ests, batch, comm=None, min_index=5,
+                             probe_type="z2"):
+    """The probe loop of :func:`run_probe_loop` for estimators that return one value per displacement:
+    `evaluate` (a probe source or a plain callable, as there) yields ests of shape (count, S).  The
+    sequential stopping rule is replayed on column `control` against level_tols[control] alone, so that
+    column's index, avg and dev are those of run_probe_loop on it; every other column is summarised over
+    the same first index + 1 probes.  Returns run_probe_loop's dictionary (avg, dev: the control column;
+    ests: (index + 1, S)) plus avgs[S], devs[S] and converged[S] = whether each displacement met its own
+    tolerance at the stopping index.  One rank only."""
+    comm = comm or _dist.default_comm()
+    if comm.world > 1:
+        raise Exception("displaced traces (x_displacements) run on one rank; got %d" % comm.world)
+    level_tols = np.asarray(level_tols, dtype=float)
+    S = level_tols.size
+    source = evaluate if hasattr(evaluate, "begin") else HostProbes(evaluate, n, probe_type)
+    entry = ProbeStream.from_numpy_state()
+    source.begin(entry)
+    ests = np.zeros((0, S), dtype=np.complex128)
+    it_f = np.zeros(0, dtype=np.int64)
+    it_c = np.zeros(0, dtype=np.int64)
+    rounds = 0
+    hit = None
+    while ests.shape[0] < max_nr_ests and hit is None:
+        count = min(batch, max_nr_ests - ests.shape[0])
+        first_new = ests.shape[0]
+        e, f, c = source(first_new, count)
+        e = np.asarray(e, dtype=np.complex128)
+        if e.shape != (count, S):
+            raise Exception("displaced probe batch of shape %s, expected %s" % (e.shape, (count, S)))
+        ests = np.concatenate([ests, e])
+        it_f = np.concatenate([it_f, np.asarray(f, dtype=np.int64)])
+        it_c = np.concatenate([it_c, np.asarray(c, dtype=np.int64)])
+        rounds += 1
+        hit = first_stop_index(ests[:, control], first_new, level_tols[control], min_index)
+    if hit is None:
+        hit = (ests.shape[0] - 1,) + _stats(ests[:, control])
+    stop_index, avg, dev = hit
+    k = stop_index + 1
+    per = [_stats(ests[:k, j]) for j in range(S)]
+    avgs = np.array([a for a, _ in per])
+    devs = np.array([d for _, d in per])
+    entry.jump(k * n)
+    np.random.set_state(entry.numpy_state())
+    return {"index": stop_index, "avg": avg, "dev": dev, "ests": ests[:k], "avgs": avgs, "devs": devs,
+            "converged": devs / sqrt(k) < level_tols,
+            "iters_fine": it_f[:k], "iters_coarse": it_c[:k], "rounds": rounds, "solved": int(ests.shape[0])}
+
+
 def _setup_solver(A, params, announce=True, defer_coarse=False):
     mg_solver = MG(A)
     if defer_coarse and "defer_coarse_levels" not in params:
@@ -221,6 +288,9 @@ def _rough_trace(mg_solver, params, n, Vx_rank, tr1):
 
 # compute tr(A^{-1}) via (deflated) Hutchinson                      stoch_trace.py:33-179
 def hutchinson(A, params):
+    displaced = displacements_of(params)
+    if displaced is not None:
+        return _hutchinson_displaced(A, params, displaced)
     mg_solver, nr_levels = _setup_solver(A, params, defer_coarse=True)
     N = A.shape[0]
     batch = int(params.get('batch', DEFAULT_BATCH))
@@ -281,8 +351,85 @@ def hutchinson(A, params):
     return result
 
 
+def _hutchinson_displaced(A, params, displaced):
+    """hutchinson() with the build-only key x_displacements: Tr(A^-1 D_s) at every listed displacement from
+    one deflation projection and one solve per probe ("Displaced traces").  The reference's
+    result keys are filled for the control displacement; the stopping rule runs on its series alone."""
+    disps, shifts, control = displaced
+    if _dist.default_comm().world > 1:
+        raise Exception("displaced traces (x_displacements) run on one rank")
+    mg_solver, nr_levels = _setup_solver(A, params, defer_coarse=True)
+    N = A.shape[0]
+    batch = int(params.get('batch', DEFAULT_BATCH))
+    kind = params.get('probe_type', 'z2')
+
+    print("\nResetting timer to zero ...", end='')
+    mg_solver.timer.reset()
+    print(" done\n")
+    nr_deflat_vctrs = params['nr_deflat_vctrs']
+    print("Computing deflation vectors ...", end='', flush=True)
+    t0 = time.time()
+    Vx, tr1 = deflation_pre_computations(A, nr_deflat_vctrs, params['defl_eigvs_tol_Hutch'],
+                                         "hutchinson", mg_solver.timer, params, mg_solver)
+    tr1 = np.asarray(tr1, dtype=np.complex128)
+    register_shifts(mg_solver, shifts)
+    print(" done. Time : " + str(time.time() - t0) + " seconds")
+    print(mg_solver.timer)
+
+    print("\nComputing rough estimation of the traces ...", end='', flush=True)
+    np.random.seed(123456)                                      # stoch_trace.py:103-115
+    t0 = time.time()
+    e, _, _ = probe_batch_shifts(mg_solver, params, draw_probes(NR_ROUGH_PROBES, N, kind))
+    rough_traces = np.sum(e, axis=0) / NR_ROUGH_PROBES + tr1
+    level_tols = np.abs(params['tol'] * rough_traces)
+    print(" done. Time : " + str(time.time() - t0) + " seconds")
+
+    print("\nResetting timer to zero ...", end='')
+    mg_solver.timer.reset()
+    mg_solver.engine.timers_reset()
+    print(" done")
+    print("\nComputing the traces stochastically ...", end='', flush=True)
+    t0 = time.time()
+    mg_solver.coarsest_lev_iters[0] = 0
+    loop = run_probe_loop_displaced(DeviceShiftProbes(mg_solver, params, kind), N, level_tols, control,
+                                    params['max_nr_ests'], batch * max(1, len(_engines(mg_solver))),
+                                    probe_type=kind)
+    loop_s = time.time() - t0
+    print(" done. Time : " + str(loop_s) + " seconds")
+
+    function_iters = int(np.sum(loop["iters_fine"]))
+    mg_solver.coarsest_lev_iters[0] = function_iters
+    mg_solver.finish_setup()
+    result = dict()
+    result['trace'] = loop["avg"] + tr1[control]
+    result['std_dev'] = loop["dev"]
+    result['nr_ests'] = loop["index"]
+    result['function_iters'] = function_iters
+    levels = mg_solver.ml.levels
+    result['total_complexity'] = flopsV_manual(len(levels), levels, 0, mg_solver) * function_iters
+    result['total_complexity'] += levels[len(levels) - 1].A.nnz * mg_solver.coarsest_lev_iters[0]
+    result['total_complexity'] += result['nr_ests'] * (2 * N * nr_deflat_vctrs) / 3.0
+    result['ests'] = loop["ests"]                   # (nr_ests + 1, S)
+    result['rough_trace'] = rough_traces[control]
+    result['level_tol'] = level_tols[control]
+    result['probe_loop_s'] = loop_s
+    result['probes_solved'] = loop["solved"]
+    result['displacements'] = list(disps)
+    result['traces'] = loop["avgs"] + tr1
+    result['std_devs'] = loop["devs"]
+    result['rough_traces'] = rough_traces
+    result['level_tols'] = level_tols
+    result['converged'] = loop["converged"]
+    mg_solver.sync_timer()
+    print(mg_solver.timer)
+    return result
+
+
 # compute tr(A^{-1}) via multigrid multilevel Monte Carlo          stoch_trace.py:185-471
 def mlmc(A, params):
+    if displacements_of(params) is not None:
+        raise Exception("x_displacements is implemented for hutchinson() only: the MLMC difference levels "
+                        "need their own displaced right-hand sides")
     mlmc_defl_setup_of(params)
     skip_list = params['mlmc_levels_to_skip']
     if len(skip_list) > 1:

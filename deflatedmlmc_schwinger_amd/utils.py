@@ -7,7 +7,8 @@ import numpy as np
 from scipy.sparse.linalg import eigsh
 
 from . import dist as _dist
-from .engine import MODE_HUTCHINSON, MODE_LEVEL, MODE_MLMC, MODE_MLMC_SKIP, EngineError
+from .engine import (MAX_SHIFTS, MODE_HUTCHINSON, MODE_HUTCHINSON_SHIFTS, MODE_LEVEL, MODE_MLMC, MODE_MLMC_SKIP,
+                     EngineError)
 
 
 # ----------------------------------------------------------------------------------------
@@ -62,7 +63,7 @@ _BUILD_KEYS = ('batch', 'device', 'engines', 'cache_dir', 'report_path', 'probe_
                'solver_testvectors', 'deflation_eigenpairs', 'ref_cycle_post', 'ref_cycle_k', 'ref_smoother',
                'solver_restart', 'stochastic_coarsest', 'stop_factor', 'ref_direct_max_n', 'ref_coarsest',
                'ref_coarse_dofs', 'setup_eigs', 'defer_coarse_levels',
-               'verbose', 'probe_rounds_max', 'mlmc_defl_setup', 'defl_setup')
+               'verbose', 'probe_rounds_max', 'mlmc_defl_setup', 'defl_setup', 'x_displacements')
 # where the eigenpairs of the MLMC difference operators come from: host ARPACK (the reference's path) or
 # the block eigensolver on the GPU (setup_gpu.device_diff_eigenpairs)
 MLMC_DEFL_SETUPS = ("host", "device")
@@ -88,6 +89,49 @@ def defl_setup_of(params):
     if how not in DEFL_SETUPS:
         raise Exception("defl_setup = %r: expected one of %s" % (how, ", ".join(DEFL_SETUPS)))
     return how
+
+
+def displacements_of(params):
+    """The build-only key x_displacements: None when absent, else (displacements, flat shifts, index of the
+    control displacement) after validation.  Displacement d is the flat-index shift latt_dims[0] * 2 * d; the
+    control displacement -- the one the reference's own run would estimate -- is x_displacement with
+    use_permuted and 0 without, and has to be in the list."""
+    if not hasattr(params, "get") or params.get('x_displacements') is None:
+        return None
+    L = int(params['latt_dims'][0])
+    disps = []
+    for d in params['x_displacements']:
+        if int(d) != d:
+            raise Exception("x_displacements: %r is not an integer" % (d,))
+        d = int(d)
+        if not 0 <= d < L:
+            raise Exception("x_displacements: %d outside [0, %d)" % (d, L))
+        if d in disps:
+            raise Exception("x_displacements: %d listed twice" % d)
+        disps.append(d)
+    if not disps:
+        raise Exception("x_displacements is empty")
+    if len(disps) > MAX_SHIFTS:
+        raise Exception("x_displacements: %d entries, at most %d" % (len(disps), MAX_SHIFTS))
+    control = int(params['x_displacement']) if params['use_permuted'] else 0
+    if control not in disps:
+        raise Exception("x_displacements has to contain the control displacement %d "
+                        "(x_displacement with use_permuted, 0 without)" % control)
+    return disps, [L * 2 * d for d in disps], disps.index(control)
+
+
+def displaced_tr1(Vx, Sy, g3, n, shifts):
+    """The deflated part of the displaced traces: tr1_s = sum_i (w_i^H D_s v_i) / |lambda_i| for every flat
+    shift s, with (lambda_i, v_i) eigenpairs of gamma_3 A (Sy, columns of Vx), w_i = gamma_3 v_i sgn(lambda_i)
+    and (D_s v)[j] = v[(j - s) mod n].  Then Tr(A^-1 D_s) = Tr(D_s A^-1 (I - W W^H)) + tr1_s.  g3: the
+    diagonal of gamma_3, or a (sparse) matrix."""
+    Vx = np.asarray(Vx, dtype=np.complex128)
+    Sy = np.asarray(Sy, dtype=float)
+    if Vx.shape[0] != n:
+        raise Exception("displaced_tr1: vectors of length %d, expected %d" % (Vx.shape[0], n))
+    W = (np.asarray(g3)[:, None] * Vx if np.ndim(g3) == 1 else np.asarray(g3 * Vx)) * np.sign(Sy)[None, :]
+    return np.array([np.sum(np.sum(W.conj() * np.roll(Vx, int(s), axis=0), axis=0) / np.abs(Sy))
+                     for s in shifts])
 
 
 def trace_params_from_params(params, example):
@@ -190,12 +234,14 @@ def deflation_pre_computations(A, nr_deflat_vctrs, tolx, method, timer, params, 
         if method == "hutchinson":
             for eng in _engines(mg_solver):
                 eng.set_deflation(None)
-            return (None, 0.0)
+            disp = displacements_of(params)
+            return (None, 0.0 if disp is None else np.zeros(len(disp[0]), dtype=np.complex128))
         for eng in _engines(mg_solver):
             eng.set_level_deflation(level_nr, None)
         return (None, None, 0.0)
 
     lev0 = mg_solver.ml.levels[0]
+    displaced = displacements_of(params) if method == "hutchinson" else None
     if method == "hutchinson":
         pre = params.get("deflation_eigenpairs") if hasattr(params, "get") else None
         how = defl_setup_of(params)
@@ -258,6 +304,15 @@ def deflation_pre_computations(A, nr_deflat_vctrs, tolx, method, timer, params, 
     Ux = Vx * sgn[None, :]
     if method == "hutchinson":
         Ux = lev0.g3 * Ux
+        if displaced is not None:
+            # W = gamma_3 V sgn(lambda) as it is: the displacement sits on the probe side of the dots
+            # (SW_MODE_HUTCHINSON_SHIFTS), tr1 is one number per displacement
+            if os.getenv('OMP_NUM_THREADS') is None:                    # utils.py:161-164
+                raise Exception("Run : << export OMP_NUM_THREADS=N >>")
+            mg_solver.solve_tol = params['function_params']['tol']
+            for eng in _engines(mg_solver):
+                eng.set_deflation(np.asarray(Ux))
+            return (Ux, displaced_tr1(Vx, Sy, lev0.g3, Vx.shape[0], displaced[1]))
         if params['use_permuted']:
             Ux = lev0.Pperm * Ux
     else:
@@ -350,6 +405,54 @@ def probe_batch(mg_solver, params, method, probes, level=0):
         futs = [pool.submit(eng.hutch_batch, mode, level, probes[idx], tol, maxiter)
                 for eng, idx in zip(engs, parts) if len(idx)]
         res = [f.result() for f in futs]
+    return tuple(np.concatenate([r[k] for r in res]) for k in range(3))
+
+
+def _shift_batch_args(mg_solver, params):
+    engs = _engines(mg_solver)
+    if not engs:
+        raise EngineError("no GPU engine attached (run MG.setup first)")
+    n = mg_solver.ml.levels[0].A.shape[0]
+    return engs, params['function_params']['tol'], n, (n if n < 1000 else 1000)
+
+
+def register_shifts(mg_solver, shifts):
+    """Hand the flat shifts of the displaced traces to every engine handle (None clears)."""
+    for eng in _engines(mg_solver):
+        eng.set_shifts(shifts)
+
+
+def probe_batch_shifts(mg_solver, params, probes):
+    """One batch of probes at every registered shift: (ests[nb, S], iters_fine, iters_coarse) with
+    e[k, j] = (D_{s_j}^T x_k)^H A^-1 (x_k - W W^H x_k) -- one projection and one solve per probe."""
+    engs, tol, _, maxiter = _shift_batch_args(mg_solver, params)
+    return engs[0].hutch_batch_shifts(0, np.asarray(probes), tol, maxiter)
+
+
+def probe_batch_shifts_generated(mg_solver, params, first_probe, count, kind="z2"):
+    """probe_batch_shifts for the probes [first_probe, first_probe + count) of the stream the engines hold
+    (Engine.stream_set), generated on the device; several engine handles share the batch as in
+    probe_batch_generated."""
+    engs, tol, n, maxiter = _shift_batch_args(mg_solver, params)
+    ne = len(engs) if count >= 2 * 64 else 1
+    bounds = [(k * count) // ne for k in range(ne + 1)]
+    active = [k for k in range(ne) if bounds[k + 1] > bounds[k]]
+    for k in active:
+        engs[k].probes_generate(0, 0, bounds[k + 1] - bounds[k], (first_probe + bounds[k]) * n, kind)
+
+    def run(k):
+        eng = engs[k]
+        eng.probes_select(0)
+        eng.hutch_run(MODE_HUTCHINSON_SHIFTS, 0, tol, maxiter)
+        _, itf, itc = eng.hutch_fetch()
+        return eng.hutch_fetch_shifts(), itf, itc
+
+    if len(active) == 1:
+        res = [run(active[0])]
+    else:
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=len(active)) as pool:
+            res = list(pool.map(run, active))
     return tuple(np.concatenate([r[k] for r in res]) for k in range(3))
 
 

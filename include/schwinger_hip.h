@@ -32,6 +32,7 @@ extern "C" {
 #define SW_MAX_LEVELS 8
 #define SW_MAX_KRYLOV 32
 #define SW_MAX_DEFL 256
+#define SW_MAX_SHIFTS 128
 
 typedef struct sw_engine sw_engine;
 
@@ -213,6 +214,10 @@ int sw_set_perm(sw_engine* h, int level, int64_t shift);
  * utils.py:288-290); n x n at `level` of hid 0. */
 int sw_set_rhsmap(sw_engine* h, int level, int n, const int64_t* indptr, const int32_t* indices,
                   const double* data);
+/* Flat-index shifts s_j of SW_MODE_HUTCHINSON_SHIFTS (build-only: displaced traces Tr(A^-1 D_s), (D_s v)[i] =
+ * v[(i - s) mod n], at many displacements from one solve per probe).  Lattice level 0 only (sw_set_lattice);
+ * every shift a multiple of 2L in [0, n), no duplicates, at most SW_MAX_SHIFTS; nshifts = 0 clears. */
+int sw_set_shifts(sw_engine* h, int nshifts, const int64_t* shifts);
 /* Outer flexible-GMRES restart length (<= SW_MAX_KRYLOV) and the hierarchy used to
  * precondition level-0 solves (0 or 1). */
 int sw_set_solver(sw_engine* h, int restart, int solver_hid);
@@ -283,6 +288,10 @@ int sw_coarsest(sw_engine* h, int hid, int nb, const double* X, double* Y);
  * Hutchinson form Pperm_0^T (I - U U^H) X at level 0 (sw_set_deflation, sw_set_perm); which = 1: the MLMC
  * form (I - V_l V_l^H) X at `level` (sw_set_level_deflation).  X,Y: complex128[nb*n_level]. */
 int sw_apply_deflation(sw_engine* h, int which, int level, int nb, const double* X, double* Y);
+/* The shifted-dot kernel of SW_MODE_HUTCHINSON_SHIFTS alone: out[j*nb + k] = sum_i conj(x_k[(i + s_j) mod n])
+ * Z_k[i] for the registered shifts; probes int8[nb*n] (codes +-1, +-2 = +-i), Z complex128[nb*n], out
+ * complex128[nshifts*nb]. */
+int sw_apply_shift_dots(sw_engine* h, int nb, const int8_t* probes, const double* Z, double* out);
 /* X = one multigrid cycle applied to B starting at level0 (MG.one_mg_step, multigrid.py:369-447). */
 int sw_vcycle(sw_engine* h, int hid, int level0, int nb, const double* B, double* X);
 /* Solve A_level0 X = B to ||r|| < tol*||b|| per right-hand side (MG.solve -> pyamg fgmres,
@@ -299,6 +308,10 @@ int sw_solve(sw_engine* h, int hid, int level0, int nb, const double* B, double*
                                   stochastically (build-only; the reference computes the coarsest
                                   term directly and raises for the stochastic form,
                                   stoch_trace.py:428-437) */
+#define SW_MODE_HUTCHINSON_SHIFTS 4 /* e_jk = (D_{s_j}^T x_k)^H A^-1 (x_k - U U^H x_k) for the shifts of
+                                  sw_set_shifts, level 0: one projection and one solve per probe serve all
+                                  shifts (build-only; U as registered, sw_set_perm ignored; its expectation
+                                  is Tr(D_s A^-1 (I - U U^H)), per-probe values are not those of HUTCHINSON) */
 /* One batch of probes x_k in {-1,+1}^n (int8, nb*n, reference ordering) at `level`
  * (build-only extension: entries +-2 encode +-i, i.e. Z4 probes {1,i,-1,-i}):
  *   HUTCHINSON: e_k = x^H A^-1 Pperm^T (x - U U^H x)
@@ -330,6 +343,9 @@ int sw_probes_fetch(sw_engine* h, int slot, int8_t* out);
 int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter);
 int sw_sync(sw_engine* h);
 int sw_hutch_fetch(sw_engine* h, double* ests, int32_t* iters);
+/* After a SW_MODE_HUTCHINSON_SHIFTS batch: ests complex128[nshifts][nb], row j = the estimates at shift j of
+ * the registration (sw_hutch_fetch returns row 0 and the iteration counts). */
+int sw_hutch_fetch_shifts(sw_engine* h, double* ests);
 
 /* ---- multi-GPU: the one collective of the path ------------------------------------ */
 /* One process per GPU, one engine per process; the probe loop shards by probe and needs a single
