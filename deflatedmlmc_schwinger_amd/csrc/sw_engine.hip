@@ -313,6 +313,16 @@ struct sw_engine {
   int8_t* pb_codes = nullptr;
   cplx* pb_sest = nullptr;
   int shift_nb = 0;   // probes of the last shifted batch (0: sw_hutch_fetch_shifts has nothing to return)
+  // timeslice loops (sw_set_loop_momenta, SW_MODE_HUTCHINSON_LOOPS): the registered momenta (on the device padded
+  // to SW_MAX_MOMENTA with the first), the phase table omega^j = e^{-2 pi i j / L}, j in [0, L), the
+  // (timeslice, x, spin) -> internal row table of the lattice level and the loops [momentum][a][b][t][probe]
+  std::vector<int32_t> momenta;
+  int* loop_mom = nullptr;
+  cplx* loop_phase = nullptr;
+  int* slicerow = nullptr;
+  cplx* pb_lest = nullptr;
+  size_t pb_lest_cap = 0;
+  int loop_nb = 0, loop_nbp = 0;   // probes and row stride of the last loop batch (0: nothing to fetch)
   std::vector<int32_t> last_iters_f, last_iters_c;
   // profiling
   bool profiling = false;
@@ -2522,6 +2532,8 @@ int sw_hier_begin(sw_engine* h, int hid, int nlevels) {
     h->pb_ws_nbp = 0;
     h->shifts.clear();
     h->shift_nb = 0;
+    h->momenta.clear();
+    h->loop_nb = 0;
   }
   return 0;
 }
@@ -4650,6 +4662,124 @@ int sw_hutch_fetch_shifts(sw_engine* h, double* ests) {
   return 0;
 }
 
+// ---- timeslice loops: spin- and momentum-resolved traces per timeslice from one solve per probe --------
+int sw_set_loop_momenta(sw_engine* h, int nmom, const int32_t* p) {
+  SWCHK(check_hier(h, 0, 0, false));
+  if (nmom < 0 || nmom > SW_MAX_MOMENTA)
+    return sw_fail(h, "%d momenta: at most %d per registration", nmom, SW_MAX_MOMENTA);
+  h->loop_nb = 0;
+  if (nmom == 0) {
+    h->momenta.clear();
+    return 0;
+  }
+  if (!p) return sw_fail(h, "null momentum list");
+  Level& lv = h->hier[0].lv[0];
+  if (!lv.stencil || lv.h_rowmap.empty())
+    return sw_fail(h, "timeslice loops need a lattice level 0 (sw_set_lattice)");
+  const int L = lv.L, n = lv.n;
+  if (L > SW_SHIFT_MAX_L) return sw_fail(h, "timeslice loops: L=%d above %d", L, SW_SHIFT_MAX_L);
+  for (int j = 0; j < nmom; ++j) {
+    if (p[j] < 0 || p[j] >= L) return sw_fail(h, "momentum %d outside [0,%d)", (int)p[j], L);
+    for (int i = 0; i < j; ++i)
+      if (p[i] == p[j]) return sw_fail(h, "momentum %d listed twice", (int)p[j]);
+  }
+  HIPCHK(hipSetDevice(h->device));
+  SWCHK(stream_sync(h));
+  std::vector<int> mom(p, p + nmom);
+  mom.resize(SW_MAX_MOMENTA, mom[0]);
+  SWCHK(upload(h, &h->loop_mom, mom.data(), mom.size()));
+  std::vector<cplx> ph((size_t)L);
+  for (int j = 0; j < L; ++j) {
+    // exact at the multiples of a quarter turn, so p = 0 and the real/imaginary axes carry no rounding
+    const int q = (4 * j) / L;
+    if ((4 * j) % L == 0) {
+      ph[j] = cplx{q == 0 ? 1.0 : q == 2 ? -1.0 : 0.0, q == 1 ? -1.0 : q == 3 ? 1.0 : 0.0};
+    } else {
+      const double a = -2.0 * M_PI * (double)j / (double)L;
+      ph[j] = cplx{std::cos(a), std::sin(a)};
+    }
+  }
+  SWCHK(upload(h, &h->loop_phase, ph.data(), ph.size()));
+  // reference index idx(a,x,t) = a L^2 + t L + x
+  std::vector<int> sr((size_t)n);
+  for (int t = 0; t < L; ++t)
+    for (int x = 0; x < L; ++x)
+      for (int a = 0; a < 2; ++a)
+        sr[((size_t)t * L + x) * 2 + a] = lv.h_rowmap[(size_t)a * L * L + (size_t)t * L + x];
+  SWCHK(upload(h, &h->slicerow, sr.data(), sr.size()));
+  h->momenta.assign(p, p + nmom);
+  return 0;
+}
+
+// pb_lest[p][a][b][t][col] = sum_x e^{-2 pi i p x / L} conj(x_col[idx(a,x,t)]) z_col[idx(b,x,t)] for the registered
+// momenta: the probes' codes from their int8 form (reference order), then k_slice_dots, one workgroup per
+// (timeslice, 64 probes); total (optional) = the scalar total of the first momentum's block per probe
+static int slice_dots(sw_engine* h, Level& lv, const int8_t* probes, int nb, const cplx* Z, int nbp,
+                      cplx* total) {
+  const int M = (int)h->momenta.size();
+  const int L = lv.L, n = lv.n;
+  h->loop_nb = 0;   // pb_lest is rewritten: only a completed loop batch sets it again
+  SWCHK(ensure_probe_ws(h, nbp));
+  const size_t need = (size_t)M * 4 * L * nbp;
+  if (h->pb_lest_cap < need) {
+    SWCHK(dev_realloc(h, &h->pb_lest, need));
+    h->pb_lest_cap = need;
+  }
+  h->loop_nbp = nbp;
+  SWCHK(launch(h, T_OTHER, swk::k_probe_codes, dim3((n + 63) / 64, nbp / 64), dim3(SW_BLOCK), probes, nb, n,
+               (const int*)lv.rowmap, h->pb_codes, nbp));
+  const dim3 grid(L, nbp / 64);
+  if (M == 1 && h->momenta[0] == 0) {
+    SWCHK(launch(h, T_DOTS, swk::k_slice_dots<1, false>, grid, dim3(SW_BLOCK), (const int8_t*)h->pb_codes, Z,
+                 (const int*)h->slicerow, (const cplx*)h->loop_phase, (const int*)h->loop_mom, L, nbp, M,
+                 h->pb_lest));
+  } else {
+    // momenta per pass: the smallest instantiation that holds them all (none of them spills)
+    SWCHK(pick_ge<1, 2, 4, 8>(M, [&](auto NPc) {
+      return launch(h, T_DOTS, swk::k_slice_dots<decltype(NPc)::value, true>, grid, dim3(SW_BLOCK),
+                    (const int8_t*)h->pb_codes, Z, (const int*)h->slicerow, (const cplx*)h->loop_phase,
+                    (const int*)h->loop_mom, L, nbp, M, h->pb_lest);
+    }));
+  }
+  if (!total) return 0;
+  return launch(h, T_DOTS, swk::k_slice_total, dim3(nbp / 64), dim3(SW_BLOCK), (const cplx*)h->pb_lest, L, nbp,
+                total);
+}
+
+static int fetch_loops(sw_engine* h, int nb, double* out) {
+  const size_t rows = h->momenta.size() * 4 * (size_t)h->hier[0].lv[0].L;
+  HIPCHK(hipMemcpy2D(out, sizeof(cplx) * nb, h->pb_lest, sizeof(cplx) * h->loop_nbp, sizeof(cplx) * nb, rows,
+                     hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The kernel alone on host inputs (reference ordering): out[p][a][b][t][k] as above with z_k = Z_k.
+int sw_apply_slice_dots(sw_engine* h, int nb, const int8_t* probes, const double* Z, double* out) {
+  SWCHK(check_hier(h, 0, 0, false));
+  if (nb <= 0 || !probes || !Z || !out) return sw_fail(h, "bad arguments");
+  if (h->momenta.empty()) return sw_fail(h, "no momenta registered (sw_set_loop_momenta)");
+  HIPCHK(hipSetDevice(h->device));
+  Level& lv = h->hier[0].lv[0];
+  const int nbp = pad64(nb);
+  cplx *a, *b;
+  SWCHK(io_vectors(h, lv, nbp, &a, &b));
+  SWCHK(pack_host(h, lv, nb, Z, a, nbp));
+  DevBuf<int8_t> pr(h);
+  SWCHK(upload(h, &pr.p, probes, (size_t)nb * lv.n));
+  SWCHK(slice_dots(h, lv, pr, nb, a, nbp, nullptr));
+  SWCHK(stream_sync(h));
+  return fetch_loops(h, nb, out);
+}
+
+int sw_hutch_fetch_loops(sw_engine* h, double* out) {
+  if (!h) return 1;
+  if (!out) return sw_fail(h, "null output");
+  if (h->loop_nb <= 0 || !h->pb_lest) return sw_fail(h, "no loop batch to fetch");
+  HIPCHK(hipSetDevice(h->device));
+  SWCHK(stream_sync(h));
+  return fetch_loops(h, h->loop_nb, out);
+}
+
 int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
   SWCHK(check_hier(h, 0, level, true));
   if (h->pb_level != level || h->pb_nb <= 0) return sw_fail(h, "no probes uploaded for level %d", level);
@@ -4657,6 +4787,10 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
   if (mode == SW_MODE_HUTCHINSON_SHIFTS) {
     if (level != 0) return sw_fail(h, "shifted Hutchinson mode runs at level 0");
     if (h->shifts.empty()) return sw_fail(h, "no shifts registered (sw_set_shifts)");
+  }
+  if (mode == SW_MODE_HUTCHINSON_LOOPS) {
+    if (level != 0) return sw_fail(h, "timeslice-loop Hutchinson mode runs at level 0");
+    if (h->momenta.empty()) return sw_fail(h, "no momenta registered (sw_set_loop_momenta)");
   }
   HIPCHK(hipSetDevice(h->device));
   Hier& H0 = h->hier[0];
@@ -4709,6 +4843,23 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
     HIPCHK(hipMemcpyAsync(h->pb_est, h->pb_sest, sizeof(cplx) * nbp, hipMemcpyDeviceToDevice, h->stream));
     SWCHK(stream_sync(h));
     h->shift_nb = nb;
+    SWCHK(record_iters(h, &h->hier[fine_hid].lv[0].sws, total, h->last_iters_f, nb));
+    h->last_iters_c.assign(nb, 0);
+    return 0;
+  }
+  if (mode == SW_MODE_HUTCHINSON_LOOPS) {
+    // z = A^-1 (x - U U^H x) exactly as SW_MODE_HUTCHINSON_SHIFTS, then the reduction that stops at the
+    // timeslice and keeps the spin components apart; pb_est = the scalar total of the first momentum
+    const cplx* rhs = h->pb_x0;
+    if (h->kd > 0) {
+      SWCHK(deflate(h, h->U, h->kd, nullptr, h->pb_x0, h->pb_rhs, n, nbp));
+      rhs = h->pb_rhs;
+    }
+    int total = 0;
+    SWCHK(solve_dev(h, fine_hid, 0, rhs, h->pb_z, tol, maxiter, nbp, &total));
+    SWCHK(slice_dots(h, lv, h->pb_probes, nb, h->pb_z, nbp, h->pb_est));
+    SWCHK(stream_sync(h));
+    h->loop_nb = nb;
     SWCHK(record_iters(h, &h->hier[fine_hid].lv[0].sws, total, h->last_iters_f, nb));
     h->last_iters_c.assign(nb, 0);
     return 0;

@@ -3380,4 +3380,139 @@ __global__ __launch_bounds__(SW_BLOCK) void k_shift_dots(const int8_t* __restric
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// Timeslice loops (SW_MODE_HUTCHINSON_LOOPS): l[p][a][b][t][k] = sum_x e^{-2 pi i p x / L} conj(x_k[idx(a,x,t)])
+// z_k[idx(b,x,t)] for the registered momenta p, the spin indices a, b in {0, 1} and every timeslice t = y of the
+// lattice level (reference order idx(s,x,y) = s L^2 + y L + x).  slicerow[(t * L + x) * 2 + a] is the internal row
+// of idx(a,x,t) (built from the level's row map: the kernel does not know the layout); codes are k_probe_codes'.
+// ------------------------------------------------------------------------------------------
+// grid = (L timeslices, nbp / 64); lane = probe.  One workgroup owns one (t, probe group): its four waves take
+// the sites x = wave, wave + 4, ...; per site a lane reads its two code bytes and the two 16-byte values z_0, z_1
+// and forms the four products conj(code_a) z_b by swap and sign flip (as k_shift_dots: code 1 -> z, -1 -> -z,
+// 2 (= i) -> -i z, -2 -> i z).  Each of the NP momenta of the pass multiplies them by its phase omega^(p x mod L),
+// omega = e^{-2 pi i / L}, from the L-entry table staged in LDS (the index is the same in all lanes: a broadcast
+// read; it advances by 4 p mod L per step, no division in the loop), into 4 NP complex accumulators held in
+// registers.  PHASE = false (only p = 0 registered, NP = 1) skips table and multiply.  The waves combine through
+// LDS in a fixed order (w0 + w1 + w2 + w3, one wave's block at a time) and wave 0 writes
+// out[((j * 4 + a * 2 + b) * L + t) * nbp + col] for the nmom registered momenta: no partials, no atomics.
+// mom[] is padded to NP entries with the first momentum.  A padded probe column (code 0) only ever touches its
+// own lane's sums, which nobody reads.
+template <int NP, bool PHASE = true>
+__global__ __launch_bounds__(SW_BLOCK) void k_slice_dots(const int8_t* __restrict__ codes,
+                                                         const cplx* __restrict__ Z,
+                                                         const int* __restrict__ slicerow,
+                                                         const cplx* __restrict__ phase,
+                                                         const int* __restrict__ mom, int L, int nbp, int nmom,
+                                                         cplx* __restrict__ out) {
+  constexpr int NA = 4 * NP;
+  __shared__ __attribute__((aligned(16))) cplx tab[PHASE ? SW_SHIFT_MAX_L : 1];
+  __shared__ __attribute__((aligned(16))) cplx red[NA][64];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int t = blockIdx.x;
+  const size_t col = (size_t)blockIdx.y * 64 + lane;
+  int idx[NP] = {}, step[NP] = {};
+  if constexpr (PHASE) {
+    for (int i = threadIdx.x; i < L; i += SW_BLOCK) tab[i] = phase[i];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      const int p = mom[j];                 // in [0, L), L <= 1024: the products below stay far inside int
+      idx[j] = (p * wave) % L;
+      step[j] = (p * SW_WAVES_PER_BLOCK) % L;
+    }
+    __syncthreads();
+  }
+  double ar[NA], ai[NA];
+#pragma unroll
+  for (int i = 0; i < NA; ++i) ar[i] = ai[i] = 0.0;
+  const int* __restrict__ sr = slicerow + (size_t)t * L * 2;
+#pragma unroll 2
+  for (int x = wave; x < L; x += SW_WAVES_PER_BLOCK) {
+    const size_t r0 = (size_t)sr[2 * x] * nbp + col, r1 = (size_t)sr[2 * x + 1] * nbp + col;
+    const int c[2] = {(int)codes[r0], (int)codes[r1]};
+    const cplx z[2] = {Z[r0], Z[r1]};
+    double pr[4], pi[4];                    // conj(code_a) z_b at [a * 2 + b]
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      const bool rot = (c[a] & 1) == 0;     // +-2: multiply by -+i
+      const bool neg = c[a] < 0;
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const double ur = rot ? z[b].y : z[b].x;
+        const double ui = rot ? -z[b].x : z[b].y;
+        pr[a * 2 + b] = neg ? -ur : ur;
+        pi[a * 2 + b] = neg ? -ui : ui;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      if constexpr (PHASE) {
+        const cplx w = tab[idx[j]];
+        idx[j] += step[j];
+        idx[j] = idx[j] >= L ? idx[j] - L : idx[j];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          ar[j * 4 + q] += w.x * pr[q] - w.y * pi[q];
+          ai[j * 4 + q] += w.x * pi[q] + w.y * pr[q];
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          ar[j * 4 + q] += pr[q];
+          ai[j * 4 + q] += pi[q];
+        }
+      }
+    }
+  }
+  for (int w = 1; w < SW_WAVES_PER_BLOCK; ++w) {
+    __syncthreads();                        // wave 0 has taken the previous wave's block
+    if (wave == w) {
+#pragma unroll
+      for (int i = 0; i < NA; ++i) red[i][lane] = cmake(ar[i], ai[i]);
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+      for (int i = 0; i < NA; ++i) {
+        const cplx v = red[i][lane];
+        ar[i] += v.x;
+        ai[i] += v.y;
+      }
+    }
+  }
+  if (wave == 0) {
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      if (j < nmom) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          out[((size_t)(j * 4 + q) * L + t) * nbp + col] = cmake(ar[j * 4 + q], ai[j * 4 + q]);
+      }
+    }
+  }
+}
+
+// est[col] = sum_t (l[0][0][0][t][col] + l[0][1][1][t][col]) of the first momentum's block of k_slice_dots'
+// output: the scalar total of the loops (x^H z when that momentum is 0).  grid = (nbp / 64); the four waves take
+// t = wave, wave + 4, ... and combine through LDS in a fixed order (deterministic).
+__global__ __launch_bounds__(SW_BLOCK) void k_slice_total(const cplx* __restrict__ loops, int L, int nbp,
+                                                          cplx* __restrict__ est) {
+  __shared__ cplx red[3][64];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const size_t col = (size_t)blockIdx.x * 64 + lane;
+  const cplx* __restrict__ d00 = loops + col;
+  const cplx* __restrict__ d11 = loops + (size_t)3 * L * nbp + col;
+  cplx s = cmake(0.0, 0.0);
+#pragma unroll 4
+  for (int t = wave; t < L; t += SW_WAVES_PER_BLOCK)
+    s = cadd(s, cadd(d00[(size_t)t * nbp], d11[(size_t)t * nbp]));
+  if (wave > 0) red[wave - 1][lane] = s;
+  __syncthreads();
+  if (wave == 0) {
+    s = cadd(s, red[0][lane]);
+    s = cadd(s, red[1][lane]);
+    s = cadd(s, red[2][lane]);
+    est[col] = s;
+  }
+}
+
 }  // namespace swk

@@ -20,7 +20,9 @@ MODE_MLMC = 1
 MODE_MLMC_SKIP = 2
 MODE_LEVEL = 3
 MODE_HUTCHINSON_SHIFTS = 4
+MODE_HUTCHINSON_LOOPS = 5
 MAX_SHIFTS = 128
+MAX_MOMENTA = 8
 PROBES_Z2 = 1
 PROBES_Z4 = 2
 PROBE_KINDS = {"z2": PROBES_Z2, "z4": PROBES_Z4}
@@ -155,6 +157,9 @@ def load_library():
     sig("sw_set_shifts", i32, vp, i32, vp)
     sig("sw_hutch_fetch_shifts", i32, vp, vp)
     sig("sw_apply_shift_dots", i32, vp, i32, vp, vp, vp)
+    sig("sw_set_loop_momenta", i32, vp, i32, vp)
+    sig("sw_hutch_fetch_loops", i32, vp, vp)
+    sig("sw_apply_slice_dots", i32, vp, i32, vp, vp, vp)
     _lib = lib
     return lib
 
@@ -176,6 +181,7 @@ EXPORTED_SYMBOLS = (
     "sw_mt_jump_poly", "sw_mt_window_jump",
     "sw_probes_stream_set", "sw_probes_generate", "sw_probes_fetch",
     "sw_set_shifts", "sw_hutch_fetch_shifts", "sw_apply_shift_dots",
+    "sw_set_loop_momenta", "sw_hutch_fetch_loops", "sw_apply_slice_dots",
 )
 
 
@@ -243,6 +249,7 @@ class Engine:
         self.level_sizes[hid] = [0] * nlevels
         if hid == 0:
             self._nshifts = 0          # the engine drops its shift registration with hierarchy 0
+            self._nmom = 0             # ... and its loop momenta
 
     def set_lattice(self, hid, L, mass, U1, U2):
         U1, U2 = _c128(U1), _c128(U2)
@@ -418,6 +425,14 @@ class Engine:
         s = np.ascontiguousarray([] if shifts is None else shifts, dtype=np.int64).ravel()
         self._chk(self._lib.sw_set_shifts(self._h, s.size, _ptr(s) if s.size else None), "sw_set_shifts")
         self._nshifts = int(s.size)
+
+    def set_loop_momenta(self, momenta):
+        """Register the spatial momenta of MODE_HUTCHINSON_LOOPS (integers in [0, L), no duplicates, at most
+        MAX_MOMENTA); None or an empty list clears the registration."""
+        p = np.ascontiguousarray([] if momenta is None else momenta, dtype=np.int32).ravel()
+        self._chk(self._lib.sw_set_loop_momenta(self._h, p.size, _ptr(p) if p.size else None),
+                  "sw_set_loop_momenta")
+        self._nmom = int(p.size)
 
     def set_rhsmap(self, level, Cmat):
         (n, m), indptr, indices, data = _csr_parts(Cmat)
@@ -597,6 +612,38 @@ class Engine:
         self._chk(self._lib.sw_apply_shift_dots(self._h, p.shape[0], _ptr(p), _ptr(Z2), _ptr(out)),
                   "sw_apply_shift_dots")
         return np.ascontiguousarray(out.T)
+
+    def _loop_shape(self, nb):
+        n = self._n(0, 0)
+        L = int(round((n // 2) ** 0.5))
+        return (getattr(self, "_nmom", 0), 2, 2, L, nb)
+
+    def hutch_batch_loops(self, level, probes, tol, maxiter=1000):
+        """One MODE_HUTCHINSON_LOOPS batch: (loops[nb, nmom, 2, 2, L], iters_fine[nb], iters_coarse[nb]),
+        loops[k, p, a, b, t] = sum_x e^{-2 pi i p x / L} conj(x_k[idx(a,x,t)]) z_k[idx(b,x,t)]."""
+        _, itf, itc = self.hutch_batch(MODE_HUTCHINSON_LOOPS, level, probes, tol, maxiter)
+        self._nb_uploaded = itf.size
+        return self.hutch_fetch_loops(), itf, itc
+
+    def hutch_fetch_loops(self):
+        """Loops of the last MODE_HUTCHINSON_LOOPS batch for every registered momentum, shape
+        (nb, nmom, 2, 2, L)."""
+        out = np.zeros(self._loop_shape(getattr(self, "_nb_uploaded", 0)), dtype=np.complex128)
+        self._chk(self._lib.sw_hutch_fetch_loops(self._h, _ptr(out)), "sw_hutch_fetch_loops")
+        return np.ascontiguousarray(np.moveaxis(out, -1, 0))
+
+    def apply_slice_dots(self, probes, Z):
+        """The slice-dot kernel alone: out[k, p, a, b, t] = sum_x e^{-2 pi i p x / L} conj(x_k[idx(a,x,t)])
+        Z[k][idx(b,x,t)] for the registered momenta; probes int8 (nb, n) codes, Z complex (nb, n), both in the
+        reference ordering idx(s,x,y) = s L^2 + y L + x."""
+        p = self._probes(probes)
+        Z2, _ = self._io(Z, self._n(0, 0))
+        if p.shape != Z2.shape:
+            raise EngineError("probes %s and Z %s differ in shape" % (p.shape, Z2.shape))
+        out = np.zeros(self._loop_shape(p.shape[0]), dtype=np.complex128)
+        self._chk(self._lib.sw_apply_slice_dots(self._h, p.shape[0], _ptr(p), _ptr(Z2), _ptr(out)),
+                  "sw_apply_slice_dots")
+        return np.ascontiguousarray(np.moveaxis(out, -1, 0))
 
     def probes_upload(self, level, probes):
         p = self._probes(probes)

@@ -18,8 +18,9 @@ from . import dist as _dist
 from .engine import ProbeStream
 from .multigrid import MG
 from .utils import (_engines, deflation_pre_computations, displacements_of, draw_probes, flopsV_manual,
-                    mlmc_defl_setup_of, probe_batch, probe_batch_generated, probe_batch_shifts,
-                    probe_batch_shifts_generated, register_shifts)
+                    loops_of, mlmc_defl_setup_of, probe_batch, probe_batch_generated, probe_batch_loops,
+                    probe_batch_loops_generated, probe_batch_shifts, probe_batch_shifts_generated,
+                    register_loop_momenta, register_shifts)
 
 DEFAULT_BATCH = 256
 NR_ROUGH_PROBES = 5
@@ -196,6 +197,35 @@ class DeviceShiftProbes:
         return probe_batch_shifts_generated(self.mg_solver, self.params, first_probe, count, self.kind)
 
 
+def loop_columns(loops, zero):
+    """The columns of the timeslice-loop estimator for run_probe_loop_displaced: loops[k][p][a][b][t] flattened
+    per probe, plus one control column, the scalar total sum_t (l[0][0][t] + l[1][1][t]) of momentum index
+    `zero` (p = 0) -- the plain Hutchinson value x^H z of the probe."""
+    loops = np.asarray(loops, dtype=np.complex128)
+    total = np.sum(loops[:, zero, 0, 0, :] + loops[:, zero, 1, 1, :], axis=1)
+    return np.concatenate([loops.reshape(loops.shape[0], -1), total[:, None]], axis=1)
+
+
+class DeviceLoopProbes:
+    """Probe source of the timeslice-loop flow: as :class:`DeviceShiftProbes`, each probe evaluated on every
+    (momentum, spin pair, timeslice); one row of loop_columns per probe."""
+
+    def __init__(self, mg_solver, params, zero, kind="z2"):
+        self.mg_solver = mg_solver
+        self.params = params
+        self.zero = zero
+        self.kind = kind
+
+    def begin(self, entry_stream):
+        window = entry_stream.window()
+        for eng in _engines(self.mg_solver):
+            eng.stream_set(window)
+
+    def __call__(self, first_probe, count):
+        e, f, c = probe_batch_loops_generated(self.mg_solver, self.params, first_probe, count, self.kind)
+        return loop_columns(e, self.zero), f, c
+
+
 def run_probe_loop_displaced(evaluate, n, level_tols, control, max_nr_ests, batch, comm=None, min_index=5,
                              probe_type="z2"):
     """The probe loop of :func:`run_probe_loop` for estimators that return one value per displacement:
@@ -288,6 +318,9 @@ def _rough_trace(mg_solver, params, n, Vx_rank, tr1):
 
 # compute tr(A^{-1}) via (deflated) Hutchinson                      stoch_trace.py:33-179
 def hutchinson(A, params):
+    momenta = loops_of(params)
+    if momenta is not None:
+        return _hutchinson_loops(A, params, momenta)
     displaced = displacements_of(params)
     if displaced is not None:
         return _hutchinson_displaced(A, params, displaced)
@@ -425,8 +458,88 @@ def _hutchinson_displaced(A, params, displaced):
     return result
 
 
+def _hutchinson_loops(A, params, momenta):
+    """hutchinson() with the build-only key timeslice_loops: the spin- and momentum-resolved loops
+    l[p][a][b][t] of every timeslice from one deflation projection and one solve per probe.
+    The columns of the probe loop are the flattened loops plus one control column, the scalar total at p = 0,
+    whose expectation plus sum(tr1) is Tr(A^-1): the reference's result keys are filled from it and the
+    stopping rule runs on it alone."""
+    if _dist.default_comm().world > 1:
+        raise Exception("timeslice loops (timeslice_loops) run on one rank")
+    mg_solver, nr_levels = _setup_solver(A, params, defer_coarse=True)
+    N = A.shape[0]
+    batch = int(params.get('batch', DEFAULT_BATCH))
+    kind = params.get('probe_type', 'z2')
+    zero = momenta.index(0)
+
+    print("\nResetting timer to zero ...", end='')
+    mg_solver.timer.reset()
+    print(" done\n")
+    nr_deflat_vctrs = params['nr_deflat_vctrs']
+    print("Computing deflation vectors ...", end='', flush=True)
+    t0 = time.time()
+    Vx, tr1 = deflation_pre_computations(A, nr_deflat_vctrs, params['defl_eigvs_tol_Hutch'],
+                                         "hutchinson", mg_solver.timer, params, mg_solver)
+    tr1 = np.asarray(tr1, dtype=np.complex128)                  # [p][a][b][t]
+    tr1_cols = loop_columns(tr1[None], zero)[0]
+    register_loop_momenta(mg_solver, momenta)
+    print(" done. Time : " + str(time.time() - t0) + " seconds")
+    print(mg_solver.timer)
+
+    print("\nComputing rough estimation of the loops ...", end='', flush=True)
+    np.random.seed(123456)                                      # stoch_trace.py:103-115
+    t0 = time.time()
+    e, _, _ = probe_batch_loops(mg_solver, params, draw_probes(NR_ROUGH_PROBES, N, kind))
+    rough = np.sum(loop_columns(e, zero), axis=0) / NR_ROUGH_PROBES + tr1_cols
+    level_tols = np.abs(params['tol'] * rough)
+    control = rough.size - 1
+    print(" done. Time : " + str(time.time() - t0) + " seconds")
+
+    print("\nResetting timer to zero ...", end='')
+    mg_solver.timer.reset()
+    mg_solver.engine.timers_reset()
+    print(" done")
+    print("\nComputing the loops stochastically ...", end='', flush=True)
+    t0 = time.time()
+    mg_solver.coarsest_lev_iters[0] = 0
+    loop = run_probe_loop_displaced(DeviceLoopProbes(mg_solver, params, zero, kind), N, level_tols, control,
+                                    params['max_nr_ests'], batch * max(1, len(_engines(mg_solver))),
+                                    probe_type=kind)
+    loop_s = time.time() - t0
+    print(" done. Time : " + str(loop_s) + " seconds")
+
+    function_iters = int(np.sum(loop["iters_fine"]))
+    mg_solver.coarsest_lev_iters[0] = function_iters
+    mg_solver.finish_setup()
+    result = dict()
+    result['trace'] = loop["avg"] + tr1_cols[control]
+    result['std_dev'] = loop["dev"]
+    result['nr_ests'] = loop["index"]
+    result['function_iters'] = function_iters
+    levels = mg_solver.ml.levels
+    result['total_complexity'] = flopsV_manual(len(levels), levels, 0, mg_solver) * function_iters
+    result['total_complexity'] += levels[len(levels) - 1].A.nnz * mg_solver.coarsest_lev_iters[0]
+    result['total_complexity'] += result['nr_ests'] * (2 * N * nr_deflat_vctrs) / 3.0
+    result['ests'] = loop["ests"][:, control]       # (nr_ests + 1,): the plain Hutchinson series
+    result['rough_trace'] = rough[control]
+    result['level_tol'] = level_tols[control]
+    result['probe_loop_s'] = loop_s
+    result['probes_solved'] = loop["solved"]
+    result['momenta'] = list(momenta)
+    result['loops'] = (loop["avgs"][:control] + tr1_cols[:control]).reshape(tr1.shape)
+    result['loop_devs'] = loop["devs"][:control].reshape(tr1.shape)
+    result['loop_ests'] = loop["ests"][:, :control].reshape((-1,) + tr1.shape) + tr1[None]
+    result['converged'] = loop["converged"][:control].reshape(tr1.shape)
+    mg_solver.sync_timer()
+    print(mg_solver.timer)
+    return result
+
+
 # compute tr(A^{-1}) via multigrid multilevel Monte Carlo          stoch_trace.py:185-471
 def mlmc(A, params):
+    if loops_of(params) is not None:
+        raise Exception("timeslice_loops is implemented for hutchinson() only: the MLMC coarse terms need a "
+                        "timeslice projection per level")
     if displacements_of(params) is not None:
         raise Exception("x_displacements is implemented for hutchinson() only: the MLMC difference levels "
                         "need their own displaced right-hand sides")

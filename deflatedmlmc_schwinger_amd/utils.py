@@ -7,8 +7,8 @@ import numpy as np
 from scipy.sparse.linalg import eigsh
 
 from . import dist as _dist
-from .engine import (MAX_SHIFTS, MODE_HUTCHINSON, MODE_HUTCHINSON_SHIFTS, MODE_LEVEL, MODE_MLMC, MODE_MLMC_SKIP,
-                     EngineError)
+from .engine import (MAX_MOMENTA, MAX_SHIFTS, MODE_HUTCHINSON, MODE_HUTCHINSON_LOOPS, MODE_HUTCHINSON_SHIFTS,
+                     MODE_LEVEL, MODE_MLMC, MODE_MLMC_SKIP, EngineError)
 
 
 # ----------------------------------------------------------------------------------------
@@ -63,7 +63,8 @@ _BUILD_KEYS = ('batch', 'device', 'engines', 'cache_dir', 'report_path', 'probe_
                'solver_testvectors', 'deflation_eigenpairs', 'ref_cycle_post', 'ref_cycle_k', 'ref_smoother',
                'solver_restart', 'stochastic_coarsest', 'stop_factor', 'ref_direct_max_n', 'ref_coarsest',
                'ref_coarse_dofs', 'setup_eigs', 'defer_coarse_levels',
-               'verbose', 'probe_rounds_max', 'mlmc_defl_setup', 'defl_setup', 'x_displacements')
+               'verbose', 'probe_rounds_max', 'mlmc_defl_setup', 'defl_setup', 'x_displacements',
+               'timeslice_loops')
 # where the eigenpairs of the MLMC difference operators come from: host ARPACK (the reference's path) or
 # the block eigensolver on the GPU (setup_gpu.device_diff_eigenpairs)
 MLMC_DEFL_SETUPS = ("host", "device")
@@ -132,6 +133,91 @@ def displaced_tr1(Vx, Sy, g3, n, shifts):
     W = (np.asarray(g3)[:, None] * Vx if np.ndim(g3) == 1 else np.asarray(g3 * Vx)) * np.sign(Sy)[None, :]
     return np.array([np.sum(np.sum(W.conj() * np.roll(Vx, int(s), axis=0), axis=0) / np.abs(Sy))
                      for s in shifts])
+
+
+def loops_of(params):
+    """The build-only key timeslice_loops: None when absent, else the validated list of spatial momenta p (integers
+    in [0, L), L = latt_dims[0]) of the loops L_Gamma(t, p).  The list has to contain 0 -- the scalar total at
+    p = 0 is the control series that estimates Tr(A^-1) -- and does not combine with x_displacements."""
+    if not hasattr(params, "get") or params.get('timeslice_loops') is None:
+        return None
+    if params.get('x_displacements') is not None:
+        raise Exception("timeslice_loops does not combine with x_displacements")
+    L = int(params['latt_dims'][0])
+    momenta = []
+    for p in params['timeslice_loops']:
+        if int(p) != p:
+            raise Exception("timeslice_loops: %r is not an integer" % (p,))
+        p = int(p)
+        if not 0 <= p < L:
+            raise Exception("timeslice_loops: momentum %d outside [0, %d)" % (p, L))
+        if p in momenta:
+            raise Exception("timeslice_loops: momentum %d listed twice" % p)
+        momenta.append(p)
+    if len(momenta) > MAX_MOMENTA:
+        raise Exception("timeslice_loops: %d momenta, at most %d" % (len(momenta), MAX_MOMENTA))
+    if 0 not in momenta:
+        raise Exception("timeslice_loops has to contain the momentum 0 (its scalar total is the control series)")
+    return momenta
+
+
+def slice_phases(L, momenta):
+    """e^{-2 pi i p x / L} as an array [p][x]."""
+    return np.exp(-2j * np.pi * np.outer(np.asarray(momenta, dtype=np.int64), np.arange(L)) / L)
+
+
+def sliced_tr1(Vx, Sy, g3, L, momenta):
+    """The deflated part of the timeslice loops: tr1[p][a][b][t] = sum_i sum_x e^{-2 pi i p x / L}
+    conj(w_i[idx(a,x,t)]) v_i[idx(b,x,t)] / |lambda_i| with (lambda_i, v_i) eigenpairs of gamma_3 A (Sy, columns
+    of Vx), w_i = gamma_3 v_i sgn(lambda_i) and idx(s,x,y) = s L^2 + y L + x.  Then the diagonal blocks of A^-1
+    are those of A^-1 (I - W W^H) plus this.  g3: the diagonal of gamma_3, or a (sparse) matrix."""
+    Vx = np.asarray(Vx, dtype=np.complex128)
+    Sy = np.asarray(Sy, dtype=float)
+    if Vx.shape[0] != 2 * L * L:
+        raise Exception("sliced_tr1: vectors of length %d, expected %d" % (Vx.shape[0], 2 * L * L))
+    W = (np.asarray(g3)[:, None] * Vx if np.ndim(g3) == 1 else np.asarray(g3 * Vx)) * np.sign(Sy)[None, :]
+    k = Vx.shape[1]
+    Wc = W.conj().reshape(2, L, L, k)                      # [a][t][x][i]
+    Vs = (Vx / np.abs(Sy)[None, :]).reshape(2, L, L, k)    # [b][t][x][i]
+    return np.einsum('px,atxi,btxi->pabt', slice_phases(L, momenta), Wc, Vs)
+
+
+_PAULI = {'1': np.array([[1, 0], [0, 1]], dtype=np.complex128),
+          'g3': np.array([[1, 0], [0, -1]], dtype=np.complex128),
+          's1': np.array([[0, 1], [1, 0]], dtype=np.complex128),
+          's2': np.array([[0, -1j], [1j, 0]], dtype=np.complex128)}
+
+
+def loop_gamma(loops, which):
+    """sum_ab Gamma[a][b] loops[..., a, b, :] for Gamma the unit matrix ('1'), gamma_3 = sigma_3 ('g3'), sigma_1
+    ('s1') or sigma_2 ('s2'): the loop L_Gamma(t, p) from the spin-resolved array [..., 2, 2, L]."""
+    if which not in _PAULI:
+        raise Exception("loop_gamma: unknown spin matrix %r (one of %s)" % (which, sorted(_PAULI)))
+    loops = np.asarray(loops)
+    if loops.ndim < 3 or loops.shape[-3:-1] != (2, 2):
+        raise Exception("loop_gamma: loops of shape %s, expected (..., 2, 2, L)" % (loops.shape,))
+    G = _PAULI[which]
+    return sum(G[a, b] * loops[..., a, b, :] for a in range(2) for b in range(2) if G[a, b] != 0)
+
+
+def loop_correlator(per_probe_a, per_probe_b):
+    """C[D] = (1/L) sum_t <L_a(t + D)> <L_b(t)>, D = 0..L-1 (t + D mod L), from per-probe series of shape (N, L)
+    that already include tr1.  The product of the two means is formed over pairs of different probes only,
+    (S_a S_b - sum_k a_k b_k) / (N (N - 1)) with S = the sum over probes: the same probe in both factors would
+    add its variance, so this keeps the estimate unbiased."""
+    a = np.asarray(per_probe_a, dtype=np.complex128)
+    b = np.asarray(per_probe_b, dtype=np.complex128)
+    if a.ndim != 2 or a.shape != b.shape:
+        raise Exception("loop_correlator: series of shapes %s and %s, expected two equal (N, L)" % (a.shape, b.shape))
+    N, L = a.shape
+    if N < 2:
+        raise Exception("loop_correlator needs at least two probes")
+    Sa, Sb = a.sum(axis=0), b.sum(axis=0)
+    out = np.empty(L, dtype=np.complex128)
+    for D in range(L):
+        ar = np.roll(a, -D, axis=1)                        # ar[k, t] = a[k, t + D]
+        out[D] = np.sum(np.roll(Sa, -D) * Sb - np.sum(ar * b, axis=0)) / (N * (N - 1.0) * L)
+    return out
 
 
 def trace_params_from_params(params, example):
@@ -235,6 +321,10 @@ def deflation_pre_computations(A, nr_deflat_vctrs, tolx, method, timer, params, 
             for eng in _engines(mg_solver):
                 eng.set_deflation(None)
             disp = displacements_of(params)
+            momenta = loops_of(params)
+            if momenta is not None:
+                L = int(params['latt_dims'][0])
+                return (None, np.zeros((len(momenta), 2, 2, L), dtype=np.complex128))
             return (None, 0.0 if disp is None else np.zeros(len(disp[0]), dtype=np.complex128))
         for eng in _engines(mg_solver):
             eng.set_level_deflation(level_nr, None)
@@ -242,6 +332,7 @@ def deflation_pre_computations(A, nr_deflat_vctrs, tolx, method, timer, params, 
 
     lev0 = mg_solver.ml.levels[0]
     displaced = displacements_of(params) if method == "hutchinson" else None
+    momenta = loops_of(params) if method == "hutchinson" else None
     if method == "hutchinson":
         pre = params.get("deflation_eigenpairs") if hasattr(params, "get") else None
         how = defl_setup_of(params)
@@ -304,14 +395,17 @@ def deflation_pre_computations(A, nr_deflat_vctrs, tolx, method, timer, params, 
     Ux = Vx * sgn[None, :]
     if method == "hutchinson":
         Ux = lev0.g3 * Ux
-        if displaced is not None:
+        if displaced is not None or momenta is not None:
             # W = gamma_3 V sgn(lambda) as it is: the displacement sits on the probe side of the dots
-            # (SW_MODE_HUTCHINSON_SHIFTS), tr1 is one number per displacement
+            # (SW_MODE_HUTCHINSON_SHIFTS), tr1 is one number per displacement; the timeslice loops
+            # (SW_MODE_HUTCHINSON_LOOPS) project with the same W, tr1 is the array [p][a][b][t]
             if os.getenv('OMP_NUM_THREADS') is None:                    # utils.py:161-164
                 raise Exception("Run : << export OMP_NUM_THREADS=N >>")
             mg_solver.solve_tol = params['function_params']['tol']
             for eng in _engines(mg_solver):
                 eng.set_deflation(np.asarray(Ux))
+            if momenta is not None:
+                return (Ux, sliced_tr1(Vx, Sy, lev0.g3, int(params['latt_dims'][0]), momenta))
             return (Ux, displaced_tr1(Vx, Sy, lev0.g3, Vx.shape[0], displaced[1]))
         if params['use_permuted']:
             Ux = lev0.Pperm * Ux
@@ -446,6 +540,46 @@ def probe_batch_shifts_generated(mg_solver, params, first_probe, count, kind="z2
         eng.hutch_run(MODE_HUTCHINSON_SHIFTS, 0, tol, maxiter)
         _, itf, itc = eng.hutch_fetch()
         return eng.hutch_fetch_shifts(), itf, itc
+
+    if len(active) == 1:
+        res = [run(active[0])]
+    else:
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=len(active)) as pool:
+            res = list(pool.map(run, active))
+    return tuple(np.concatenate([r[k] for r in res]) for k in range(3))
+
+
+def register_loop_momenta(mg_solver, momenta):
+    """Hand the momenta of the timeslice loops to every engine handle (None clears)."""
+    for eng in _engines(mg_solver):
+        eng.set_loop_momenta(momenta)
+
+
+def probe_batch_loops(mg_solver, params, probes):
+    """One batch of probes through MODE_HUTCHINSON_LOOPS: (loops[nb, nmom, 2, 2, L], iters_fine, iters_coarse)
+    -- one projection and one solve per probe."""
+    engs, tol, _, maxiter = _shift_batch_args(mg_solver, params)
+    return engs[0].hutch_batch_loops(0, np.asarray(probes), tol, maxiter)
+
+
+def probe_batch_loops_generated(mg_solver, params, first_probe, count, kind="z2"):
+    """probe_batch_loops for the probes [first_probe, first_probe + count) of the stream the engines hold
+    (Engine.stream_set), generated on the device; several engine handles share the batch as in
+    probe_batch_generated."""
+    engs, tol, n, maxiter = _shift_batch_args(mg_solver, params)
+    ne = len(engs) if count >= 2 * 64 else 1
+    bounds = [(k * count) // ne for k in range(ne + 1)]
+    active = [k for k in range(ne) if bounds[k + 1] > bounds[k]]
+    for k in active:
+        engs[k].probes_generate(0, 0, bounds[k + 1] - bounds[k], (first_probe + bounds[k]) * n, kind)
+
+    def run(k):
+        eng = engs[k]
+        eng.probes_select(0)
+        eng.hutch_run(MODE_HUTCHINSON_LOOPS, 0, tol, maxiter)
+        _, itf, itc = eng.hutch_fetch()
+        return eng.hutch_fetch_loops(), itf, itc
 
     if len(active) == 1:
         res = [run(active[0])]

@@ -33,6 +33,7 @@ extern "C" {
 #define SW_MAX_KRYLOV 32
 #define SW_MAX_DEFL 256
 #define SW_MAX_SHIFTS 128
+#define SW_MAX_MOMENTA 8
 
 typedef struct sw_engine sw_engine;
 
@@ -218,6 +219,10 @@ int sw_set_rhsmap(sw_engine* h, int level, int n, const int64_t* indptr, const i
  * v[(i - s) mod n], at many displacements from one solve per probe).  Lattice level 0 only (sw_set_lattice);
  * every shift a multiple of 2L in [0, n), no duplicates, at most SW_MAX_SHIFTS; nshifts = 0 clears. */
 int sw_set_shifts(sw_engine* h, int nshifts, const int64_t* shifts);
+/* Spatial momenta p_j of SW_MODE_HUTCHINSON_LOOPS (build-only: timeslice loops, the phase of site x is
+ * e^{-2 pi i p x / L}).  Lattice level 0 only (sw_set_lattice); every p in [0, L), no duplicates, at most
+ * SW_MAX_MOMENTA; nmom = 0 clears. */
+int sw_set_loop_momenta(sw_engine* h, int nmom, const int32_t* p);
 /* Outer flexible-GMRES restart length (<= SW_MAX_KRYLOV) and the hierarchy used to
  * precondition level-0 solves (0 or 1). */
 int sw_set_solver(sw_engine* h, int restart, int solver_hid);
@@ -292,6 +297,10 @@ int sw_apply_deflation(sw_engine* h, int which, int level, int nb, const double*
  * Z_k[i] for the registered shifts; probes int8[nb*n] (codes +-1, +-2 = +-i), Z complex128[nb*n], out
  * complex128[nshifts*nb]. */
 int sw_apply_shift_dots(sw_engine* h, int nb, const int8_t* probes, const double* Z, double* out);
+/* The slice-dot kernel of SW_MODE_HUTCHINSON_LOOPS alone: out[p][a][b][t][k] = sum_x e^{-2 pi i p x / L}
+ * conj(x_k[idx(a,x,t)]) Z_k[idx(b,x,t)] for the registered momenta, idx(s,x,y) = s L^2 + y L + x; probes
+ * int8[nb*n] (codes +-1, +-2 = +-i), Z complex128[nb*n], out complex128[nmom*2*2*L*nb]. */
+int sw_apply_slice_dots(sw_engine* h, int nb, const int8_t* probes, const double* Z, double* out);
 /* X = one multigrid cycle applied to B starting at level0 (MG.one_mg_step, multigrid.py:369-447). */
 int sw_vcycle(sw_engine* h, int hid, int level0, int nb, const double* B, double* X);
 /* Solve A_level0 X = B to ||r|| < tol*||b|| per right-hand side (MG.solve -> pyamg fgmres,
@@ -312,6 +321,13 @@ int sw_solve(sw_engine* h, int hid, int level0, int nb, const double* B, double*
                                   sw_set_shifts, level 0: one projection and one solve per probe serve all
                                   shifts (build-only; U as registered, sw_set_perm ignored; its expectation
                                   is Tr(D_s A^-1 (I - U U^H)), per-probe values are not those of HUTCHINSON) */
+#define SW_MODE_HUTCHINSON_LOOPS 5 /* l_k[p][a][b][t] = sum_x e^{-2 pi i p x / L} conj(x_k[idx(a,x,t)])
+                                  z_k[idx(b,x,t)], z_k = A^-1 (x_k - U U^H x_k), for the momenta of
+                                  sw_set_loop_momenta, level 0: projection and solve exactly as
+                                  HUTCHINSON_SHIFTS (build-only; U as registered, sw_set_perm ignored).
+                                  sw_hutch_fetch returns sum_t (l[0][0][t] + l[1][1][t]) of the FIRST
+                                  registered momentum, which is x^H z -- the shift-0 value of
+                                  HUTCHINSON_SHIFTS -- only when that momentum is 0 */
 /* One batch of probes x_k in {-1,+1}^n (int8, nb*n, reference ordering) at `level`
  * (build-only extension: entries +-2 encode +-i, i.e. Z4 probes {1,i,-1,-i}):
  *   HUTCHINSON: e_k = x^H A^-1 Pperm^T (x - U U^H x)
@@ -346,6 +362,10 @@ int sw_hutch_fetch(sw_engine* h, double* ests, int32_t* iters);
 /* After a SW_MODE_HUTCHINSON_SHIFTS batch: ests complex128[nshifts][nb], row j = the estimates at shift j of
  * the registration (sw_hutch_fetch returns row 0 and the iteration counts). */
 int sw_hutch_fetch_shifts(sw_engine* h, double* ests);
+/* After a SW_MODE_HUTCHINSON_LOOPS batch: out complex128[nmom][2][2][L][nb], the loops l_k[p][a][b][t] of every
+ * probe k of the batch (sw_hutch_fetch returns the scalar total of the first momentum and the iteration
+ * counts). */
+int sw_hutch_fetch_loops(sw_engine* h, double* out);
 
 /* ---- multi-GPU: the one collective of the path ------------------------------------ */
 /* One process per GPU, one engine per process; the probe loop shards by probe and needs a single
