@@ -61,9 +61,11 @@ enum TimerCat { T_MVM = 0, T_DEFL, T_P, T_R, T_AXPY, T_DOTS, T_COARSEST, T_OTHER
                 T_MFMA_OP2,     // k_bsr_mfma on level operators below level 1 of the solver hierarchy
                 T_SCHUR,        // k_schur_step / k_eo_hop: even-odd smoother of the stencil level
                 T_SCHUR_OP,     // k_schur_step<0/1>: operator / residual of the even-odd reduced system
+                T_TP_SOURCES,   // k_slice_sources of SW_MODE_TWO_POINT
+                T_TP_DOTS,      // k_slice_pair_dots / k_pair_total of SW_MODE_TWO_POINT
                 T_NCAT };
-// classes >= T_STENCIL are folded into the mvm / coarsest buckets by sw_timers and reported
-// separately by sw_kernel_stats
+// classes >= T_STENCIL are folded into the mvm / coarsest (two-point: other / dots) buckets by sw_timers and
+// reported separately by sw_kernel_stats
 
 struct EllOp {
   int nrows = 0, ncols = 0, K = 0, G = 1, ngroups = 0;
@@ -323,6 +325,19 @@ struct sw_engine {
   cplx* pb_lest = nullptr;
   size_t pb_lest_cap = 0;
   int loop_nb = 0, loop_nbp = 0;   // probes and row stride of the last loop batch (0: nothing to fetch)
+  // one-end-trick two-point functions (sw_set_two_point, SW_MODE_TWO_POINT): a registration of its own (source
+  // timeslice, momenta, the index of momentum 0, tables as for the loops), the sources and solutions [n][2 M nq]
+  // and the pair sums T[momentum][a][b][c][d][t][noise]
+  std::vector<int32_t> tp_momenta;
+  int tp_t0 = 0, tp_j0 = 0;
+  int* tp_mom = nullptr;
+  cplx* tp_phase = nullptr;
+  int* tp_slicerow = nullptr;
+  cplx *tp_rhs = nullptr, *tp_z = nullptr;
+  size_t tp_ws_cap = 0;
+  cplx* tp_est = nullptr;
+  size_t tp_est_cap = 0;
+  int tp_nb = 0, tp_nq = 0;        // noises and row stride of the last two-point batch (0: nothing to fetch)
   std::vector<int32_t> last_iters_f, last_iters_c;
   // profiling
   bool profiling = false;
@@ -2534,6 +2549,8 @@ int sw_hier_begin(sw_engine* h, int hid, int nlevels) {
     h->shift_nb = 0;
     h->momenta.clear();
     h->loop_nb = 0;
+    h->tp_momenta.clear();
+    h->tp_nb = 0;
   }
   return 0;
 }
@@ -4663,31 +4680,30 @@ int sw_hutch_fetch_shifts(sw_engine* h, double* ests) {
 }
 
 // ---- timeslice loops: spin- and momentum-resolved traces per timeslice from one solve per probe --------
-int sw_set_loop_momenta(sw_engine* h, int nmom, const int32_t* p) {
-  SWCHK(check_hier(h, 0, 0, false));
-  if (nmom < 0 || nmom > SW_MAX_MOMENTA)
-    return sw_fail(h, "%d momenta: at most %d per registration", nmom, SW_MAX_MOMENTA);
-  h->loop_nb = 0;
-  if (nmom == 0) {
-    h->momenta.clear();
-    return 0;
-  }
+// The checks and device tables of a momentum registration (`what` names the mode in the messages): every p in
+// [0, L), no duplicates, at most SW_MAX_MOMENTA; mom = the momenta padded to SW_MAX_MOMENTA with the first,
+// phase = omega^j = e^{-2 pi i j / L}, j in [0, L), slicerow = the (timeslice, x, spin) -> internal row table.
+static int check_momenta(sw_engine* h, const char* what, int nmom, const int32_t* p) {
   if (!p) return sw_fail(h, "null momentum list");
   Level& lv = h->hier[0].lv[0];
   if (!lv.stencil || lv.h_rowmap.empty())
-    return sw_fail(h, "timeslice loops need a lattice level 0 (sw_set_lattice)");
-  const int L = lv.L, n = lv.n;
-  if (L > SW_SHIFT_MAX_L) return sw_fail(h, "timeslice loops: L=%d above %d", L, SW_SHIFT_MAX_L);
+    return sw_fail(h, "%s need a lattice level 0 (sw_set_lattice)", what);
+  const int L = lv.L;
+  if (L > SW_SHIFT_MAX_L) return sw_fail(h, "%s: L=%d above %d", what, L, SW_SHIFT_MAX_L);
   for (int j = 0; j < nmom; ++j) {
     if (p[j] < 0 || p[j] >= L) return sw_fail(h, "momentum %d outside [0,%d)", (int)p[j], L);
     for (int i = 0; i < j; ++i)
       if (p[i] == p[j]) return sw_fail(h, "momentum %d listed twice", (int)p[j]);
   }
-  HIPCHK(hipSetDevice(h->device));
-  SWCHK(stream_sync(h));
+  return 0;
+}
+static int upload_slice_tables(sw_engine* h, int nmom, const int32_t* p, int** d_mom, cplx** d_phase,
+                               int** d_slicerow) {
+  Level& lv = h->hier[0].lv[0];
+  const int L = lv.L, n = lv.n;
   std::vector<int> mom(p, p + nmom);
   mom.resize(SW_MAX_MOMENTA, mom[0]);
-  SWCHK(upload(h, &h->loop_mom, mom.data(), mom.size()));
+  SWCHK(upload(h, d_mom, mom.data(), mom.size()));
   std::vector<cplx> ph((size_t)L);
   for (int j = 0; j < L; ++j) {
     // exact at the multiples of a quarter turn, so p = 0 and the real/imaginary axes carry no rounding
@@ -4699,14 +4715,29 @@ int sw_set_loop_momenta(sw_engine* h, int nmom, const int32_t* p) {
       ph[j] = cplx{std::cos(a), std::sin(a)};
     }
   }
-  SWCHK(upload(h, &h->loop_phase, ph.data(), ph.size()));
+  SWCHK(upload(h, d_phase, ph.data(), ph.size()));
   // reference index idx(a,x,t) = a L^2 + t L + x
   std::vector<int> sr((size_t)n);
   for (int t = 0; t < L; ++t)
     for (int x = 0; x < L; ++x)
       for (int a = 0; a < 2; ++a)
         sr[((size_t)t * L + x) * 2 + a] = lv.h_rowmap[(size_t)a * L * L + (size_t)t * L + x];
-  SWCHK(upload(h, &h->slicerow, sr.data(), sr.size()));
+  return upload(h, d_slicerow, sr.data(), sr.size());
+}
+
+int sw_set_loop_momenta(sw_engine* h, int nmom, const int32_t* p) {
+  SWCHK(check_hier(h, 0, 0, false));
+  if (nmom < 0 || nmom > SW_MAX_MOMENTA)
+    return sw_fail(h, "%d momenta: at most %d per registration", nmom, SW_MAX_MOMENTA);
+  h->loop_nb = 0;
+  if (nmom == 0) {
+    h->momenta.clear();
+    return 0;
+  }
+  SWCHK(check_momenta(h, "timeslice loops", nmom, p));
+  HIPCHK(hipSetDevice(h->device));
+  SWCHK(stream_sync(h));
+  SWCHK(upload_slice_tables(h, nmom, p, &h->loop_mom, &h->loop_phase, &h->slicerow));
   h->momenta.assign(p, p + nmom);
   return 0;
 }
@@ -4780,6 +4811,135 @@ int sw_hutch_fetch_loops(sw_engine* h, double* out) {
   return fetch_loops(h, h->loop_nb, out);
 }
 
+// ---- one-end-trick two-point functions from timeslice sources ------------------------------------------
+int sw_set_two_point(sw_engine* h, int t0, int nmom, const int32_t* p) {
+  SWCHK(check_hier(h, 0, 0, false));
+  if (nmom < 0 || nmom > SW_MAX_MOMENTA)
+    return sw_fail(h, "%d momenta: at most %d per registration", nmom, SW_MAX_MOMENTA);
+  h->tp_nb = 0;
+  if (nmom == 0) {
+    h->tp_momenta.clear();
+    return 0;
+  }
+  SWCHK(check_momenta(h, "two-point functions", nmom, p));
+  const int L = h->hier[0].lv[0].L;
+  if (t0 < 0 || t0 >= L) return sw_fail(h, "source timeslice %d outside [0,%d)", t0, L);
+  int j0 = -1;
+  for (int j = 0; j < nmom; ++j)
+    if (p[j] == 0) j0 = j;
+  if (j0 < 0) return sw_fail(h, "the two-point momenta have to contain 0 (its solutions are the conjugated factor)");
+  HIPCHK(hipSetDevice(h->device));
+  SWCHK(stream_sync(h));
+  SWCHK(upload_slice_tables(h, nmom, p, &h->tp_mom, &h->tp_phase, &h->tp_slicerow));
+  h->tp_momenta.assign(p, p + nmom);
+  h->tp_t0 = t0;
+  h->tp_j0 = j0;
+  return 0;
+}
+
+// the sources and solutions of a two-point batch: two blocks [n][ncols], ncols = 2 M nq
+static int ensure_two_point_ws(sw_engine* h, size_t cnt) {
+  if (h->tp_ws_cap >= cnt && h->tp_rhs) return 0;
+  SWCHK(dev_realloc(h, &h->tp_rhs, cnt));
+  SWCHK(dev_realloc(h, &h->tp_z, cnt));
+  h->tp_ws_cap = cnt;
+  return 0;
+}
+
+// rhs[row][(2 j + a) nq + k] = the source eta_k^(j,a) of every registered momentum j, spin a and noise k < nb
+static int slice_sources(sw_engine* h, Level& lv, const int8_t* probes, int nb, int nq, cplx* rhs) {
+  const int ncols = 2 * (int)h->tp_momenta.size() * nq;
+  return launch(h, T_TP_SOURCES, swk::k_slice_sources, dim3((lv.n + 15) / 16, ncols / 64), dim3(SW_BLOCK), probes, nb,
+                lv.n, (const int*)lv.rowmap, (const cplx*)h->tp_phase, (const int*)h->tp_mom, lv.L, h->tp_t0, nq,
+                ncols, rhs);
+}
+
+// tp_est[j][a][b][c][d][t][k] from the solutions Z [n][2 M nq]: the p = 0 instantiation for the registered
+// momentum 0, the phased one over the others; total (optional) = sum_t sum_ac T[j0][a][a][c][c][t][k]
+static int pair_dots(sw_engine* h, Level& lv, const cplx* Z, int nq, cplx* total) {
+  const int M = (int)h->tp_momenta.size(), L = lv.L;
+  const int ncols = 2 * M * nq;
+  h->tp_nb = 0;   // tp_est is rewritten: only a completed two-point batch sets it again
+  const size_t need = (size_t)M * 16 * L * nq;
+  if (h->tp_est_cap < need) {
+    SWCHK(dev_realloc(h, &h->tp_est, need));
+    h->tp_est_cap = need;
+  }
+  h->tp_nq = nq;
+  SWCHK(launch(h, T_TP_DOTS, swk::k_slice_pair_dots<false>, dim3(L, nq / 64, 1), dim3(SW_BLOCK), Z,
+               (const int*)h->tp_slicerow, (const cplx*)h->tp_phase, (const int*)h->tp_mom, h->tp_j0, L, nq, ncols,
+               h->tp_est));
+  if (M > 1)
+    SWCHK(launch(h, T_TP_DOTS, swk::k_slice_pair_dots<true>, dim3(L, nq / 64, M - 1), dim3(SW_BLOCK), Z,
+                 (const int*)h->tp_slicerow, (const cplx*)h->tp_phase, (const int*)h->tp_mom, h->tp_j0, L, nq,
+                 ncols, h->tp_est));
+  if (!total) return 0;
+  return launch(h, T_TP_DOTS, swk::k_pair_total, dim3(nq / 64), dim3(SW_BLOCK), (const cplx*)h->tp_est, h->tp_j0, L,
+                nq, total);
+}
+
+static int fetch_two_point(sw_engine* h, int nb, double* out) {
+  const size_t rows = h->tp_momenta.size() * 16 * (size_t)h->hier[0].lv[0].L;
+  HIPCHK(hipMemcpy2D(out, sizeof(cplx) * nb, h->tp_est, sizeof(cplx) * h->tp_nq, sizeof(cplx) * nb, rows,
+                     hipMemcpyDeviceToHost));
+  return 0;
+}
+
+static int two_point_args(sw_engine* h, int nb, const void* in, const void* out) {
+  SWCHK(check_hier(h, 0, 0, false));
+  if (h->tp_momenta.empty()) return sw_fail(h, "no two-point registration (sw_set_two_point)");
+  if (nb <= 0 || !in || !out) return sw_fail(h, "bad arguments");
+  return 0;
+}
+
+// The source kernel alone: out[g][k][n] (reference ordering), g = 2 j + a, from the int8 probes [nb][n].
+int sw_apply_slice_sources(sw_engine* h, int nb, const int8_t* probes, double* out) {
+  SWCHK(two_point_args(h, nb, probes, out));
+  HIPCHK(hipSetDevice(h->device));
+  Level& lv = h->hier[0].lv[0];
+  const int nq = pad64(nb), G = 2 * (int)h->tp_momenta.size();
+  SWCHK(ensure_two_point_ws(h, (size_t)lv.n * G * nq));
+  DevBuf<int8_t> pr(h);
+  SWCHK(upload(h, &pr.p, probes, (size_t)nb * lv.n));
+  SWCHK(slice_sources(h, lv, pr, nb, nq, h->tp_rhs));
+  const size_t per = (size_t)nb * lv.n;
+  SWCHK(ensure_stage(h, per * G * sizeof(cplx)));
+  for (int g = 0; g < G; ++g)
+    SWCHK(launch(h, T_OTHER, swk::k_unpack_c, dim3((lv.n + 63) / 64, nq / 64), dim3(SW_BLOCK),
+                 (const cplx*)(h->tp_rhs + (size_t)g * nq), G * nq, lv.n, (const int*)lv.rowmap,
+                 (cplx*)h->stage + (size_t)g * per, nb));
+  HIPCHK(hipMemcpyAsync(out, h->stage, per * G * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
+  return stream_sync(h);
+}
+
+// The pair-dot kernels alone on host solutions Z[g][k][n] (reference ordering): out[j][a][b][c][d][t][k].
+int sw_apply_pair_dots(sw_engine* h, int nb, const double* Z, double* out) {
+  SWCHK(two_point_args(h, nb, Z, out));
+  HIPCHK(hipSetDevice(h->device));
+  Level& lv = h->hier[0].lv[0];
+  const int nq = pad64(nb), G = 2 * (int)h->tp_momenta.size();
+  SWCHK(ensure_two_point_ws(h, (size_t)lv.n * G * nq));
+  const size_t per = (size_t)nb * lv.n;
+  SWCHK(ensure_stage(h, per * G * sizeof(cplx)));
+  HIPCHK(hipMemcpyAsync(h->stage, Z, per * G * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
+  for (int g = 0; g < G; ++g)
+    SWCHK(launch(h, T_OTHER, swk::k_pack_c, dim3((lv.n + 63) / 64, nq / 64), dim3(SW_BLOCK),
+                 (const cplx*)h->stage + (size_t)g * per, nb, lv.n, (const int*)lv.rowmap,
+                 h->tp_z + (size_t)g * nq, G * nq));
+  SWCHK(pair_dots(h, lv, h->tp_z, nq, nullptr));
+  SWCHK(stream_sync(h));
+  return fetch_two_point(h, nb, out);
+}
+
+int sw_hutch_fetch_two_point(sw_engine* h, double* out) {
+  if (!h) return 1;
+  if (!out) return sw_fail(h, "null output");
+  if (h->tp_nb <= 0 || !h->tp_est) return sw_fail(h, "no two-point batch to fetch");
+  HIPCHK(hipSetDevice(h->device));
+  SWCHK(stream_sync(h));
+  return fetch_two_point(h, h->tp_nb, out);
+}
+
 int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
   SWCHK(check_hier(h, 0, level, true));
   if (h->pb_level != level || h->pb_nb <= 0) return sw_fail(h, "no probes uploaded for level %d", level);
@@ -4792,6 +4952,10 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
     if (level != 0) return sw_fail(h, "timeslice-loop Hutchinson mode runs at level 0");
     if (h->momenta.empty()) return sw_fail(h, "no momenta registered (sw_set_loop_momenta)");
   }
+  if (mode == SW_MODE_TWO_POINT) {
+    if (level != 0) return sw_fail(h, "two-point mode runs at level 0");
+    if (h->tp_momenta.empty()) return sw_fail(h, "no two-point registration (sw_set_two_point)");
+  }
   HIPCHK(hipSetDevice(h->device));
   Hier& H0 = h->hier[0];
   const int nb = h->pb_nb, nbp = h->pb_nbp;
@@ -4803,6 +4967,28 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
     // the slot was (or is being) generated on the generation stream
     HIPCHK(hipStreamWaitEvent(h->stream, h->slots[h->pb_slot].ready, 0));
     h->slots[h->pb_slot].pending = false;
+  }
+  if (mode == SW_MODE_TWO_POINT) {
+    // the 2 M sources of every noise straight from the int8 probes, one solve over all 2 M nq columns (no
+    // deflation), then the reduction that is bilinear in two solution columns; pb_est = the pion total at p = 0
+    const int G = 2 * (int)h->tp_momenta.size(), ncols = G * nbp;
+    SWCHK(ensure_two_point_ws(h, (size_t)n * ncols));
+    SWCHK(slice_sources(h, lv, h->pb_probes, nb, nbp, h->tp_rhs));
+    const int hid = h->hier[h->solver_hid].ready ? h->solver_hid : 0;
+    if (hid != 0 && h->hier[hid].lv[0].n != n) return sw_fail(h, "solver hierarchy level-0 size mismatch");
+    int total = 0;
+    SWCHK(solve_dev(h, hid, 0, h->tp_rhs, h->tp_z, tol, maxiter, ncols, &total));
+    SWCHK(pair_dots(h, lv, h->tp_z, nbp, h->pb_est));
+    SWCHK(stream_sync(h));
+    h->tp_nb = nb;
+    // iterations of a noise = the largest count among its 2 M columns
+    std::vector<int32_t> all;
+    SWCHK(record_iters(h, &h->hier[hid].lv[0].sws, total, all, ncols));
+    h->last_iters_f.assign(nb, 0);
+    for (int g = 0; g < G; ++g)
+      for (int k = 0; k < nb; ++k) h->last_iters_f[k] = std::max(h->last_iters_f[k], all[(size_t)g * nbp + k]);
+    h->last_iters_c.assign(nb, 0);
+    return 0;
   }
   // x0 <- probes
   SWCHK(launch(h, T_OTHER, swk::k_pack_i8, dim3((n + 63) / 64, nbp / 64), dim3(SW_BLOCK), h->pb_probes, nb, n,
@@ -5124,6 +5310,8 @@ int sw_timers(sw_engine* h, double t[8]) {
   t[T_MVM] += h->tacc[T_STENCIL] + h->tacc[T_STENCIL_RES] + h->tacc[T_STENCIL_SM] + h->tacc[T_MFMA_OP] +
               h->tacc[T_MFMA_OP2] + h->tacc[T_SCHUR] + h->tacc[T_SCHUR_OP];
   t[T_COARSEST] += h->tacc[T_MFMA_DENSE];
+  t[T_OTHER] += h->tacc[T_TP_SOURCES];
+  t[T_DOTS] += h->tacc[T_TP_DOTS];
   return 0;
 }
 int sw_timers_reset(sw_engine* h) {

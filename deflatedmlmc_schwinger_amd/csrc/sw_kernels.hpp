@@ -3515,4 +3515,165 @@ __global__ __launch_bounds__(SW_BLOCK) void k_slice_total(const cplx* __restrict
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// One-end-trick two-point functions (SW_MODE_TWO_POINT): per noise k one Z2 / Z4 vector xi_k(y) on the source
+// timeslice t0 gives the 2 M sources eta^(j,a)[idx(a',y,t)] = delta_aa' delta_t,t0 e^{+2 pi i p_j y / L} xi_k(y)
+// (M momenta p_j, spin a), and from their solutions z^(j,a) the spin-resolved pair sums
+//   T[j][a][b][c][d][t][k] = sum_x e^{-2 pi i p_j x / L} conj(z_k^(j0,a)[idx(c,x,t)]) z_k^(j,b)[idx(d,x,t)],
+// j0 = the registered momentum 0.  Sources and solutions live in one block of 2 M nq columns, nq = the noise count
+// padded to 64; group g = 2 j + a owns the columns [g nq, (g + 1) nq).  slicerow and the phase table omega^i =
+// e^{-2 pi i i / L} are those of k_slice_dots.
+// ------------------------------------------------------------------------------------------
+// grid = (ceil(n / 16), 2 M nq / 64); lane = noise.  Each wave writes four rows of its 64 columns: zero, except on
+// the L rows idx(a,y,t0) of group (j, a), which hold xi_k(y) = the code of probe k at idx(0,y,t0) (int8, reference
+// order [probe][n]) times conj(omega^(p_j y mod L)) -- a swap and sign flip of the table entry, so the source is
+// the table's value exactly; p_j = 0 takes no table entry.  Columns of padded noises (k >= nb) stay exactly zero.
+__global__ __launch_bounds__(SW_BLOCK) void k_slice_sources(const int8_t* __restrict__ probes, int nb, int n,
+                                                            const int* __restrict__ rowmap,
+                                                            const cplx* __restrict__ phase,
+                                                            const int* __restrict__ mom, int L, int t0, int nq,
+                                                            int ncols, cplx* __restrict__ out) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int c0 = blockIdx.y * 64;
+  const int g = c0 / nq, k = c0 - g * nq + lane;
+  const int p = mom[g >> 1], a = g & 1;
+  const int first = a * L * L + t0 * L;         // idx(a, 0, t0)
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int i = blockIdx.x * 16 + wave * 4 + r;
+    if (i >= n) return;
+    cplx v = cmake(0.0, 0.0);
+    const int y = i - first;
+    if (y >= 0 && y < L && k < nb) {
+      const int c = (int)probes[(size_t)k * n + (size_t)t0 * L + y];
+      cplx w = cmake(1.0, 0.0);
+      if (p != 0) {
+        const cplx e = phase[(p * y) % L];
+        w = cmake(e.x, -e.y);
+      }
+      const bool rot = (c & 1) == 0;            // +-2 = +-i: i w = (-w.y, w.x)
+      const double ur = rot ? -w.y : w.x;
+      const double ui = rot ? w.x : w.y;
+      v = c < 0 ? cmake(-ur, -ui) : cmake(ur, ui);
+    }
+    const size_t row = rowmap ? (size_t)rowmap[i] : (size_t)i;
+    out[row * ncols + c0 + lane] = v;
+  }
+}
+
+// grid = (L timeslices, nq / 64, momenta of the launch); lane = noise.  One workgroup owns one (t, noise group, j)
+// completely: its four waves take the sites x = wave, wave + 4, ...; per site a lane reads the four values
+// u[a][c] = z^(j0,a)_c and the four values v[b][d] = z^(j,b)_d (16 bytes each), forms the 16 products conj(u) v
+// and multiplies them by the phase omega^(p_j x mod L) from the L-entry table staged in LDS (the index is the same
+// in all lanes: a broadcast read; it advances by 4 p_j mod L per step, no division in the loop), into 16 complex
+// accumulators held in registers.  PHASE = false serves j = j0 (p = 0): no table, no multiply, and v = u is read
+// once; it runs with grid.z = 1.  PHASE = true runs with grid.z = M - 1 over the other momenta (blockIdx.z skips
+// j0).  The waves combine through LDS in a fixed order (w0 + w1 + w2 + w3, one wave's block at a time) and wave 0
+// writes out[((j * 16 + a * 8 + b * 4 + c * 2 + d) * L + t) * nq + k]: no partials, no atomics.  A padded noise
+// column (zero solutions) only ever touches its own lane's sums.
+template <bool PHASE>
+__global__ __launch_bounds__(SW_BLOCK) void k_slice_pair_dots(const cplx* __restrict__ Z,
+                                                              const int* __restrict__ slicerow,
+                                                              const cplx* __restrict__ phase,
+                                                              const int* __restrict__ mom, int j0, int L, int nq,
+                                                              int ncols, cplx* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) cplx tab[PHASE ? SW_SHIFT_MAX_L : 1];
+  __shared__ __attribute__((aligned(16))) cplx red[16][64];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int t = blockIdx.x;
+  const int k = blockIdx.y * 64 + lane;
+  const int j = PHASE ? (int)blockIdx.z + ((int)blockIdx.z >= j0 ? 1 : 0) : j0;
+  int idx = 0, step = 0;
+  if constexpr (PHASE) {
+    for (int i = threadIdx.x; i < L; i += SW_BLOCK) tab[i] = phase[i];
+    const int p = mom[j];                     // in [0, L), L <= 1024: the products below stay far inside int
+    idx = (p * wave) % L;
+    step = (p * SW_WAVES_PER_BLOCK) % L;
+    __syncthreads();
+  }
+  double ar[16], ai[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) ar[i] = ai[i] = 0.0;
+  const int* __restrict__ sr = slicerow + (size_t)t * L * 2;
+  const size_t cu = (size_t)(2 * j0) * nq + k, cv = (size_t)(2 * j) * nq + k;
+  for (int x = wave; x < L; x += SW_WAVES_PER_BLOCK) {
+    const size_t r0 = (size_t)sr[2 * x] * ncols, r1 = (size_t)sr[2 * x + 1] * ncols;
+    cplx u[4], v[4];                          // [group a or b][spin c or d]
+    u[0] = Z[r0 + cu];
+    u[1] = Z[r1 + cu];
+    u[2] = Z[r0 + cu + nq];
+    u[3] = Z[r1 + cu + nq];
+    if constexpr (PHASE) {
+      const cplx w = tab[idx];
+      idx += step;
+      idx = idx >= L ? idx - L : idx;
+      const cplx s[4] = {Z[r0 + cv], Z[r1 + cv], Z[r0 + cv + nq], Z[r1 + cv + nq]};
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[q] = cmake(w.x * s[q].x - w.y * s[q].y, w.x * s[q].y + w.y * s[q].x);
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[q] = u[q];
+    }
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+          for (int d = 0; d < 2; ++d) {
+            const cplx uu = u[a * 2 + c], vv = v[b * 2 + d];
+            const int i = a * 8 + b * 4 + c * 2 + d;
+            ar[i] += uu.x * vv.x + uu.y * vv.y;
+            ai[i] += uu.x * vv.y - uu.y * vv.x;
+          }
+  }
+  for (int w = 1; w < SW_WAVES_PER_BLOCK; ++w) {
+    __syncthreads();                          // wave 0 has taken the previous wave's block
+    if (wave == w) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) red[i][lane] = cmake(ar[i], ai[i]);
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const cplx q = red[i][lane];
+        ar[i] += q.x;
+        ai[i] += q.y;
+      }
+    }
+  }
+  if (wave == 0) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) out[((size_t)(j * 16 + i) * L + t) * nq + k] = cmake(ar[i], ai[i]);
+  }
+}
+
+// est[k] = sum_t sum_{a,c} T[j0][a][a][c][c][t][k] of k_slice_pair_dots' output: the pion two-point function at
+// p = 0 summed over the timeslices, sum_a ||z^(j0,a)||^2.  grid = (nq / 64); the four waves take t = wave, wave + 4,
+// ... and combine through LDS in a fixed order (deterministic).
+__global__ __launch_bounds__(SW_BLOCK) void k_pair_total(const cplx* __restrict__ T, int j0, int L, int nq,
+                                                         cplx* __restrict__ est) {
+  __shared__ cplx red[3][64];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const size_t col = (size_t)blockIdx.x * 64 + lane;
+  const cplx* __restrict__ base = T + (size_t)j0 * 16 * L * nq + col;
+  cplx s = cmake(0.0, 0.0);
+  for (int t = wave; t < L; t += SW_WAVES_PER_BLOCK) {
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int c = 0; c < 2; ++c) s = cadd(s, base[((size_t)(a * 12 + c * 3) * L + t) * nq]);   // b = a, d = c
+  }
+  if (wave > 0) red[wave - 1][lane] = s;
+  __syncthreads();
+  if (wave == 0) {
+    s = cadd(s, red[0][lane]);
+    s = cadd(s, red[1][lane]);
+    s = cadd(s, red[2][lane]);
+    est[col] = s;
+  }
+}
+
 }  // namespace swk

@@ -21,6 +21,9 @@ MODE_MLMC_SKIP = 2
 MODE_LEVEL = 3
 MODE_HUTCHINSON_SHIFTS = 4
 MODE_HUTCHINSON_LOOPS = 5
+MODE_TWO_POINT = 6
+KCLASS_TP_SOURCES = 17     # sw_kernel_stats classes of the two-point kernels
+KCLASS_TP_DOTS = 18
 MAX_SHIFTS = 128
 MAX_MOMENTA = 8
 PROBES_Z2 = 1
@@ -160,6 +163,10 @@ def load_library():
     sig("sw_set_loop_momenta", i32, vp, i32, vp)
     sig("sw_hutch_fetch_loops", i32, vp, vp)
     sig("sw_apply_slice_dots", i32, vp, i32, vp, vp, vp)
+    sig("sw_set_two_point", i32, vp, i32, i32, vp)
+    sig("sw_hutch_fetch_two_point", i32, vp, vp)
+    sig("sw_apply_slice_sources", i32, vp, i32, vp, vp)
+    sig("sw_apply_pair_dots", i32, vp, i32, vp, vp)
     _lib = lib
     return lib
 
@@ -182,6 +189,7 @@ EXPORTED_SYMBOLS = (
     "sw_probes_stream_set", "sw_probes_generate", "sw_probes_fetch",
     "sw_set_shifts", "sw_hutch_fetch_shifts", "sw_apply_shift_dots",
     "sw_set_loop_momenta", "sw_hutch_fetch_loops", "sw_apply_slice_dots",
+    "sw_set_two_point", "sw_hutch_fetch_two_point", "sw_apply_slice_sources", "sw_apply_pair_dots",
 )
 
 
@@ -643,6 +651,53 @@ class Engine:
         out = np.zeros(self._loop_shape(p.shape[0]), dtype=np.complex128)
         self._chk(self._lib.sw_apply_slice_dots(self._h, p.shape[0], _ptr(p), _ptr(Z2), _ptr(out)),
                   "sw_apply_slice_dots")
+        return np.ascontiguousarray(np.moveaxis(out, -1, 0))
+
+    def set_two_point(self, t0, momenta):
+        """Source timeslice and momenta of MODE_TWO_POINT (None or an empty list clears)."""
+        m = np.ascontiguousarray([] if momenta is None else momenta, dtype=np.int32)
+        self._chk(self._lib.sw_set_two_point(self._h, int(t0), m.size, _ptr(m) if m.size else None),
+                  "sw_set_two_point")
+        self._tp_nmom = int(m.size)
+
+    def _two_point_shape(self, nb):
+        n = self._n(0, 0)
+        L = int(round((n // 2) ** 0.5))
+        return (getattr(self, "_tp_nmom", 0), 2, 2, 2, 2, L, nb)
+
+    def hutch_batch_two_point(self, level, probes, tol, maxiter=1000):
+        """One MODE_TWO_POINT batch, the probes being the noises: (T[nb, nmom, 2, 2, 2, 2, L], iters_fine[nb],
+        iters_coarse[nb]); iters_fine[k] is the largest count among the 2 nmom solves of noise k."""
+        _, itf, itc = self.hutch_batch(MODE_TWO_POINT, level, probes, tol, maxiter)
+        self._nb_uploaded = itf.size
+        return self.hutch_fetch_two_point(), itf, itc
+
+    def hutch_fetch_two_point(self):
+        """Pair sums of the last MODE_TWO_POINT batch, shape (nb, nmom, 2, 2, 2, 2, L): T[k, j, a, b, c, d, t]."""
+        out = np.zeros(self._two_point_shape(getattr(self, "_nb_uploaded", 0)), dtype=np.complex128)
+        self._chk(self._lib.sw_hutch_fetch_two_point(self._h, _ptr(out)), "sw_hutch_fetch_two_point")
+        return np.ascontiguousarray(np.moveaxis(out, -1, 0))
+
+    def apply_slice_sources(self, probes):
+        """The source kernel alone: out[2 j + a, k, :] = the source of momentum j, spin a and noise k of the
+        registration, reference ordering; probes int8 (nb, n) codes."""
+        p = self._probes(probes)
+        if p.shape[1] != self._n(0, 0):
+            raise EngineError("probes of length %d, expected %d" % (p.shape[1], self._n(0, 0)))
+        out = np.zeros((2 * getattr(self, "_tp_nmom", 0),) + p.shape, dtype=np.complex128)
+        self._chk(self._lib.sw_apply_slice_sources(self._h, p.shape[0], _ptr(p), _ptr(out)),
+                  "sw_apply_slice_sources")
+        return out
+
+    def apply_pair_dots(self, Z):
+        """The pair-dot kernels alone: Z complex (2 nmom, nb, n) in the layout of apply_slice_sources; returns
+        T[k, j, a, b, c, d, t]."""
+        Z = _c128(Z)
+        if Z.ndim != 3 or Z.shape[0] != 2 * getattr(self, "_tp_nmom", 0) or Z.shape[2] != self._n(0, 0):
+            raise EngineError("Z of shape %s, expected (%d, nb, %d)"
+                              % (Z.shape, 2 * getattr(self, "_tp_nmom", 0), self._n(0, 0)))
+        out = np.zeros(self._two_point_shape(Z.shape[1]), dtype=np.complex128)
+        self._chk(self._lib.sw_apply_pair_dots(self._h, Z.shape[1], _ptr(Z), _ptr(out)), "sw_apply_pair_dots")
         return np.ascontiguousarray(np.moveaxis(out, -1, 0))
 
     def probes_upload(self, level, probes):

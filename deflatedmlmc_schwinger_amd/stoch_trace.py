@@ -20,7 +20,8 @@ from .multigrid import MG
 from .utils import (_engines, deflation_pre_computations, displacements_of, draw_probes, flopsV_manual,
                     loops_of, mlmc_defl_setup_of, probe_batch, probe_batch_generated, probe_batch_loops,
                     probe_batch_loops_generated, probe_batch_shifts, probe_batch_shifts_generated,
-                    register_loop_momenta, register_shifts)
+                    probe_batch_two_point, probe_batch_two_point_generated, register_loop_momenta, register_shifts,
+                    register_two_point, two_point_of)
 
 DEFAULT_BATCH = 256
 NR_ROUGH_PROBES = 5
@@ -226,6 +227,34 @@ class DeviceLoopProbes:
         return loop_columns(e, self.zero), f, c
 
 
+def two_point_columns(T, zero):
+    """The columns of the two-point estimator for run_probe_loop_displaced: T[k][j][a][b][c][d][t] flattened per
+    noise, plus one control column, the pion total sum_t sum_ac T[zero][a][a][c][c][t] = sum_a ||z^(0,a)||^2 of
+    momentum index `zero` (p = 0), which is real and positive."""
+    T = np.asarray(T, dtype=np.complex128)
+    total = sum(np.sum(T[:, zero, a, a, c, c, :], axis=1) for a in range(2) for c in range(2))
+    return np.concatenate([T.reshape(T.shape[0], -1), total[:, None]], axis=1)
+
+
+class DeviceTwoPointProbes:
+    """Noise source of the two-point flow: as :class:`DeviceLoopProbes`; one row of two_point_columns per noise."""
+
+    def __init__(self, mg_solver, params, zero, kind="z2"):
+        self.mg_solver = mg_solver
+        self.params = params
+        self.zero = zero
+        self.kind = kind
+
+    def begin(self, entry_stream):
+        window = entry_stream.window()
+        for eng in _engines(self.mg_solver):
+            eng.stream_set(window)
+
+    def __call__(self, first_probe, count):
+        e, f, c = probe_batch_two_point_generated(self.mg_solver, self.params, first_probe, count, self.kind)
+        return two_point_columns(e, self.zero), f, c
+
+
 def run_probe_loop_displaced(evaluate, n, level_tols, control, max_nr_ests, batch, comm=None, min_index=5,
                              probe_type="z2"):
     """The probe loop of :func:`run_probe_loop` for estimators that return one value per displacement:
@@ -318,6 +347,8 @@ def _rough_trace(mg_solver, params, n, Vx_rank, tr1):
 
 # compute tr(A^{-1}) via (deflated) Hutchinson                      stoch_trace.py:33-179
 def hutchinson(A, params):
+    if two_point_of(params) is not None:
+        raise Exception("source_timeslice belongs to two_point(), not to hutchinson()")
     momenta = loops_of(params)
     if momenta is not None:
         return _hutchinson_loops(A, params, momenta)
@@ -536,7 +567,80 @@ def _hutchinson_loops(A, params, momenta):
 
 
 # compute tr(A^{-1}) via multigrid multilevel Monte Carlo          stoch_trace.py:185-471
+def two_point(A, params):
+    """Connected meson two-point functions by the one-end trick.  The build-only keys
+    source_timeslice = t0 and two_point_momenta = [p_0, ...] (default [0]; it has to contain 0) select the sources:
+    per noise k one Z2 / Z4 vector xi_k(y) on the timeslice t0 -- the code of probe k of the usual stream at
+    idx(0, y, t0) -- is solved for at both spins and every momentum, 2 M solves without deflation, and
+
+        T_k[j][a][b][c][d][t] = sum_x e^{-2 pi i p_j x / L} conj(z_k^(0,a)[idx(c,x,t)]) z_k^(j,b)[idx(d,x,t)]
+
+    averages to sum_{x,y} e^{-2 pi i p_j (x - y) / L} conj(A^-1[idx(c,x,t), idx(a,y,t0)]) A^-1[idx(d,x,t),
+    idx(b,y,t0)]; utils.meson_correlator contracts it into any of the 16 channels.  No fermion-loop sign is
+    applied.  The columns of the probe loop are the flattened T plus one control column, the pion total
+    sum_t C_pi(t, 0), which is real and positive, and the stopping rule runs on it alone.  `batch` counts noises;
+    the solve is 2 M batch columns wide.
+
+    Returns two_point (the mean, [p][a][b][c][d][t]), two_point_devs, two_point_ests (per noise), converged,
+    momenta, source_timeslice, nr_ests, function_iters (a noise counts the largest iteration number among its
+    2 M solves), ests (the control series), probe_loop_s and probes_solved."""
+    sel = two_point_of(params)
+    if sel is None:
+        raise Exception("two_point() needs the key source_timeslice")
+    t0, momenta = sel
+    if _dist.default_comm().world > 1:
+        raise Exception("two-point functions (source_timeslice) run on one rank")
+    mg_solver, nr_levels = _setup_solver(A, params, defer_coarse=True)
+    N = A.shape[0]
+    L = int(params['latt_dims'][0])
+    batch = int(params.get('batch', DEFAULT_BATCH))
+    kind = params.get('probe_type', 'z2')
+    zero = momenta.index(0)
+    shape = (len(momenta), 2, 2, 2, 2, L)
+    register_two_point(mg_solver, t0, momenta)
+
+    print("\nComputing rough estimation of the two-point functions ...", end='', flush=True)
+    np.random.seed(123456)                                      # stoch_trace.py:103-115
+    t0_s = time.time()
+    e, _, _ = probe_batch_two_point(mg_solver, params, draw_probes(NR_ROUGH_PROBES, N, kind))
+    rough = np.sum(two_point_columns(e, zero), axis=0) / NR_ROUGH_PROBES
+    level_tols = np.abs(params['tol'] * rough)
+    control = rough.size - 1
+    print(" done. Time : " + str(time.time() - t0_s) + " seconds")
+
+    print("\nResetting timer to zero ...", end='')
+    mg_solver.timer.reset()
+    mg_solver.engine.timers_reset()
+    print(" done")
+    print("\nComputing the two-point functions stochastically ...", end='', flush=True)
+    t0_s = time.time()
+    loop = run_probe_loop_displaced(DeviceTwoPointProbes(mg_solver, params, zero, kind), N, level_tols, control,
+                                    params['max_nr_ests'], batch * max(1, len(_engines(mg_solver))),
+                                    probe_type=kind)
+    loop_s = time.time() - t0_s
+    print(" done. Time : " + str(loop_s) + " seconds")
+
+    mg_solver.finish_setup()
+    result = dict()
+    result['two_point'] = loop["avgs"][:control].reshape(shape)
+    result['two_point_devs'] = loop["devs"][:control].reshape(shape)
+    result['two_point_ests'] = loop["ests"][:, :control].reshape((-1,) + shape)
+    result['converged'] = loop["converged"][:control].reshape(shape)
+    result['momenta'] = list(momenta)
+    result['source_timeslice'] = t0
+    result['nr_ests'] = loop["index"]
+    result['function_iters'] = int(np.sum(loop["iters_fine"]))
+    result['ests'] = loop["ests"][:, control]       # (nr_ests + 1,): sum_t C_pi(t, 0) per noise
+    result['probe_loop_s'] = loop_s
+    result['probes_solved'] = loop["solved"]
+    mg_solver.sync_timer()
+    print(mg_solver.timer)
+    return result
+
+
 def mlmc(A, params):
+    if two_point_of(params) is not None:
+        raise Exception("source_timeslice belongs to two_point(), not to mlmc()")
     if loops_of(params) is not None:
         raise Exception("timeslice_loops is implemented for hutchinson() only: the MLMC coarse terms need a "
                         "timeslice projection per level")

@@ -8,7 +8,7 @@ from scipy.sparse.linalg import eigsh
 
 from . import dist as _dist
 from .engine import (MAX_MOMENTA, MAX_SHIFTS, MODE_HUTCHINSON, MODE_HUTCHINSON_LOOPS, MODE_HUTCHINSON_SHIFTS,
-                     MODE_LEVEL, MODE_MLMC, MODE_MLMC_SKIP, EngineError)
+                     MODE_LEVEL, MODE_MLMC, MODE_MLMC_SKIP, MODE_TWO_POINT, EngineError)
 
 
 # ----------------------------------------------------------------------------------------
@@ -64,7 +64,7 @@ _BUILD_KEYS = ('batch', 'device', 'engines', 'cache_dir', 'report_path', 'probe_
                'solver_restart', 'stochastic_coarsest', 'stop_factor', 'ref_direct_max_n', 'ref_coarsest',
                'ref_coarse_dofs', 'setup_eigs', 'defer_coarse_levels',
                'verbose', 'probe_rounds_max', 'mlmc_defl_setup', 'defl_setup', 'x_displacements',
-               'timeslice_loops')
+               'timeslice_loops', 'source_timeslice', 'two_point_momenta')
 # where the eigenpairs of the MLMC difference operators come from: host ARPACK (the reference's path) or
 # the block eigensolver on the GPU (setup_gpu.device_diff_eigenpairs)
 MLMC_DEFL_SETUPS = ("host", "device")
@@ -217,6 +217,111 @@ def loop_correlator(per_probe_a, per_probe_b):
     for D in range(L):
         ar = np.roll(a, -D, axis=1)                        # ar[k, t] = a[k, t + D]
         out[D] = np.sum(np.roll(Sa, -D) * Sb - np.sum(ar * b, axis=0)) / (N * (N - 1.0) * L)
+    return out
+
+
+def two_point_of(params):
+    """The build-only keys of two_point(): None when source_timeslice is absent, else (t0, momenta) after
+    validation -- t0 an integer in [0, L), L = latt_dims[0]; two_point_momenta ([0] when absent) a list of at most
+    MAX_MOMENTA different integers in [0, L) that contains 0 (its solutions are the conjugated factor of every
+    momentum).  The keys combine with neither x_displacements nor timeslice_loops."""
+    has = hasattr(params, "get")
+    if not has or params.get('source_timeslice') is None:
+        if has and params.get('two_point_momenta') is not None:
+            raise Exception("two_point_momenta needs source_timeslice")
+        return None
+    if params.get('x_displacements') is not None:
+        raise Exception("source_timeslice does not combine with x_displacements")
+    if params.get('timeslice_loops') is not None:
+        raise Exception("source_timeslice does not combine with timeslice_loops")
+    L = int(params['latt_dims'][0])
+    t0 = params['source_timeslice']
+    if isinstance(t0, bool) or int(t0) != t0:
+        raise Exception("source_timeslice: %r is not an integer" % (t0,))
+    t0 = int(t0)
+    if not 0 <= t0 < L:
+        raise Exception("source_timeslice: %d outside [0, %d)" % (t0, L))
+    given = params.get('two_point_momenta')
+    momenta = []
+    for p in ([0] if given is None else given):
+        if int(p) != p:
+            raise Exception("two_point_momenta: %r is not an integer" % (p,))
+        p = int(p)
+        if not 0 <= p < L:
+            raise Exception("two_point_momenta: momentum %d outside [0, %d)" % (p, L))
+        if p in momenta:
+            raise Exception("two_point_momenta: momentum %d listed twice" % p)
+        momenta.append(p)
+    if len(momenta) > MAX_MOMENTA:
+        raise Exception("two_point_momenta: %d momenta, at most %d" % (len(momenta), MAX_MOMENTA))
+    if 0 not in momenta:
+        raise Exception("two_point_momenta has to contain the momentum 0")
+    return t0, momenta
+
+
+def _phase_table(L):
+    """omega^j = e^{-2 pi i j / L}, j in [0, L), exact at the multiples of a quarter turn (as the engine's table)."""
+    j = np.arange(L)
+    tab = np.exp(-2j * np.pi * j / L)
+    quarter = (4 * j) % L == 0
+    tab[quarter] = np.array([1, -1j, -1, 1j])[(4 * j[quarter]) // L]
+    return tab
+
+
+def slice_sources(probes, L, t0, momenta):
+    """The one-end-trick sources of two_point(): out[2 j + a, k, idx(a', y, t)] = delta_aa' delta_{t,t0}
+    e^{+2 pi i p_j y / L} xi_k(y) with xi_k(y) = the code of probe k at idx(0, y, t0) -- the same noise for both
+    spins and all momenta; idx(s,x,y) = s L^2 + y L + x.  probes: int8 codes (nb, 2 L^2)."""
+    probes = np.asarray(probes)
+    if probes.ndim != 2 or probes.shape[1] != 2 * L * L:
+        raise Exception("slice_sources: probes of shape %s, expected (nb, %d)" % (probes.shape, 2 * L * L))
+    xi = probes_as_complex(probes[:, t0 * L:(t0 + 1) * L])                # [k][y]
+    tab = _phase_table(L)
+    out = np.zeros((2 * len(momenta),) + probes.shape, dtype=np.complex128)
+    for j, p in enumerate(momenta):
+        ph = np.conj(tab[(int(p) * np.arange(L)) % L])
+        for a in range(2):
+            first = a * L * L + t0 * L
+            out[2 * j + a][:, first:first + L] = xi * ph[None, :]
+    return out
+
+
+def pair_dots(Z, L, momenta):
+    """T[k, j, a, b, c, d, t] = sum_x e^{-2 pi i p_j x / L} conj(Z[2 j0 + a, k, idx(c,x,t)]) Z[2 j + b, k, idx(d,x,t)]
+    with j0 = the index of momentum 0: the reduction of two_point() on solutions Z of shape (2 M, nb, 2 L^2) in
+    the layout of slice_sources."""
+    Z = np.asarray(Z, dtype=np.complex128)
+    M = len(momenta)
+    if Z.ndim != 3 or Z.shape[0] != 2 * M or Z.shape[2] != 2 * L * L:
+        raise Exception("pair_dots: Z of shape %s, expected (%d, nb, %d)" % (Z.shape, 2 * M, 2 * L * L))
+    j0 = [int(p) for p in momenta].index(0)
+    Zr = Z.reshape(M, 2, Z.shape[1], 2, L, L)                             # [j][a][k][c][t][x]
+    tab = _phase_table(L)
+    ph = tab[np.outer(np.asarray(momenta, dtype=np.int64), np.arange(L)) % L]
+    return np.einsum('jx,akctx,jbkdtx->kjabcdt', ph, Zr[j0].conj(), Zr)
+
+
+def meson_correlator(T, sink, source):
+    """C(t, p_j) = sum_abcd Gamma[c][d] Gamma'[b][a] g_a g_c T[..., a, b, c, d, t], Gamma = `sink`, Gamma' = `source`
+    out of '1', 'g3', 's1', 's2' and g = (+1, -1) the diagonal of gamma_3: the connected two-point function
+    sum_{x,y} e^{-2 pi i p (x - y) / L} tr[Gamma A^-1(x,t; y,t0) Gamma' A^-1(y,t0; x,t)] from the spin-resolved pair
+    sums of two_point() (T of shape (..., 2, 2, 2, 2, L); the result keeps the leading axes and t).  gamma_3
+    Hermiticity, A^-1 = gamma_3 A^-H gamma_3, supplies the backward propagator.  No fermion-loop sign is applied."""
+    for which in (sink, source):
+        if which not in _PAULI:
+            raise Exception("meson_correlator: unknown spin matrix %r (one of %s)" % (which, sorted(_PAULI)))
+    T = np.asarray(T)
+    if T.ndim < 5 or T.shape[-5:-1] != (2, 2, 2, 2):
+        raise Exception("meson_correlator: T of shape %s, expected (..., 2, 2, 2, 2, L)" % (T.shape,))
+    G, Gp, g = _PAULI[sink], _PAULI[source], (1.0, -1.0)
+    out = np.zeros(T.shape[:-5] + T.shape[-1:], dtype=np.complex128)
+    for a in range(2):
+        for b in range(2):
+            for c in range(2):
+                for d in range(2):
+                    w = G[c, d] * Gp[b, a] * g[a] * g[c]
+                    if w != 0:
+                        out = out + w * T[..., a, b, c, d, :]
     return out
 
 
@@ -580,6 +685,46 @@ def probe_batch_loops_generated(mg_solver, params, first_probe, count, kind="z2"
         eng.hutch_run(MODE_HUTCHINSON_LOOPS, 0, tol, maxiter)
         _, itf, itc = eng.hutch_fetch()
         return eng.hutch_fetch_loops(), itf, itc
+
+    if len(active) == 1:
+        res = [run(active[0])]
+    else:
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=len(active)) as pool:
+            res = list(pool.map(run, active))
+    return tuple(np.concatenate([r[k] for r in res]) for k in range(3))
+
+
+def register_two_point(mg_solver, t0, momenta):
+    """Hand the source timeslice and momenta of two_point() to every engine handle (momenta None clears)."""
+    for eng in _engines(mg_solver):
+        eng.set_two_point(t0, momenta)
+
+
+def probe_batch_two_point(mg_solver, params, probes):
+    """One batch of noises through MODE_TWO_POINT: (T[nb, nmom, 2, 2, 2, 2, L], iters_fine, iters_coarse) -- 2 nmom
+    solves per noise, no deflation; iters_fine is the largest count among a noise's solves."""
+    engs, tol, _, maxiter = _shift_batch_args(mg_solver, params)
+    return engs[0].hutch_batch_two_point(0, np.asarray(probes), tol, maxiter)
+
+
+def probe_batch_two_point_generated(mg_solver, params, first_probe, count, kind="z2"):
+    """probe_batch_two_point for the noises [first_probe, first_probe + count) of the stream the engines hold
+    (Engine.stream_set), generated on the device; several engine handles share the batch as in
+    probe_batch_generated."""
+    engs, tol, n, maxiter = _shift_batch_args(mg_solver, params)
+    ne = len(engs) if count >= 2 * 64 else 1
+    bounds = [(k * count) // ne for k in range(ne + 1)]
+    active = [k for k in range(ne) if bounds[k + 1] > bounds[k]]
+    for k in active:
+        engs[k].probes_generate(0, 0, bounds[k + 1] - bounds[k], (first_probe + bounds[k]) * n, kind)
+
+    def run(k):
+        eng = engs[k]
+        eng.probes_select(0)
+        eng.hutch_run(MODE_TWO_POINT, 0, tol, maxiter)
+        _, itf, itc = eng.hutch_fetch()
+        return eng.hutch_fetch_two_point(), itf, itc
 
     if len(active) == 1:
         res = [run(active[0])]

@@ -223,6 +223,10 @@ int sw_set_shifts(sw_engine* h, int nshifts, const int64_t* shifts);
  * e^{-2 pi i p x / L}).  Lattice level 0 only (sw_set_lattice); every p in [0, L), no duplicates, at most
  * SW_MAX_MOMENTA; nmom = 0 clears. */
 int sw_set_loop_momenta(sw_engine* h, int nmom, const int32_t* p);
+/* Source timeslice t0 and spatial momenta p_j of SW_MODE_TWO_POINT (build-only: one-end-trick meson two-point
+ * functions).  A registration of its own, independent of sw_set_loop_momenta; the same checks, plus 0 <= t0 < L
+ * and 0 among the momenta (its solutions are the conjugated factor of every momentum); nmom = 0 clears. */
+int sw_set_two_point(sw_engine* h, int t0, int nmom, const int32_t* p);
 /* Outer flexible-GMRES restart length (<= SW_MAX_KRYLOV) and the hierarchy used to
  * precondition level-0 solves (0 or 1). */
 int sw_set_solver(sw_engine* h, int restart, int solver_hid);
@@ -301,6 +305,15 @@ int sw_apply_shift_dots(sw_engine* h, int nb, const int8_t* probes, const double
  * conj(x_k[idx(a,x,t)]) Z_k[idx(b,x,t)] for the registered momenta, idx(s,x,y) = s L^2 + y L + x; probes
  * int8[nb*n] (codes +-1, +-2 = +-i), Z complex128[nb*n], out complex128[nmom*2*2*L*nb]. */
 int sw_apply_slice_dots(sw_engine* h, int nb, const int8_t* probes, const double* Z, double* out);
+/* The source kernel of SW_MODE_TWO_POINT alone: out[2 j + a][k][i] = the source eta_k^(j,a) of the registration
+ * (sw_set_two_point) in the reference ordering, delta_{a,a'} delta_{t,t0} e^{+2 pi i p_j y / L} xi_k(y) at
+ * i = idx(a',y,t), xi_k(y) = the code of probe k at idx(0,y,t0); probes int8[nb*n], out complex128[2*nmom*nb*n]. */
+int sw_apply_slice_sources(sw_engine* h, int nb, const int8_t* probes, double* out);
+/* The pair-dot kernels of SW_MODE_TWO_POINT alone on host solutions: Z complex128[2*nmom][nb][n] in the layout of
+ * sw_apply_slice_sources' output, out complex128[nmom][2][2][2][2][L][nb], out[j][a][b][c][d][t][k] =
+ * sum_x e^{-2 pi i p_j x / L} conj(Z[2 j0 + a][k][idx(c,x,t)]) Z[2 j + b][k][idx(d,x,t)], j0 = the registered
+ * momentum 0. */
+int sw_apply_pair_dots(sw_engine* h, int nb, const double* Z, double* out);
 /* X = one multigrid cycle applied to B starting at level0 (MG.one_mg_step, multigrid.py:369-447). */
 int sw_vcycle(sw_engine* h, int hid, int level0, int nb, const double* B, double* X);
 /* Solve A_level0 X = B to ||r|| < tol*||b|| per right-hand side (MG.solve -> pyamg fgmres,
@@ -328,6 +341,13 @@ int sw_solve(sw_engine* h, int hid, int level0, int nb, const double* B, double*
                                   sw_hutch_fetch returns sum_t (l[0][0][t] + l[1][1][t]) of the FIRST
                                   registered momentum, which is x^H z -- the shift-0 value of
                                   HUTCHINSON_SHIFTS -- only when that momentum is 0 */
+#define SW_MODE_TWO_POINT 6     /* T_k[j][a][b][c][d][t] = sum_x e^{-2 pi i p_j x / L} conj(z_k^(j0,a)[idx(c,x,t)])
+                                  z_k^(j,b)[idx(d,x,t)], z_k^(j,a) = A^-1 eta_k^(j,a), for the source timeslice
+                                  and momenta of sw_set_two_point, level 0 (build-only; no deflation, no
+                                  permutation).  The probes are the noises: probe k's code at idx(0,y,t0) is
+                                  xi_k(y); one solve runs over all 2 nmom pad64(nb) columns.  sw_hutch_fetch
+                                  returns sum_t sum_ac T[j0][a][a][c][c][t] = sum_a ||z^(j0,a)||^2 and, as the
+                                  fine iteration count of a noise, the largest count among its 2 nmom columns. */
 /* One batch of probes x_k in {-1,+1}^n (int8, nb*n, reference ordering) at `level`
  * (build-only extension: entries +-2 encode +-i, i.e. Z4 probes {1,i,-1,-i}):
  *   HUTCHINSON: e_k = x^H A^-1 Pperm^T (x - U U^H x)
@@ -366,6 +386,10 @@ int sw_hutch_fetch_shifts(sw_engine* h, double* ests);
  * probe k of the batch (sw_hutch_fetch returns the scalar total of the first momentum and the iteration
  * counts). */
 int sw_hutch_fetch_loops(sw_engine* h, double* out);
+/* After a SW_MODE_TWO_POINT batch: out complex128[nmom][2][2][2][2][L][nb], the pair sums T_k[j][a][b][c][d][t] of
+ * every noise k of the batch.  The results of the modes 4, 5 and 6 live in buffers of their own: each fetch
+ * returns its own mode's last batch whatever ran since. */
+int sw_hutch_fetch_two_point(sw_engine* h, double* out);
 
 /* ---- multi-GPU: the one collective of the path ------------------------------------ */
 /* One process per GPU, one engine per process; the probe loop shards by probe and needs a single
@@ -399,6 +423,8 @@ int sw_timers_reset(sw_engine* h);
 /* (class 13: unused; it was a fused two-step stencil, removed after it measured no faster) */
 #define SW_KCLASS_MFMA_OP2 14       /* k_bsr_mfma, level operators below level 1   */
 #define SW_KCLASS_SCHUR 15          /* k_schur_step / k_eo_hop, even-odd smoother  */
+#define SW_KCLASS_TP_SOURCES 17     /* k_slice_sources (SW_MODE_TWO_POINT); in sw_timers: other */
+#define SW_KCLASS_TP_DOTS 18        /* k_slice_pair_dots, k_pair_total (SW_MODE_TWO_POINT); in sw_timers: dots */
 int sw_kernel_stats(sw_engine* h, int which, double* total_ms, int64_t* launches);
 /* Floating-point operations issued by the launches of an MFMA kernel class since the last reset
  * (profiling on): 8 flops per complex multiply-add over every (row tile, k-step, probe). */
