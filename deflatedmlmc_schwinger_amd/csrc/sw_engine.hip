@@ -63,9 +63,10 @@ enum TimerCat { T_MVM = 0, T_DEFL, T_P, T_R, T_AXPY, T_DOTS, T_COARSEST, T_OTHER
                 T_SCHUR_OP,     // k_schur_step<0/1>: operator / residual of the even-odd reduced system
                 T_TP_SOURCES,   // k_slice_sources of SW_MODE_TWO_POINT
                 T_TP_DOTS,      // k_slice_pair_dots / k_pair_total of SW_MODE_TWO_POINT
+                T_SLICE_CDOTS,  // k_slice_cdots of SW_MODE_MLMC_LOOPS / sw_coarsest_loops
                 T_NCAT };
-// classes >= T_STENCIL are folded into the mvm / coarsest (two-point: other / dots) buckets by sw_timers and
-// reported separately by sw_kernel_stats
+// classes >= T_STENCIL are folded into the mvm / coarsest (two-point: other / dots; slice cdots: dots) buckets by
+// sw_timers and reported separately by sw_kernel_stats
 
 struct EllOp {
   int nrows = 0, ncols = 0, K = 0, G = 1, ngroups = 0;
@@ -325,6 +326,11 @@ struct sw_engine {
   cplx* pb_lest = nullptr;
   size_t pb_lest_cap = 0;
   int loop_nb = 0, loop_nbp = 0;   // probes and row stride of the last loop batch (0: nothing to fetch)
+  // MLMC level loops (SW_MODE_MLMC_LOOPS / _SKIP, sw_apply_slice_cdots): the same momenta and tables, results in a
+  // buffer of their own so that sw_hutch_fetch_loops keeps returning mode 5's last batch
+  cplx* pb_mlest = nullptr;
+  size_t pb_mlest_cap = 0;
+  int mloop_nb = 0, mloop_nbp = 0;
   // one-end-trick two-point functions (sw_set_two_point, SW_MODE_TWO_POINT): a registration of its own (source
   // timeslice, momenta, the index of momentum 0, tables as for the loops), the sources and solutions [n][2 M nq]
   // and the pair sums T[momentum][a][b][c][d][t][noise]
@@ -2548,7 +2554,7 @@ int sw_hier_begin(sw_engine* h, int hid, int nlevels) {
     h->shifts.clear();
     h->shift_nb = 0;
     h->momenta.clear();
-    h->loop_nb = 0;
+    h->loop_nb = h->mloop_nb = 0;
     h->tp_momenta.clear();
     h->tp_nb = 0;
   }
@@ -4729,7 +4735,7 @@ int sw_set_loop_momenta(sw_engine* h, int nmom, const int32_t* p) {
   SWCHK(check_hier(h, 0, 0, false));
   if (nmom < 0 || nmom > SW_MAX_MOMENTA)
     return sw_fail(h, "%d momenta: at most %d per registration", nmom, SW_MAX_MOMENTA);
-  h->loop_nb = 0;
+  h->loop_nb = h->mloop_nb = 0;
   if (nmom == 0) {
     h->momenta.clear();
     return 0;
@@ -4742,44 +4748,79 @@ int sw_set_loop_momenta(sw_engine* h, int nmom, const int32_t* p) {
   return 0;
 }
 
-// pb_lest[p][a][b][t][col] = sum_x e^{-2 pi i p x / L} conj(x_col[idx(a,x,t)]) z_col[idx(b,x,t)] for the registered
-// momenta: the probes' codes from their int8 form (reference order), then k_slice_dots, one workgroup per
-// (timeslice, 64 probes); total (optional) = the scalar total of the first momentum's block per probe
+// The loop buffer of a reduction, [p][a][b][t][col] for the registered momenta: mode 5's (mlmc = false) or the one
+// of the MLMC level loops.  The buffer is about to be rewritten: only a completed batch marks it fetchable again.
+static int loop_buffer(sw_engine* h, bool mlmc, int L, int nbp, cplx** out) {
+  cplx** buf = mlmc ? &h->pb_mlest : &h->pb_lest;
+  size_t& cap = mlmc ? h->pb_mlest_cap : h->pb_lest_cap;
+  (mlmc ? h->mloop_nb : h->loop_nb) = 0;
+  const size_t need = h->momenta.size() * 4 * (size_t)L * nbp;
+  if (cap < need) {
+    SWCHK(dev_realloc(h, buf, need));
+    cap = need;
+  }
+  (mlmc ? h->mloop_nbp : h->loop_nbp) = nbp;
+  *out = *buf;
+  return 0;
+}
+
+// loops[p][a][b][t][col] = sum_x e^{-2 pi i p x / L} conj(x_col[idx(a,x,t)]) z_col[idx(b,x,t)] for the registered
+// momenta (mlmc: into the MLMC loop buffer): the probes' codes from their int8 form (reference order), then
+// k_slice_dots, one workgroup per (timeslice, 64 probes); total (optional) = the scalar total of the first
+// momentum's block per probe
 static int slice_dots(sw_engine* h, Level& lv, const int8_t* probes, int nb, const cplx* Z, int nbp,
-                      cplx* total) {
+                      cplx* total, bool mlmc = false) {
   const int M = (int)h->momenta.size();
   const int L = lv.L, n = lv.n;
-  h->loop_nb = 0;   // pb_lest is rewritten: only a completed loop batch sets it again
   SWCHK(ensure_probe_ws(h, nbp));
-  const size_t need = (size_t)M * 4 * L * nbp;
-  if (h->pb_lest_cap < need) {
-    SWCHK(dev_realloc(h, &h->pb_lest, need));
-    h->pb_lest_cap = need;
-  }
-  h->loop_nbp = nbp;
+  cplx* out;
+  SWCHK(loop_buffer(h, mlmc, L, nbp, &out));
   SWCHK(launch(h, T_OTHER, swk::k_probe_codes, dim3((n + 63) / 64, nbp / 64), dim3(SW_BLOCK), probes, nb, n,
                (const int*)lv.rowmap, h->pb_codes, nbp));
   const dim3 grid(L, nbp / 64);
   if (M == 1 && h->momenta[0] == 0) {
     SWCHK(launch(h, T_DOTS, swk::k_slice_dots<1, false>, grid, dim3(SW_BLOCK), (const int8_t*)h->pb_codes, Z,
-                 (const int*)h->slicerow, (const cplx*)h->loop_phase, (const int*)h->loop_mom, L, nbp, M,
-                 h->pb_lest));
+                 (const int*)h->slicerow, (const cplx*)h->loop_phase, (const int*)h->loop_mom, L, nbp, M, out));
   } else {
     // momenta per pass: the smallest instantiation that holds them all (none of them spills)
     SWCHK(pick_ge<1, 2, 4, 8>(M, [&](auto NPc) {
       return launch(h, T_DOTS, swk::k_slice_dots<decltype(NPc)::value, true>, grid, dim3(SW_BLOCK),
                     (const int8_t*)h->pb_codes, Z, (const int*)h->slicerow, (const cplx*)h->loop_phase,
-                    (const int*)h->loop_mom, L, nbp, M, h->pb_lest);
+                    (const int*)h->loop_mom, L, nbp, M, out);
     }));
   }
   if (!total) return 0;
-  return launch(h, T_DOTS, swk::k_slice_total, dim3(nbp / 64), dim3(SW_BLOCK), (const cplx*)h->pb_lest, L, nbp,
-                total);
+  return launch(h, T_DOTS, swk::k_slice_total, dim3(nbp / 64), dim3(SW_BLOCK), (const cplx*)out, L, nbp, total);
 }
 
-static int fetch_loops(sw_engine* h, int nb, double* out) {
+// out[p][a][b][t][col] = sum_x e^{-2 pi i p x / L} conj(U_col[idx(a,x,t)]) V_col[idx(b,x,t)] for the registered
+// momenta, U and V two blocks [n_0][nbp] of the lattice level (k_slice_cdots: same grid, same choice of momenta
+// per pass as slice_dots; none of the instantiations spills)
+static int slice_cdots_into(sw_engine* h, Level& lv0, const cplx* U, const cplx* V, int nbp, cplx* out) {
+  const int M = (int)h->momenta.size(), L = lv0.L;
+  const dim3 grid(L, nbp / 64);
+  if (M == 1 && h->momenta[0] == 0)
+    return launch(h, T_SLICE_CDOTS, swk::k_slice_cdots<1, false>, grid, dim3(SW_BLOCK), U, V,
+                  (const int*)h->slicerow, (const cplx*)h->loop_phase, (const int*)h->loop_mom, L, nbp, M, out);
+  return pick_ge<1, 2, 4, 8>(M, [&](auto NPc) {
+    return launch(h, T_SLICE_CDOTS, swk::k_slice_cdots<decltype(NPc)::value, true>, grid, dim3(SW_BLOCK), U, V,
+                  (const int*)h->slicerow, (const cplx*)h->loop_phase, (const int*)h->loop_mom, L, nbp, M, out);
+  });
+}
+
+// the same into the MLMC loop buffer; total (optional) = the scalar total of the first momentum's block
+static int slice_cdots(sw_engine* h, Level& lv0, const cplx* U, const cplx* V, int nbp, cplx* total) {
+  cplx* out;
+  SWCHK(loop_buffer(h, true, lv0.L, nbp, &out));
+  SWCHK(slice_cdots_into(h, lv0, U, V, nbp, out));
+  if (!total) return 0;
+  return launch(h, T_DOTS, swk::k_slice_total, dim3(nbp / 64), dim3(SW_BLOCK), (const cplx*)out, lv0.L, nbp, total);
+}
+
+static int fetch_loops(sw_engine* h, bool mlmc, int nb, double* out) {
   const size_t rows = h->momenta.size() * 4 * (size_t)h->hier[0].lv[0].L;
-  HIPCHK(hipMemcpy2D(out, sizeof(cplx) * nb, h->pb_lest, sizeof(cplx) * h->loop_nbp, sizeof(cplx) * nb, rows,
+  HIPCHK(hipMemcpy2D(out, sizeof(cplx) * nb, mlmc ? h->pb_mlest : h->pb_lest,
+                     sizeof(cplx) * (mlmc ? h->mloop_nbp : h->loop_nbp), sizeof(cplx) * nb, rows,
                      hipMemcpyDeviceToHost));
   return 0;
 }
@@ -4799,7 +4840,24 @@ int sw_apply_slice_dots(sw_engine* h, int nb, const int8_t* probes, const double
   SWCHK(upload(h, &pr.p, probes, (size_t)nb * lv.n));
   SWCHK(slice_dots(h, lv, pr, nb, a, nbp, nullptr));
   SWCHK(stream_sync(h));
-  return fetch_loops(h, nb, out);
+  return fetch_loops(h, false, nb, out);
+}
+
+// k_slice_cdots alone on host inputs (reference ordering): out[p][a][b][t][k] with the complex left operand U_k.
+int sw_apply_slice_cdots(sw_engine* h, int nb, const double* U, const double* V, double* out) {
+  SWCHK(check_hier(h, 0, 0, false));
+  if (nb <= 0 || !U || !V || !out) return sw_fail(h, "bad arguments");
+  if (h->momenta.empty()) return sw_fail(h, "no momenta registered (sw_set_loop_momenta)");
+  HIPCHK(hipSetDevice(h->device));
+  Level& lv = h->hier[0].lv[0];
+  const int nbp = pad64(nb);
+  cplx *a, *b;
+  SWCHK(io_vectors(h, lv, nbp, &a, &b));
+  SWCHK(pack_host(h, lv, nb, U, a, nbp));
+  SWCHK(pack_host(h, lv, nb, V, b, nbp));
+  SWCHK(slice_cdots(h, lv, a, b, nbp, nullptr));
+  SWCHK(stream_sync(h));
+  return fetch_loops(h, true, nb, out);
 }
 
 int sw_hutch_fetch_loops(sw_engine* h, double* out) {
@@ -4808,7 +4866,82 @@ int sw_hutch_fetch_loops(sw_engine* h, double* out) {
   if (h->loop_nb <= 0 || !h->pb_lest) return sw_fail(h, "no loop batch to fetch");
   HIPCHK(hipSetDevice(h->device));
   SWCHK(stream_sync(h));
-  return fetch_loops(h, h->loop_nb, out);
+  return fetch_loops(h, false, h->loop_nb, out);
+}
+
+int sw_hutch_fetch_mlmc_loops(sw_engine* h, double* out) {
+  if (!h) return 1;
+  if (!out) return sw_fail(h, "null output");
+  if (h->mloop_nb <= 0 || !h->pb_mlest) return sw_fail(h, "no MLMC loop batch to fetch");
+  HIPCHK(hipSetDevice(h->device));
+  SWCHK(stream_sync(h));
+  return fetch_loops(h, true, h->mloop_nb, out);
+}
+
+// X (level `level` of hierarchy 0, [n_level][nbp]) prolonged to the lattice level through P_{level-1} ... P_0,
+// alternating between the scratch blocks s0 and s1 (each [n_0][nbp] at least); *res = where the result is
+// (X itself at level 0)
+static int prolong_to_lattice(sw_engine* h, int level, const cplx* X, cplx* s0, cplx* s1, int nbp, const cplx** res) {
+  Hier& H0 = h->hier[0];
+  const cplx* cur = X;
+  for (int l = level - 1; l >= 0; --l) {
+    cplx* dst = cur == s0 ? s1 : s0;
+    SWCHK(launch_ell(h, H0.lv[l].P, 0, cur, nullptr, dst, nbp, T_P));
+    cur = dst;
+  }
+  *res = cur;
+  return 0;
+}
+
+// The exact coarsest term of the MLMC loops: out[p][a][b][t] = sum_j S_q(Pi e_j, Pi A_c^-1 e_j), Pi = P_0 ... P_{M-2},
+// on 64-column blocks of the identity and of the coarsest inverse, both prolonged to the lattice level and reduced
+// with k_slice_cdots; the blocks are added in ascending order and the 64 columns of the sum by one host loop in
+// ascending order, so two calls agree bit for bit.
+int sw_coarsest_loops(sw_engine* h, double* out) {
+  SWCHK(check_hier(h, 0, 0, true));
+  if (!out) return sw_fail(h, "null output");
+  if (h->momenta.empty()) return sw_fail(h, "no momenta registered (sw_set_loop_momenta)");
+  Hier& H0 = h->hier[0];
+  if (H0.nlevels < 2) return sw_fail(h, "the coarsest loops need at least two levels");
+  HIPCHK(hipSetDevice(h->device));
+  const int last = H0.nlevels - 1;
+  Level& lv0 = H0.lv[0];
+  Level& lc = H0.lv[last];
+  const int nc = lc.n, nbp = 64, L = lv0.L;
+  const size_t rows = h->momenta.size() * 4 * (size_t)L;
+  int nmax = 0;
+  for (int l = 0; l < H0.nlevels; ++l) nmax = std::max(nmax, H0.lv[l].n);
+  DevBuf<cplx> E(h), Y(h), s[4] = {DevBuf<cplx>(h), DevBuf<cplx>(h), DevBuf<cplx>(h), DevBuf<cplx>(h)}, acc(h),
+      part(h);
+  SWCHK(dev_realloc(h, &E.p, (size_t)nc * nbp));
+  SWCHK(dev_realloc(h, &Y.p, (size_t)nc * nbp));
+  for (auto& b : s) SWCHK(dev_realloc(h, &b.p, (size_t)nmax * nbp));
+  SWCHK(dev_realloc(h, &acc.p, rows * nbp));
+  SWCHK(dev_realloc(h, &part.p, rows * nbp));
+  SWCHK(zero_vec(h, acc, (int)rows, nbp));
+  std::vector<std::complex<double>> he((size_t)nc * nbp);
+  for (int j0 = 0; j0 < nc; j0 += 64) {
+    std::fill(he.begin(), he.end(), std::complex<double>(0.0, 0.0));
+    for (int c = 0; c < 64 && j0 + c < nc; ++c) he[(size_t)(j0 + c) * nbp + c] = 1.0;   // any order of the unit vectors gives the sum
+    SWCHK(stream_sync(h));                 // the previous block's reads of E are done
+    HIPCHK(hipMemcpy(E.p, he.data(), he.size() * sizeof(cplx), hipMemcpyHostToDevice));
+    SWCHK(apply_coarsest(h, H0, E, Y, nbp));
+    const cplx *u, *v;
+    SWCHK(prolong_to_lattice(h, last, E, s[0], s[1], nbp, &u));
+    SWCHK(prolong_to_lattice(h, last, Y, s[2], s[3], nbp, &v));
+    SWCHK(slice_cdots_into(h, lv0, u, v, nbp, part));
+    SWCHK(vec_add(h, acc, part, acc, (int)rows, nbp));
+  }
+  SWCHK(stream_sync(h));
+  std::vector<std::complex<double>> ha(rows * nbp);
+  HIPCHK(hipMemcpy(ha.data(), acc.p, ha.size() * sizeof(cplx), hipMemcpyDeviceToHost));
+  for (size_t r = 0; r < rows; ++r) {
+    std::complex<double> sum(0.0, 0.0);
+    for (int c = 0; c < nbp; ++c) sum += ha[r * nbp + c];
+    out[2 * r] = sum.real();
+    out[2 * r + 1] = sum.imag();
+  }
+  return 0;
 }
 
 // ---- one-end-trick two-point functions from timeslice sources ------------------------------------------
@@ -4956,6 +5089,13 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
     if (level != 0) return sw_fail(h, "two-point mode runs at level 0");
     if (h->tp_momenta.empty()) return sw_fail(h, "no two-point registration (sw_set_two_point)");
   }
+  const bool mloops = (mode == SW_MODE_MLMC_LOOPS || mode == SW_MODE_MLMC_LOOPS_SKIP);
+  if (mloops) {
+    if (h->momenta.empty()) return sw_fail(h, "no momenta registered (sw_set_loop_momenta)");
+    if (h->lkd[level] > 0)
+      return sw_fail(h, "MLMC loops do not combine with MLMC-level deflation (level %d holds %d vectors)", level,
+                     h->lkd[level]);
+  }
   HIPCHK(hipSetDevice(h->device));
   Hier& H0 = h->hier[0];
   const int nb = h->pb_nb, nbp = h->pb_nbp;
@@ -5068,8 +5208,8 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
     h->last_iters_c.assign(nb, 0);
     return 0;
   }
-  if (mode != SW_MODE_MLMC && mode != SW_MODE_MLMC_SKIP) return sw_fail(h, "unknown mode %d", mode);
-  const bool skip = (mode == SW_MODE_MLMC_SKIP);
+  if (mode != SW_MODE_MLMC && mode != SW_MODE_MLMC_SKIP && !mloops) return sw_fail(h, "unknown mode %d", mode);
+  const bool skip = (mode == SW_MODE_MLMC_SKIP || mode == SW_MODE_MLMC_LOOPS_SKIP);
   if (skip && level != 0) return sw_fail(h, "level skipping is defined for level 0 only");
   const int lcoarse = level + (skip ? 2 : 1);
   if (lcoarse >= H0.nlevels) return sw_fail(h, "no coarse level %d", lcoarse);
@@ -5080,7 +5220,7 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
     SWCHK(deflate(h, h->lV[level], h->lkd[level], nullptr, h->pb_x0, h->pb_xd, n, nbp));
     xdef = h->pb_xd;
   }
-  if (h->rhsmap[level].set) {
+  if (h->rhsmap[level].set && !mloops) {   // the loops take the plain probe, as mode 5 ignores sw_set_perm
     SWCHK(launch_ell(h, h->rhsmap[level], 0, xdef, nullptr, h->pb_rhs, nbp, T_OTHER));
     xdef = h->pb_rhs;
   }
@@ -5101,6 +5241,30 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
   SWCHK(stream_sync(h));
   if (lcoarse == H0.nlevels - 1 || level_is_direct(h, H0, lcoarse)) h->last_iters_c.assign(nb, 1);
   else SWCHK(record_iters(h, &H0.lv[lcoarse].sws, total_c, h->last_iters_c, nb));
+  if (mloops) {
+    // d = z - P y on level `level` (skip: z - P0 P1 y), one launch with the prolongation
+    const cplx* yc = h->pb_y;
+    if (skip) {
+      SWCHK(launch_ell(h, H0.lv[1].P, 0, h->pb_y, nullptr, h->pb_w2, nbp, T_P));
+      yc = h->pb_w2;
+    }
+    SWCHK(launch_ell(h, lv.P, 1, yc, h->pb_z, h->pb_w, nbp, T_P));
+    Level& lv0 = H0.lv[0];
+    if (level == 0) {
+      // the probe is the int8 codes themselves: mode 5's reduction on d, one pass
+      SWCHK(slice_dots(h, lv0, h->pb_probes, nb, h->pb_w, nbp, h->pb_est, true));
+    } else {
+      // u = P_0 ... P_{level-1} x, v = P_0 ... P_{level-1} d on the lattice, then the reduction with a complex
+      // left operand
+      const cplx *u, *v;
+      SWCHK(prolong_to_lattice(h, level, h->pb_x0, h->pb_xc, h->pb_xc2, nbp, &u));
+      SWCHK(prolong_to_lattice(h, level, h->pb_w, h->pb_y, h->pb_w2, nbp, &v));
+      SWCHK(slice_cdots(h, lv0, u, v, nbp, h->pb_est));
+    }
+    SWCHK(stream_sync(h));
+    h->mloop_nb = nb;
+    return 0;
+  }
   // w = P y (skip: P0 P1 y)                  utils.py:337-341
   const cplx* w;
   if (skip) {
@@ -5311,7 +5475,7 @@ int sw_timers(sw_engine* h, double t[8]) {
               h->tacc[T_MFMA_OP2] + h->tacc[T_SCHUR] + h->tacc[T_SCHUR_OP];
   t[T_COARSEST] += h->tacc[T_MFMA_DENSE];
   t[T_OTHER] += h->tacc[T_TP_SOURCES];
-  t[T_DOTS] += h->tacc[T_TP_DOTS];
+  t[T_DOTS] += h->tacc[T_TP_DOTS] + h->tacc[T_SLICE_CDOTS];
   return 0;
 }
 int sw_timers_reset(sw_engine* h) {

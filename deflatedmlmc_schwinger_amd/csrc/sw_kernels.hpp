@@ -3515,6 +3515,103 @@ __global__ __launch_bounds__(SW_BLOCK) void k_slice_total(const cplx* __restrict
   }
 }
 
+// The slice reduction with a complex left operand (SW_MODE_MLMC_LOOPS, sw_coarsest_loops): out[p][a][b][t][k] =
+// sum_x e^{-2 pi i p x / L} conj(U_k[idx(a,x,t)]) V_k[idx(b,x,t)] for two blocks U, V [row][col] of the lattice
+// level -- the prolonged probe and the prolonged difference of a coarse MLMC level, which are no int8 codes.
+// k_slice_dots in everything else: grid = (L timeslices, nbp / 64), lane = column, the four waves take the sites
+// x = wave, wave + 4, ...; per site a lane reads u_0, u_1, v_0, v_1 (four 16-byte loads) and forms the four
+// conj(u_a) v_b -- real multiplications here --, the phase table omega^(p x mod L) is staged in LDS, the 4 NP
+// complex accumulators stay in registers, the waves combine through LDS in the fixed order w0 + w1 + w2 + w3 and
+// wave 0 writes out[((j * 4 + a * 2 + b) * L + t) * nbp + col]: no partials, no atomics.  A padded column (zeros
+// in U or V) only ever touches its own lane's sums.
+template <int NP, bool PHASE = true>
+__global__ __launch_bounds__(SW_BLOCK) void k_slice_cdots(const cplx* __restrict__ U, const cplx* __restrict__ V,
+                                                          const int* __restrict__ slicerow,
+                                                          const cplx* __restrict__ phase,
+                                                          const int* __restrict__ mom, int L, int nbp, int nmom,
+                                                          cplx* __restrict__ out) {
+  constexpr int NA = 4 * NP;
+  __shared__ __attribute__((aligned(16))) cplx tab[PHASE ? SW_SHIFT_MAX_L : 1];
+  __shared__ __attribute__((aligned(16))) cplx red[NA][64];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int t = blockIdx.x;
+  const size_t col = (size_t)blockIdx.y * 64 + lane;
+  int idx[NP] = {}, step[NP] = {};
+  if constexpr (PHASE) {
+    for (int i = threadIdx.x; i < L; i += SW_BLOCK) tab[i] = phase[i];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      const int p = mom[j];                 // in [0, L), L <= 1024: the products below stay far inside int
+      idx[j] = (p * wave) % L;
+      step[j] = (p * SW_WAVES_PER_BLOCK) % L;
+    }
+    __syncthreads();
+  }
+  double ar[NA], ai[NA];
+#pragma unroll
+  for (int i = 0; i < NA; ++i) ar[i] = ai[i] = 0.0;
+  const int* __restrict__ sr = slicerow + (size_t)t * L * 2;
+#pragma unroll 2
+  for (int x = wave; x < L; x += SW_WAVES_PER_BLOCK) {
+    const size_t r0 = (size_t)sr[2 * x] * nbp + col, r1 = (size_t)sr[2 * x + 1] * nbp + col;
+    const cplx u[2] = {U[r0], U[r1]};
+    const cplx v[2] = {V[r0], V[r1]};
+    double pr[4], pi[4];                    // conj(u_a) v_b at [a * 2 + b]
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        pr[a * 2 + b] = u[a].x * v[b].x + u[a].y * v[b].y;
+        pi[a * 2 + b] = u[a].x * v[b].y - u[a].y * v[b].x;
+      }
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      if constexpr (PHASE) {
+        const cplx w = tab[idx[j]];
+        idx[j] += step[j];
+        idx[j] = idx[j] >= L ? idx[j] - L : idx[j];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          ar[j * 4 + q] += w.x * pr[q] - w.y * pi[q];
+          ai[j * 4 + q] += w.x * pi[q] + w.y * pr[q];
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          ar[j * 4 + q] += pr[q];
+          ai[j * 4 + q] += pi[q];
+        }
+      }
+    }
+  }
+  for (int w = 1; w < SW_WAVES_PER_BLOCK; ++w) {
+    __syncthreads();                        // wave 0 has taken the previous wave's block
+    if (wave == w) {
+#pragma unroll
+      for (int i = 0; i < NA; ++i) red[i][lane] = cmake(ar[i], ai[i]);
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+      for (int i = 0; i < NA; ++i) {
+        const cplx q = red[i][lane];
+        ar[i] += q.x;
+        ai[i] += q.y;
+      }
+    }
+  }
+  if (wave == 0) {
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      if (j < nmom) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          out[((size_t)(j * 4 + q) * L + t) * nbp + col] = cmake(ar[j * 4 + q], ai[j * 4 + q]);
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // One-end-trick two-point functions (SW_MODE_TWO_POINT): per noise k one Z2 / Z4 vector xi_k(y) on the source
 // timeslice t0 gives the 2 M sources eta^(j,a)[idx(a',y,t)] = delta_aa' delta_t,t0 e^{+2 pi i p_j y / L} xi_k(y)

@@ -22,8 +22,11 @@ MODE_LEVEL = 3
 MODE_HUTCHINSON_SHIFTS = 4
 MODE_HUTCHINSON_LOOPS = 5
 MODE_TWO_POINT = 6
+MODE_MLMC_LOOPS = 7
+MODE_MLMC_LOOPS_SKIP = 8
 KCLASS_TP_SOURCES = 17     # sw_kernel_stats classes of the two-point kernels
 KCLASS_TP_DOTS = 18
+KCLASS_SLICE_CDOTS = 19    # ... and of k_slice_cdots (MLMC loops)
 MAX_SHIFTS = 128
 MAX_MOMENTA = 8
 PROBES_Z2 = 1
@@ -167,6 +170,9 @@ def load_library():
     sig("sw_hutch_fetch_two_point", i32, vp, vp)
     sig("sw_apply_slice_sources", i32, vp, i32, vp, vp)
     sig("sw_apply_pair_dots", i32, vp, i32, vp, vp)
+    sig("sw_apply_slice_cdots", i32, vp, i32, vp, vp, vp)
+    sig("sw_coarsest_loops", i32, vp, vp)
+    sig("sw_hutch_fetch_mlmc_loops", i32, vp, vp)
     _lib = lib
     return lib
 
@@ -190,6 +196,7 @@ EXPORTED_SYMBOLS = (
     "sw_set_shifts", "sw_hutch_fetch_shifts", "sw_apply_shift_dots",
     "sw_set_loop_momenta", "sw_hutch_fetch_loops", "sw_apply_slice_dots",
     "sw_set_two_point", "sw_hutch_fetch_two_point", "sw_apply_slice_sources", "sw_apply_pair_dots",
+    "sw_apply_slice_cdots", "sw_coarsest_loops", "sw_hutch_fetch_mlmc_loops",
 )
 
 
@@ -652,6 +659,38 @@ class Engine:
         self._chk(self._lib.sw_apply_slice_dots(self._h, p.shape[0], _ptr(p), _ptr(Z2), _ptr(out)),
                   "sw_apply_slice_dots")
         return np.ascontiguousarray(np.moveaxis(out, -1, 0))
+
+    def hutch_batch_mlmc_loops(self, level, probes, tol, maxiter=1000, skip=False):
+        """One MODE_MLMC_LOOPS batch (skip: MODE_MLMC_LOOPS_SKIP) at `level`: (loops[nb, nmom, 2, 2, L], iters_fine[nb],
+        iters_coarse[nb]), loops[k, p, a, b, t] = S_q(Pi_l x_k, Pi_l d_k) with d_k the MLMC difference of probe k."""
+        mode = MODE_MLMC_LOOPS_SKIP if skip else MODE_MLMC_LOOPS
+        _, itf, itc = self.hutch_batch(mode, level, probes, tol, maxiter)
+        self._nb_uploaded = itf.size
+        return self.hutch_fetch_mlmc_loops(), itf, itc
+
+    def hutch_fetch_mlmc_loops(self):
+        """Level loops of the last MODE_MLMC_LOOPS / _SKIP batch, shape (nb, nmom, 2, 2, L)."""
+        out = np.zeros(self._loop_shape(getattr(self, "_nb_uploaded", 0)), dtype=np.complex128)
+        self._chk(self._lib.sw_hutch_fetch_mlmc_loops(self._h, _ptr(out)), "sw_hutch_fetch_mlmc_loops")
+        return np.ascontiguousarray(np.moveaxis(out, -1, 0))
+
+    def apply_slice_cdots(self, U, V):
+        """k_slice_cdots alone: out[k, p, a, b, t] = sum_x e^{-2 pi i p x / L} conj(U[k][idx(a,x,t)]) V[k][idx(b,x,t)]
+        for the registered momenta; U, V complex (nb, n) in the reference ordering."""
+        U2, _ = self._io(U, self._n(0, 0))
+        V2, _ = self._io(V, self._n(0, 0))
+        if U2.shape != V2.shape:
+            raise EngineError("U %s and V %s differ in shape" % (U2.shape, V2.shape))
+        out = np.zeros(self._loop_shape(U2.shape[0]), dtype=np.complex128)
+        self._chk(self._lib.sw_apply_slice_cdots(self._h, U2.shape[0], _ptr(U2), _ptr(V2), _ptr(out)),
+                  "sw_apply_slice_cdots")
+        return np.ascontiguousarray(np.moveaxis(out, -1, 0))
+
+    def coarsest_loops(self):
+        """The exact coarsest term of the MLMC loops, shape (nmom, 2, 2, L): sum_j S_q(Pi e_j, Pi A_c^-1 e_j)."""
+        out = np.zeros(self._loop_shape(1)[:-1], dtype=np.complex128)
+        self._chk(self._lib.sw_coarsest_loops(self._h, _ptr(out)), "sw_coarsest_loops")
+        return out
 
     def set_two_point(self, t0, momenta):
         """Source timeslice and momenta of MODE_TWO_POINT (None or an empty list clears)."""

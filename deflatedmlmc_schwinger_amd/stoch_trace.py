@@ -19,7 +19,8 @@ from .engine import ProbeStream
 from .multigrid import MG
 from .utils import (_engines, deflation_pre_computations, displacements_of, draw_probes, flopsV_manual,
                     loops_of, mlmc_defl_setup_of, probe_batch, probe_batch_generated, probe_batch_loops,
-                    probe_batch_loops_generated, probe_batch_shifts, probe_batch_shifts_generated,
+                    probe_batch_loops_generated, probe_batch_mlmc_loops_generated, probe_batch_shifts,
+                    probe_batch_shifts_generated,
                     probe_batch_two_point, probe_batch_two_point_generated, register_loop_momenta, register_shifts,
                     register_two_point, two_point_of)
 
@@ -224,6 +225,28 @@ class DeviceLoopProbes:
 
     def __call__(self, first_probe, count):
         e, f, c = probe_batch_loops_generated(self.mg_solver, self.params, first_probe, count, self.kind)
+        return loop_columns(e, self.zero), f, c
+
+
+class DeviceMLMCLoopProbes:
+    """Probe source of the MLMC loop flow: the probes of `level` through MODE_MLMC_LOOPS; one row of loop_columns
+    per probe, the control column being the scalar MLMC difference x^H (z - P y) of the probe."""
+
+    def __init__(self, mg_solver, params, level, zero, kind="z2"):
+        self.mg_solver = mg_solver
+        self.params = params
+        self.level = level
+        self.zero = zero
+        self.kind = kind
+
+    def begin(self, entry_stream):
+        window = entry_stream.window()
+        for eng in _engines(self.mg_solver):
+            eng.stream_set(window)
+
+    def __call__(self, first_probe, count):
+        e, f, c = probe_batch_mlmc_loops_generated(self.mg_solver, self.params, self.level, first_probe, count,
+                                                   self.kind)
         return loop_columns(e, self.zero), f, c
 
 
@@ -643,7 +666,7 @@ def mlmc(A, params):
         raise Exception("source_timeslice belongs to two_point(), not to mlmc()")
     if loops_of(params) is not None:
         raise Exception("timeslice_loops is implemented for hutchinson() only: the MLMC coarse terms need a "
-                        "timeslice projection per level")
+                        "timeslice projection per level (mlmc_loops() has it)")
     if displacements_of(params) is not None:
         raise Exception("x_displacements is implemented for hutchinson() only: the MLMC difference levels "
                         "need their own displaced right-hand sides")
@@ -797,6 +820,172 @@ def mlmc(A, params):
     for i in range(nr_levels):
         output_params['total_complexity'] += output_params['results'][i]['level_complexity']
         output_params['trace'] += output_params['results'][i]['ests_avg']
+    mg_solver.sync_timer()
+    print(mg_solver.timer)
+    return output_params
+
+
+def _mlmc_loops_checks(params):
+    """The validation of mlmc_loops(), before any setup: (momenta, skip_level)."""
+    has = hasattr(params, "get")
+    if has and params.get('source_timeslice') is not None:
+        raise Exception("source_timeslice belongs to two_point(), not to mlmc_loops()")
+    if has and params.get('x_displacements') is not None:
+        raise Exception("x_displacements does not combine with the MLMC loops")
+    momenta = loops_of(params)
+    if momenta is None:
+        raise Exception("mlmc_loops() needs the key timeslice_loops")
+    if any(int(k) != 0 for k in params['mlmc_deflat_vctrs']):
+        raise Exception("mlmc_loops() runs without MLMC-level deflation (mlmc_deflat_vctrs all zero): the deflated "
+                        "part would need a sliced tr1 of the difference operators")
+    if params['coarsest_level_directly'] != True:   # noqa: E712  (as mlmc() tests it)
+        raise Exception("mlmc_loops() computes the coarsest term exactly: coarsest_level_directly has to be true")
+    if _dist.default_comm().world > 1:
+        raise Exception("MLMC loops (mlmc_loops) run on one rank")
+    skip_list = params['mlmc_levels_to_skip']
+    if len(skip_list) > 1:
+        raise Exception("Only allowed to skip one level for now")
+    skip_level = len(skip_list) == 1
+    if skip_level and not skip_list[0] == 1:
+        raise Exception("Only allowed to skip the second level for now")
+    return momenta, skip_level
+
+
+def mlmc_loops(A, params):
+    """The timeslice loops l[p][a][b][t] = Tr(Gamma_q A^-1) by multigrid multilevel Monte Carlo:
+
+        l_q = sum_i E_x[ S_q(Pi_i x, Pi_i D_i x) ] + sum_j S_q(Pi e_j, Pi A_c^-1 e_j)
+
+    with D_i the MLMC difference operator of level i, Pi_i = P_0 ... P_{i-1} and S_q the slice reduction -- mlmc()
+    with every level's estimate resolved in momentum, spin and timeslice (MODE_MLMC_LOOPS), the coarsest term exact
+    (Engine.coarsest_loops).  Needs the key timeslice_loops (momenta, 0 among them); mlmc_deflat_vctrs all zero,
+    coarsest_level_directly true, one rank; use_permuted and x_displacement are ignored, as in the Hutchinson loop
+    flow.  Per level the probe loop's columns are the flattened level loops plus one control column, the scalar
+    MLMC difference of the probe; the stopping rule runs on it against mlmc()'s tolerance split of the rough trace,
+    which comes from five MODE_HUTCHINSON_LOOPS probes with the Hutchinson deflation vectors.
+
+    Returns mlmc()'s dictionary (trace estimates Tr(A^-1)) with, per level, results[i]['loops' | 'loop_devs' |
+    'loop_ests' | 'converged'] (the last level's loops are exact), and at top level loops = the sum over the levels,
+    loop_errs = sqrt(sum_i loop_devs_i^2 / (nr_ests_i + 1)) and momenta."""
+    momenta, skip_level = _mlmc_loops_checks(params)
+    mg_solver, nr_levels = _setup_solver(A, params)
+    N = A.shape[0]
+    L = int(params['latt_dims'][0])
+    batch = int(params.get('batch', DEFAULT_BATCH))
+    kind = params.get('probe_type', 'z2')
+    zero = momenta.index(0)
+    shape = (len(momenta), 2, 2, L)
+    mg_solver.skip_level = skip_level
+
+    print("\nResetting timer to zero ...", end='')
+    mg_solver.timer.reset()
+    print(" done\n")
+    for ix in range(nr_levels - 1):
+        # no MLMC-level deflation: clears what an earlier flow on these engines may have registered
+        deflation_pre_computations(A, 0, params['defl_eigvs_tol_MLMC'], "mlmc", mg_solver.timer, params, mg_solver,
+                                   None, level_nr=ix)
+    print("Computing deflation vectors (for rough estimation purposes only) ...", end='', flush=True)
+    t0 = time.time()
+    Vx, tr1 = deflation_pre_computations(A, params['nr_deflat_vctrs'], params['defl_eigvs_tol_Hutch'], "hutchinson",
+                                         mg_solver.timer, params, mg_solver)
+    tr1_cols = loop_columns(np.asarray(tr1, dtype=np.complex128)[None], zero)[0]
+    register_loop_momenta(mg_solver, momenta)
+    print(" done. Time : " + str(time.time() - t0) + " seconds")
+    print("\nComputing rough estimation of the loops ...", end='', flush=True)
+    np.random.seed(123456)                                      # stoch_trace.py:288-302
+    t0 = time.time()
+    e, _, _ = probe_batch_loops(mg_solver, params, draw_probes(NR_ROUGH_PROBES, N, kind))
+    rough = np.sum(loop_columns(e, zero), axis=0) / NR_ROUGH_PROBES + tr1_cols
+    control = rough.size - 1
+    rough_trace = rough[control]
+    print(" done. Time : " + str(time.time() - t0) + " seconds")
+
+    output_params = {'nr_levels': nr_levels, 'trace': 0.0, 'total_complexity': 0.0,
+                     'std_dev': 0.0, 'results': [], 'rough_trace': rough_trace}
+    for i in range(nr_levels):
+        output_params['results'].append({'function_iters': 0, 'nr_ests': 0, 'ests_avg': 0.0,
+                                         'ests_dev': 0.0, 'level_complexity': 0.0,
+                                         'loops': np.zeros(shape, dtype=np.complex128),
+                                         'loop_devs': np.zeros(shape),
+                                         'loop_ests': np.zeros((0,) + shape, dtype=np.complex128),
+                                         'converged': np.ones(shape, dtype=bool)})
+
+    # tolerance split between the difference levels               stoch_trace.py:327-336
+    if nr_levels == 3:
+        frac0, frac1 = 0.8, 0.2
+    else:
+        frac0, frac1 = 0.45, 0.45
+    if skip_level:
+        frac0 = frac0 + frac1
+
+    print("\nResetting timer to zero ...", end='')
+    mg_solver.timer.reset()
+    mg_solver.engine.timers_reset()
+    print(" done\n")
+    mg_solver.coarsest_lev_iters[0] = 0
+    levels = mg_solver.ml.levels
+    res = output_params['results']
+
+    for i in range(nr_levels - 1):
+        if skip_level and i == 1:
+            continue
+        t0 = time.time()
+        if i == 0:
+            tol_fctr = sqrt(frac0)
+        elif i == 1:
+            tol_fctr = sqrt(frac1)
+        elif skip_level:
+            tol_fctr = sqrt(1.0 - frac0) / sqrt(nr_levels - 3)
+        else:
+            tol_fctr = sqrt(1.0 - frac0 - frac1) / sqrt(nr_levels - 3)
+        level_tols = np.abs(params['tol'] * rough * tol_fctr)
+        n_i = levels[i].A.shape[0]
+        lc = i + 2 if (skip_level and i == 0) else i + 1
+        print("Computing for level " + str(i) + " ...", end='', flush=True)
+        loop = run_probe_loop_displaced(DeviceMLMCLoopProbes(mg_solver, params, i, zero, kind), n_i, level_tols,
+                                        control, params['max_nr_ests'], batch * max(1, len(_engines(mg_solver))),
+                                        probe_type=kind)
+        res[i]['function_iters'] += int(np.sum(loop["iters_fine"]))
+        res[lc]['function_iters'] += int(np.sum(loop["iters_coarse"]))
+        mg_solver.coarsest_lev_iters[i] += int(np.sum(loop["iters_fine"]))
+        res[i]['nr_ests'] += loop["index"]
+        res[i]['ests_avg'] = loop["avg"]
+        res[i]['ests_dev'] = loop["dev"]
+        res[i]['ests'] = loop["ests"][:, control]  # build-only extras
+        res[i]['level_tol'] = level_tols[control]
+        res[i]['probe_loop_s'] = time.time() - t0
+        res[i]['probes_solved'] = loop["solved"]
+        res[i]['loops'] = loop["avgs"][:control].reshape(shape)
+        res[i]['loop_devs'] = loop["devs"][:control].reshape(shape)
+        res[i]['loop_ests'] = loop["ests"][:, :control].reshape((-1,) + shape)
+        res[i]['converged'] = loop["converged"][:control].reshape(shape)
+        print(" done. Time : " + str(time.time() - t0) + " seconds")
+
+    # coarsest level, computed directly                            stoch_trace.py:418-437
+    last = nr_levels - 1
+    if levels[last].A.shape[0] == 1:
+        raise Exception("your coarsest-level matrix is of size 1 ... is this what you want?")
+    res[last]['nr_ests'] += 1
+    res[last]['loops'] = mg_solver.engine.coarsest_loops()
+    res[last]['ests_avg'] = np.trace(mg_solver.coarsest_inv)
+    res[last]['ests_dev'] = 0
+
+    # work model                                                    stoch_trace.py:443-467
+    for i in range(nr_levels - 1):
+        res[i]['level_complexity'] = res[i]['function_iters'] * flopsV_manual(i, levels, i, mg_solver)
+        res[i]['level_complexity'] += levels[last].A.nnz * mg_solver.coarsest_lev_iters[i]
+    nc = levels[last].A.shape[0]
+    res[last]['level_complexity'] = pow(nc, 3) + res[last]['function_iters'] * pow(nc, 2)
+    output_params['loops'] = np.zeros(shape, dtype=np.complex128)
+    var = np.zeros(shape)
+    for i in range(nr_levels):
+        output_params['total_complexity'] += res[i]['level_complexity']
+        output_params['trace'] += res[i]['ests_avg']
+        output_params['loops'] = output_params['loops'] + res[i]['loops']
+        if i < last:
+            var = var + np.square(res[i]['loop_devs']) / (res[i]['nr_ests'] + 1)
+    output_params['loop_errs'] = np.sqrt(var)
+    output_params['momenta'] = list(momenta)
     mg_solver.sync_timer()
     print(mg_solver.timer)
     return output_params

@@ -8,7 +8,8 @@ from scipy.sparse.linalg import eigsh
 
 from . import dist as _dist
 from .engine import (MAX_MOMENTA, MAX_SHIFTS, MODE_HUTCHINSON, MODE_HUTCHINSON_LOOPS, MODE_HUTCHINSON_SHIFTS,
-                     MODE_LEVEL, MODE_MLMC, MODE_MLMC_SKIP, MODE_TWO_POINT, EngineError)
+                     MODE_LEVEL, MODE_MLMC, MODE_MLMC_LOOPS, MODE_MLMC_LOOPS_SKIP, MODE_MLMC_SKIP, MODE_TWO_POINT,
+                     EngineError)
 
 
 # ----------------------------------------------------------------------------------------
@@ -218,6 +219,101 @@ def loop_correlator(per_probe_a, per_probe_b):
         ar = np.roll(a, -D, axis=1)                        # ar[k, t] = a[k, t + D]
         out[D] = np.sum(np.roll(Sa, -D) * Sb - np.sum(ar * b, axis=0)) / (N * (N - 1.0) * L)
     return out
+
+
+def slice_cdots(U, V, L, momenta):
+    """S_q(u, v) of the MLMC loops for a batch: out[k, p, a, b, t] = sum_x e^{-2 pi i p x / L} conj(U[k, idx(a,x,t)])
+    V[k, idx(b,x,t)], idx(s,x,y) = s L^2 + y L + x, for two complex arrays (nb, 2 L^2) -- the reduction of
+    MODE_MLMC_LOOPS on the prolonged probe U and the prolonged difference V (phases as the engine's table)."""
+    U = np.atleast_2d(np.asarray(U))
+    V = np.atleast_2d(np.asarray(V))
+    if U.shape != V.shape or U.shape[1] != 2 * L * L:
+        raise Exception("slice_cdots: U %s and V %s, expected two equal (nb, %d)" % (U.shape, V.shape, 2 * L * L))
+    ph = _phase_table(L)[np.outer(np.asarray(momenta, dtype=np.int64), np.arange(L)) % L]
+    ph = ph.astype(np.result_type(U.dtype, V.dtype, np.complex128))
+    Ur, Vr = U.reshape(-1, 2, L, L), V.reshape(-1, 2, L, L)               # [k][s][t][x]
+    prod = Ur.conj()[:, :, None] * Vr[:, None]                            # [k][a][b][t][x]
+    return np.ascontiguousarray(np.moveaxis(prod @ ph.T, -1, 1))
+
+
+def block_loops(M, L, momenta):
+    """out[p][a][b][t] = sum_x e^{-2 pi i p x / L} M[idx(b,x,t), idx(a,x,t)] = Tr(Gamma_q M) of a dense 2 L^2 x 2 L^2
+    matrix: the loops that a probe average of slice_cdots(x, M x) converges to."""
+    M = np.asarray(M)
+    V = L * L
+    if M.shape != (2 * V, 2 * V):
+        raise Exception("block_loops: matrix of shape %s, expected (%d, %d)" % (M.shape, 2 * V, 2 * V))
+    ph = _phase_table(L)[np.outer(np.asarray(momenta, dtype=np.int64), np.arange(L)) % L]
+    out = np.zeros((len(momenta), 2, 2, L), dtype=np.complex128)
+    for a in range(2):
+        for b in range(2):
+            d = np.diagonal(M[b * V:(b + 1) * V, a * V:(a + 1) * V]).reshape(L, L)      # [t][x]
+            out[:, a, b, :] = ph @ d.T
+    return out
+
+
+def mlmc_level_loops_exact(levels, coarsest_inv, L, momenta, skip=False):
+    """The exact terms of the telescoping sum of the loops, from dense inverses (small lattices only):
+    (terms, coarsest) with terms[i][p][a][b][t] = Tr(Gamma_q Pi_i D_i Pi_i^H) for every level but the last,
+    D_i = A_i^-1 - P_i A_{i+1}^-1 R_i and Pi_i = P_0 ... P_{i-1} (skip: D_0 = A_0^-1 - P_0 P_1 A_2^-1 R_1 R_0 and
+    terms[1] = 0), and coarsest = Tr(Gamma_q Pi A_c^-1 Pi^H) with A_c^-1 = coarsest_inv.  Their sum is
+    block_loops(A_0^-1).  levels: objects with .A and .P (R = P^H), finest first."""
+    nl = len(levels)
+    if nl < 2:
+        raise Exception("mlmc_level_loops_exact needs at least two levels")
+    if skip and nl < 3:
+        raise Exception("level skipping needs at least three levels")
+    dense = lambda X: np.asarray(X.toarray() if hasattr(X, "toarray") else X, dtype=np.complex128)
+    P = [dense(levels[i].P) for i in range(nl - 1)]
+    inv = [np.linalg.inv(dense(levels[i].A)) for i in range(nl - 1)] + [dense(coarsest_inv)]
+    Pi = [np.eye(P[0].shape[0], dtype=np.complex128)]
+    for i in range(nl - 1):
+        Pi.append(Pi[i] @ P[i])
+    terms = []
+    for i in range(nl - 1):
+        if skip and i == 1:
+            terms.append(np.zeros((len(momenta), 2, 2, L), dtype=np.complex128))
+            continue
+        if skip and i == 0:
+            PP = P[0] @ P[1]
+            D = inv[0] - PP @ inv[2] @ PP.conj().T
+        else:
+            D = inv[i] - P[i] @ inv[i + 1] @ P[i].conj().T
+        terms.append(block_loops(Pi[i] @ D @ Pi[i].conj().T, L, momenta))
+    return terms, block_loops(Pi[nl - 1] @ inv[nl - 1] @ Pi[nl - 1].conj().T, L, momenta)
+
+
+def mlmc_loop_correlator(level_series_a, level_series_b, exact_a, exact_b):
+    """C[D] = (1/L) sum_t <L_a(t + D)> <L_b(t)>, D = 0..L-1, when each loop is a sum over independent MLMC levels:
+    level_series_x[i] holds the per-probe series (N_i, L) of level i's term (both loops from the same N_i probes),
+    exact_x (L,) is the exact coarsest term, a constant.  Pairs of different levels, and pairs with the constant,
+    take the product of the means; pairs within a level take loop_correlator's distinct-probe form, so no probe
+    meets itself and the estimate is unbiased."""
+    if len(level_series_a) != len(level_series_b):
+        raise Exception("mlmc_loop_correlator: %d and %d levels" % (len(level_series_a), len(level_series_b)))
+    ea = np.asarray(exact_a, dtype=np.complex128)
+    eb = np.asarray(exact_b, dtype=np.complex128)
+    if ea.ndim != 1 or ea.shape != eb.shape:
+        raise Exception("mlmc_loop_correlator: exact terms of shapes %s and %s, expected two equal (L,)"
+                        % (ea.shape, eb.shape))
+    L = ea.size
+
+    def of_means(ma, mb):
+        return np.array([np.sum(np.roll(ma, -D) * mb) for D in range(L)]) / L
+
+    sa, sb = ea.copy(), eb.copy()
+    out = np.zeros(L, dtype=np.complex128)
+    for a, b in zip(level_series_a, level_series_b):
+        a = np.asarray(a, dtype=np.complex128)
+        b = np.asarray(b, dtype=np.complex128)
+        if a.ndim != 2 or a.shape != b.shape or a.shape[1] != L:
+            raise Exception("mlmc_loop_correlator: level series of shapes %s and %s, expected two equal (N, %d)"
+                            % (a.shape, b.shape, L))
+        ma, mb = a.mean(axis=0), b.mean(axis=0)
+        sa += ma
+        sb += mb
+        out += loop_correlator(a, b) - of_means(ma, mb)
+    return out + of_means(sa, sb)
 
 
 def two_point_of(params):
@@ -685,6 +781,54 @@ def probe_batch_loops_generated(mg_solver, params, first_probe, count, kind="z2"
         eng.hutch_run(MODE_HUTCHINSON_LOOPS, 0, tol, maxiter)
         _, itf, itc = eng.hutch_fetch()
         return eng.hutch_fetch_loops(), itf, itc
+
+    if len(active) == 1:
+        res = [run(active[0])]
+    else:
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=len(active)) as pool:
+            res = list(pool.map(run, active))
+    return tuple(np.concatenate([r[k] for r in res]) for k in range(3))
+
+
+def _mlmc_loops_skip(mg_solver, level):
+    return bool(getattr(mg_solver, "skip_level", False)) and level == 0
+
+
+def _level_batch_args(mg_solver, params, level):
+    engs = _engines(mg_solver)
+    if not engs:
+        raise EngineError("no GPU engine attached (run MG.setup first)")
+    n = mg_solver.ml.levels[level].A.shape[0]
+    return engs, params['function_params']['tol'], n, (n if n < 1000 else 1000)
+
+
+def probe_batch_mlmc_loops(mg_solver, params, level, probes):
+    """One batch of probes of `level` through MODE_MLMC_LOOPS (MODE_MLMC_LOOPS_SKIP at level 0 with
+    mg_solver.skip_level): (loops[nb, nmom, 2, 2, L], iters_fine, iters_coarse), the level's term of the loops."""
+    engs, tol, _, maxiter = _level_batch_args(mg_solver, params, level)
+    return engs[0].hutch_batch_mlmc_loops(level, np.asarray(probes), tol, maxiter,
+                                          skip=_mlmc_loops_skip(mg_solver, level))
+
+
+def probe_batch_mlmc_loops_generated(mg_solver, params, level, first_probe, count, kind="z2"):
+    """probe_batch_mlmc_loops for the probes [first_probe, first_probe + count) of the stream the engines hold
+    (Engine.stream_set), generated on the device; several engine handles share the batch as in
+    probe_batch_generated."""
+    engs, tol, n, maxiter = _level_batch_args(mg_solver, params, level)
+    mode = MODE_MLMC_LOOPS_SKIP if _mlmc_loops_skip(mg_solver, level) else MODE_MLMC_LOOPS
+    ne = len(engs) if count >= 2 * 64 else 1
+    bounds = [(k * count) // ne for k in range(ne + 1)]
+    active = [k for k in range(ne) if bounds[k + 1] > bounds[k]]
+    for k in active:
+        engs[k].probes_generate(0, level, bounds[k + 1] - bounds[k], (first_probe + bounds[k]) * n, kind)
+
+    def run(k):
+        eng = engs[k]
+        eng.probes_select(0)
+        eng.hutch_run(mode, level, tol, maxiter)
+        _, itf, itc = eng.hutch_fetch()
+        return eng.hutch_fetch_mlmc_loops(), itf, itc
 
     if len(active) == 1:
         res = [run(active[0])]

@@ -305,6 +305,16 @@ int sw_apply_shift_dots(sw_engine* h, int nb, const int8_t* probes, const double
  * conj(x_k[idx(a,x,t)]) Z_k[idx(b,x,t)] for the registered momenta, idx(s,x,y) = s L^2 + y L + x; probes
  * int8[nb*n] (codes +-1, +-2 = +-i), Z complex128[nb*n], out complex128[nmom*2*2*L*nb]. */
 int sw_apply_slice_dots(sw_engine* h, int nb, const int8_t* probes, const double* Z, double* out);
+/* The slice-dot kernel with a complex left operand (SW_MODE_MLMC_LOOPS on coarse levels, sw_coarsest_loops) alone:
+ * out[p][a][b][t][k] = sum_x e^{-2 pi i p x / L} conj(U_k[idx(a,x,t)]) V_k[idx(b,x,t)] for the registered momenta;
+ * U, V complex128[nb*n] of the lattice level, out complex128[nmom*2*2*L*nb]. */
+int sw_apply_slice_cdots(sw_engine* h, int nb, const double* U, const double* V, double* out);
+/* The exact coarsest term of the MLMC loops (build-only): out[p][a][b][t] = sum_j S_q(Pi e_j, Pi A_c^-1 e_j) over the
+ * unit vectors e_j of the coarsest level of hid 0, Pi = P_0 ... P_{M-2}, S_q(u, v) = sum_x e^{-2 pi i p x / L}
+ * conj(u[idx(a,x,t)]) v[idx(b,x,t)], for the registered momenta (sw_set_loop_momenta): 64-column blocks of the
+ * identity and of the coarsest inverse prolonged to the lattice and reduced on the device, summed in a fixed
+ * order (two calls agree bit for bit).  out complex128[nmom*2*2*L]. */
+int sw_coarsest_loops(sw_engine* h, double* out);
 /* The source kernel of SW_MODE_TWO_POINT alone: out[2 j + a][k][i] = the source eta_k^(j,a) of the registration
  * (sw_set_two_point) in the reference ordering, delta_{a,a'} delta_{t,t0} e^{+2 pi i p_j y / L} xi_k(y) at
  * i = idx(a',y,t), xi_k(y) = the code of probe k at idx(0,y,t0); probes int8[nb*n], out complex128[2*nmom*nb*n]. */
@@ -348,6 +358,17 @@ int sw_solve(sw_engine* h, int hid, int level0, int nb, const double* B, double*
                                   xi_k(y); one solve runs over all 2 nmom pad64(nb) columns.  sw_hutch_fetch
                                   returns sum_t sum_ac T[j0][a][a][c][c][t] = sum_a ||z^(j0,a)||^2 and, as the
                                   fine iteration count of a noise, the largest count among its 2 nmom columns. */
+#define SW_MODE_MLMC_LOOPS 7    /* l_k[p][a][b][t] = S_q(Pi_l x_k, Pi_l d_k), S_q(u, v) = sum_x e^{-2 pi i p x / L}
+                                  conj(u[idx(a,x,t)]) v[idx(b,x,t)], d_k = A_l^-1 x_k - P_l A_{l+1}^-1 R_l x_k the
+                                  MLMC difference of the plain probe at `level` of hid 0, Pi_l = P_0 ... P_{l-1}
+                                  (Pi_0 = I), for the momenta of sw_set_loop_momenta: the level term of the
+                                  timeslice loops (build-only).  Solves and iteration counts as SW_MODE_MLMC;
+                                  sw_set_perm / sw_set_rhsmap are ignored (as HUTCHINSON_LOOPS ignores sw_set_perm)
+                                  and a level with MLMC-level deflation vectors is refused.  sw_hutch_fetch returns
+                                  sum_t (l[0][0][t] + l[1][1][t]) of the FIRST registered momentum, which is
+                                  x^H d -- the SW_MODE_MLMC value of the probe -- when that momentum is 0 */
+#define SW_MODE_MLMC_LOOPS_SKIP 8 /* the same with d_k = A_0^-1 x_k - P_0 P_1 A_2^-1 R_1 R_0 x_k, level 0 only
+                                  (as SW_MODE_MLMC_SKIP) */
 /* One batch of probes x_k in {-1,+1}^n (int8, nb*n, reference ordering) at `level`
  * (build-only extension: entries +-2 encode +-i, i.e. Z4 probes {1,i,-1,-i}):
  *   HUTCHINSON: e_k = x^H A^-1 Pperm^T (x - U U^H x)
@@ -386,6 +407,9 @@ int sw_hutch_fetch_shifts(sw_engine* h, double* ests);
  * probe k of the batch (sw_hutch_fetch returns the scalar total of the first momentum and the iteration
  * counts). */
 int sw_hutch_fetch_loops(sw_engine* h, double* out);
+/* After a SW_MODE_MLMC_LOOPS / _SKIP batch: out complex128[nmom][2][2][L][nb], the level loops of every probe of the
+ * batch (a buffer of its own: sw_hutch_fetch_loops keeps returning the last SW_MODE_HUTCHINSON_LOOPS batch). */
+int sw_hutch_fetch_mlmc_loops(sw_engine* h, double* out);
 /* After a SW_MODE_TWO_POINT batch: out complex128[nmom][2][2][2][2][L][nb], the pair sums T_k[j][a][b][c][d][t] of
  * every noise k of the batch.  The results of the modes 4, 5 and 6 live in buffers of their own: each fetch
  * returns its own mode's last batch whatever ran since. */
@@ -425,6 +449,7 @@ int sw_timers_reset(sw_engine* h);
 #define SW_KCLASS_SCHUR 15          /* k_schur_step / k_eo_hop, even-odd smoother  */
 #define SW_KCLASS_TP_SOURCES 17     /* k_slice_sources (SW_MODE_TWO_POINT); in sw_timers: other */
 #define SW_KCLASS_TP_DOTS 18        /* k_slice_pair_dots, k_pair_total (SW_MODE_TWO_POINT); in sw_timers: dots */
+#define SW_KCLASS_SLICE_CDOTS 19    /* k_slice_cdots (SW_MODE_MLMC_LOOPS, sw_coarsest_loops); in sw_timers: dots */
 int sw_kernel_stats(sw_engine* h, int which, double* total_ms, int64_t* launches);
 /* Floating-point operations issued by the launches of an MFMA kernel class since the last reset
  * (profiling on): 8 flops per complex multiply-add over every (row tile, k-step, probe). */
