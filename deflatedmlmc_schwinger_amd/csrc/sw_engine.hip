@@ -4944,6 +4944,87 @@ int sw_coarsest_loops(sw_engine* h, double* out) {
   return 0;
 }
 
+// The deflated part of a level's term of the MLMC loops: out[p][a][b][t] = sum_j S_q(Pi V_j, Pi D V_j) over the
+// vectors V_j registered at `level` (sw_set_level_deflation), D the level's difference operator built as the probe
+// body of sw_hutch_run builds it (fine solve on the solver hierarchy at level 0 when it is ready, R / P of hierarchy
+// 0, coarse solve on hierarchy 0), Pi = P_0 ... P_{level-1}.  64 columns of V per pass; the passes are added in
+// ascending order on the device and the 64 columns by one host loop in ascending order (as sw_coarsest_loops), so
+// two calls agree bit for bit.  The probe workspace and the loop buffers of the modes are not touched.
+int sw_level_deflation_loops(sw_engine* h, int level, int skip, double tol, int maxiter, double* out) {
+  SWCHK(check_hier(h, 0, level, true));
+  if (!out) return sw_fail(h, "null output");
+  if (skip != 0 && skip != 1) return sw_fail(h, "skip must be 0 or 1");
+  if (maxiter < 1) return sw_fail(h, "maxiter must be >= 1");
+  if (h->momenta.empty()) return sw_fail(h, "no momenta registered (sw_set_loop_momenta)");
+  Hier& H0 = h->hier[0];
+  if (skip && level != 0) return sw_fail(h, "level skipping is defined for level 0 only");
+  const int lcoarse = level + (skip ? 2 : 1);
+  if (lcoarse >= H0.nlevels) return sw_fail(h, "no coarse level %d", lcoarse);
+  const int k = h->lkd[level];
+  if (k <= 0 || !h->lV[level]) return sw_fail(h, "no deflation vectors registered at level %d", level);
+  HIPCHK(hipSetDevice(h->device));
+  Level& lv0 = H0.lv[0];
+  Level& lv = H0.lv[level];
+  const int n = lv.n, n1 = H0.lv[level + 1].n, nbp = 64, L = lv0.L, ld = defl_ld(k);
+  const int fine_hid = (level == 0 && h->hier[h->solver_hid].ready) ? h->solver_hid : 0;
+  if (fine_hid != 0 && h->hier[fine_hid].lv[0].n != n) return sw_fail(h, "solver hierarchy level-0 size mismatch");
+  const size_t rows = h->momenta.size() * 4 * (size_t)L;
+  DevBuf<cplx> X(h), Z(h), Dv(h), ca(h), cb(h), s[4] = {DevBuf<cplx>(h), DevBuf<cplx>(h), DevBuf<cplx>(h), DevBuf<cplx>(h)},
+      acc(h), part(h);
+  SWCHK(dev_realloc(h, &X.p, (size_t)n * nbp));
+  SWCHK(dev_realloc(h, &Z.p, (size_t)n * nbp));
+  SWCHK(dev_realloc(h, &Dv.p, (size_t)n * nbp));
+  // two coarse blocks of the level below (with skip the level two below is smaller and fits in them)
+  SWCHK(dev_realloc(h, &ca.p, (size_t)n1 * nbp));
+  SWCHK(dev_realloc(h, &cb.p, (size_t)n1 * nbp));
+  int nmax = 0;
+  for (int l = 0; l < H0.nlevels; ++l) nmax = std::max(nmax, H0.lv[l].n);
+  if (level > 0)
+    for (auto& b : s) SWCHK(dev_realloc(h, &b.p, (size_t)nmax * nbp));
+  SWCHK(dev_realloc(h, &acc.p, rows * nbp));
+  SWCHK(dev_realloc(h, &part.p, rows * nbp));
+  SWCHK(zero_vec(h, acc, (int)rows, nbp));
+  for (int j0 = 0; j0 < k; j0 += 64) {
+    // x = the columns [j0, j0 + 64) of V, zero beyond the last vector (a zero column adds exact zeros)
+    const int nc = std::min(64, k - j0);
+    SWCHK(zero_vec(h, X, n, nbp));
+    HIPCHK(hipMemcpy2DAsync(X.p, (size_t)nbp * sizeof(cplx), h->lV[level] + j0, (size_t)ld * sizeof(cplx),
+                            (size_t)nc * sizeof(cplx), (size_t)n, hipMemcpyDeviceToDevice, h->stream));
+    // xc = R x (skip: R_1 R_0 x), z = A_l^-1 x, y = A_c^-1 xc, d = z - P y (skip: z - P_0 P_1 y)
+    SWCHK(launch_ell(h, lv.R, 0, X, nullptr, ca, nbp, T_R));
+    const cplx* xc = ca;
+    cplx* y = cb;
+    if (skip) {
+      SWCHK(launch_ell(h, H0.lv[1].R, 0, ca, nullptr, cb, nbp, T_R));
+      xc = cb;
+      y = ca;
+    }
+    int total_f = 0, total_c = 0;
+    SWCHK(solve_dev(h, fine_hid, level, X, Z, tol, maxiter, nbp, &total_f));
+    SWCHK(solve_dev(h, 0, lcoarse, xc, y, tol, maxiter, nbp, &total_c));
+    if (skip) {
+      SWCHK(launch_ell(h, H0.lv[1].P, 0, y, nullptr, cb, nbp, T_P));
+      y = cb;
+    }
+    SWCHK(launch_ell(h, lv.P, 1, y, Z, Dv, nbp, T_P));
+    const cplx *u, *v;
+    SWCHK(prolong_to_lattice(h, level, X, s[0], s[1], nbp, &u));
+    SWCHK(prolong_to_lattice(h, level, Dv, s[2], s[3], nbp, &v));
+    SWCHK(slice_cdots_into(h, lv0, u, v, nbp, part));
+    SWCHK(vec_add(h, acc, part, acc, (int)rows, nbp));
+  }
+  SWCHK(stream_sync(h));
+  std::vector<std::complex<double>> ha(rows * nbp);
+  HIPCHK(hipMemcpy(ha.data(), acc.p, ha.size() * sizeof(cplx), hipMemcpyDeviceToHost));
+  for (size_t r = 0; r < rows; ++r) {
+    std::complex<double> sum(0.0, 0.0);
+    for (int c = 0; c < nbp; ++c) sum += ha[r * nbp + c];
+    out[2 * r] = sum.real();
+    out[2 * r + 1] = sum.imag();
+  }
+  return 0;
+}
+
 // ---- one-end-trick two-point functions from timeslice sources ------------------------------------------
 int sw_set_two_point(sw_engine* h, int t0, int nmom, const int32_t* p) {
   SWCHK(check_hier(h, 0, 0, false));
@@ -5089,10 +5170,12 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
     if (level != 0) return sw_fail(h, "two-point mode runs at level 0");
     if (h->tp_momenta.empty()) return sw_fail(h, "no two-point registration (sw_set_two_point)");
   }
-  const bool mloops = (mode == SW_MODE_MLMC_LOOPS || mode == SW_MODE_MLMC_LOOPS_SKIP);
+  // the deflated level loops: modes 7 / 8 with the level's registered projection on the right-hand side
+  const bool dloops = (mode == SW_MODE_MLMC_DEFL_LOOPS || mode == SW_MODE_MLMC_DEFL_LOOPS_SKIP);
+  const bool mloops = (mode == SW_MODE_MLMC_LOOPS || mode == SW_MODE_MLMC_LOOPS_SKIP || dloops);
   if (mloops) {
     if (h->momenta.empty()) return sw_fail(h, "no momenta registered (sw_set_loop_momenta)");
-    if (h->lkd[level] > 0)
+    if (!dloops && h->lkd[level] > 0)
       return sw_fail(h, "MLMC loops do not combine with MLMC-level deflation (level %d holds %d vectors)", level,
                      h->lkd[level]);
   }
@@ -5209,14 +5292,16 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
     return 0;
   }
   if (mode != SW_MODE_MLMC && mode != SW_MODE_MLMC_SKIP && !mloops) return sw_fail(h, "unknown mode %d", mode);
-  const bool skip = (mode == SW_MODE_MLMC_SKIP || mode == SW_MODE_MLMC_LOOPS_SKIP);
+  const bool skip = (mode == SW_MODE_MLMC_SKIP || mode == SW_MODE_MLMC_LOOPS_SKIP ||
+                     mode == SW_MODE_MLMC_DEFL_LOOPS_SKIP);
   if (skip && level != 0) return sw_fail(h, "level skipping is defined for level 0 only");
   const int lcoarse = level + (skip ? 2 : 1);
   if (lcoarse >= H0.nlevels) return sw_fail(h, "no coarse level %d", lcoarse);
   // x_def = Bblock_perm * Pperm^T * x0      utils.py:288-290
   const cplx* xdef = h->pb_x0;
   if (h->lkd[level] > 0) {
-    // x_def = x0 - V V^H x0                 utils.py:260-266 (defl_type exact / inexact_01)
+    // x_def = x0 - V V^H x0                 utils.py:260-266 (defl_type exact / inexact_01); the deflated level
+    // loops solve and restrict x_def too, and keep the plain x0 (level 0: the int8 codes) as the left operand
     SWCHK(deflate(h, h->lV[level], h->lkd[level], nullptr, h->pb_x0, h->pb_xd, n, nbp));
     xdef = h->pb_xd;
   }

@@ -24,6 +24,8 @@ MODE_HUTCHINSON_LOOPS = 5
 MODE_TWO_POINT = 6
 MODE_MLMC_LOOPS = 7
 MODE_MLMC_LOOPS_SKIP = 8
+MODE_MLMC_DEFL_LOOPS = 9
+MODE_MLMC_DEFL_LOOPS_SKIP = 10
 KCLASS_TP_SOURCES = 17     # sw_kernel_stats classes of the two-point kernels
 KCLASS_TP_DOTS = 18
 KCLASS_SLICE_CDOTS = 19    # ... and of k_slice_cdots (MLMC loops)
@@ -173,6 +175,7 @@ def load_library():
     sig("sw_apply_slice_cdots", i32, vp, i32, vp, vp, vp)
     sig("sw_coarsest_loops", i32, vp, vp)
     sig("sw_hutch_fetch_mlmc_loops", i32, vp, vp)
+    sig("sw_level_deflation_loops", i32, vp, i32, i32, dbl, i32, vp)
     _lib = lib
     return lib
 
@@ -196,7 +199,7 @@ EXPORTED_SYMBOLS = (
     "sw_set_shifts", "sw_hutch_fetch_shifts", "sw_apply_shift_dots",
     "sw_set_loop_momenta", "sw_hutch_fetch_loops", "sw_apply_slice_dots",
     "sw_set_two_point", "sw_hutch_fetch_two_point", "sw_apply_slice_sources", "sw_apply_pair_dots",
-    "sw_apply_slice_cdots", "sw_coarsest_loops", "sw_hutch_fetch_mlmc_loops",
+    "sw_apply_slice_cdots", "sw_coarsest_loops", "sw_hutch_fetch_mlmc_loops", "sw_level_deflation_loops",
 )
 
 
@@ -660,10 +663,14 @@ class Engine:
                   "sw_apply_slice_dots")
         return np.ascontiguousarray(np.moveaxis(out, -1, 0))
 
-    def hutch_batch_mlmc_loops(self, level, probes, tol, maxiter=1000, skip=False):
+    def hutch_batch_mlmc_loops(self, level, probes, tol, maxiter=1000, skip=False, deflated=False):
         """One MODE_MLMC_LOOPS batch (skip: MODE_MLMC_LOOPS_SKIP) at `level`: (loops[nb, nmom, 2, 2, L], iters_fine[nb],
-        iters_coarse[nb]), loops[k, p, a, b, t] = S_q(Pi_l x_k, Pi_l d_k) with d_k the MLMC difference of probe k."""
-        mode = MODE_MLMC_LOOPS_SKIP if skip else MODE_MLMC_LOOPS
+        iters_coarse[nb]), loops[k, p, a, b, t] = S_q(Pi_l x_k, Pi_l d_k) with d_k the MLMC difference of probe k.
+        deflated: MODE_MLMC_DEFL_LOOPS / _SKIP, d_k the difference of x_k - V V^H x_k for the level's registered V."""
+        if deflated:
+            mode = MODE_MLMC_DEFL_LOOPS_SKIP if skip else MODE_MLMC_DEFL_LOOPS
+        else:
+            mode = MODE_MLMC_LOOPS_SKIP if skip else MODE_MLMC_LOOPS
         _, itf, itc = self.hutch_batch(mode, level, probes, tol, maxiter)
         self._nb_uploaded = itf.size
         return self.hutch_fetch_mlmc_loops(), itf, itc
@@ -690,6 +697,14 @@ class Engine:
         """The exact coarsest term of the MLMC loops, shape (nmom, 2, 2, L): sum_j S_q(Pi e_j, Pi A_c^-1 e_j)."""
         out = np.zeros(self._loop_shape(1)[:-1], dtype=np.complex128)
         self._chk(self._lib.sw_coarsest_loops(self._h, _ptr(out)), "sw_coarsest_loops")
+        return out
+
+    def level_deflation_loops(self, level, skip=False, tol=1e-12, maxiter=1000):
+        """The deflated part of level `level`'s term of the MLMC loops, shape (nmom, 2, 2, L): sum_j S_q(Pi V_j,
+        Pi D V_j) over the vectors registered with set_level_deflation, D applied on the device (solves to `tol`)."""
+        out = np.zeros(self._loop_shape(1)[:-1], dtype=np.complex128)
+        self._chk(self._lib.sw_level_deflation_loops(self._h, int(level), int(bool(skip)), float(tol), int(maxiter),
+                                                     _ptr(out)), "sw_level_deflation_loops")
         return out
 
     def set_two_point(self, t0, momenta):

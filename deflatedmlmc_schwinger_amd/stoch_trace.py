@@ -232,12 +232,13 @@ class DeviceMLMCLoopProbes:
     """Probe source of the MLMC loop flow: the probes of `level` through MODE_MLMC_LOOPS; one row of loop_columns
     per probe, the control column being the scalar MLMC difference x^H (z - P y) of the probe."""
 
-    def __init__(self, mg_solver, params, level, zero, kind="z2"):
+    def __init__(self, mg_solver, params, level, zero, kind="z2", deflated=False):
         self.mg_solver = mg_solver
         self.params = params
         self.level = level
         self.zero = zero
         self.kind = kind
+        self.deflated = deflated       # MODE_MLMC_DEFL_LOOPS: the level's registered projection on the right
 
     def begin(self, entry_stream):
         window = entry_stream.window()
@@ -246,7 +247,7 @@ class DeviceMLMCLoopProbes:
 
     def __call__(self, first_probe, count):
         e, f, c = probe_batch_mlmc_loops_generated(self.mg_solver, self.params, self.level, first_probe, count,
-                                                   self.kind)
+                                                   self.kind, deflated=self.deflated)
         return loop_columns(e, self.zero), f, c
 
 
@@ -825,23 +826,30 @@ def mlmc(A, params):
     return output_params
 
 
-def _mlmc_loops_checks(params):
-    """The validation of mlmc_loops(), before any setup: (momenta, skip_level)."""
+def _mlmc_loops_checks(params, deflated=False):
+    """The validation of mlmc_loops() (deflated: of deflated_mlmc_loops()), before any setup: (momenta, skip_level)."""
+    who = "deflated_mlmc_loops" if deflated else "mlmc_loops"
     has = hasattr(params, "get")
     if has and params.get('source_timeslice') is not None:
-        raise Exception("source_timeslice belongs to two_point(), not to mlmc_loops()")
+        raise Exception("source_timeslice belongs to two_point(), not to %s()" % who)
     if has and params.get('x_displacements') is not None:
         raise Exception("x_displacements does not combine with the MLMC loops")
     momenta = loops_of(params)
     if momenta is None:
-        raise Exception("mlmc_loops() needs the key timeslice_loops")
-    if any(int(k) != 0 for k in params['mlmc_deflat_vctrs']):
+        raise Exception("%s() needs the key timeslice_loops" % who)
+    if deflated:
+        mlmc_defl_setup_of(params)
+        if params['defl_type'] in ("inexact_02", "inexact_03"):
+            raise Exception("deflated_mlmc_loops() computes the deflated part from applications of the difference "
+                            "operators (the inexact_01 form): defl_type %s is not defined for it"
+                            % params['defl_type'])
+    elif any(int(k) != 0 for k in params['mlmc_deflat_vctrs']):
         raise Exception("mlmc_loops() runs without MLMC-level deflation (mlmc_deflat_vctrs all zero): the deflated "
                         "part would need a sliced tr1 of the difference operators")
     if params['coarsest_level_directly'] != True:   # noqa: E712  (as mlmc() tests it)
-        raise Exception("mlmc_loops() computes the coarsest term exactly: coarsest_level_directly has to be true")
+        raise Exception("%s() computes the coarsest term exactly: coarsest_level_directly has to be true" % who)
     if _dist.default_comm().world > 1:
-        raise Exception("MLMC loops (mlmc_loops) run on one rank")
+        raise Exception("MLMC loops (%s) run on one rank" % who)
     skip_list = params['mlmc_levels_to_skip']
     if len(skip_list) > 1:
         raise Exception("Only allowed to skip one level for now")
@@ -867,7 +875,25 @@ def mlmc_loops(A, params):
     Returns mlmc()'s dictionary (trace estimates Tr(A^-1)) with, per level, results[i]['loops' | 'loop_devs' |
     'loop_ests' | 'converged'] (the last level's loops are exact), and at top level loops = the sum over the levels,
     loop_errs = sqrt(sum_i loop_devs_i^2 / (nr_ests_i + 1)) and momenta."""
-    momenta, skip_level = _mlmc_loops_checks(params)
+    return _mlmc_loops_flow(A, params, False)
+
+
+def deflated_mlmc_loops(A, params):
+    """mlmc_loops() with MLMC-level deflation of the difference operators: for the vectors V_i of
+    level i (mlmc_deflat_vctrs[i] of them, computed and registered as mlmc() does, mlmc_defl_setup honoured)
+
+        Tr(Pi_i^H Gamma_q Pi_i D_i) = E_x[ S_q(Pi_i x, Pi_i D_i (x - V_i V_i^H x)) ] + sum_j S_q(Pi_i V_j, Pi_i D_i V_j)
+
+    the first term from probes through MODE_MLMC_DEFL_LOOPS, the second (results[i]['loop_tr1']) exactly from one
+    application of D_i to V_i at function_params['tol'] (Engine.level_deflation_loops) -- never from eigenvalues, so
+    the accuracy of the vectors changes the variance only.  results[i]['loops'] = probe mean + loop_tr1 (loop_ests
+    stay the per-probe series without it), ests_avg = control mean + the scalar total of loop_tr1.  defl_type
+    inexact_02 / inexact_03 raise; everything else as mlmc_loops()."""
+    return _mlmc_loops_flow(A, params, True)
+
+
+def _mlmc_loops_flow(A, params, deflated):
+    momenta, skip_level = _mlmc_loops_checks(params, deflated)
     mg_solver, nr_levels = _setup_solver(A, params)
     N = A.shape[0]
     L = int(params['latt_dims'][0])
@@ -880,16 +906,35 @@ def mlmc_loops(A, params):
     print("\nResetting timer to zero ...", end='')
     mg_solver.timer.reset()
     print(" done\n")
+    register_loop_momenta(mg_solver, momenta)
+    loop_tr1 = [np.zeros(shape, dtype=np.complex128) for _ in range(nr_levels)]
+    if deflated:
+        print("Computing deflation vectors ...", end='', flush=True)
+        t0 = time.time()
     for ix in range(nr_levels - 1):
-        # no MLMC-level deflation: clears what an earlier flow on these engines may have registered
-        deflation_pre_computations(A, 0, params['defl_eigvs_tol_MLMC'], "mlmc", mg_solver.timer, params, mg_solver,
-                                   None, level_nr=ix)
+        # mlmc_loops(): no MLMC-level deflation, which clears what an earlier flow on these engines may have
+        # registered; deflated_mlmc_loops(): the vectors of mlmc() (stoch_trace.py:257-270), then their sliced tr1
+        k_ix = int(params['mlmc_deflat_vctrs'][ix]) if deflated and not (skip_level and ix == 1) else 0
+        lop = None
+        if k_ix > 0:
+            mg_solver.level_for_diff_op = ix
+            n_ix = mg_solver.ml.levels[ix].A.shape[0]
+            lop = LinearOperator((n_ix, n_ix), dtype=np.complex128,
+                                 matvec=lambda v: mg_solver.diff_op_Q(np.array(v, dtype=np.complex128)))
+        deflation_pre_computations(A, k_ix, params['defl_eigvs_tol_MLMC'], "mlmc", mg_solver.timer, params, mg_solver,
+                                   lop, level_nr=ix)
+        if k_ix > 0:
+            n_ix = mg_solver.ml.levels[ix].A.shape[0]
+            loop_tr1[ix] = mg_solver.engine.level_deflation_loops(ix, skip_level and ix == 0,
+                                                                  params['function_params']['tol'],
+                                                                  n_ix if n_ix < 1000 else 1000)
+    if deflated:
+        print(" done. Time : " + str(time.time() - t0) + " seconds")
     print("Computing deflation vectors (for rough estimation purposes only) ...", end='', flush=True)
     t0 = time.time()
     Vx, tr1 = deflation_pre_computations(A, params['nr_deflat_vctrs'], params['defl_eigvs_tol_Hutch'], "hutchinson",
                                          mg_solver.timer, params, mg_solver)
     tr1_cols = loop_columns(np.asarray(tr1, dtype=np.complex128)[None], zero)[0]
-    register_loop_momenta(mg_solver, momenta)
     print(" done. Time : " + str(time.time() - t0) + " seconds")
     print("\nComputing rough estimation of the loops ...", end='', flush=True)
     np.random.seed(123456)                                      # stoch_trace.py:288-302
@@ -942,9 +987,9 @@ def mlmc_loops(A, params):
         n_i = levels[i].A.shape[0]
         lc = i + 2 if (skip_level and i == 0) else i + 1
         print("Computing for level " + str(i) + " ...", end='', flush=True)
-        loop = run_probe_loop_displaced(DeviceMLMCLoopProbes(mg_solver, params, i, zero, kind), n_i, level_tols,
-                                        control, params['max_nr_ests'], batch * max(1, len(_engines(mg_solver))),
-                                        probe_type=kind)
+        loop = run_probe_loop_displaced(DeviceMLMCLoopProbes(mg_solver, params, i, zero, kind, deflated), n_i,
+                                        level_tols, control, params['max_nr_ests'],
+                                        batch * max(1, len(_engines(mg_solver))), probe_type=kind)
         res[i]['function_iters'] += int(np.sum(loop["iters_fine"]))
         res[lc]['function_iters'] += int(np.sum(loop["iters_coarse"]))
         mg_solver.coarsest_lev_iters[i] += int(np.sum(loop["iters_fine"]))
@@ -959,6 +1004,12 @@ def mlmc_loops(A, params):
         res[i]['loop_devs'] = loop["devs"][:control].reshape(shape)
         res[i]['loop_ests'] = loop["ests"][:, :control].reshape((-1,) + shape)
         res[i]['converged'] = loop["converged"][:control].reshape(shape)
+        if deflated:
+            # the exact deflated part: added to the means, the per-probe series stay as the probes gave them
+            t1 = loop_columns(loop_tr1[i][None], zero)[0]
+            res[i]['ests_avg'] = loop["avg"] + t1[control]
+            res[i]['loops'] = res[i]['loops'] + loop_tr1[i]
+            res[i]['loop_tr1'] = loop_tr1[i]
         print(" done. Time : " + str(time.time() - t0) + " seconds")
 
     # coarsest level, computed directly                            stoch_trace.py:418-437

@@ -8,8 +8,8 @@ from scipy.sparse.linalg import eigsh
 
 from . import dist as _dist
 from .engine import (MAX_MOMENTA, MAX_SHIFTS, MODE_HUTCHINSON, MODE_HUTCHINSON_LOOPS, MODE_HUTCHINSON_SHIFTS,
-                     MODE_LEVEL, MODE_MLMC, MODE_MLMC_LOOPS, MODE_MLMC_LOOPS_SKIP, MODE_MLMC_SKIP, MODE_TWO_POINT,
-                     EngineError)
+                     MODE_LEVEL, MODE_MLMC, MODE_MLMC_DEFL_LOOPS, MODE_MLMC_DEFL_LOOPS_SKIP, MODE_MLMC_LOOPS,
+                     MODE_MLMC_LOOPS_SKIP, MODE_MLMC_SKIP, MODE_TWO_POINT, EngineError)
 
 
 # ----------------------------------------------------------------------------------------
@@ -234,6 +234,13 @@ def slice_cdots(U, V, L, momenta):
     Ur, Vr = U.reshape(-1, 2, L, L), V.reshape(-1, 2, L, L)               # [k][s][t][x]
     prod = Ur.conj()[:, :, None] * Vr[:, None]                            # [k][a][b][t][x]
     return np.ascontiguousarray(np.moveaxis(prod @ ph.T, -1, 1))
+
+
+def sliced_level_tr1(PiV, PiDV, L, momenta):
+    """The deflated part of one level's term of the MLMC loops: tr1[p][a][b][t] = sum_j S_q(Pi V_j, Pi D V_j) from
+    the prolonged vectors PiV and the prolonged D V, both (k, 2 L^2) -- what Engine.level_deflation_loops computes.
+    With E_x[S_q(Pi x, Pi D (x - V V^H x))] it adds up to Tr(Pi^H Gamma_q Pi D) for any V."""
+    return slice_cdots(PiV, PiDV, L, momenta).sum(axis=0)
 
 
 def block_loops(M, L, momenta):
@@ -803,20 +810,24 @@ def _level_batch_args(mg_solver, params, level):
     return engs, params['function_params']['tol'], n, (n if n < 1000 else 1000)
 
 
-def probe_batch_mlmc_loops(mg_solver, params, level, probes):
+def probe_batch_mlmc_loops(mg_solver, params, level, probes, deflated=False):
     """One batch of probes of `level` through MODE_MLMC_LOOPS (MODE_MLMC_LOOPS_SKIP at level 0 with
-    mg_solver.skip_level): (loops[nb, nmom, 2, 2, L], iters_fine, iters_coarse), the level's term of the loops."""
+    mg_solver.skip_level): (loops[nb, nmom, 2, 2, L], iters_fine, iters_coarse), the level's term of the loops.
+    deflated: through MODE_MLMC_DEFL_LOOPS / _SKIP, with the level's registered projection."""
     engs, tol, _, maxiter = _level_batch_args(mg_solver, params, level)
     return engs[0].hutch_batch_mlmc_loops(level, np.asarray(probes), tol, maxiter,
-                                          skip=_mlmc_loops_skip(mg_solver, level))
+                                          skip=_mlmc_loops_skip(mg_solver, level), deflated=deflated)
 
 
-def probe_batch_mlmc_loops_generated(mg_solver, params, level, first_probe, count, kind="z2"):
+def probe_batch_mlmc_loops_generated(mg_solver, params, level, first_probe, count, kind="z2", deflated=False):
     """probe_batch_mlmc_loops for the probes [first_probe, first_probe + count) of the stream the engines hold
     (Engine.stream_set), generated on the device; several engine handles share the batch as in
     probe_batch_generated."""
     engs, tol, n, maxiter = _level_batch_args(mg_solver, params, level)
-    mode = MODE_MLMC_LOOPS_SKIP if _mlmc_loops_skip(mg_solver, level) else MODE_MLMC_LOOPS
+    if deflated:
+        mode = MODE_MLMC_DEFL_LOOPS_SKIP if _mlmc_loops_skip(mg_solver, level) else MODE_MLMC_DEFL_LOOPS
+    else:
+        mode = MODE_MLMC_LOOPS_SKIP if _mlmc_loops_skip(mg_solver, level) else MODE_MLMC_LOOPS
     ne = len(engs) if count >= 2 * 64 else 1
     bounds = [(k * count) // ne for k in range(ne + 1)]
     active = [k for k in range(ne) if bounds[k + 1] > bounds[k]]

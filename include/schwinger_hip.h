@@ -315,6 +315,14 @@ int sw_apply_slice_cdots(sw_engine* h, int nb, const double* U, const double* V,
  * identity and of the coarsest inverse prolonged to the lattice and reduced on the device, summed in a fixed
  * order (two calls agree bit for bit).  out complex128[nmom*2*2*L]. */
 int sw_coarsest_loops(sw_engine* h, double* out);
+/* The deflated part of a level's term of the MLMC loops (build-only): out[p][a][b][t] = sum_j S_q(Pi_l V_j, Pi_l D_l V_j)
+ * over the vectors V_j registered at `level` of hid 0 (sw_set_level_deflation), D_l = A_l^-1 - P_l A_{l+1}^-1 R_l
+ * (skip = 1, level 0 only: A_0^-1 - P_0 P_1 A_2^-1 R_1 R_0) applied on the device with solves to `tol`, for the
+ * registered momenta (sw_set_loop_momenta).  With the SW_MODE_MLMC_DEFL_LOOPS expectation it adds up to the level's
+ * term Tr(Pi_l^H Gamma_q Pi_l D_l) for any V, orthonormal or not.  64 columns per pass, summed in a fixed order (two
+ * calls agree bit for bit).  Fails without momenta, without vectors at `level`, with skip at a level other than 0
+ * and without a coarser level.  out complex128[nmom*2*2*L]. */
+int sw_level_deflation_loops(sw_engine* h, int level, int skip, double tol, int maxiter, double* out);
 /* The source kernel of SW_MODE_TWO_POINT alone: out[2 j + a][k][i] = the source eta_k^(j,a) of the registration
  * (sw_set_two_point) in the reference ordering, delta_{a,a'} delta_{t,t0} e^{+2 pi i p_j y / L} xi_k(y) at
  * i = idx(a',y,t), xi_k(y) = the code of probe k at idx(0,y,t0); probes int8[nb*n], out complex128[2*nmom*nb*n]. */
@@ -369,6 +377,16 @@ int sw_solve(sw_engine* h, int hid, int level0, int nb, const double* B, double*
                                   x^H d -- the SW_MODE_MLMC value of the probe -- when that momentum is 0 */
 #define SW_MODE_MLMC_LOOPS_SKIP 8 /* the same with d_k = A_0^-1 x_k - P_0 P_1 A_2^-1 R_1 R_0 x_k, level 0 only
                                   (as SW_MODE_MLMC_SKIP) */
+#define SW_MODE_MLMC_DEFL_LOOPS 9 /* SW_MODE_MLMC_LOOPS with the MLMC-level deflation of `level` (sw_set_level_deflation):
+                                  l_k[p][a][b][t] = S_q(Pi_l x_k, Pi_l d_k) with d_k the MLMC difference of the
+                                  projected probe x_k - V_l V_l^H x_k (the fine solve and the restriction take it),
+                                  the left operand stays the plain probe (build-only).  Its expectation is
+                                  Tr(Pi_l^H Gamma_q Pi_l D_l (I - V_l V_l^H)); sw_level_deflation_loops gives the rest.
+                                  With no vectors at `level` the batch equals the SW_MODE_MLMC_LOOPS batch bit for
+                                  bit.  Buffer and fetch of SW_MODE_MLMC_LOOPS (sw_hutch_fetch_mlmc_loops);
+                                  sw_hutch_fetch returns x^H d -- the SW_MODE_MLMC value of the probe with the same
+                                  vectors and no perm / rhsmap -- when the first registered momentum is 0 */
+#define SW_MODE_MLMC_DEFL_LOOPS_SKIP 10 /* the same on SW_MODE_MLMC_LOOPS_SKIP's difference, level 0 only */
 /* One batch of probes x_k in {-1,+1}^n (int8, nb*n, reference ordering) at `level`
  * (build-only extension: entries +-2 encode +-i, i.e. Z4 probes {1,i,-1,-i}):
  *   HUTCHINSON: e_k = x^H A^-1 Pperm^T (x - U U^H x)
