@@ -26,6 +26,35 @@ MODE_MLMC_LOOPS = 7
 MODE_MLMC_LOOPS_SKIP = 8
 MODE_MLMC_DEFL_LOOPS = 9
 MODE_MLMC_DEFL_LOOPS_SKIP = 10
+# estimator method -> (mode, mode of the level-skipping form at level 0); "mlmc_defl_loops" is "mlmc_loops" deflated
+_METHOD_MODES = {"hutchinson": (MODE_HUTCHINSON, MODE_HUTCHINSON),
+                 "mlmc": (MODE_MLMC, MODE_MLMC_SKIP),
+                 "level": (MODE_LEVEL, MODE_LEVEL),
+                 "shifts": (MODE_HUTCHINSON_SHIFTS, MODE_HUTCHINSON_SHIFTS),
+                 "loops": (MODE_HUTCHINSON_LOOPS, MODE_HUTCHINSON_LOOPS),
+                 "two_point": (MODE_TWO_POINT, MODE_TWO_POINT),
+                 "mlmc_loops": (MODE_MLMC_LOOPS, MODE_MLMC_LOOPS_SKIP),
+                 "mlmc_defl_loops": (MODE_MLMC_DEFL_LOOPS, MODE_MLMC_DEFL_LOOPS_SKIP)}
+# the modes whose batches leave a resolved result beside the scalar estimates -> the Engine method that fetches it
+RESOLVED_FETCH = {MODE_HUTCHINSON_SHIFTS: "hutch_fetch_shifts",
+                  MODE_HUTCHINSON_LOOPS: "hutch_fetch_loops",
+                  MODE_TWO_POINT: "hutch_fetch_two_point",
+                  MODE_MLMC_LOOPS: "hutch_fetch_mlmc_loops",
+                  MODE_MLMC_LOOPS_SKIP: "hutch_fetch_mlmc_loops",
+                  MODE_MLMC_DEFL_LOOPS: "hutch_fetch_mlmc_loops",
+                  MODE_MLMC_DEFL_LOOPS_SKIP: "hutch_fetch_mlmc_loops"}
+
+
+def probe_mode(method, level=0, skip_level=False, deflated=False):
+    """The engine mode of estimator `method` at `level`: with skip_level (MG.skip_level) the difference methods
+    take their level-skipping mode at level 0; deflated selects the MLMC loops with the level's projection."""
+    if method == "mlmc_loops" and deflated:
+        method = "mlmc_defl_loops"
+    if method not in _METHOD_MODES:
+        raise Exception("unknown method")
+    return _METHOD_MODES[method][1 if (skip_level and level == 0) else 0]
+
+
 KCLASS_TP_SOURCES = 17     # sw_kernel_stats classes of the two-point kernels
 KCLASS_TP_DOTS = 18
 KCLASS_SLICE_CDOTS = 19    # ... and of k_slice_cdots (MLMC loops)
@@ -606,12 +635,22 @@ class Engine:
                   "sw_hutch_batch")
         return ests, iters[:nb].copy(), iters[nb:].copy()
 
+    def hutch_batch_resolved(self, mode, level, probes, tol, maxiter=1000):
+        """One batch of a mode of RESOLVED_FETCH: (its resolved result, iters_fine[nb], iters_coarse[nb])."""
+        _, itf, itc = self.hutch_batch(mode, level, probes, tol, maxiter)
+        self._nb_uploaded = itf.size
+        return self.hutch_fetch_resolved(mode), itf, itc
+
+    def hutch_fetch_resolved(self, mode):
+        """The resolved result of the last batch of `mode`, one row per probe (a scalar mode has none: an error)."""
+        if mode not in RESOLVED_FETCH:
+            raise EngineError("mode %d leaves no resolved result" % mode)
+        return getattr(self, RESOLVED_FETCH[mode])()
+
     def hutch_batch_shifts(self, level, probes, tol, maxiter=1000):
         """One MODE_HUTCHINSON_SHIFTS batch: (ests[nb, S], iters_fine[nb], iters_coarse[nb]) with one
         column per registered shift."""
-        _, itf, itc = self.hutch_batch(MODE_HUTCHINSON_SHIFTS, level, probes, tol, maxiter)
-        self._nb_uploaded = itf.size
-        return self.hutch_fetch_shifts(), itf, itc
+        return self.hutch_batch_resolved(MODE_HUTCHINSON_SHIFTS, level, probes, tol, maxiter)
 
     def hutch_fetch_shifts(self):
         """Estimates of the last MODE_HUTCHINSON_SHIFTS batch at every registered shift, shape (nb, S)."""
@@ -639,9 +678,7 @@ class Engine:
     def hutch_batch_loops(self, level, probes, tol, maxiter=1000):
         """One MODE_HUTCHINSON_LOOPS batch: (loops[nb, nmom, 2, 2, L], iters_fine[nb], iters_coarse[nb]),
         loops[k, p, a, b, t] = sum_x e^{-2 pi i p x / L} conj(x_k[idx(a,x,t)]) z_k[idx(b,x,t)]."""
-        _, itf, itc = self.hutch_batch(MODE_HUTCHINSON_LOOPS, level, probes, tol, maxiter)
-        self._nb_uploaded = itf.size
-        return self.hutch_fetch_loops(), itf, itc
+        return self.hutch_batch_resolved(MODE_HUTCHINSON_LOOPS, level, probes, tol, maxiter)
 
     def hutch_fetch_loops(self):
         """Loops of the last MODE_HUTCHINSON_LOOPS batch for every registered momentum, shape
@@ -667,13 +704,8 @@ class Engine:
         """One MODE_MLMC_LOOPS batch (skip: MODE_MLMC_LOOPS_SKIP) at `level`: (loops[nb, nmom, 2, 2, L], iters_fine[nb],
         iters_coarse[nb]), loops[k, p, a, b, t] = S_q(Pi_l x_k, Pi_l d_k) with d_k the MLMC difference of probe k.
         deflated: MODE_MLMC_DEFL_LOOPS / _SKIP, d_k the difference of x_k - V V^H x_k for the level's registered V."""
-        if deflated:
-            mode = MODE_MLMC_DEFL_LOOPS_SKIP if skip else MODE_MLMC_DEFL_LOOPS
-        else:
-            mode = MODE_MLMC_LOOPS_SKIP if skip else MODE_MLMC_LOOPS
-        _, itf, itc = self.hutch_batch(mode, level, probes, tol, maxiter)
-        self._nb_uploaded = itf.size
-        return self.hutch_fetch_mlmc_loops(), itf, itc
+        # `skip` is the caller's word (the engine refuses it above level 0), so the mode is looked up at level 0
+        return self.hutch_batch_resolved(probe_mode("mlmc_loops", 0, skip, deflated), level, probes, tol, maxiter)
 
     def hutch_fetch_mlmc_loops(self):
         """Level loops of the last MODE_MLMC_LOOPS / _SKIP batch, shape (nb, nmom, 2, 2, L)."""
@@ -722,9 +754,7 @@ class Engine:
     def hutch_batch_two_point(self, level, probes, tol, maxiter=1000):
         """One MODE_TWO_POINT batch, the probes being the noises: (T[nb, nmom, 2, 2, 2, 2, L], iters_fine[nb],
         iters_coarse[nb]); iters_fine[k] is the largest count among the 2 nmom solves of noise k."""
-        _, itf, itc = self.hutch_batch(MODE_TWO_POINT, level, probes, tol, maxiter)
-        self._nb_uploaded = itf.size
-        return self.hutch_fetch_two_point(), itf, itc
+        return self.hutch_batch_resolved(MODE_TWO_POINT, level, probes, tol, maxiter)
 
     def hutch_fetch_two_point(self):
         """Pair sums of the last MODE_TWO_POINT batch, shape (nb, nmom, 2, 2, 2, 2, L): T[k, j, a, b, c, d, t]."""

@@ -15,14 +15,11 @@ from scipy.sparse import csr_matrix
 from scipy.sparse.linalg import LinearOperator
 
 from . import dist as _dist
-from .engine import ProbeStream
+from .engine import RESOLVED_FETCH, ProbeStream, probe_mode
 from .multigrid import MG
 from .utils import (_engines, deflation_pre_computations, displacements_of, draw_probes, flopsV_manual,
-                    loops_of, mlmc_defl_setup_of, probe_batch, probe_batch_generated, probe_batch_loops,
-                    probe_batch_loops_generated, probe_batch_mlmc_loops_generated, probe_batch_shifts,
-                    probe_batch_shifts_generated,
-                    probe_batch_two_point, probe_batch_two_point_generated, register_loop_momenta, register_shifts,
-                    register_two_point, two_point_of)
+                    loops_of, mlmc_defl_setup_of, probe_batch, probe_batch_generated, register_loop_momenta,
+                    register_shifts, register_two_point, two_point_of)
 
 DEFAULT_BATCH = 256
 NR_ROUGH_PROBES = 5
@@ -88,15 +85,21 @@ class HostProbes:
 class DeviceProbes:
     """Probe source of the GPU estimators: the engines generate their probes in HBM at the
     probes' stream positions (k_mt_generate) and evaluate them; nothing of size n touches the host.
-    The probes of the round expected next (`round_stride` probes further down the stream, set by the
-    loop) are drawn on the engines' generation streams while the current round is being solved."""
+    `method`, `level` and `deflated` are those of utils.probe_batch_generated.  For a resolved method each probe
+    yields one row; `columns` (None: the row as it is) turns the batch's resolved array into the columns of
+    run_probe_loop(control=...): loop_columns(., zero) or two_point_columns(., zero).
+    For the scalar methods the probes of the round expected next (`round_stride` probes further down the stream,
+    set by the loop) are drawn on the engines' generation streams while the current round is being solved."""
 
-    def __init__(self, mg_solver, params, method, level, kind="z2"):
+    def __init__(self, mg_solver, params, method, level, kind="z2", columns=None, deflated=False):
         self.mg_solver = mg_solver
         self.params = params
         self.method = method
         self.level = level
         self.kind = kind
+        self.columns = columns
+        self.deflated = deflated       # MODE_MLMC_DEFL_LOOPS: the level's registered projection on the right
+        self.prefetches = probe_mode(method, level, deflated=deflated) not in RESOLVED_FETCH
         self.round_stride = 0          # distance (in probes) to this rank's slice of the next round
         self._ready = None
 
@@ -107,15 +110,15 @@ class DeviceProbes:
         self._ready = None
 
     def __call__(self, first_probe, count):
-        nxt = (first_probe + self.round_stride, count) if self.round_stride > 0 else None
+        nxt = (first_probe + self.round_stride, count) if self.prefetches and self.round_stride > 0 else None
         e, f, c, self._ready = probe_batch_generated(self.mg_solver, self.params, self.method, self.level,
                                                      first_probe, count, self.kind, prefetch=nxt,
-                                                     ready=self._ready)
-        return e, f, c
+                                                     ready=self._ready, deflated=self.deflated)
+        return (e if self.columns is None else self.columns(e)), f, c
 
 
 def run_probe_loop(evaluate, n, level_tol, max_nr_ests, batch, comm=None, min_index=5,
-                   verbose=False, probe_type="z2"):
+                   verbose=False, probe_type="z2", control=None):
     """The probe loop of stoch_trace.py:137-154 / 386-406 in rounds of batched probes.
 
     `evaluate` is a probe source -- called as source(first_probe, count) for the probes
@@ -125,37 +128,57 @@ def run_probe_loop(evaluate, n, level_tol, max_nr_ests, batch, comm=None, min_in
     in :class:`HostProbes`.  Every rank evaluates only its contiguous slice of a round.
     Returns dict(index, avg, dev, ests, iters_fine, iters_coarse, rounds) where `index` is the
     loop index at which the reference would have left the loop.  On return the global NumPy
-    stream sits exactly where the one-by-one loop would have left it."""
+    stream sits exactly where the one-by-one loop would have left it.
+
+    control = j: for estimators that return one value per displacement (or loop entry, ...): `evaluate` yields
+    ests of shape (count, S) and `level_tol` holds S tolerances.  The sequential stopping rule is replayed on
+    column j against level_tol[j] alone, so that column's index, avg and dev are those of the scalar loop on it;
+    every other column is summarised over the same first index + 1 probes.  The dictionary (avg, dev: the control
+    column; ests: (index + 1, S)) then also has avgs[S], devs[S] and converged[S] = whether each column met its own
+    tolerance at the stopping index.  One rank only."""
     comm = comm or _dist.default_comm()
+    width = ()
+    if control is not None:
+        if comm.world > 1:
+            raise Exception("displaced traces (x_displacements) run on one rank; got %d" % comm.world)
+        level_tols = np.asarray(level_tol, dtype=float)
+        width = (level_tols.size,)
+        level_tol = level_tols[control]
     source = evaluate if hasattr(evaluate, "begin") else HostProbes(evaluate, n, probe_type)
     entry = ProbeStream.from_numpy_state()
     source.begin(entry)
-    ests = np.zeros(0, dtype=np.complex128)
+    ests = np.zeros((0,) + width, dtype=np.complex128)
     it_f = np.zeros(0, dtype=np.int64)
     it_c = np.zeros(0, dtype=np.int64)
     rounds = 0
     stop_index = None
     avg = dev = 0.0
-    while ests.size < max_nr_ests:
-        round_size = min(batch * comm.world, max_nr_ests - ests.size)
-        first_new = ests.size
+
+    def series():
+        return ests if control is None else ests[:, control]
+
+    while ests.shape[0] < max_nr_ests:
+        round_size = min(batch * comm.world, max_nr_ests - ests.shape[0])
+        first_new = ests.shape[0]
         lo, hi = comm.my_slice(round_size)
         if hasattr(source, "round_stride"):
             # the next round (if the loop goes on and is a full one) starts round_size probes further on
-            source.round_stride = round_size if ests.size + 2 * round_size <= max_nr_ests else 0
+            source.round_stride = round_size if first_new + 2 * round_size <= max_nr_ests else 0
         if hi > lo:
             e, f, c = source(first_new + lo, hi - lo)
         else:
             e, f, c = np.zeros(0, complex), np.zeros(0, np.int64), np.zeros(0, np.int64)
         e, f, c = comm.allgather_probe_results(e, f, c, round_size)
+        if control is not None and e.shape != (round_size,) + width:
+            raise Exception("displaced probe batch of shape %s, expected %s" % (e.shape, (round_size,) + width))
         ests = np.concatenate([ests, e])
         it_f = np.concatenate([it_f, f])
         it_c = np.concatenate([it_c, c])
         rounds += 1
         if verbose:
             # the reference's per-probe debug prints (stoch_trace.py:150-152): its own O(N^2) loop
-            for i in range(first_new, ests.size):
-                avg, dev = _stats(ests[:i + 1])
+            for i in range(first_new, ests.shape[0]):
+                avg, dev = _stats(series()[:i + 1])
                 err = dev / sqrt(i + 1)
                 print(dev)
                 print(err)
@@ -164,43 +187,31 @@ def run_probe_loop(evaluate, n, level_tol, max_nr_ests, batch, comm=None, min_in
                     stop_index = i
                     break
         else:
-            hit = first_stop_index(ests, first_new, level_tol, min_index)
+            hit = first_stop_index(series(), first_new, level_tol, min_index)
             if hit is not None:
                 stop_index, avg, dev = hit
         if stop_index is not None:
             break
     if stop_index is None:
-        stop_index = ests.size - 1
-        avg, dev = _stats(ests)
+        stop_index = ests.shape[0] - 1
+        avg, dev = _stats(series())
     k = stop_index + 1
     # leave the global stream where the one-by-one loop leaves it: k probes of n draws each
     entry.jump(k * n)
     np.random.set_state(entry.numpy_state())
-    return {"index": stop_index, "avg": avg, "dev": dev, "ests": ests[:k],
-            "iters_fine": it_f[:k], "iters_coarse": it_c[:k], "rounds": rounds,
-            "solved": int(ests.size)}
-
-
-class DeviceShiftProbes:
-    """Probe source of the displaced-trace loop: as :class:`DeviceProbes`, each probe evaluated at every
-    registered shift (one row of S estimates per probe)."""
-
-    def __init__(self, mg_solver, params, kind="z2"):
-        self.mg_solver = mg_solver
-        self.params = params
-        self.kind = kind
-
-    def begin(self, entry_stream):
-        window = entry_stream.window()
-        for eng in _engines(self.mg_solver):
-            eng.stream_set(window)
-
-    def __call__(self, first_probe, count):
-        return probe_batch_shifts_generated(self.mg_solver, self.params, first_probe, count, self.kind)
+    out = {"index": stop_index, "avg": avg, "dev": dev, "ests": ests[:k],
+           "iters_fine": it_f[:k], "iters_coarse": it_c[:k], "rounds": rounds,
+           "solved": int(ests.shape[0])}
+    if control is not None:
+        per = [_stats(ests[:k, j]) for j in range(width[0])]
+        out["avgs"] = np.array([a for a, _ in per])
+        out["devs"] = np.array([d for _, d in per])
+        out["converged"] = out["devs"] / sqrt(k) < level_tols
+    return out
 
 
 def loop_columns(loops, zero):
-    """The columns of the timeslice-loop estimator for run_probe_loop_displaced: loops[k][p][a][b][t] flattened
+    """The columns of the timeslice-loop estimator for run_probe_loop(control=...): loops[k][p][a][b][t] flattened
     per probe, plus one control column, the scalar total sum_t (l[0][0][t] + l[1][1][t]) of momentum index
     `zero` (p = 0) -- the plain Hutchinson value x^H z of the probe."""
     loops = np.asarray(loops, dtype=np.complex128)
@@ -208,123 +219,13 @@ def loop_columns(loops, zero):
     return np.concatenate([loops.reshape(loops.shape[0], -1), total[:, None]], axis=1)
 
 
-class DeviceLoopProbes:
-    """Probe source of the timeslice-loop flow: as :class:`DeviceShiftProbes`, each probe evaluated on every
-    (momentum, spin pair, timeslice); one row of loop_columns per probe."""
-
-    def __init__(self, mg_solver, params, zero, kind="z2"):
-        self.mg_solver = mg_solver
-        self.params = params
-        self.zero = zero
-        self.kind = kind
-
-    def begin(self, entry_stream):
-        window = entry_stream.window()
-        for eng in _engines(self.mg_solver):
-            eng.stream_set(window)
-
-    def __call__(self, first_probe, count):
-        e, f, c = probe_batch_loops_generated(self.mg_solver, self.params, first_probe, count, self.kind)
-        return loop_columns(e, self.zero), f, c
-
-
-class DeviceMLMCLoopProbes:
-    """Probe source of the MLMC loop flow: the probes of `level` through MODE_MLMC_LOOPS; one row of loop_columns
-    per probe, the control column being the scalar MLMC difference x^H (z - P y) of the probe."""
-
-    def __init__(self, mg_solver, params, level, zero, kind="z2", deflated=False):
-        self.mg_solver = mg_solver
-        self.params = params
-        self.level = level
-        self.zero = zero
-        self.kind = kind
-        self.deflated = deflated       # MODE_MLMC_DEFL_LOOPS: the level's registered projection on the right
-
-    def begin(self, entry_stream):
-        window = entry_stream.window()
-        for eng in _engines(self.mg_solver):
-            eng.stream_set(window)
-
-    def __call__(self, first_probe, count):
-        e, f, c = probe_batch_mlmc_loops_generated(self.mg_solver, self.params, self.level, first_probe, count,
-                                                   self.kind, deflated=self.deflated)
-        return loop_columns(e, self.zero), f, c
-
-
 def two_point_columns(T, zero):
-    """The columns of the two-point estimator for run_probe_loop_displaced: T[k][j][a][b][c][d][t] flattened per
+    """The columns of the two-point estimator for run_probe_loop(control=...): T[k][j][a][b][c][d][t] flattened per
     noise, plus one control column, the pion total sum_t sum_ac T[zero][a][a][c][c][t] = sum_a ||z^(0,a)||^2 of
     momentum index `zero` (p = 0), which is real and positive."""
     T = np.asarray(T, dtype=np.complex128)
     total = sum(np.sum(T[:, zero, a, a, c, c, :], axis=1) for a in range(2) for c in range(2))
     return np.concatenate([T.reshape(T.shape[0], -1), total[:, None]], axis=1)
-
-
-class DeviceTwoPointProbes:
-    """Noise source of the two-point flow: as :class:`DeviceLoopProbes`; one row of two_point_columns per noise."""
-
-    def __init__(self, mg_solver, params, zero, kind="z2"):
-        self.mg_solver = mg_solver
-        self.params = params
-        self.zero = zero
-        self.kind = kind
-
-    def begin(self, entry_stream):
-        window = entry_stream.window()
-        for eng in _engines(self.mg_solver):
-            eng.stream_set(window)
-
-    def __call__(self, first_probe, count):
-        e, f, c = probe_batch_two_point_generated(self.mg_solver, self.params, first_probe, count, self.kind)
-        return two_point_columns(e, self.zero), f, c
-
-
-def run_probe_loop_displaced(evaluate, n, level_tols, control, max_nr_ests, batch, comm=None, min_index=5,
-                             probe_type="z2"):
-    """The probe loop of :func:`run_probe_loop` for estimators that return one value per displacement:
-    `evaluate` (a probe source or a plain callable, as there) yields ests of shape (count, S).  The
-    sequential stopping rule is replayed on column `control` against level_tols[control] alone, so that
-    column's index, avg and dev are those of run_probe_loop on it; every other column is summarised over
-    the same first index + 1 probes.  Returns run_probe_loop's dictionary (avg, dev: the control column;
-    ests: (index + 1, S)) plus avgs[S], devs[S] and converged[S] = whether each displacement met its own
-    tolerance at the stopping index.  One rank only."""
-    comm = comm or _dist.default_comm()
-    if comm.world > 1:
-        raise Exception("displaced traces (x_displacements) run on one rank; got %d" % comm.world)
-    level_tols = np.asarray(level_tols, dtype=float)
-    S = level_tols.size
-    source = evaluate if hasattr(evaluate, "begin") else HostProbes(evaluate, n, probe_type)
-    entry = ProbeStream.from_numpy_state()
-    source.begin(entry)
-    ests = np.zeros((0, S), dtype=np.complex128)
-    it_f = np.zeros(0, dtype=np.int64)
-    it_c = np.zeros(0, dtype=np.int64)
-    rounds = 0
-    hit = None
-    while ests.shape[0] < max_nr_ests and hit is None:
-        count = min(batch, max_nr_ests - ests.shape[0])
-        first_new = ests.shape[0]
-        e, f, c = source(first_new, count)
-        e = np.asarray(e, dtype=np.complex128)
-        if e.shape != (count, S):
-            raise Exception("displaced probe batch of shape %s, expected %s" % (e.shape, (count, S)))
-        ests = np.concatenate([ests, e])
-        it_f = np.concatenate([it_f, np.asarray(f, dtype=np.int64)])
-        it_c = np.concatenate([it_c, np.asarray(c, dtype=np.int64)])
-        rounds += 1
-        hit = first_stop_index(ests[:, control], first_new, level_tols[control], min_index)
-    if hit is None:
-        hit = (ests.shape[0] - 1,) + _stats(ests[:, control])
-    stop_index, avg, dev = hit
-    k = stop_index + 1
-    per = [_stats(ests[:k, j]) for j in range(S)]
-    avgs = np.array([a for a, _ in per])
-    devs = np.array([d for _, d in per])
-    entry.jump(k * n)
-    np.random.set_state(entry.numpy_state())
-    return {"index": stop_index, "avg": avg, "dev": dev, "ests": ests[:k], "avgs": avgs, "devs": devs,
-            "converged": devs / sqrt(k) < level_tols,
-            "iters_fine": it_f[:k], "iters_coarse": it_c[:k], "rounds": rounds, "solved": int(ests.shape[0])}
 
 
 def _setup_solver(A, params, announce=True, defer_coarse=False):
@@ -357,31 +258,172 @@ def _setup_solver(A, params, announce=True, defer_coarse=False):
     return mg_solver, nr_levels
 
 
-def _rough_trace(mg_solver, params, n, Vx_rank, tr1):
-    """stoch_trace.py:103-115 / 288-302: seed 123456, five deflated Hutchinson probes."""
+def _rough_estimate(mg_solver, params, n, method="hutchinson", columns=None):
+    """stoch_trace.py:103-115 / 288-302: seed 123456, the mean of five probes of `method` at level 0 (of their
+    `columns`, if given); the caller adds the deflated part."""
     np.random.seed(123456)
     t0 = time.time()
     probes = draw_probes(NR_ROUGH_PROBES, n, params.get('probe_type', 'z2'))
-    e, _, _ = probe_batch(mg_solver, params, "hutchinson", probes, 0)
-    rough = np.sum(e[0:NR_ROUGH_PROBES]) / NR_ROUGH_PROBES
-    rough += tr1
+    e, _, _ = probe_batch(mg_solver, params, method, probes, 0)
+    if columns is not None:
+        e = columns(e)
+    rough = np.sum(e[0:NR_ROUGH_PROBES], axis=0) / NR_ROUGH_PROBES
     print(" done. Time : " + str(time.time() - t0) + " seconds")
     return rough
 
 
+class _Observable:
+    """What a Hutchinson-type flow estimates, as hutchinson() and _estimate_stage need it.  This one is the
+    plain trace: one scalar series per probe, any number of ranks.  The resolved ones estimate `columns` of each
+    probe's row and stop on the column `control`, on one rank (`one_rank`: the refusal otherwise)."""
+    what = "trace"                     # ... in the printed lines
+    method = "hutchinson"              # of utils.probe_batch / probe_batch_generated
+    columns = None                     # the resolved array of a batch -> the columns of the probe loop
+    one_rank = None
+
+    def register(self, mg_solver):
+        """What the engines have to know besides the deflation vectors."""
+
+    def tr1_columns(self, tr1):
+        """The deflated part as deflation_pre_computations returns it -> one value per column."""
+        return tr1
+
+    def control(self, rough):
+        """The column the stopping rule runs on (None: the estimates are scalars)."""
+        return None
+
+    def fill(self, result, loop, tr1_cols, rough, level_tols):
+        """The result keys beyond the reference's, from the loop's avgs / devs / ests / converged."""
+
+
+class _Displaced(_Observable):
+    """x_displacements: Tr(A^-1 D_s) at every listed displacement, one column each; the reference's keys are those
+    of the control displacement."""
+    what = "traces"
+    method = "shifts"
+    one_rank = "displaced traces (x_displacements) run on one rank"
+
+    def __init__(self, displaced):
+        self.disps, self.shifts, self.control_index = displaced
+
+    def register(self, mg_solver):
+        register_shifts(mg_solver, self.shifts)
+
+    def tr1_columns(self, tr1):
+        return np.asarray(tr1, dtype=np.complex128)
+
+    def control(self, rough):
+        return self.control_index
+
+    def fill(self, result, loop, tr1_cols, rough, level_tols):
+        result['ests'] = loop["ests"]                   # (nr_ests + 1, S)
+        result['displacements'] = list(self.disps)
+        result['traces'] = loop["avgs"] + tr1_cols
+        result['std_devs'] = loop["devs"]
+        result['rough_traces'] = rough
+        result['level_tols'] = level_tols
+        result['converged'] = loop["converged"]
+
+
+class _Loops(_Observable):
+    """timeslice_loops: the loops l[p][a][b][t], flattened, plus one control column, the scalar total at p = 0, whose
+    expectation plus sum(tr1) is Tr(A^-1): the reference's keys are filled from it."""
+    what = "loops"
+    method = "loops"
+    one_rank = "timeslice loops (timeslice_loops) run on one rank"
+
+    def __init__(self, momenta):
+        self.momenta = momenta
+        self.zero = momenta.index(0)
+        self.tr1 = None                # the deflated part [p][a][b][t]
+
+    def columns(self, loops):
+        return loop_columns(loops, self.zero)
+
+    def register(self, mg_solver):
+        register_loop_momenta(mg_solver, self.momenta)
+
+    def tr1_columns(self, tr1):
+        self.tr1 = np.asarray(tr1, dtype=np.complex128)
+        return loop_columns(self.tr1[None], self.zero)[0]
+
+    def control(self, rough):
+        return rough.size - 1
+
+    def fill(self, result, loop, tr1_cols, rough, level_tols):
+        control, shape = rough.size - 1, self.tr1.shape
+        result['momenta'] = list(self.momenta)
+        result['loops'] = (loop["avgs"][:control] + tr1_cols[:control]).reshape(shape)
+        result['loop_devs'] = loop["devs"][:control].reshape(shape)
+        result['loop_ests'] = loop["ests"][:, :control].reshape((-1,) + shape) + self.tr1[None]
+        result['converged'] = loop["converged"][:control].reshape(shape)
+
+
+class _TwoPoint(_Observable):
+    """two_point(): the pair sums T[j][a][b][c][d][t], flattened, plus one control column, the pion total."""
+    what = "two-point functions"
+    method = "two_point"
+    one_rank = "two-point functions (source_timeslice) run on one rank"
+
+    def __init__(self, momenta):
+        self.zero = momenta.index(0)
+
+    def columns(self, T):
+        return two_point_columns(T, self.zero)
+
+    def control(self, rough):
+        return rough.size - 1
+
+
+def _estimate_stage(mg_solver, params, n, obs, tr1_cols=None):
+    """The second half of a Hutchinson-type flow: the rough estimate from five probes (plus tr1_cols), the level
+    tolerances |tol * rough|, the timers' reset and the probe loop of `obs` at level 0.
+    Returns (rough, level_tols, control, loop, loop_s); control None: rough and level_tols are scalars."""
+    kind = params.get('probe_type', 'z2')
+    print("\nComputing rough estimation of the " + obs.what + " ...", end='', flush=True)
+    rough = _rough_estimate(mg_solver, params, n, obs.method, obs.columns)
+    if tr1_cols is not None:
+        rough = rough + tr1_cols
+    level_tols = np.abs(params['tol'] * rough)
+    control = obs.control(rough)
+
+    print("\nResetting timer to zero ...", end='')
+    mg_solver.timer.reset()
+    mg_solver.engine.timers_reset()
+    print(" done")
+    print("\nComputing the " + obs.what + " stochastically ...", end='', flush=True)
+    t0 = time.time()
+    source = DeviceProbes(mg_solver, params, obs.method, 0, kind, obs.columns)
+    # a round = one batch per engine handle (concurrent HIP streams) per rank
+    loop = run_probe_loop(source, n, level_tols, params['max_nr_ests'],
+                          int(params.get('batch', DEFAULT_BATCH)) * max(1, len(_engines(mg_solver))),
+                          verbose=control is None and bool(params.get('verbose', False)),
+                          probe_type=kind, control=control)
+    loop_s = time.time() - t0
+    print(" done. Time : " + str(loop_s) + " seconds")
+    return rough, level_tols, control, loop, loop_s
+
+
 # compute tr(A^{-1}) via (deflated) Hutchinson                      stoch_trace.py:33-179
 def hutchinson(A, params):
+    """The build-only keys x_displacements (Tr(A^-1 D_s) at every listed displacement; DESIGN.md, "Displaced
+    traces") and timeslice_loops (the spin- and momentum-resolved loops l[p][a][b][t] of every timeslice; DESIGN.md
+    4c) resolve the estimate, from one deflation projection and one solve per probe: the reference's result keys
+    are then those of the control column, and the stopping rule runs on its series alone."""
     if two_point_of(params) is not None:
         raise Exception("source_timeslice belongs to two_point(), not to hutchinson()")
     momenta = loops_of(params)
+    displaced = displacements_of(params) if momenta is None else None
     if momenta is not None:
-        return _hutchinson_loops(A, params, momenta)
-    displaced = displacements_of(params)
-    if displaced is not None:
-        return _hutchinson_displaced(A, params, displaced)
+        obs = _Loops(momenta)
+    elif displaced is not None:
+        obs = _Displaced(displaced)
+    else:
+        obs = _Observable()
+    if obs.one_rank and _dist.default_comm().world > 1:
+        raise Exception(obs.one_rank)
     mg_solver, nr_levels = _setup_solver(A, params, defer_coarse=True)
     N = A.shape[0]
-    batch = int(params.get('batch', DEFAULT_BATCH))
 
     print("\nResetting timer to zero ...", end='')
     mg_solver.timer.reset()
@@ -391,35 +433,22 @@ def hutchinson(A, params):
     t0 = time.time()
     Vx, tr1 = deflation_pre_computations(A, nr_deflat_vctrs, params['defl_eigvs_tol_Hutch'],
                                          "hutchinson", mg_solver.timer, params, mg_solver)
+    tr1_cols = obs.tr1_columns(tr1)
+    obs.register(mg_solver)
     print(" done. Time : " + str(time.time() - t0) + " seconds")
     print(mg_solver.timer)
 
-    print("\nComputing rough estimation of the trace ...", end='', flush=True)
-    rough_trace = _rough_trace(mg_solver, params, N, Vx, tr1)
-    rough_trace_tol = abs(params['tol'] * rough_trace)
-
-    print("\nResetting timer to zero ...", end='')
-    mg_solver.timer.reset()
-    mg_solver.engine.timers_reset()
-    print(" done")
-    print("\nComputing the trace stochastically ...", end='', flush=True)
-    t0 = time.time()
     mg_solver.coarsest_lev_iters[0] = 0
+    rough, level_tols, control, loop, loop_s = _estimate_stage(mg_solver, params, N, obs, tr1_cols)
 
-    source = DeviceProbes(mg_solver, params, "hutchinson", 0, params.get('probe_type', 'z2'))
-    # a round = one batch per engine handle (concurrent HIP streams) per rank
-    loop = run_probe_loop(source, N, rough_trace_tol, params['max_nr_ests'],
-                          batch * max(1, len(_engines(mg_solver))),
-                          verbose=bool(params.get('verbose', False)),
-                          probe_type=params.get('probe_type', 'z2'))
-    loop_s = time.time() - t0
-    print(" done. Time : " + str(loop_s) + " seconds")
+    def at_control(v):
+        return v if control is None else v[control]
 
     function_iters = int(np.sum(loop["iters_fine"]))
     mg_solver.coarsest_lev_iters[0] = function_iters
     mg_solver.finish_setup()          # the coarse levels (built beside the probe loop): the work model reads their nnz
     result = dict()
-    result['trace'] = loop["avg"] + tr1
+    result['trace'] = loop["avg"] + at_control(tr1_cols)
     result['std_dev'] = loop["dev"]
     result['nr_ests'] = loop["index"]
     result['function_iters'] = function_iters
@@ -429,168 +458,17 @@ def hutchinson(A, params):
     # stoch_trace.py:173-175 (hard-coded 1/3 kept)
     result['total_complexity'] += result['nr_ests'] * (2 * N * nr_deflat_vctrs) / 3.0
     # build-only extras (not in the reference's dictionary)
-    result['ests'] = loop["ests"]
-    result['rough_trace'] = rough_trace
-    result['level_tol'] = rough_trace_tol
+    result['ests'] = loop["ests"] if control is None else loop["ests"][:, control]      # (nr_ests + 1,)
+    result['rough_trace'] = at_control(rough)
+    result['level_tol'] = at_control(level_tols)
     result['probe_loop_s'] = loop_s                 # wall clock of the probe loop and what it solved
     result['probes_solved'] = loop["solved"]        # (whole rounds: >= nr_ests + 1)
+    obs.fill(result, loop, tr1_cols, rough, level_tols)
     mg_solver.sync_timer()
     print(mg_solver.timer)
     return result
 
 
-def _hutchinson_displaced(A, params, displaced):
-    """hutchinson() with the build-only key x_displacements: Tr(A^-1 D_s) at every listed displacement from
-    one deflation projection and one solve per probe ("Displaced traces").  The reference's
-    result keys are filled for the control displacement; the stopping rule runs on its series alone."""
-    disps, shifts, control = displaced
-    if _dist.default_comm().world > 1:
-        raise Exception("displaced traces (x_displacements) run on one rank")
-    mg_solver, nr_levels = _setup_solver(A, params, defer_coarse=True)
-    N = A.shape[0]
-    batch = int(params.get('batch', DEFAULT_BATCH))
-    kind = params.get('probe_type', 'z2')
-
-    print("\nResetting timer to zero ...", end='')
-    mg_solver.timer.reset()
-    print(" done\n")
-    nr_deflat_vctrs = params['nr_deflat_vctrs']
-    print("Computing deflation vectors ...", end='', flush=True)
-    t0 = time.time()
-    Vx, tr1 = deflation_pre_computations(A, nr_deflat_vctrs, params['defl_eigvs_tol_Hutch'],
-                                         "hutchinson", mg_solver.timer, params, mg_solver)
-    tr1 = np.asarray(tr1, dtype=np.complex128)
-    register_shifts(mg_solver, shifts)
-    print(" done. Time : " + str(time.time() - t0) + " seconds")
-    print(mg_solver.timer)
-
-    print("\nComputing rough estimation of the traces ...", end='', flush=True)
-    np.random.seed(123456)                                      # stoch_trace.py:103-115
-    t0 = time.time()
-    e, _, _ = probe_batch_shifts(mg_solver, params, draw_probes(NR_ROUGH_PROBES, N, kind))
-    rough_traces = np.sum(e, axis=0) / NR_ROUGH_PROBES + tr1
-    level_tols = np.abs(params['tol'] * rough_traces)
-    print(" done. Time : " + str(time.time() - t0) + " seconds")
-
-    print("\nResetting timer to zero ...", end='')
-    mg_solver.timer.reset()
-    mg_solver.engine.timers_reset()
-    print(" done")
-    print("\nComputing the traces stochastically ...", end='', flush=True)
-    t0 = time.time()
-    mg_solver.coarsest_lev_iters[0] = 0
-    loop = run_probe_loop_displaced(DeviceShiftProbes(mg_solver, params, kind), N, level_tols, control,
-                                    params['max_nr_ests'], batch * max(1, len(_engines(mg_solver))),
-                                    probe_type=kind)
-    loop_s = time.time() - t0
-    print(" done. Time : " + str(loop_s) + " seconds")
-
-    function_iters = int(np.sum(loop["iters_fine"]))
-    mg_solver.coarsest_lev_iters[0] = function_iters
-    mg_solver.finish_setup()
-    result = dict()
-    result['trace'] = loop["avg"] + tr1[control]
-    result['std_dev'] = loop["dev"]
-    result['nr_ests'] = loop["index"]
-    result['function_iters'] = function_iters
-    levels = mg_solver.ml.levels
-    result['total_complexity'] = flopsV_manual(len(levels), levels, 0, mg_solver) * function_iters
-    result['total_complexity'] += levels[len(levels) - 1].A.nnz * mg_solver.coarsest_lev_iters[0]
-    result['total_complexity'] += result['nr_ests'] * (2 * N * nr_deflat_vctrs) / 3.0
-    result['ests'] = loop["ests"]                   # (nr_ests + 1, S)
-    result['rough_trace'] = rough_traces[control]
-    result['level_tol'] = level_tols[control]
-    result['probe_loop_s'] = loop_s
-    result['probes_solved'] = loop["solved"]
-    result['displacements'] = list(disps)
-    result['traces'] = loop["avgs"] + tr1
-    result['std_devs'] = loop["devs"]
-    result['rough_traces'] = rough_traces
-    result['level_tols'] = level_tols
-    result['converged'] = loop["converged"]
-    mg_solver.sync_timer()
-    print(mg_solver.timer)
-    return result
-
-
-def _hutchinson_loops(A, params, momenta):
-    """hutchinson() with the build-only key timeslice_loops: the spin- and momentum-resolved loops
-    l[p][a][b][t] of every timeslice from one deflation projection and one solve per probe.
-    The columns of the probe loop are the flattened loops plus one control column, the scalar total at p = 0,
-    whose expectation plus sum(tr1) is Tr(A^-1): the reference's result keys are filled from it and the
-    stopping rule runs on it alone."""
-    if _dist.default_comm().world > 1:
-        raise Exception("timeslice loops (timeslice_loops) run on one rank")
-    mg_solver, nr_levels = _setup_solver(A, params, defer_coarse=True)
-    N = A.shape[0]
-    batch = int(params.get('batch', DEFAULT_BATCH))
-    kind = params.get('probe_type', 'z2')
-    zero = momenta.index(0)
-
-    print("\nResetting timer to zero ...", end='')
-    mg_solver.timer.reset()
-    print(" done\n")
-    nr_deflat_vctrs = params['nr_deflat_vctrs']
-    print("Computing deflation vectors ...", end='', flush=True)
-    t0 = time.time()
-    Vx, tr1 = deflation_pre_computations(A, nr_deflat_vctrs, params['defl_eigvs_tol_Hutch'],
-                                         "hutchinson", mg_solver.timer, params, mg_solver)
-    tr1 = np.asarray(tr1, dtype=np.complex128)                  # [p][a][b][t]
-    tr1_cols = loop_columns(tr1[None], zero)[0]
-    register_loop_momenta(mg_solver, momenta)
-    print(" done. Time : " + str(time.time() - t0) + " seconds")
-    print(mg_solver.timer)
-
-    print("\nComputing rough estimation of the loops ...", end='', flush=True)
-    np.random.seed(123456)                                      # stoch_trace.py:103-115
-    t0 = time.time()
-    e, _, _ = probe_batch_loops(mg_solver, params, draw_probes(NR_ROUGH_PROBES, N, kind))
-    rough = np.sum(loop_columns(e, zero), axis=0) / NR_ROUGH_PROBES + tr1_cols
-    level_tols = np.abs(params['tol'] * rough)
-    control = rough.size - 1
-    print(" done. Time : " + str(time.time() - t0) + " seconds")
-
-    print("\nResetting timer to zero ...", end='')
-    mg_solver.timer.reset()
-    mg_solver.engine.timers_reset()
-    print(" done")
-    print("\nComputing the loops stochastically ...", end='', flush=True)
-    t0 = time.time()
-    mg_solver.coarsest_lev_iters[0] = 0
-    loop = run_probe_loop_displaced(DeviceLoopProbes(mg_solver, params, zero, kind), N, level_tols, control,
-                                    params['max_nr_ests'], batch * max(1, len(_engines(mg_solver))),
-                                    probe_type=kind)
-    loop_s = time.time() - t0
-    print(" done. Time : " + str(loop_s) + " seconds")
-
-    function_iters = int(np.sum(loop["iters_fine"]))
-    mg_solver.coarsest_lev_iters[0] = function_iters
-    mg_solver.finish_setup()
-    result = dict()
-    result['trace'] = loop["avg"] + tr1_cols[control]
-    result['std_dev'] = loop["dev"]
-    result['nr_ests'] = loop["index"]
-    result['function_iters'] = function_iters
-    levels = mg_solver.ml.levels
-    result['total_complexity'] = flopsV_manual(len(levels), levels, 0, mg_solver) * function_iters
-    result['total_complexity'] += levels[len(levels) - 1].A.nnz * mg_solver.coarsest_lev_iters[0]
-    result['total_complexity'] += result['nr_ests'] * (2 * N * nr_deflat_vctrs) / 3.0
-    result['ests'] = loop["ests"][:, control]       # (nr_ests + 1,): the plain Hutchinson series
-    result['rough_trace'] = rough[control]
-    result['level_tol'] = level_tols[control]
-    result['probe_loop_s'] = loop_s
-    result['probes_solved'] = loop["solved"]
-    result['momenta'] = list(momenta)
-    result['loops'] = (loop["avgs"][:control] + tr1_cols[:control]).reshape(tr1.shape)
-    result['loop_devs'] = loop["devs"][:control].reshape(tr1.shape)
-    result['loop_ests'] = loop["ests"][:, :control].reshape((-1,) + tr1.shape) + tr1[None]
-    result['converged'] = loop["converged"][:control].reshape(tr1.shape)
-    mg_solver.sync_timer()
-    print(mg_solver.timer)
-    return result
-
-
-# compute tr(A^{-1}) via multigrid multilevel Monte Carlo          stoch_trace.py:185-471
 def two_point(A, params):
     """Connected meson two-point functions by the one-end trick.  The build-only keys
     source_timeslice = t0 and two_point_momenta = [p_0, ...] (default [0]; it has to contain 0) select the sources:
@@ -612,37 +490,13 @@ def two_point(A, params):
     if sel is None:
         raise Exception("two_point() needs the key source_timeslice")
     t0, momenta = sel
+    obs = _TwoPoint(momenta)
     if _dist.default_comm().world > 1:
-        raise Exception("two-point functions (source_timeslice) run on one rank")
+        raise Exception(obs.one_rank)
     mg_solver, nr_levels = _setup_solver(A, params, defer_coarse=True)
-    N = A.shape[0]
-    L = int(params['latt_dims'][0])
-    batch = int(params.get('batch', DEFAULT_BATCH))
-    kind = params.get('probe_type', 'z2')
-    zero = momenta.index(0)
-    shape = (len(momenta), 2, 2, 2, 2, L)
+    shape = (len(momenta), 2, 2, 2, 2, int(params['latt_dims'][0]))
     register_two_point(mg_solver, t0, momenta)
-
-    print("\nComputing rough estimation of the two-point functions ...", end='', flush=True)
-    np.random.seed(123456)                                      # stoch_trace.py:103-115
-    t0_s = time.time()
-    e, _, _ = probe_batch_two_point(mg_solver, params, draw_probes(NR_ROUGH_PROBES, N, kind))
-    rough = np.sum(two_point_columns(e, zero), axis=0) / NR_ROUGH_PROBES
-    level_tols = np.abs(params['tol'] * rough)
-    control = rough.size - 1
-    print(" done. Time : " + str(time.time() - t0_s) + " seconds")
-
-    print("\nResetting timer to zero ...", end='')
-    mg_solver.timer.reset()
-    mg_solver.engine.timers_reset()
-    print(" done")
-    print("\nComputing the two-point functions stochastically ...", end='', flush=True)
-    t0_s = time.time()
-    loop = run_probe_loop_displaced(DeviceTwoPointProbes(mg_solver, params, zero, kind), N, level_tols, control,
-                                    params['max_nr_ests'], batch * max(1, len(_engines(mg_solver))),
-                                    probe_type=kind)
-    loop_s = time.time() - t0_s
-    print(" done. Time : " + str(loop_s) + " seconds")
+    _, _, control, loop, loop_s = _estimate_stage(mg_solver, params, A.shape[0], obs)
 
     mg_solver.finish_setup()
     result = dict()
@@ -662,6 +516,78 @@ def two_point(A, params):
     return result
 
 
+# ---- the pieces mlmc() and the MLMC loop flows share -------------------------------------------------------
+def _skip_level_of(params):
+    """mlmc_levels_to_skip: whether the second level is skipped (the only form allowed)."""
+    skip_list = params['mlmc_levels_to_skip']
+    if len(skip_list) > 1:
+        raise Exception("Only allowed to skip one level for now")
+    skip_level = len(skip_list) == 1
+    if skip_level and not skip_list[0] == 1:
+        raise Exception("Only allowed to skip the second level for now")
+    return skip_level
+
+
+def _level_tol_fctr(i, nr_levels, skip_level):
+    """The share of the tolerance that level i takes (stoch_trace.py:327-336, 376-384); i = nr_levels - 1, the
+    coarsest level estimated stochastically, takes the share of the last difference level."""
+    if nr_levels < 3:
+        raise Exception("Number of levels restricted to >2 for now ...")
+    if nr_levels == 3:
+        frac0, frac1 = 0.8, 0.2
+    else:
+        frac0, frac1 = 0.45, 0.45
+    if skip_level:
+        frac0 = frac0 + frac1
+    if i == 0:
+        return sqrt(frac0)
+    if i == 1:
+        return sqrt(frac1)
+    if nr_levels == 3:                  # the coarsest level of three
+        return sqrt(1.0 - frac0) if skip_level else sqrt(frac1)
+    if skip_level:
+        return sqrt(1.0 - frac0) / sqrt(nr_levels - 3)
+    return sqrt(1.0 - frac0 - frac1) / sqrt(nr_levels - 3)
+
+
+def _diff_operator(mg_solver, ix):
+    """The difference operator (A_f^-1 - P A_c^-1 R) g3 of level ix for ARPACK            stoch_trace.py:257-270"""
+    mg_solver.level_for_diff_op = ix
+    n_ix = mg_solver.ml.levels[ix].A.shape[0]
+    return LinearOperator((n_ix, n_ix), dtype=np.complex128,
+                          matvec=lambda v: mg_solver.diff_op_Q(np.array(v, dtype=np.complex128)))
+
+
+def _mlmc_output(nr_levels, rough_trace, per_level=None):
+    """The result dictionary of the MLMC flows before any level ran; per_level(): further keys of every level."""
+    output_params = {'nr_levels': nr_levels, 'trace': 0.0, 'total_complexity': 0.0,
+                     'std_dev': 0.0, 'results': [], 'rough_trace': rough_trace}
+    for i in range(nr_levels):
+        output_params['results'].append({'function_iters': 0, 'nr_ests': 0, 'ests_avg': 0.0,
+                                         'ests_dev': 0.0, 'level_complexity': 0.0})
+        if per_level is not None:
+            output_params['results'][i].update(per_level())
+    return output_params
+
+
+def _mlmc_work_model(output_params, mg_solver):
+    """stoch_trace.py:443-467: the levels' complexities, their total and the total trace."""
+    levels = mg_solver.ml.levels
+    nr_levels = output_params['nr_levels']
+    last = nr_levels - 1
+    for i in range(nr_levels - 1):
+        res = output_params['results'][i]
+        res['level_complexity'] = res['function_iters'] * flopsV_manual(i, levels, i, mg_solver)
+        res['level_complexity'] += levels[last].A.nnz * mg_solver.coarsest_lev_iters[i]
+    nc = levels[last].A.shape[0]
+    output_params['results'][last]['level_complexity'] = \
+        pow(nc, 3) + output_params['results'][last]['function_iters'] * pow(nc, 2)
+    for i in range(nr_levels):
+        output_params['total_complexity'] += output_params['results'][i]['level_complexity']
+        output_params['trace'] += output_params['results'][i]['ests_avg']
+
+
+# compute tr(A^{-1}) via multigrid multilevel Monte Carlo          stoch_trace.py:185-471
 def mlmc(A, params):
     if two_point_of(params) is not None:
         raise Exception("source_timeslice belongs to two_point(), not to mlmc()")
@@ -672,16 +598,12 @@ def mlmc(A, params):
         raise Exception("x_displacements is implemented for hutchinson() only: the MLMC difference levels "
                         "need their own displaced right-hand sides")
     mlmc_defl_setup_of(params)
-    skip_list = params['mlmc_levels_to_skip']
-    if len(skip_list) > 1:
-        raise Exception("Only allowed to skip one level for now")
-    skip_level = len(skip_list) == 1
-    if skip_level and not skip_list[0] == 1:
-        raise Exception("Only allowed to skip the second level for now")
+    skip_level = _skip_level_of(params)
 
     mg_solver, nr_levels = _setup_solver(A, params)
     N = A.shape[0]
     batch = int(params.get('batch', DEFAULT_BATCH))
+    kind = params.get('probe_type', 'z2')
     mg_solver.skip_level = skip_level
 
     print("\nResetting timer to zero ...", end='')
@@ -696,13 +618,8 @@ def mlmc(A, params):
         if skip_level and ix == 1:
             tr1s.append(0.0)
             continue
-        # eigenvectors of the difference operator (A_f^-1 - P A_c^-1 R) g3   stoch_trace.py:257-270
-        mg_solver.level_for_diff_op = ix
-        n_ix = mg_solver.ml.levels[ix].A.shape[0]
-        lop = LinearOperator((n_ix, n_ix), dtype=np.complex128,
-                             matvec=lambda v: mg_solver.diff_op_Q(np.array(v, dtype=np.complex128)))
         _, _, tr1 = deflation_pre_computations(A, nr_deflat_vctrs[ix], tolx, "mlmc", mg_solver.timer,
-                                               params, mg_solver, lop, level_nr=ix)
+                                               params, mg_solver, _diff_operator(mg_solver, ix), level_nr=ix)
         tr1s.append(tr1)
     print(" done. Time : " + str(time.time() - t0) + " seconds")
     print(mg_solver.timer)
@@ -715,23 +632,9 @@ def mlmc(A, params):
                                          mg_solver.timer, params, mg_solver)
     print(" done. Time : " + str(time.time() - t0) + " seconds")
     print("\nComputing rough estimation of the trace ...", end='', flush=True)
-    rough_trace = _rough_trace(mg_solver, params, N, Vx, tr1)
+    rough_trace = _rough_estimate(mg_solver, params, N) + tr1
 
-    output_params = {'nr_levels': nr_levels, 'trace': 0.0, 'total_complexity': 0.0,
-                     'std_dev': 0.0, 'results': [], 'rough_trace': rough_trace}
-    for i in range(nr_levels):
-        output_params['results'].append({'function_iters': 0, 'nr_ests': 0, 'ests_avg': 0.0,
-                                         'ests_dev': 0.0, 'level_complexity': 0.0})
-
-    # tolerance split between the difference levels               stoch_trace.py:327-336
-    if nr_levels < 3:
-        raise Exception("Number of levels restricted to >2 for now ...")
-    if nr_levels == 3:
-        frac0, frac1 = 0.8, 0.2
-    else:
-        frac0, frac1 = 0.45, 0.45
-    if skip_level:
-        frac0 = frac0 + frac1
+    output_params = _mlmc_output(nr_levels, rough_trace)
 
     print("\nResetting timer to zero ...", end='')
     mg_solver.timer.reset()
@@ -744,23 +647,14 @@ def mlmc(A, params):
         if skip_level and i == 1:
             continue
         t0 = time.time()
-        if i == 0:
-            tol_fctr = sqrt(frac0)
-        elif i == 1:
-            tol_fctr = sqrt(frac1)
-        elif skip_level:
-            tol_fctr = sqrt(1.0 - frac0) / sqrt(nr_levels - 3)
-        else:
-            tol_fctr = sqrt(1.0 - frac0 - frac1) / sqrt(nr_levels - 3)
-        level_trace_tol = abs(params['tol'] * rough_trace * tol_fctr)
+        level_trace_tol = abs(params['tol'] * rough_trace * _level_tol_fctr(i, nr_levels, skip_level))
         n_i = levels[i].A.shape[0]
         lc = i + 2 if (skip_level and i == 0) else i + 1
         print("Computing for level " + str(i) + " ...", end='', flush=True)
 
-        source = DeviceProbes(mg_solver, params, "mlmc", i, params.get('probe_type', 'z2'))
+        source = DeviceProbes(mg_solver, params, "mlmc", i, kind)
         loop = run_probe_loop(source, n_i, level_trace_tol, params['max_nr_ests'],
-                              batch * max(1, len(_engines(mg_solver))),
-                              probe_type=params.get('probe_type', 'z2'))
+                              batch * max(1, len(_engines(mg_solver))), probe_type=kind)
         res = output_params['results']
         res[i]['function_iters'] += int(np.sum(loop["iters_fine"]))
         res[lc]['function_iters'] += int(np.sum(loop["iters_coarse"]))
@@ -790,16 +684,9 @@ def mlmc(A, params):
         # by plain Hutchinson probes on the coarsest level, with the tolerance share of the last
         # difference level
         n_c = levels[last].A.shape[0]
-        if nr_levels == 3:
-            tol_fctr = sqrt(1.0 - frac0) if skip_level else sqrt(frac1)
-        elif skip_level:
-            tol_fctr = sqrt(1.0 - frac0) / sqrt(nr_levels - 3)
-        else:
-            tol_fctr = sqrt(1.0 - frac0 - frac1) / sqrt(nr_levels - 3)
-        level_trace_tol = abs(params['tol'] * rough_trace * tol_fctr)
-        source = DeviceProbes(mg_solver, params, "level", last, params.get('probe_type', 'z2'))
-        loop = run_probe_loop(source, n_c, level_trace_tol, params['max_nr_ests'], batch,
-                              probe_type=params.get('probe_type', 'z2'))
+        level_trace_tol = abs(params['tol'] * rough_trace * _level_tol_fctr(last, nr_levels, skip_level))
+        source = DeviceProbes(mg_solver, params, "level", last, kind)
+        loop = run_probe_loop(source, n_c, level_trace_tol, params['max_nr_ests'], batch, probe_type=kind)
         res = output_params['results'][last]
         res['function_iters'] += int(np.sum(loop["iters_fine"]))
         res['nr_ests'] += loop["index"]
@@ -810,17 +697,7 @@ def mlmc(A, params):
     else:
         raise Exception("Stochastic coarsest-level computation is disabled at the moment.")
 
-    # work model                                                    stoch_trace.py:443-467
-    for i in range(nr_levels - 1):
-        res = output_params['results'][i]
-        res['level_complexity'] = res['function_iters'] * flopsV_manual(i, levels, i, mg_solver)
-        res['level_complexity'] += levels[last].A.nnz * mg_solver.coarsest_lev_iters[i]
-    nc = levels[last].A.shape[0]
-    output_params['results'][last]['level_complexity'] = \
-        pow(nc, 3) + output_params['results'][last]['function_iters'] * pow(nc, 2)
-    for i in range(nr_levels):
-        output_params['total_complexity'] += output_params['results'][i]['level_complexity']
-        output_params['trace'] += output_params['results'][i]['ests_avg']
+    _mlmc_work_model(output_params, mg_solver)
     mg_solver.sync_timer()
     print(mg_solver.timer)
     return output_params
@@ -850,13 +727,7 @@ def _mlmc_loops_checks(params, deflated=False):
         raise Exception("%s() computes the coarsest term exactly: coarsest_level_directly has to be true" % who)
     if _dist.default_comm().world > 1:
         raise Exception("MLMC loops (%s) run on one rank" % who)
-    skip_list = params['mlmc_levels_to_skip']
-    if len(skip_list) > 1:
-        raise Exception("Only allowed to skip one level for now")
-    skip_level = len(skip_list) == 1
-    if skip_level and not skip_list[0] == 1:
-        raise Exception("Only allowed to skip the second level for now")
-    return momenta, skip_level
+    return momenta, _skip_level_of(params)
 
 
 def mlmc_loops(A, params):
@@ -903,6 +774,9 @@ def _mlmc_loops_flow(A, params, deflated):
     shape = (len(momenta), 2, 2, L)
     mg_solver.skip_level = skip_level
 
+    def columns(loops):
+        return loop_columns(loops, zero)
+
     print("\nResetting timer to zero ...", end='')
     mg_solver.timer.reset()
     print(" done\n")
@@ -915,12 +789,7 @@ def _mlmc_loops_flow(A, params, deflated):
         # mlmc_loops(): no MLMC-level deflation, which clears what an earlier flow on these engines may have
         # registered; deflated_mlmc_loops(): the vectors of mlmc() (stoch_trace.py:257-270), then their sliced tr1
         k_ix = int(params['mlmc_deflat_vctrs'][ix]) if deflated and not (skip_level and ix == 1) else 0
-        lop = None
-        if k_ix > 0:
-            mg_solver.level_for_diff_op = ix
-            n_ix = mg_solver.ml.levels[ix].A.shape[0]
-            lop = LinearOperator((n_ix, n_ix), dtype=np.complex128,
-                                 matvec=lambda v: mg_solver.diff_op_Q(np.array(v, dtype=np.complex128)))
+        lop = _diff_operator(mg_solver, ix) if k_ix > 0 else None
         deflation_pre_computations(A, k_ix, params['defl_eigvs_tol_MLMC'], "mlmc", mg_solver.timer, params, mg_solver,
                                    lop, level_nr=ix)
         if k_ix > 0:
@@ -934,34 +803,17 @@ def _mlmc_loops_flow(A, params, deflated):
     t0 = time.time()
     Vx, tr1 = deflation_pre_computations(A, params['nr_deflat_vctrs'], params['defl_eigvs_tol_Hutch'], "hutchinson",
                                          mg_solver.timer, params, mg_solver)
-    tr1_cols = loop_columns(np.asarray(tr1, dtype=np.complex128)[None], zero)[0]
+    tr1_cols = columns(np.asarray(tr1, dtype=np.complex128)[None])[0]
     print(" done. Time : " + str(time.time() - t0) + " seconds")
     print("\nComputing rough estimation of the loops ...", end='', flush=True)
-    np.random.seed(123456)                                      # stoch_trace.py:288-302
-    t0 = time.time()
-    e, _, _ = probe_batch_loops(mg_solver, params, draw_probes(NR_ROUGH_PROBES, N, kind))
-    rough = np.sum(loop_columns(e, zero), axis=0) / NR_ROUGH_PROBES + tr1_cols
+    rough = _rough_estimate(mg_solver, params, N, "loops", columns) + tr1_cols
     control = rough.size - 1
-    rough_trace = rough[control]
-    print(" done. Time : " + str(time.time() - t0) + " seconds")
 
-    output_params = {'nr_levels': nr_levels, 'trace': 0.0, 'total_complexity': 0.0,
-                     'std_dev': 0.0, 'results': [], 'rough_trace': rough_trace}
-    for i in range(nr_levels):
-        output_params['results'].append({'function_iters': 0, 'nr_ests': 0, 'ests_avg': 0.0,
-                                         'ests_dev': 0.0, 'level_complexity': 0.0,
-                                         'loops': np.zeros(shape, dtype=np.complex128),
-                                         'loop_devs': np.zeros(shape),
-                                         'loop_ests': np.zeros((0,) + shape, dtype=np.complex128),
-                                         'converged': np.ones(shape, dtype=bool)})
-
-    # tolerance split between the difference levels               stoch_trace.py:327-336
-    if nr_levels == 3:
-        frac0, frac1 = 0.8, 0.2
-    else:
-        frac0, frac1 = 0.45, 0.45
-    if skip_level:
-        frac0 = frac0 + frac1
+    output_params = _mlmc_output(nr_levels, rough[control],
+                                 lambda: {'loops': np.zeros(shape, dtype=np.complex128),
+                                          'loop_devs': np.zeros(shape),
+                                          'loop_ests': np.zeros((0,) + shape, dtype=np.complex128),
+                                          'converged': np.ones(shape, dtype=bool)})
 
     print("\nResetting timer to zero ...", end='')
     mg_solver.timer.reset()
@@ -975,21 +827,13 @@ def _mlmc_loops_flow(A, params, deflated):
         if skip_level and i == 1:
             continue
         t0 = time.time()
-        if i == 0:
-            tol_fctr = sqrt(frac0)
-        elif i == 1:
-            tol_fctr = sqrt(frac1)
-        elif skip_level:
-            tol_fctr = sqrt(1.0 - frac0) / sqrt(nr_levels - 3)
-        else:
-            tol_fctr = sqrt(1.0 - frac0 - frac1) / sqrt(nr_levels - 3)
-        level_tols = np.abs(params['tol'] * rough * tol_fctr)
+        level_tols = np.abs(params['tol'] * rough * _level_tol_fctr(i, nr_levels, skip_level))
         n_i = levels[i].A.shape[0]
         lc = i + 2 if (skip_level and i == 0) else i + 1
         print("Computing for level " + str(i) + " ...", end='', flush=True)
-        loop = run_probe_loop_displaced(DeviceMLMCLoopProbes(mg_solver, params, i, zero, kind, deflated), n_i,
-                                        level_tols, control, params['max_nr_ests'],
-                                        batch * max(1, len(_engines(mg_solver))), probe_type=kind)
+        source = DeviceProbes(mg_solver, params, "mlmc_loops", i, kind, columns, deflated)
+        loop = run_probe_loop(source, n_i, level_tols, params['max_nr_ests'],
+                              batch * max(1, len(_engines(mg_solver))), probe_type=kind, control=control)
         res[i]['function_iters'] += int(np.sum(loop["iters_fine"]))
         res[lc]['function_iters'] += int(np.sum(loop["iters_coarse"]))
         mg_solver.coarsest_lev_iters[i] += int(np.sum(loop["iters_fine"]))
@@ -1006,7 +850,7 @@ def _mlmc_loops_flow(A, params, deflated):
         res[i]['converged'] = loop["converged"][:control].reshape(shape)
         if deflated:
             # the exact deflated part: added to the means, the per-probe series stay as the probes gave them
-            t1 = loop_columns(loop_tr1[i][None], zero)[0]
+            t1 = columns(loop_tr1[i][None])[0]
             res[i]['ests_avg'] = loop["avg"] + t1[control]
             res[i]['loops'] = res[i]['loops'] + loop_tr1[i]
             res[i]['loop_tr1'] = loop_tr1[i]
@@ -1021,17 +865,10 @@ def _mlmc_loops_flow(A, params, deflated):
     res[last]['ests_avg'] = np.trace(mg_solver.coarsest_inv)
     res[last]['ests_dev'] = 0
 
-    # work model                                                    stoch_trace.py:443-467
-    for i in range(nr_levels - 1):
-        res[i]['level_complexity'] = res[i]['function_iters'] * flopsV_manual(i, levels, i, mg_solver)
-        res[i]['level_complexity'] += levels[last].A.nnz * mg_solver.coarsest_lev_iters[i]
-    nc = levels[last].A.shape[0]
-    res[last]['level_complexity'] = pow(nc, 3) + res[last]['function_iters'] * pow(nc, 2)
+    _mlmc_work_model(output_params, mg_solver)
     output_params['loops'] = np.zeros(shape, dtype=np.complex128)
     var = np.zeros(shape)
     for i in range(nr_levels):
-        output_params['total_complexity'] += res[i]['level_complexity']
-        output_params['trace'] += res[i]['ests_avg']
         output_params['loops'] = output_params['loops'] + res[i]['loops']
         if i < last:
             var = var + np.square(res[i]['loop_devs']) / (res[i]['nr_ests'] + 1)

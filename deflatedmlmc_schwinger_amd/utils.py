@@ -7,9 +7,7 @@ import numpy as np
 from scipy.sparse.linalg import eigsh
 
 from . import dist as _dist
-from .engine import (MAX_MOMENTA, MAX_SHIFTS, MODE_HUTCHINSON, MODE_HUTCHINSON_LOOPS, MODE_HUTCHINSON_SHIFTS,
-                     MODE_LEVEL, MODE_MLMC, MODE_MLMC_DEFL_LOOPS, MODE_MLMC_DEFL_LOOPS_SKIP, MODE_MLMC_LOOPS,
-                     MODE_MLMC_LOOPS_SKIP, MODE_MLMC_SKIP, MODE_TWO_POINT, EngineError)
+from .engine import MAX_MOMENTA, MAX_SHIFTS, RESOLVED_FETCH, EngineError, probe_mode
 
 
 # ----------------------------------------------------------------------------------------
@@ -682,21 +680,34 @@ def probes_as_complex(probes):
     return np.where(np.abs(p) == 2, 1j * (p // 2), p).astype(np.complex128)
 
 
-def probe_batch(mg_solver, params, method, probes, level=0):
+def _batch_args(mg_solver, params, method, level, deflated):
+    """(engine handles, mode, solve tolerance, level size, iteration cap) of a probe batch of `method` at `level`."""
+    engs = _engines(mg_solver)
+    if not engs:
+        raise EngineError("no GPU engine attached (run MG.setup first)")
+    n = mg_solver.ml.levels[level].A.shape[0]
+    mode = probe_mode(method, level, getattr(mg_solver, "skip_level", False), deflated)
+    return engs, mode, params['function_params']['tol'], n, (n if n < 1000 else 1000)
+
+
+def probe_batch(mg_solver, params, method, probes, level=0, deflated=False):
     """Evaluate one batch of probes on the GPU: returns (ests, iters_fine, iters_coarse).
 
     hutchinson: e = x^H A^-1 Pperm^T (x - U U^H x)            utils.py:210-250
     mlmc      : e = x^H A_f^-1 C x - x^H P A_c^-1 R C x        utils.py:252-361
-    (deflation vectors and permutation were registered with the engine at setup)."""
-    engs = _engines(mg_solver)
-    if not engs:
-        raise EngineError("no GPU engine attached (run MG.setup first)")
-    tol = params['function_params']['tol']
-    n = mg_solver.ml.levels[level].A.shape[0]
-    maxiter = n if n < 1000 else 1000
-    mode = _probe_mode(mg_solver, method, level)
+    (deflation vectors and permutation were registered with the engine at setup).  The resolved methods return
+    one row per probe from one projection and one solve per probe, on the first engine handle:
+    shifts    : ests[nb, S], e[k, j] = (D_{s_j}^T x_k)^H A^-1 (x_k - W W^H x_k) at every registered shift
+    loops     : loops[nb, nmom, 2, 2, L] (MODE_HUTCHINSON_LOOPS)
+    mlmc_loops: loops[nb, nmom, 2, 2, L], the term of `level` (MODE_MLMC_LOOPS, _SKIP at level 0 with
+                mg_solver.skip_level; deflated: MODE_MLMC_DEFL_LOOPS / _SKIP, the level's registered projection)
+    two_point : T[nb, nmom, 2, 2, 2, 2, L], the probes being the noises: 2 nmom solves per noise, no deflation;
+                iters_fine is the largest count among a noise's solves."""
+    engs, mode, tol, _, maxiter = _batch_args(mg_solver, params, method, level, deflated)
     probes = np.asarray(probes)
     nb = probes.shape[0]
+    if mode in RESOLVED_FETCH:
+        return engs[0].hutch_batch_resolved(mode, level, probes, tol, maxiter)
     if len(engs) == 1 or nb < 2 * 64:
         return engs[0].hutch_batch(mode, level, probes, tol, maxiter)
     # several engine handles = several HIP streams on the same GPU: the sub-batches overlap
@@ -710,52 +721,10 @@ def probe_batch(mg_solver, params, method, probes, level=0):
     return tuple(np.concatenate([r[k] for r in res]) for k in range(3))
 
 
-def _shift_batch_args(mg_solver, params):
-    engs = _engines(mg_solver)
-    if not engs:
-        raise EngineError("no GPU engine attached (run MG.setup first)")
-    n = mg_solver.ml.levels[0].A.shape[0]
-    return engs, params['function_params']['tol'], n, (n if n < 1000 else 1000)
-
-
 def register_shifts(mg_solver, shifts):
     """Hand the flat shifts of the displaced traces to every engine handle (None clears)."""
     for eng in _engines(mg_solver):
         eng.set_shifts(shifts)
-
-
-def probe_batch_shifts(mg_solver, params, probes):
-    """One batch of probes at every registered shift: (ests[nb, S], iters_fine, iters_coarse) with
-    e[k, j] = (D_{s_j}^T x_k)^H A^-1 (x_k - W W^H x_k) -- one projection and one solve per probe."""
-    engs, tol, _, maxiter = _shift_batch_args(mg_solver, params)
-    return engs[0].hutch_batch_shifts(0, np.asarray(probes), tol, maxiter)
-
-
-def probe_batch_shifts_generated(mg_solver, params, first_probe, count, kind="z2"):
-    """probe_batch_shifts for the probes [first_probe, first_probe + count) of the stream the engines hold
-    (Engine.stream_set), generated on the device; several engine handles share the batch as in
-    probe_batch_generated."""
-    engs, tol, n, maxiter = _shift_batch_args(mg_solver, params)
-    ne = len(engs) if count >= 2 * 64 else 1
-    bounds = [(k * count) // ne for k in range(ne + 1)]
-    active = [k for k in range(ne) if bounds[k + 1] > bounds[k]]
-    for k in active:
-        engs[k].probes_generate(0, 0, bounds[k + 1] - bounds[k], (first_probe + bounds[k]) * n, kind)
-
-    def run(k):
-        eng = engs[k]
-        eng.probes_select(0)
-        eng.hutch_run(MODE_HUTCHINSON_SHIFTS, 0, tol, maxiter)
-        _, itf, itc = eng.hutch_fetch()
-        return eng.hutch_fetch_shifts(), itf, itc
-
-    if len(active) == 1:
-        res = [run(active[0])]
-    else:
-        from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=len(active)) as pool:
-            res = list(pool.map(run, active))
-    return tuple(np.concatenate([r[k] for r in res]) for k in range(3))
 
 
 def register_loop_momenta(mg_solver, momenta):
@@ -764,161 +733,26 @@ def register_loop_momenta(mg_solver, momenta):
         eng.set_loop_momenta(momenta)
 
 
-def probe_batch_loops(mg_solver, params, probes):
-    """One batch of probes through MODE_HUTCHINSON_LOOPS: (loops[nb, nmom, 2, 2, L], iters_fine, iters_coarse)
-    -- one projection and one solve per probe."""
-    engs, tol, _, maxiter = _shift_batch_args(mg_solver, params)
-    return engs[0].hutch_batch_loops(0, np.asarray(probes), tol, maxiter)
-
-
-def probe_batch_loops_generated(mg_solver, params, first_probe, count, kind="z2"):
-    """probe_batch_loops for the probes [first_probe, first_probe + count) of the stream the engines hold
-    (Engine.stream_set), generated on the device; several engine handles share the batch as in
-    probe_batch_generated."""
-    engs, tol, n, maxiter = _shift_batch_args(mg_solver, params)
-    ne = len(engs) if count >= 2 * 64 else 1
-    bounds = [(k * count) // ne for k in range(ne + 1)]
-    active = [k for k in range(ne) if bounds[k + 1] > bounds[k]]
-    for k in active:
-        engs[k].probes_generate(0, 0, bounds[k + 1] - bounds[k], (first_probe + bounds[k]) * n, kind)
-
-    def run(k):
-        eng = engs[k]
-        eng.probes_select(0)
-        eng.hutch_run(MODE_HUTCHINSON_LOOPS, 0, tol, maxiter)
-        _, itf, itc = eng.hutch_fetch()
-        return eng.hutch_fetch_loops(), itf, itc
-
-    if len(active) == 1:
-        res = [run(active[0])]
-    else:
-        from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=len(active)) as pool:
-            res = list(pool.map(run, active))
-    return tuple(np.concatenate([r[k] for r in res]) for k in range(3))
-
-
-def _mlmc_loops_skip(mg_solver, level):
-    return bool(getattr(mg_solver, "skip_level", False)) and level == 0
-
-
-def _level_batch_args(mg_solver, params, level):
-    engs = _engines(mg_solver)
-    if not engs:
-        raise EngineError("no GPU engine attached (run MG.setup first)")
-    n = mg_solver.ml.levels[level].A.shape[0]
-    return engs, params['function_params']['tol'], n, (n if n < 1000 else 1000)
-
-
-def probe_batch_mlmc_loops(mg_solver, params, level, probes, deflated=False):
-    """One batch of probes of `level` through MODE_MLMC_LOOPS (MODE_MLMC_LOOPS_SKIP at level 0 with
-    mg_solver.skip_level): (loops[nb, nmom, 2, 2, L], iters_fine, iters_coarse), the level's term of the loops.
-    deflated: through MODE_MLMC_DEFL_LOOPS / _SKIP, with the level's registered projection."""
-    engs, tol, _, maxiter = _level_batch_args(mg_solver, params, level)
-    return engs[0].hutch_batch_mlmc_loops(level, np.asarray(probes), tol, maxiter,
-                                          skip=_mlmc_loops_skip(mg_solver, level), deflated=deflated)
-
-
-def probe_batch_mlmc_loops_generated(mg_solver, params, level, first_probe, count, kind="z2", deflated=False):
-    """probe_batch_mlmc_loops for the probes [first_probe, first_probe + count) of the stream the engines hold
-    (Engine.stream_set), generated on the device; several engine handles share the batch as in
-    probe_batch_generated."""
-    engs, tol, n, maxiter = _level_batch_args(mg_solver, params, level)
-    if deflated:
-        mode = MODE_MLMC_DEFL_LOOPS_SKIP if _mlmc_loops_skip(mg_solver, level) else MODE_MLMC_DEFL_LOOPS
-    else:
-        mode = MODE_MLMC_LOOPS_SKIP if _mlmc_loops_skip(mg_solver, level) else MODE_MLMC_LOOPS
-    ne = len(engs) if count >= 2 * 64 else 1
-    bounds = [(k * count) // ne for k in range(ne + 1)]
-    active = [k for k in range(ne) if bounds[k + 1] > bounds[k]]
-    for k in active:
-        engs[k].probes_generate(0, level, bounds[k + 1] - bounds[k], (first_probe + bounds[k]) * n, kind)
-
-    def run(k):
-        eng = engs[k]
-        eng.probes_select(0)
-        eng.hutch_run(mode, level, tol, maxiter)
-        _, itf, itc = eng.hutch_fetch()
-        return eng.hutch_fetch_mlmc_loops(), itf, itc
-
-    if len(active) == 1:
-        res = [run(active[0])]
-    else:
-        from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=len(active)) as pool:
-            res = list(pool.map(run, active))
-    return tuple(np.concatenate([r[k] for r in res]) for k in range(3))
-
-
 def register_two_point(mg_solver, t0, momenta):
     """Hand the source timeslice and momenta of two_point() to every engine handle (momenta None clears)."""
     for eng in _engines(mg_solver):
         eng.set_two_point(t0, momenta)
 
 
-def probe_batch_two_point(mg_solver, params, probes):
-    """One batch of noises through MODE_TWO_POINT: (T[nb, nmom, 2, 2, 2, 2, L], iters_fine, iters_coarse) -- 2 nmom
-    solves per noise, no deflation; iters_fine is the largest count among a noise's solves."""
-    engs, tol, _, maxiter = _shift_batch_args(mg_solver, params)
-    return engs[0].hutch_batch_two_point(0, np.asarray(probes), tol, maxiter)
-
-
-def probe_batch_two_point_generated(mg_solver, params, first_probe, count, kind="z2"):
-    """probe_batch_two_point for the noises [first_probe, first_probe + count) of the stream the engines hold
-    (Engine.stream_set), generated on the device; several engine handles share the batch as in
-    probe_batch_generated."""
-    engs, tol, n, maxiter = _shift_batch_args(mg_solver, params)
-    ne = len(engs) if count >= 2 * 64 else 1
-    bounds = [(k * count) // ne for k in range(ne + 1)]
-    active = [k for k in range(ne) if bounds[k + 1] > bounds[k]]
-    for k in active:
-        engs[k].probes_generate(0, 0, bounds[k + 1] - bounds[k], (first_probe + bounds[k]) * n, kind)
-
-    def run(k):
-        eng = engs[k]
-        eng.probes_select(0)
-        eng.hutch_run(MODE_TWO_POINT, 0, tol, maxiter)
-        _, itf, itc = eng.hutch_fetch()
-        return eng.hutch_fetch_two_point(), itf, itc
-
-    if len(active) == 1:
-        res = [run(active[0])]
-    else:
-        from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=len(active)) as pool:
-            res = list(pool.map(run, active))
-    return tuple(np.concatenate([r[k] for r in res]) for k in range(3))
-
-
-def _probe_mode(mg_solver, method, level):
-    if method == "hutchinson":
-        return MODE_HUTCHINSON
-    if method == "mlmc":
-        return MODE_MLMC_SKIP if (mg_solver.skip_level and level == 0) else MODE_MLMC
-    if method == "level":
-        return MODE_LEVEL
-    raise Exception("unknown method")
-
-
 def probe_batch_generated(mg_solver, params, method, level, first_probe, count, kind="z2",
-                          prefetch=None, ready=None):
+                          prefetch=None, ready=None, deflated=False):
     """Like probe_batch, for the probes [first_probe, first_probe + count) of the stream the
     engines were handed with Engine.stream_set: each engine GENERATES its contiguous share in
     HBM (k_mt_generate, bit-exact with np.random.randint, utils.py:213-216,255-258) and
-    evaluates it; only the 16-byte estimates come back.
+    evaluates it; only the 16-byte estimates -- and the rows of a resolved method -- come back.
 
     Generation is asynchronous on the engines' generation streams.  `prefetch` = (first_probe, count)
     of the batch expected NEXT: its probes are queued into the engines' other slot before this batch is
     solved, so they are drawn while the solve runs; `ready` = the (first_probe, count, slot) a previous
     call prefetched (skips this batch's own generation when it matches).  Returns
     (ests, iters_fine, iters_coarse, prefetched) with prefetched = (first, count, slot) or None."""
-    engs = _engines(mg_solver)
-    if not engs:
-        raise EngineError("no GPU engine attached (run MG.setup first)")
-    tol = params['function_params']['tol']
-    n = mg_solver.ml.levels[level].A.shape[0]
-    maxiter = n if n < 1000 else 1000
-    mode = _probe_mode(mg_solver, method, level)
+    engs, mode, tol, n, maxiter = _batch_args(mg_solver, params, method, level, deflated)
+    resolved = mode in RESOLVED_FETCH
     ne = len(engs) if count >= 2 * 64 else 1
 
     def shares(cnt):
@@ -946,7 +780,8 @@ def probe_batch_generated(mg_solver, params, method, level, first_probe, count, 
     def run(eng):
         eng.probes_select(slot)
         eng.hutch_run(mode, level, tol, maxiter)
-        return eng.hutch_fetch()
+        ests, itf, itc = eng.hutch_fetch()
+        return (eng.hutch_fetch_resolved(mode) if resolved else ests), itf, itc
 
     active = [engs[k] for k in range(ne) if bounds[k + 1] > bounds[k]]
     if len(active) == 1:

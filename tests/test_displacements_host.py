@@ -71,7 +71,7 @@ def test_displaced_loop_control_column_replays_run_probe_loop(lib_built):
                                      batch)
     state_ref = np.random.get_state()[1].copy()
     np.random.seed(99)
-    got = stoch_trace.run_probe_loop_displaced(fake, n, tols, control, 4000, batch)
+    got = stoch_trace.run_probe_loop(fake, n, tols, 4000, batch, control=control)
     assert got["index"] == ref["index"] and got["index"] >= batch        # more than one round
     assert got["avg"] == ref["avg"] and got["dev"] == ref["dev"]
     assert np.array_equal(got["ests"][:, control], ref["ests"])
