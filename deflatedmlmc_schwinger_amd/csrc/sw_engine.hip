@@ -3963,6 +3963,109 @@ int sw_vcycle(sw_engine* h, int hid, int level0, int nb, const double* B, double
   return unpack_host(h, lv, nb, b, X, nbp);
 }
 
+// One operation of the complex64 cycle alone on host vectors (the per-kernel parity tests): fp64 in, cast to
+// complex64 (k_cast), ONE launch through the launcher vcycle32 / vcycle32_even use -- with the kernel category
+// they pass, so the options pick the variant exactly as in the cycle --, cast back (exact), fp64 out.  Rows the
+// operation does not write come back zero (in place: as they went in).
+int sw_apply_op32(sw_engine* h, int hid, int level, int which, int mode, int nb, const double* X, const double* B,
+                  double w_re, double w_im, int flags, double* Y, int32_t* info) {
+  SWCHK(check_hier(h, hid, level, true));
+  const bool inplace = (flags & SW_OP32_INPLACE) != 0;
+  const bool square = which == SW_OP32_A || (which >= SW_OP32_EO0 && which <= SW_OP32_EO0 + 4);
+  const bool smoother = which == SW_OP32_EO_SMOOTH || which == SW_OP32_EO_SMOOTH_REDUCED;
+  if (which < 0 || which > SW_OP32_EO_SMOOTH_REDUCED || nb <= 0 || !X || !Y || (flags & ~SW_OP32_INPLACE))
+    return sw_fail(h, "sw_apply_op32: bad arguments");
+  if (!(mode == 0 || (square && (mode == 1 || mode == 3))))
+    return sw_fail(h, "sw_apply_op32: operation %d has no mode %d", which, mode);
+  if (inplace && !(square && mode == 1))
+    return sw_fail(h, "sw_apply_op32: the in-place form is Y = X - op X (mode 1) of a square operator");
+  if (!B && ((mode != 0 && !inplace) || smoother)) return sw_fail(h, "sw_apply_op32: operation %d needs B", which);
+  HIPCHK(hipSetDevice(h->device));
+  Hier& H = h->hier[hid];
+  const int last = H.nlevels - 1;
+  const bool transfer = which >= SW_OP32_R && which <= SW_OP32_RE;
+  if (transfer && level >= last) return sw_fail(h, "no transfer at the coarsest level");
+  if (which == SW_OP32_COARSEST && level != last)
+    return sw_fail(h, "sw_apply_op32: the coarsest inverse acts on level %d", last);
+  Level& lv = H.lv[level];
+  Level& lc = H.lv[transfer ? level + 1 : level];
+  const bool on_stencil = which == SW_OP32_RE || which == SW_OP32_SCHUR || smoother;
+  if (on_stencil && !(lv.stencil && lv.U1 && !lv.w_eo.empty()))
+    return sw_fail(h, "level %d is not a lattice level with the even-odd smoother", level);
+  const EllOp* op = nullptr;
+  int cat = T_MVM;
+  if (which == SW_OP32_A) op = &lv.A;
+  if (which == SW_OP32_R) { op = &lv.R; cat = T_R; }
+  if (which == SW_OP32_P || which == SW_OP32_P_EVEN) { op = &lv.P; cat = T_P; }
+  if (which == SW_OP32_COARSEST) { op = &H.cinv; cat = T_COARSEST; }
+  if (square && which != SW_OP32_A) {
+    op = &lv.eo_op[which - SW_OP32_EO0];
+    if (which == SW_OP32_EO0 + 4) cat = T_COARSEST;
+  }
+  if (which == SW_OP32_A && lv.stencil) return sw_fail(h, "level %d is the lattice level: no complex64 operator", level);
+  if (op && !op->set) return sw_fail(h, "level %d: operation %d has no operator", level, which);
+  const int nbp = pad64(nb);
+  SWCHK(ensure_f32(h, H));
+  if (which == SW_OP32_RE || which == SW_OP32_P_EVEN) {
+    SWCHK(ensure_even_orders(h, H));
+    if (which == SW_OP32_RE) {
+      if (!lv.Re.set) return sw_fail(h, "level %d has no even-column restrictor", level);
+      SWCHK(mirror_op32(h, lv.Re));
+      op = &lv.Re;
+      cat = T_R;
+    } else if (!(lv.P.order_even && h->p_even)) {
+      return sw_fail(h, "level %d has no even-sites-only prolongation", level);
+    }
+  }
+  if (info) {
+    info[0] = op ? (op->bsr_RT > 0 ? op->bsr_RT : (op->bsr_KS > 0 ? op->nrows / 16 : 0)) : 0;
+    info[1] = op ? op->bsr_KS : 0;
+    info[2] = (op && op->cols) ? op->G : 0;
+    info[3] = (op && op->cols) ? op->K : 0;
+  }
+  // input on `lin`, output on `lout` (they differ for the transfers only)
+  const bool up = which == SW_OP32_P || which == SW_OP32_P_EVEN;
+  Level& lin = up ? lc : lv;
+  Level& lout = up ? lv : lc;
+  SWCHK(ensure_level_ws32(h, lin, nbp));
+  SWCHK(ensure_level_ws32(h, lout, nbp));
+  cplx *a, *b, *c, *d;
+  SWCHK(io_vectors(h, lin, nbp, &a, &b));
+  SWCHK(io_vectors(h, lout, nbp, &c, &d));
+  (void)b;
+  const size_t cin = (size_t)lin.n * nbp, cout = (size_t)lout.n * nbp;
+  const cplxf w{(float)w_re, (float)w_im};
+  cplxf* x32 = lin.x32;
+  cplxf* y32 = inplace ? x32 : lout.t32;
+  if (smoother) {
+    // as vcycle32 / vcycle32_even: the iterate starts in the buffer from which the last step lands in Xout
+    const bool odd_steps = (lv.w_eo.size() & 1) != 0;
+    y32 = lv.x32;
+    x32 = odd_steps ? lv.t32 : lv.x32;
+  }
+  SWCHK(pack_host(h, lin, nb, X, a, nbp));
+  SWCHK(cast_vec(h, (const cplx*)a, x32, cin));
+  const cplxf* b32 = inplace ? x32 : nullptr;
+  if (B && !inplace && (mode != 0 || smoother)) {
+    SWCHK(pack_host(h, lout, nb, B, c, nbp));
+    SWCHK(cast_vec(h, (const cplx*)c, lout.b32, cout));
+    b32 = lout.b32;
+  }
+  if (!inplace && !smoother) HIPCHK(hipMemsetAsync(y32, 0, cout * sizeof(cplxf), h->stream));
+  if (which == SW_OP32_SCHUR) {
+    SWCHK(schur_apply32(h, lv, x32, y32, nbp));
+  } else if (smoother) {
+    cplxf* other = (x32 == lv.x32) ? lv.t32 : lv.x32;
+    SWCHK(eo_smooth32(h, lv, b32, x32, other, y32, nbp, which == SW_OP32_EO_SMOOTH_REDUCED));
+  } else {
+    SWCHK(launch_ell32(h, *op, mode, x32, b32, y32, nbp, cat, w, which == SW_OP32_P_EVEN));
+  }
+  SWCHK(cast_vec(h, (const cplxf*)y32, d, cout));
+  if (which == SW_OP32_EO_SMOOTH_REDUCED)      // half vectors: the odd sites' rows were never the smoother's
+    HIPCHK(hipMemsetAsync(d + cout / 2, 0, (cout / 2) * sizeof(cplx), h->stream));
+  return unpack_host(h, lout, nb, d, Y, nbp);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Outer solve of an even-odd smoothed stencil level on the EVEN-ODD REDUCED system.
 //   A x = b  <=>  S x_e = b'_e,  b'_e = b_e - A_eo A_oo^-1 b_o,  x_o = A_oo^-1 (b_o - A_oe x_e),

@@ -60,6 +60,18 @@ KCLASS_TP_DOTS = 18
 KCLASS_SLICE_CDOTS = 19    # ... and of k_slice_cdots (MLMC loops)
 MAX_SHIFTS = 128
 MAX_MOMENTA = 8
+# operations of Engine.apply_op32 (SW_OP32_* of the header): one kernel of the complex64 cycle at a time
+OP32_A = 0
+OP32_R = 1
+OP32_P = 2
+OP32_P_EVEN = 3
+OP32_RE = 4
+OP32_COARSEST = 5
+OP32_EO0 = 6                 # + q: even-odd operator q = 0..4 of a block level
+OP32_SCHUR = 11
+OP32_EO_SMOOTH = 12
+OP32_EO_SMOOTH_REDUCED = 13
+OP32_INPLACE = 1
 PROBES_Z2 = 1
 PROBES_Z4 = 2
 PROBE_KINDS = {"z2": PROBES_Z2, "z4": PROBES_Z4}
@@ -157,6 +169,7 @@ def load_library():
     sig("sw_coarsest", i32, vp, i32, i32, vp, vp)
     sig("sw_apply_deflation", i32, vp, i32, i32, i32, vp, vp)
     sig("sw_vcycle", i32, vp, i32, i32, i32, vp, vp)
+    sig("sw_apply_op32", i32, vp, i32, i32, i32, i32, i32, vp, vp, dbl, dbl, i32, vp, vp)
     sig("sw_solve", i32, vp, i32, i32, i32, vp, vp, dbl, i32, vp, vp)
     sig("sw_hutch_batch", i32, vp, i32, i32, i32, vp, dbl, i32, vp, vp)
     sig("sw_probes_upload", i32, vp, i32, i32, vp)
@@ -216,7 +229,7 @@ EXPORTED_SYMBOLS = (
     "sw_get_level_bsr", "sw_setup_testvectors", "sw_setup_transfer",
     "sw_setup_galerkin", "sw_get_level_dense", "sw_setup_invert_coarsest", "sw_setup_direct_level", "sw_setup_level_inverse", "sw_setup_arnoldi", "sw_hier_end", "sw_set_deflation", "sw_set_level_deflation", "sw_set_perm", "sw_set_rhsmap", "sw_set_solver", "sw_set_option", "sw_get_option",
     "sw_pool_trim", "sw_get_coarsest_inv", "sw_eig_begin", "sw_eig_begin_wide", "sw_eig_load", "sw_eig_solve", "sw_eig_apply_diff", "sw_eig_gram", "sw_eig_rotate", "sw_eig_fetch", "sw_eig_end",
-    "sw_apply_dirac", "sw_restrict", "sw_prolong", "sw_coarsest", "sw_apply_deflation", "sw_vcycle", "sw_solve",
+    "sw_apply_dirac", "sw_restrict", "sw_prolong", "sw_coarsest", "sw_apply_deflation", "sw_vcycle", "sw_apply_op32", "sw_solve",
     "sw_hutch_batch", "sw_probes_upload", "sw_probes_upload_slot", "sw_probes_select",
     "sw_kernel_stats", "sw_kernel_work", "sw_hutch_run", "sw_sync", "sw_hutch_fetch",
     "sw_comm_unique_id", "sw_comm_init", "sw_allreduce_stats", "sw_comm_destroy",
@@ -604,6 +617,27 @@ class Engine:
         self._chk(self._lib.sw_vcycle(self._h, hid, level0, B2.shape[0], _ptr(B2), _ptr(X)),
                   "sw_vcycle")
         return X[0] if single else X
+
+    def apply_op32(self, hid, level, which, X, B=None, mode=0, w=0.0, in_place=False):
+        """One operation of the complex64 cycle alone (sw_apply_op32; which = OP32_*): Y = op X (mode 0),
+        B - op X (1) or X + w (B - op X) (3) in complex64 through the cycle's own launcher, widened to complex128;
+        in_place: mode 1 with B = Y = X on the device.  Returns (Y, info) with info = (row tiles, k-steps, ELL
+        group size G, ELL entries per row K) of the operator applied."""
+        n_in = self._n(hid, level + 1) if which in (OP32_P, OP32_P_EVEN) else self._n(hid, level)
+        n_out = self._n(hid, level + 1) if which in (OP32_R, OP32_RE) else self._n(hid, level)
+        X2, single = self._io(X, n_in)
+        B2 = None
+        if B is not None:
+            B2, _ = self._io(B, n_out)
+            if B2.shape[0] != X2.shape[0]:
+                raise EngineError("X and B differ in the number of vectors")
+        Y = np.empty((X2.shape[0], n_out), dtype=np.complex128)
+        info = np.zeros(4, dtype=np.int32)
+        w = complex(w)
+        self._chk(self._lib.sw_apply_op32(self._h, hid, level, int(which), int(mode), X2.shape[0], _ptr(X2),
+                                          _ptr(B2) if B2 is not None else None, w.real, w.imag,
+                                          OP32_INPLACE if in_place else 0, _ptr(Y), _ptr(info)), "sw_apply_op32")
+        return (Y[0] if single else Y), tuple(int(v) for v in info)
 
     def solve(self, hid, level0, B, tol, maxiter=1000):
         B2, single = self._io(B, self._n(hid, level0))

@@ -334,6 +334,47 @@ int sw_apply_slice_sources(sw_engine* h, int nb, const int8_t* probes, double* o
 int sw_apply_pair_dots(sw_engine* h, int nb, const double* Z, double* out);
 /* X = one multigrid cycle applied to B starting at level0 (MG.one_mg_step, multigrid.py:369-447). */
 int sw_vcycle(sw_engine* h, int hid, int level0, int nb, const double* B, double* X);
+/* ONE operation of the complex64 cycle (option "precond_f32") alone on host vectors, for the per-kernel parity
+ * tests: X (and B) are cast to complex64 on the device, the operation is launched through the launcher the
+ * complex64 cycle uses, with the kernel category the cycle passes -- so "f32_tiles", "f32_stages",
+ * "f32_dense_stages", "f32_splitk", "f32_pairs" and the batch width pick the kernel variant exactly as they do
+ * there --, and the result is widened (exact) into Y.  The complex64 mirrors are made whatever "precond_f32" is.
+ * `which` at `level`:
+ *   SW_OP32_A           the level operator of a block level (block-row kernel, or grouped ELL where the level has
+ *                       no block rows); modes 0, 1, 3
+ *   SW_OP32_R           Y = R_level X        X: level vectors, Y: vectors of level + 1
+ *   SW_OP32_P           Y = P_level X        X: vectors of level + 1, Y: level vectors
+ *   SW_OP32_P_EVEN      the same onto the even sites' rows only (option "p_even", an even-odd smoothed level)
+ *   SW_OP32_RE          Y = R_level X from the even sites' columns only (lattice level smoothed even-odd; the
+ *                       odd sites' entries of X are not read)
+ *   SW_OP32_COARSEST    Y = coarsest_inv X   (level = the coarsest level)
+ *   SW_OP32_EO0 + q     even-odd operator q = 0..4 of a block level (sw_set_eo_operator); modes 0, 1, 3; q = 4
+ *                       is launched as a dense operator, like the coarsest inverse
+ *   SW_OP32_SCHUR       Y_e = S X_e on the lattice level (k_schur_step, half vectors: the odd sites' entries of X
+ *                       are not read)
+ *   SW_OP32_EO_SMOOTH   the lattice level's even-odd smoother as the cycle runs it: b'_e = b_e + H_eo b_o / D,
+ *                       the registered steps x_e <- x_e + w_k (b'_e - S x_e) from x_e = the even sites' entries
+ *                       of X, then x_o = (b_o + H_oe x_e) / D; B = b, Y = x
+ *   SW_OP32_EO_SMOOTH_REDUCED  the steps alone, as the even-odd reduced cycle runs them: B holds b'_e
+ * mode (operations that list modes; 0 otherwise): 0: Y = op X, 1: Y = B - op X, 3: Y = X + w (B - op X) with
+ * w = w_re + i w_im rounded to complex64.  flags = SW_OP32_INPLACE (mode 1 only): B and Y are X itself on the
+ * device, Y = X - op X written over X, as the cycle calls even-odd operator 3.  B may be NULL where it is not
+ * read.  Rows an operation does not write come back zero (in place: as they went in).  info (may be NULL)
+ * receives {row tiles, k-steps per tile} of the operator's block-row form (0, 0 without one) and {group size G,
+ * entries per row K} of its grouped-ELL form (0, 0 without one; lattice-level kernels: all four 0). */
+#define SW_OP32_A 0
+#define SW_OP32_R 1
+#define SW_OP32_P 2
+#define SW_OP32_P_EVEN 3
+#define SW_OP32_RE 4
+#define SW_OP32_COARSEST 5
+#define SW_OP32_EO0 6
+#define SW_OP32_SCHUR 11
+#define SW_OP32_EO_SMOOTH 12
+#define SW_OP32_EO_SMOOTH_REDUCED 13
+#define SW_OP32_INPLACE 1
+int sw_apply_op32(sw_engine* h, int hid, int level, int which, int mode, int nb, const double* X, const double* B,
+                  double w_re, double w_im, int flags, double* Y, int32_t* info);
 /* Solve A_level0 X = B to ||r|| < tol*||b|| per right-hand side (MG.solve -> pyamg fgmres,
  * multigrid.py:347-366).  iters[nb], relres[nb] may be NULL.  Non-convergence within
  * maxiter is NOT an error (the reference discards exitCode); it is visible in relres. */
