@@ -64,8 +64,9 @@ enum TimerCat { T_MVM = 0, T_DEFL, T_P, T_R, T_AXPY, T_DOTS, T_COARSEST, T_OTHER
                 T_TP_SOURCES,   // k_slice_sources of SW_MODE_TWO_POINT
                 T_TP_DOTS,      // k_slice_pair_dots / k_pair_total of SW_MODE_TWO_POINT
                 T_SLICE_CDOTS,  // k_slice_cdots of SW_MODE_MLMC_LOOPS / sw_coarsest_loops
+                T_MESON_FIELD,  // k_meson_field of sw_meson_fields
                 T_NCAT };
-// classes >= T_STENCIL are folded into the mvm / coarsest (two-point: other / dots; slice cdots: dots) buckets by
+// classes >= T_STENCIL are folded into the mvm / coarsest (two-point: other / dots; slice cdots, meson fields: dots) buckets by
 // sw_timers and reported separately by sw_kernel_stats
 
 struct EllOp {
@@ -344,6 +345,20 @@ struct sw_engine {
   cplx* tp_est = nullptr;
   size_t tp_est_cap = 0;
   int tp_nb = 0, tp_nq = 0;        // noises and row stride of the last two-point batch (0: nothing to fetch)
+  // low-mode averaging (sw_set_low_mode_inverse, sw_meson_fields, SW_MODE_TWO_POINT_LMA): G [lm_k][lm_k] row-major
+  // for the registered deflation vectors (lm_k = kd, 0: none), the tables of sw_meson_fields, the coefficients
+  // c and c' [2][ld][columns], and the remainder R = T(z, z) - T(z_L, z_L) of the last batch with T(z_L, z_L)'s
+  // scratch beside it -- buffers of the mode's own, sw_hutch_fetch_two_point keeps returning mode 6's last batch
+  int lm_k = 0;
+  cplx* lm_G = nullptr;
+  int* lm_mom = nullptr;
+  cplx* lm_phase = nullptr;
+  int* lm_slicerow = nullptr;
+  cplx* lm_coef = nullptr;
+  size_t lm_coef_cap = 0;
+  cplx *lma_est = nullptr, *lma_tmp = nullptr;
+  size_t lma_est_cap = 0, lma_tmp_cap = 0;
+  int lma_nb = 0, lma_nq = 0;
   std::vector<int32_t> last_iters_f, last_iters_c;
   // profiling
   bool profiling = false;
@@ -2557,6 +2572,8 @@ int sw_hier_begin(sw_engine* h, int hid, int nlevels) {
     h->loop_nb = h->mloop_nb = 0;
     h->tp_momenta.clear();
     h->tp_nb = 0;
+    h->lm_k = 0;
+    h->lma_nb = 0;
   }
   return 0;
 }
@@ -3821,6 +3838,7 @@ int sw_set_deflation(sw_engine* h, int k, const double* U) {
   HIPCHK(hipSetDevice(h->device));
   Level& lv = h->hier[0].lv[0];
   h->kd = 0;
+  h->lm_k = 0;   // the low-mode inverse belongs to the vectors it was formed with
   if (k == 0) return 0;
   if (!U) return sw_fail(h, "null deflation vectors");
   if (lv.n <= 0) return sw_fail(h, "level 0 undefined");
@@ -4619,15 +4637,12 @@ static int record_iters(sw_engine* h, KrylovWS* ws, int total_or_const, std::vec
   return 0;
 }
 
-// out[r] = X[s] - sum_k U[s][k] (U^H X)[k],  s = srcrow[r] (NULL: identity)   (utils.py:221-225)
-// U is [n][defl_ld(kd)].  Up to kd = 64 (and defl_gemm = 0): k_defl_dots in chunks of 32 vectors, then
-// k_defl_apply; above, or with defl_gemm = 1: the matrix-core pair k_defl_gemm_dots / k_defl_gemm_apply,
-// which read the probe block once for all kd vectors.
-static int deflate(sw_engine* h, const cplx* U, int kd, const int* srcrow, const cplx* X, cplx* out,
-                   int n, int nbp) {
+// The first half of deflate(), cbuf[ld][nbp] = U^H X (the scalar kernels write the rows below kd only): returns in *gemm which
+// kernel pair the rank and the option select.
+static int defl_coeffs(sw_engine* h, const cplx* U, int kd, const cplx* X, int n, int nbp, cplx* cbuf, bool* gemm) {
   const int ld = defl_ld(kd);
-  cplx* cbuf = h->small + 8 * nbp;  // [ld][nbp], ld <= SW_MAX_DEFL
-  if (h->defl_gemm || kd > 64) {
+  *gemm = h->defl_gemm || kd > 64;
+  if (*gemm) {
     // ~2048 workgroups of 16 probes, at least 64 rows per slice
     const int nchunks = nbp / 16;
     const int pmax = std::max(1, (n + 63) / 64);
@@ -4640,10 +4655,8 @@ static int deflate(sw_engine* h, const cplx* U, int kd, const int* srcrow, const
       return launch(h, T_DEFL, swk::k_defl_gemm_dots<LD / 64>, dim3(P, nchunks), dim3(SW_BLOCK), U, ld, X, n, nbp,
                     rpb, h->partial);
     }));
-    SWCHK(launch(h, T_DEFL, swk::k_reduce_partials, dim3(ld, nbp / 64), dim3(SW_BLOCK), h->partial, P, ld, nbp,
-                 cbuf, (const cplx*)nullptr, (cplx*)nullptr));
-    return launch(h, T_DEFL, swk::k_defl_gemm_apply, dim3((n + 63) / 64, nbp / 64), dim3(SW_BLOCK), U, ld,
-                  (const cplx*)cbuf, srcrow, X, out, n, nbp);
+    return launch(h, T_DEFL, swk::k_reduce_partials, dim3(ld, nbp / 64), dim3(SW_BLOCK), h->partial, P, ld, nbp,
+                  cbuf, (const cplx*)nullptr, (cplx*)nullptr);
   }
   int P, rpb;
   row_blocking(n, nbp, true, &P, &rpb);
@@ -4657,11 +4670,80 @@ static int deflate(sw_engine* h, const cplx* U, int kd, const int* srcrow, const
     SWCHK(launch(h, T_DEFL, swk::k_reduce_partials, dim3(kc, nbp / 64), dim3(SW_BLOCK), h->partial, P, kc, nbp,
                  cbuf + (size_t)k0 * nbp, (const cplx*)nullptr, (cplx*)nullptr));
   }
-  {
-    dim3 grid((n + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK, nbp / 64);
-    SWCHK(launch(h, T_DEFL, swk::k_defl_apply, grid, dim3(SW_BLOCK), U, ld, kd, cbuf, srcrow, X, out, n, nbp));
-  }
   return 0;
+}
+
+// out[r] = X[s] - sum_k U[s][k] (U^H X)[k],  s = srcrow[r] (NULL: identity)   (utils.py:221-225)
+// U is [n][defl_ld(kd)].  Up to kd = 64 (and defl_gemm = 0): k_defl_dots in chunks of 32 vectors, then
+// k_defl_apply; above, or with defl_gemm = 1: the matrix-core pair k_defl_gemm_dots / k_defl_gemm_apply,
+// which read the probe block once for all kd vectors.
+static int deflate(sw_engine* h, const cplx* U, int kd, const int* srcrow, const cplx* X, cplx* out,
+                   int n, int nbp) {
+  const int ld = defl_ld(kd);
+  cplx* cbuf = h->small + 8 * nbp;  // [ld][nbp], ld <= SW_MAX_DEFL
+  bool gemm;
+  SWCHK(defl_coeffs(h, U, kd, X, n, nbp, cbuf, &gemm));
+  if (gemm)
+    return launch(h, T_DEFL, swk::k_defl_gemm_apply<true>, dim3((n + 63) / 64, nbp / 64), dim3(SW_BLOCK), U, ld,
+                  (const cplx*)cbuf, srcrow, X, out, n, nbp);
+  dim3 grid((n + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK, nbp / 64);
+  return launch(h, T_DEFL, swk::k_defl_apply, grid, dim3(SW_BLOCK), U, ld, kd, cbuf, srcrow, X, out, n, nbp);
+}
+
+// out = U G' U^H X on ncols columns (a multiple of 64) with the registered vectors U and low-mode inverse G:
+// c = U^H X by deflate()'s first half, c' = s G c (k_low_mode_coef; nq > 0: s = +1 / -1 on the column groups of
+// nq columns of even / odd index, the g_a of a two-point source; nq = 0: s = 1), out = U c' by the apply kernel
+// without its subtraction.  X is not read after the first half, so out may be X itself.
+static int low_mode_apply(sw_engine* h, const cplx* X, int n, int ncols, int nq, cplx* out) {
+  const int kd = h->kd, ld = defl_ld(kd);
+  const size_t per = (size_t)ld * ncols;
+  if (h->lm_coef_cap < 2 * per) {
+    SWCHK(dev_realloc(h, &h->lm_coef, 2 * per));
+    h->lm_coef_cap = 2 * per;
+  }
+  cplx *c = h->lm_coef, *c2 = h->lm_coef + per;
+  bool gemm;
+  SWCHK(defl_coeffs(h, h->U, kd, X, n, ncols, c, &gemm));
+  SWCHK(launch(h, T_DEFL, swk::k_low_mode_coef, dim3((ld + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK, ncols / 64),
+               dim3(SW_BLOCK), (const cplx*)h->lm_G, kd, ld, (const cplx*)c, ncols, nq, c2));
+  return launch(h, T_DEFL, swk::k_defl_gemm_apply<false>, dim3((n + 63) / 64, ncols / 64), dim3(SW_BLOCK),
+                (const cplx*)h->U, ld, (const cplx*)c2, (const int*)nullptr, (const cplx*)nullptr, out, n, ncols);
+}
+
+static int low_mode_ready(sw_engine* h) {
+  if (h->kd <= 0 || !h->U) return sw_fail(h, "no deflation vectors registered (sw_set_deflation)");
+  if (h->lm_k != h->kd || !h->lm_G)
+    return sw_fail(h, "no low-mode inverse registered for the %d deflation vectors (sw_set_low_mode_inverse)", h->kd);
+  return 0;
+}
+
+int sw_set_low_mode_inverse(sw_engine* h, int k, const double* G) {
+  SWCHK(check_hier(h, 0, 0, false));
+  h->lm_k = 0;
+  if (k == 0) return 0;
+  if (h->kd <= 0) return sw_fail(h, "no deflation vectors registered (sw_set_deflation)");
+  if (k != h->kd) return sw_fail(h, "low-mode inverse of rank %d, %d deflation vectors are registered", k, h->kd);
+  if (!G) return sw_fail(h, "null low-mode inverse");
+  HIPCHK(hipSetDevice(h->device));
+  SWCHK(stream_sync(h));
+  SWCHK(upload(h, &h->lm_G, (const cplx*)G, (size_t)k * k));
+  h->lm_k = k;
+  return 0;
+}
+
+// Y = U G U^H X on host vectors (reference order): the low-mode chain of SW_MODE_TWO_POINT_LMA without the sign.
+int sw_apply_low_mode(sw_engine* h, int nb, const double* X, double* Y) {
+  SWCHK(check_hier(h, 0, 0, false));
+  if (nb <= 0 || !X || !Y) return sw_fail(h, "bad arguments");
+  SWCHK(low_mode_ready(h));
+  HIPCHK(hipSetDevice(h->device));
+  Level& lv = h->hier[0].lv[0];
+  const int nbp = pad64(nb);
+  cplx *a, *b;
+  SWCHK(io_vectors(h, lv, nbp, &a, &b));
+  SWCHK(pack_host(h, lv, nb, X, a, nbp));
+  SWCHK(low_mode_apply(h, a, lv.n, nbp, 0, b));
+  return unpack_host(h, lv, nb, b, Y, nbp);
 }
 
 // Y = the registered deflation projection of the host vectors X (reference order, nb contiguous vectors):
@@ -4848,6 +4930,35 @@ int sw_set_loop_momenta(sw_engine* h, int nmom, const int32_t* p) {
   SWCHK(stream_sync(h));
   SWCHK(upload_slice_tables(h, nmom, p, &h->loop_mom, &h->loop_phase, &h->slicerow));
   h->momenta.assign(p, p + nmom);
+  return 0;
+}
+
+// Meson fields of the registered deflation vectors for the momentum p: out[c][d][t][m][m'], complex128
+// [2][2][L][kd][kd], k_meson_field on the engine's U; tables of its own (no momentum registration is touched).
+int sw_meson_fields(sw_engine* h, int p, double* out) {
+  SWCHK(check_hier(h, 0, 0, false));
+  if (!out) return sw_fail(h, "null output");
+  if (h->kd <= 0 || !h->U) return sw_fail(h, "no deflation vectors registered (sw_set_deflation)");
+  const int32_t p32 = p;
+  SWCHK(check_momenta(h, "meson fields", 1, &p32));
+  HIPCHK(hipSetDevice(h->device));
+  SWCHK(stream_sync(h));
+  SWCHK(upload_slice_tables(h, 1, &p32, &h->lm_mom, &h->lm_phase, &h->lm_slicerow));
+  Level& lv = h->hier[0].lv[0];
+  const int L = lv.L, kd = h->kd, ld = defl_ld(kd);
+  const size_t cnt = (size_t)4 * L * kd * kd;
+  DevBuf<cplx> phi(h);
+  SWCHK(dev_realloc(h, &phi.p, cnt));
+  if (h->profiling) h->twork[T_MESON_FIELD] += 32.0 * (double)L * (double)L * (double)ld * (double)ld;
+  const dim3 grid(L, 4, (ld / 16 + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK);
+  if (p == 0)
+    SWCHK(launch(h, T_MESON_FIELD, swk::k_meson_field<false>, grid, dim3(SW_BLOCK), (const cplx*)h->U, ld, kd,
+                 (const int*)h->lm_slicerow, (const cplx*)h->lm_phase, p, L, phi.p));
+  else
+    SWCHK(launch(h, T_MESON_FIELD, swk::k_meson_field<true>, grid, dim3(SW_BLOCK), (const cplx*)h->U, ld, kd,
+                 (const int*)h->lm_slicerow, (const cplx*)h->lm_phase, p, L, phi.p));
+  SWCHK(stream_sync(h));
+  HIPCHK(hipMemcpy(out, phi.p, cnt * sizeof(cplx), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -5133,7 +5244,7 @@ int sw_set_two_point(sw_engine* h, int t0, int nmom, const int32_t* p) {
   SWCHK(check_hier(h, 0, 0, false));
   if (nmom < 0 || nmom > SW_MAX_MOMENTA)
     return sw_fail(h, "%d momenta: at most %d per registration", nmom, SW_MAX_MOMENTA);
-  h->tp_nb = 0;
+  h->tp_nb = h->lma_nb = 0;
   if (nmom == 0) {
     h->tp_momenta.clear();
     return 0;
@@ -5173,33 +5284,39 @@ static int slice_sources(sw_engine* h, Level& lv, const int8_t* probes, int nb, 
 
 // tp_est[j][a][b][c][d][t][k] from the solutions Z [n][2 M nq]: the p = 0 instantiation for the registered
 // momentum 0, the phased one over the others; total (optional) = sum_t sum_ac T[j0][a][a][c][c][t][k]
-static int pair_dots(sw_engine* h, Level& lv, const cplx* Z, int nq, cplx* total) {
+static int pair_dots_into(sw_engine* h, Level& lv, const cplx* Z, int nq, cplx** est, size_t* cap, cplx* total) {
   const int M = (int)h->tp_momenta.size(), L = lv.L;
   const int ncols = 2 * M * nq;
-  h->tp_nb = 0;   // tp_est is rewritten: only a completed two-point batch sets it again
   const size_t need = (size_t)M * 16 * L * nq;
-  if (h->tp_est_cap < need) {
-    SWCHK(dev_realloc(h, &h->tp_est, need));
-    h->tp_est_cap = need;
+  if (*cap < need) {
+    SWCHK(dev_realloc(h, est, need));
+    *cap = need;
   }
-  h->tp_nq = nq;
   SWCHK(launch(h, T_TP_DOTS, swk::k_slice_pair_dots<false>, dim3(L, nq / 64, 1), dim3(SW_BLOCK), Z,
                (const int*)h->tp_slicerow, (const cplx*)h->tp_phase, (const int*)h->tp_mom, h->tp_j0, L, nq, ncols,
-               h->tp_est));
+               *est));
   if (M > 1)
     SWCHK(launch(h, T_TP_DOTS, swk::k_slice_pair_dots<true>, dim3(L, nq / 64, M - 1), dim3(SW_BLOCK), Z,
                  (const int*)h->tp_slicerow, (const cplx*)h->tp_phase, (const int*)h->tp_mom, h->tp_j0, L, nq,
-                 ncols, h->tp_est));
+                 ncols, *est));
   if (!total) return 0;
-  return launch(h, T_TP_DOTS, swk::k_pair_total, dim3(nq / 64), dim3(SW_BLOCK), (const cplx*)h->tp_est, h->tp_j0, L,
+  return launch(h, T_TP_DOTS, swk::k_pair_total, dim3(nq / 64), dim3(SW_BLOCK), (const cplx*)*est, h->tp_j0, L,
                 nq, total);
 }
+static int pair_dots(sw_engine* h, Level& lv, const cplx* Z, int nq, cplx* total) {
+  h->tp_nb = 0;   // tp_est is rewritten: only a completed two-point batch sets it again
+  h->tp_nq = nq;
+  return pair_dots_into(h, lv, Z, nq, &h->tp_est, &h->tp_est_cap, total);
+}
 
-static int fetch_two_point(sw_engine* h, int nb, double* out) {
+static int fetch_pair_sums(sw_engine* h, const cplx* est, int nq, int nb, double* out) {
   const size_t rows = h->tp_momenta.size() * 16 * (size_t)h->hier[0].lv[0].L;
-  HIPCHK(hipMemcpy2D(out, sizeof(cplx) * nb, h->tp_est, sizeof(cplx) * h->tp_nq, sizeof(cplx) * nb, rows,
+  HIPCHK(hipMemcpy2D(out, sizeof(cplx) * nb, est, sizeof(cplx) * nq, sizeof(cplx) * nb, rows,
                      hipMemcpyDeviceToHost));
   return 0;
+}
+static int fetch_two_point(sw_engine* h, int nb, double* out) {
+  return fetch_pair_sums(h, h->tp_est, h->tp_nq, nb, out);
 }
 
 static int two_point_args(sw_engine* h, int nb, const void* in, const void* out) {
@@ -5257,6 +5374,15 @@ int sw_hutch_fetch_two_point(sw_engine* h, double* out) {
   return fetch_two_point(h, h->tp_nb, out);
 }
 
+int sw_hutch_fetch_two_point_lma(sw_engine* h, double* out) {
+  if (!h) return 1;
+  if (!out) return sw_fail(h, "null output");
+  if (h->lma_nb <= 0 || !h->lma_est) return sw_fail(h, "no low-mode averaged two-point batch to fetch");
+  HIPCHK(hipSetDevice(h->device));
+  SWCHK(stream_sync(h));
+  return fetch_pair_sums(h, h->lma_est, h->lma_nq, h->lma_nb, out);
+}
+
 int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
   SWCHK(check_hier(h, 0, level, true));
   if (h->pb_level != level || h->pb_nb <= 0) return sw_fail(h, "no probes uploaded for level %d", level);
@@ -5269,9 +5395,11 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
     if (level != 0) return sw_fail(h, "timeslice-loop Hutchinson mode runs at level 0");
     if (h->momenta.empty()) return sw_fail(h, "no momenta registered (sw_set_loop_momenta)");
   }
-  if (mode == SW_MODE_TWO_POINT) {
+  const bool lma = mode == SW_MODE_TWO_POINT_LMA;
+  if (mode == SW_MODE_TWO_POINT || lma) {
     if (level != 0) return sw_fail(h, "two-point mode runs at level 0");
     if (h->tp_momenta.empty()) return sw_fail(h, "no two-point registration (sw_set_two_point)");
+    if (lma) SWCHK(low_mode_ready(h));
   }
   // the deflated level loops: modes 7 / 8 with the level's registered projection on the right-hand side
   const bool dloops = (mode == SW_MODE_MLMC_DEFL_LOOPS || mode == SW_MODE_MLMC_DEFL_LOOPS_SKIP);
@@ -5294,7 +5422,7 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
     HIPCHK(hipStreamWaitEvent(h->stream, h->slots[h->pb_slot].ready, 0));
     h->slots[h->pb_slot].pending = false;
   }
-  if (mode == SW_MODE_TWO_POINT) {
+  if (mode == SW_MODE_TWO_POINT || lma) {
     // the 2 M sources of every noise straight from the int8 probes, one solve over all 2 M nq columns (no
     // deflation), then the reduction that is bilinear in two solution columns; pb_est = the pion total at p = 0
     const int G = 2 * (int)h->tp_momenta.size(), ncols = G * nbp;
@@ -5304,9 +5432,26 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
     if (hid != 0 && h->hier[hid].lv[0].n != n) return sw_fail(h, "solver hierarchy level-0 size mismatch");
     int total = 0;
     SWCHK(solve_dev(h, hid, 0, h->tp_rhs, h->tp_z, tol, maxiter, ncols, &total));
-    SWCHK(pair_dots(h, lv, h->tp_z, nbp, h->pb_est));
-    SWCHK(stream_sync(h));
-    h->tp_nb = nb;
+    if (lma) {
+      // R = T(z, z) - T(z_L, z_L), z_L = A_L^-1 eta = g_a U G (U^H eta) written over the sources; buffers of the
+      // mode's own (mode 6's last batch stays fetchable); pb_est = the pion total of R
+      h->lma_nb = 0;
+      SWCHK(pair_dots_into(h, lv, h->tp_z, nbp, &h->lma_est, &h->lma_est_cap, nullptr));
+      SWCHK(low_mode_apply(h, h->tp_rhs, n, ncols, nbp, h->tp_rhs));
+      SWCHK(pair_dots_into(h, lv, h->tp_rhs, nbp, &h->lma_tmp, &h->lma_tmp_cap, nullptr));
+      const size_t cnt = h->tp_momenta.size() * 16 * (size_t)lv.L * nbp;
+      SWCHK(launch(h, T_TP_DOTS, swk::k_sub_inplace, dim3((unsigned)std::min<size_t>(2048, (cnt + 255) / 256)),
+                   dim3(256), h->lma_est, (const cplx*)h->lma_tmp, cnt));
+      SWCHK(launch(h, T_TP_DOTS, swk::k_pair_total, dim3(nbp / 64), dim3(SW_BLOCK), (const cplx*)h->lma_est,
+                   h->tp_j0, lv.L, nbp, h->pb_est));
+      SWCHK(stream_sync(h));
+      h->lma_nb = nb;
+      h->lma_nq = nbp;
+    } else {
+      SWCHK(pair_dots(h, lv, h->tp_z, nbp, h->pb_est));
+      SWCHK(stream_sync(h));
+      h->tp_nb = nb;
+    }
     // iterations of a noise = the largest count among its 2 M columns
     std::vector<int32_t> all;
     SWCHK(record_iters(h, &h->hier[hid].lv[0].sws, total, all, ncols));
@@ -5663,7 +5808,7 @@ int sw_timers(sw_engine* h, double t[8]) {
               h->tacc[T_MFMA_OP2] + h->tacc[T_SCHUR] + h->tacc[T_SCHUR_OP];
   t[T_COARSEST] += h->tacc[T_MFMA_DENSE];
   t[T_OTHER] += h->tacc[T_TP_SOURCES];
-  t[T_DOTS] += h->tacc[T_TP_DOTS] + h->tacc[T_SLICE_CDOTS];
+  t[T_DOTS] += h->tacc[T_TP_DOTS] + h->tacc[T_SLICE_CDOTS] + h->tacc[T_MESON_FIELD];
   return 0;
 }
 int sw_timers_reset(sw_engine* h) {

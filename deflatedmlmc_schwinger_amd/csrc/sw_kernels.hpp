@@ -2810,7 +2810,10 @@ __global__ __launch_bounds__(SW_BLOCK) void k_defl_gemm_dots(const cplx* __restr
   }
 }
 
+// SUB = false: out[r][j] = sum_k U[s][k] C[k][j] alone (the low-mode solutions z_L = U c' of
+// SW_MODE_TWO_POINT_LMA): X is not read.
 #define SW_DG_KC 32
+template <bool SUB>
 __global__ __launch_bounds__(SW_BLOCK) void k_defl_gemm_apply(const cplx* __restrict__ U, int ldu,
                                                               const cplx* __restrict__ C,
                                                               const int* __restrict__ srcrow,
@@ -2855,8 +2858,12 @@ __global__ __launch_bounds__(SW_BLOCK) void k_defl_gemm_apply(const cplx* __rest
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const size_t j = j0 + t * 16 + c;
-      const cplx x = X[s * nbp + j];
-      out[(size_t)row * nbp + j] = cmake(x.x - re[t][r], x.y - im[t][r]);
+      if constexpr (SUB) {
+        const cplx x = X[s * nbp + j];
+        out[(size_t)row * nbp + j] = cmake(x.x - re[t][r], x.y - im[t][r]);
+      } else {
+        out[(size_t)row * nbp + j] = cmake(re[t][r], im[t][r]);
+      }
     }
   }
 }
@@ -3771,6 +3778,104 @@ __global__ __launch_bounds__(SW_BLOCK) void k_pair_total(const cplx* __restrict_
     s = cadd(s, red[2][lane]);
     est[col] = s;
   }
+}
+
+// ------------------------------------------------------------------------------------------
+// Low-mode averaging of the two-point functions (sw_meson_fields, SW_MODE_TWO_POINT_LMA).
+// ------------------------------------------------------------------------------------------
+// Meson fields of the registered deflation vectors for one momentum p:
+//   out[c][d][t][m][m'] = sum_x omega^(p x) conj(U[row(c,x,t)][m]) U[row(d,x,t)][m'],  omega = e^{-2 pi i / L},
+// a batched 16 x L x 16 complex product per (t, c, d) and pair of 16-vector tiles on v_mfma_f64_16x16x4_f64, K = x
+// (operand layout as k_defl_gemm_dots: lane l holds A[l&15][l>>4] = conj(U[row(c, x0 + (l>>4), t)][16 mt + (l&15)]),
+// B[l>>4][l&15] = omega^(p x) U[row(d, x0 + (l>>4), t)][16 mt' + (l&15)], D[(l>>4)+4r][l&15]).  U is [n][ldu], the
+// padding columns zero; rows from slicerow[(t L + x) 2 + spin], phases from the L-entry table (PHASE = false: p = 0,
+// no table, no multiply).  grid = (L, 4 = 2 c + d, ceil(ldu / 64)); wave w of a workgroup owns the row tile
+// mt = 4 blockIdx.z + w and walks the column tiles four at a time: its A element is loaded once per K step and
+// serves the four column tiles from a register, the B elements are shared by the four waves through the cache.
+// Every output tile is summed by one wave in the order x = 0, 4, 8, ... (L not a multiple of 4: the missing rows
+// enter as zeros), written once: no partials, no atomics, two calls agree bit for bit.  The output is dense
+// [kd][kd] per (c, d, t): the padding rows and columns are not stored.  No barrier, no LDS.
+template <bool PHASE>
+__global__ __launch_bounds__(SW_BLOCK) void k_meson_field(const cplx* __restrict__ U, int ldu, int kd,
+                                                          const int* __restrict__ slicerow,
+                                                          const cplx* __restrict__ phase, int p, int L,
+                                                          cplx* __restrict__ out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int k = lane >> 4, c = lane & 15;
+  const int t = blockIdx.x, sc = blockIdx.y >> 1, sd = blockIdx.y & 1;
+  const int nt = ldu / 16;
+  const int mt = blockIdx.z * SW_WAVES_PER_BLOCK + wave;
+  if (mt >= nt) return;
+  const int* __restrict__ sr = slicerow + (size_t)t * L * 2;
+  cplx* __restrict__ o = out + ((size_t)blockIdx.y * L + t) * kd * kd;
+  for (int g0 = 0; g0 < nt; g0 += 4) {
+    const int ng = min(4, nt - g0);
+    sw_double4 re[4], im[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) re[q] = im[q] = sw_double4{0.0, 0.0, 0.0, 0.0};
+    for (int x0 = 0; x0 < L; x0 += 4) {
+      const int x = x0 + k;
+      const bool in = x < L;
+      cplx a = cmake(0.0, 0.0), w = cmake(1.0, 0.0);
+      const cplx* bp = U;
+      if (in) {
+        a = U[(size_t)sr[2 * x + sc] * ldu + mt * 16 + c];
+        bp = U + (size_t)sr[2 * x + sd] * ldu + g0 * 16 + c;
+        if constexpr (PHASE) w = phase[(p * x) % L];
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (q < ng) {
+          cplx b = in ? bp[q * 16] : cmake(0.0, 0.0);
+          if constexpr (PHASE) b = cmul(w, b);
+          // conj(a) b = (ar br + ai bi) + i (ar bi - ai br)
+          re[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, b.x, re[q], 0, 0, 0);
+          re[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, b.y, re[q], 0, 0, 0);
+          im[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, b.y, im[q], 0, 0, 0);
+          im[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(-a.y, b.x, im[q], 0, 0, 0);
+        }
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if (q < ng) {
+        const int mc = (g0 + q) * 16 + c;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int mr = mt * 16 + k + 4 * r;
+          if (mr < kd && mc < kd) o[(size_t)mr * kd + mc] = cmake(re[q][r], im[q][r]);
+        }
+      }
+    }
+  }
+}
+
+// out[i][col] = s(col) sum_m G[i][m] C[m][col] for i < kd, zero on the padding rows kd <= i < ld: the coefficients
+// c' = g_a G c of the low-mode solutions.  G is [kd][kd] row-major, C and out are [ld][ncols]; lane = column, a wave
+// owns one row i, whose G entries are wave-uniform.  nq > 0: s = g_a = +1 / -1 on the column groups of even / odd
+// index col / nq (the spin of a two-point source); nq = 0: s = 1.  grid = (ceil(ld / 4), ncols / 64).
+__global__ __launch_bounds__(SW_BLOCK) void k_low_mode_coef(const cplx* __restrict__ G, int kd, int ld,
+                                                            const cplx* __restrict__ C, int ncols, int nq,
+                                                            cplx* __restrict__ out) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * SW_WAVES_PER_BLOCK + wave);
+  if (i >= ld) return;
+  const size_t col = (size_t)blockIdx.y * 64 + lane;
+  cplx s = cmake(0.0, 0.0);
+  if (i < kd) {
+    const cplx* __restrict__ g = G + (size_t)i * kd;
+    for (int m = 0; m < kd; ++m) cfma(s, g[m], C[(size_t)m * ncols + col]);
+    if (nq > 0 && (((int)col / nq) & 1)) s = cmake(-s.x, -s.y);
+  }
+  out[(size_t)i * ncols + col] = s;
+}
+
+// a -= b, elementwise (the stochastic remainder R = T(z, z) - T(z_L, z_L) of SW_MODE_TWO_POINT_LMA)
+__global__ __launch_bounds__(SW_BLOCK) void k_sub_inplace(cplx* __restrict__ a, const cplx* __restrict__ b,
+                                                          size_t count) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (; i < count; i += stride) a[i] = csub(a[i], b[i]);
 }
 
 }  // namespace swk

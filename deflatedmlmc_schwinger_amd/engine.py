@@ -26,6 +26,7 @@ MODE_MLMC_LOOPS = 7
 MODE_MLMC_LOOPS_SKIP = 8
 MODE_MLMC_DEFL_LOOPS = 9
 MODE_MLMC_DEFL_LOOPS_SKIP = 10
+MODE_TWO_POINT_LMA = 11
 # estimator method -> (mode, mode of the level-skipping form at level 0); "mlmc_defl_loops" is "mlmc_loops" deflated
 _METHOD_MODES = {"hutchinson": (MODE_HUTCHINSON, MODE_HUTCHINSON),
                  "mlmc": (MODE_MLMC, MODE_MLMC_SKIP),
@@ -33,12 +34,14 @@ _METHOD_MODES = {"hutchinson": (MODE_HUTCHINSON, MODE_HUTCHINSON),
                  "shifts": (MODE_HUTCHINSON_SHIFTS, MODE_HUTCHINSON_SHIFTS),
                  "loops": (MODE_HUTCHINSON_LOOPS, MODE_HUTCHINSON_LOOPS),
                  "two_point": (MODE_TWO_POINT, MODE_TWO_POINT),
+                 "two_point_lma": (MODE_TWO_POINT_LMA, MODE_TWO_POINT_LMA),
                  "mlmc_loops": (MODE_MLMC_LOOPS, MODE_MLMC_LOOPS_SKIP),
                  "mlmc_defl_loops": (MODE_MLMC_DEFL_LOOPS, MODE_MLMC_DEFL_LOOPS_SKIP)}
 # the modes whose batches leave a resolved result beside the scalar estimates -> the Engine method that fetches it
 RESOLVED_FETCH = {MODE_HUTCHINSON_SHIFTS: "hutch_fetch_shifts",
                   MODE_HUTCHINSON_LOOPS: "hutch_fetch_loops",
                   MODE_TWO_POINT: "hutch_fetch_two_point",
+                  MODE_TWO_POINT_LMA: "hutch_fetch_two_point_lma",
                   MODE_MLMC_LOOPS: "hutch_fetch_mlmc_loops",
                   MODE_MLMC_LOOPS_SKIP: "hutch_fetch_mlmc_loops",
                   MODE_MLMC_DEFL_LOOPS: "hutch_fetch_mlmc_loops",
@@ -58,6 +61,7 @@ def probe_mode(method, level=0, skip_level=False, deflated=False):
 KCLASS_TP_SOURCES = 17     # sw_kernel_stats classes of the two-point kernels
 KCLASS_TP_DOTS = 18
 KCLASS_SLICE_CDOTS = 19    # ... and of k_slice_cdots (MLMC loops)
+KCLASS_MESON_FIELD = 20    # ... and of k_meson_field (low-mode averaging)
 MAX_SHIFTS = 128
 MAX_MOMENTA = 8
 # operations of Engine.apply_op32 (SW_OP32_* of the header): one kernel of the complex64 cycle at a time
@@ -218,6 +222,10 @@ def load_library():
     sig("sw_coarsest_loops", i32, vp, vp)
     sig("sw_hutch_fetch_mlmc_loops", i32, vp, vp)
     sig("sw_level_deflation_loops", i32, vp, i32, i32, dbl, i32, vp)
+    sig("sw_meson_fields", i32, vp, i32, vp)
+    sig("sw_set_low_mode_inverse", i32, vp, i32, vp)
+    sig("sw_apply_low_mode", i32, vp, i32, vp, vp)
+    sig("sw_hutch_fetch_two_point_lma", i32, vp, vp)
     _lib = lib
     return lib
 
@@ -242,6 +250,7 @@ EXPORTED_SYMBOLS = (
     "sw_set_loop_momenta", "sw_hutch_fetch_loops", "sw_apply_slice_dots",
     "sw_set_two_point", "sw_hutch_fetch_two_point", "sw_apply_slice_sources", "sw_apply_pair_dots",
     "sw_apply_slice_cdots", "sw_coarsest_loops", "sw_hutch_fetch_mlmc_loops", "sw_level_deflation_loops",
+    "sw_meson_fields", "sw_set_low_mode_inverse", "sw_apply_low_mode", "sw_hutch_fetch_two_point_lma",
 )
 
 
@@ -466,6 +475,32 @@ class Engine:
             return
         U = _c128(np.asarray(U))
         self._chk(self._lib.sw_set_deflation(self._h, U.shape[1], _ptr(U)), "sw_set_deflation")
+
+    def set_low_mode_inverse(self, G):
+        """The low-mode inverse G (k, k) of the registered deflation vectors, A_L^-1 = U G U^H gamma_3 (None clears;
+        every set_deflation drops it)."""
+        if G is None:
+            self._chk(self._lib.sw_set_low_mode_inverse(self._h, 0, None), "sw_set_low_mode_inverse")
+            return
+        G = _c128(np.asarray(G))
+        if G.ndim != 2 or G.shape[0] != G.shape[1]:
+            raise EngineError("low-mode inverse of shape %s, expected (k, k)" % (G.shape,))
+        self._chk(self._lib.sw_set_low_mode_inverse(self._h, G.shape[0], _ptr(G)), "sw_set_low_mode_inverse")
+
+    def meson_fields(self, p, k):
+        """Meson fields of the k registered deflation vectors for the momentum p: Phi[c, d, t, m, m'] =
+        sum_x e^{-2 pi i p x / L} conj(U[idx(c,x,t), m]) U[idx(d,x,t), m'], shape (2, 2, L, k, k)."""
+        L = int(round((self._n(0, 0) // 2) ** 0.5))
+        out = np.zeros((2, 2, L, int(k), int(k)), dtype=np.complex128)
+        self._chk(self._lib.sw_meson_fields(self._h, int(p), _ptr(out)), "sw_meson_fields")
+        return out
+
+    def apply_low_mode(self, X):
+        """Y = U G U^H X with the registered vectors and low-mode inverse (the low-mode chain of MODE_TWO_POINT_LMA)."""
+        X2, single = self._io(X, self._n(0, 0))
+        Y = np.empty_like(X2)
+        self._chk(self._lib.sw_apply_low_mode(self._h, X2.shape[0], _ptr(X2), _ptr(Y)), "sw_apply_low_mode")
+        return Y[0] if single else Y
 
     def set_level_deflation(self, level, V):
         if V is None:
@@ -794,6 +829,13 @@ class Engine:
         """Pair sums of the last MODE_TWO_POINT batch, shape (nb, nmom, 2, 2, 2, 2, L): T[k, j, a, b, c, d, t]."""
         out = np.zeros(self._two_point_shape(getattr(self, "_nb_uploaded", 0)), dtype=np.complex128)
         self._chk(self._lib.sw_hutch_fetch_two_point(self._h, _ptr(out)), "sw_hutch_fetch_two_point")
+        return np.ascontiguousarray(np.moveaxis(out, -1, 0))
+
+    def hutch_fetch_two_point_lma(self):
+        """Remainders of the last MODE_TWO_POINT_LMA batch, shape (nb, nmom, 2, 2, 2, 2, L): R[k, j, a, b, c, d, t] =
+        T(z, z) - T(z_L, z_L)."""
+        out = np.zeros(self._two_point_shape(getattr(self, "_nb_uploaded", 0)), dtype=np.complex128)
+        self._chk(self._lib.sw_hutch_fetch_two_point_lma(self._h, _ptr(out)), "sw_hutch_fetch_two_point_lma")
         return np.ascontiguousarray(np.moveaxis(out, -1, 0))
 
     def apply_slice_sources(self, probes):

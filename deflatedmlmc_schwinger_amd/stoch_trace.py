@@ -19,7 +19,8 @@ from .engine import RESOLVED_FETCH, ProbeStream, probe_mode
 from .multigrid import MG
 from .utils import (_engines, deflation_pre_computations, displacements_of, draw_probes, flopsV_manual,
                     loops_of, mlmc_defl_setup_of, probe_batch, probe_batch_generated, register_loop_momenta,
-                    register_shifts, register_two_point, two_point_of)
+                    register_shifts, register_two_point, two_point_of, low_mode_inverse, low_mode_two_point,
+                    register_low_modes)
 
 DEFAULT_BATCH = 256
 NR_ROUGH_PROBES = 5
@@ -375,6 +376,13 @@ class _TwoPoint(_Observable):
         return rough.size - 1
 
 
+class _TwoPointLMA(_TwoPoint):
+    """lma_two_point(): the remainders R[j][a][b][c][d][t] = T(z, z) - T(z_L, z_L), flattened, plus their pion total;
+    the exact low-mode part E_L(t0) enters as tr1_cols."""
+    what = "low-mode averaged two-point functions"
+    method = "two_point_lma"
+
+
 def _estimate_stage(mg_solver, params, n, obs, tr1_cols=None):
     """The second half of a Hutchinson-type flow: the rough estimate from five probes (plus tr1_cols), the level
     tolerances |tol * rough|, the timers' reset and the probe loop of `obs` at level 0.
@@ -509,6 +517,74 @@ def two_point(A, params):
     result['nr_ests'] = loop["index"]
     result['function_iters'] = int(np.sum(loop["iters_fine"]))
     result['ests'] = loop["ests"][:, control]       # (nr_ests + 1,): sum_t C_pi(t, 0) per noise
+    result['probe_loop_s'] = loop_s
+    result['probes_solved'] = loop["solved"]
+    mg_solver.sync_timer()
+    print(mg_solver.timer)
+    return result
+
+
+def lma_two_point(A, params):
+    """two_point() with low-mode averaging: the nr_deflat_vctrs > 0 lowest eigenvectors V of gamma_3 A
+    (hutchinson()'s deflation step) give the low-mode inverse A_L^-1 = V G V^H gamma_3, G = (V^H gamma_3 A V)^-1 made
+    Hermitian.  Its pair sums E_L[p][a][b][c][d][t][t0] are exact, from the device meson fields of V, for every source
+    timeslice; the noises estimate only the remainder R_k = T(z_k, z_k) - T(z_L, z_L), z_L = A_L^-1 eta_k, whose
+    expectation is E[T] - E_L(t0) for any V and G.  Keys, sources, probe loop and stopping rule are two_point()'s; the
+    level tolerances are relative to E_L(t0) plus the rough remainder, i.e. to the full correlator.
+
+    Returns two_point()'s keys with two_point = E_L(t0) + the remainder's mean, plus two_point_low (E_L, all t0),
+    two_point_rest (the remainder's mean), two_point_rest_devs and nr_deflat_vctrs; two_point_ests are the per-noise
+    remainders plus E_L(t0)."""
+    sel = two_point_of(params)
+    if sel is None:
+        raise Exception("lma_two_point() needs the key source_timeslice")
+    t0, momenta = sel
+    nr_deflat_vctrs = int(params['nr_deflat_vctrs'])
+    if nr_deflat_vctrs <= 0:
+        raise Exception("lma_two_point() needs nr_deflat_vctrs > 0 (two_point() is the estimator without low modes)")
+    obs = _TwoPointLMA(momenta)
+    if _dist.default_comm().world > 1:
+        raise Exception(obs.one_rank)
+    mg_solver, nr_levels = _setup_solver(A, params, defer_coarse=True)
+    L = int(params['latt_dims'][0])
+    shape = (len(momenta), 2, 2, 2, 2, L)
+
+    print("Computing deflation vectors ...", end='', flush=True)
+    t1 = time.time()
+    plain = dict(params, use_permuted=False)
+    Ux, _ = deflation_pre_computations(A, nr_deflat_vctrs, params['defl_eigvs_tol_Hutch'], "hutchinson",
+                                       mg_solver.timer, plain, mg_solver)
+    g3 = mg_solver.ml.levels[0].g3
+    V = np.ascontiguousarray(g3 * np.asarray(Ux))          # the eigenvectors up to their signs: gamma_3^2 = 1
+    eng = mg_solver.engine
+    QV = np.asarray(g3 * eng.apply_dirac(0, 0, np.ascontiguousarray(V.T)).T)
+    G = low_mode_inverse(V, QV)
+    for e in _engines(mg_solver):
+        e.set_deflation(V)
+    register_low_modes(mg_solver, G)
+    low = np.empty(shape + (L,), dtype=np.complex128)
+    for j, p in enumerate(momenta):
+        low[j] = low_mode_two_point(eng.meson_fields(p, nr_deflat_vctrs)[None], G)[0]
+    print(" done. Time : " + str(time.time() - t1) + " seconds")
+    register_two_point(mg_solver, t0, momenta)
+    tr1_cols = obs.columns(low[None, ..., t0])[0]
+    _, _, control, loop, loop_s = _estimate_stage(mg_solver, params, A.shape[0], obs, tr1_cols)
+
+    mg_solver.finish_setup()
+    result = dict()
+    result['two_point_low'] = low
+    result['two_point_rest'] = loop["avgs"][:control].reshape(shape)
+    result['two_point_rest_devs'] = loop["devs"][:control].reshape(shape)
+    result['two_point'] = low[..., t0] + result['two_point_rest']
+    result['two_point_devs'] = result['two_point_rest_devs']
+    result['two_point_ests'] = loop["ests"][:, :control].reshape((-1,) + shape) + low[None, ..., t0]
+    result['converged'] = loop["converged"][:control].reshape(shape)
+    result['momenta'] = list(momenta)
+    result['source_timeslice'] = t0
+    result['nr_deflat_vctrs'] = nr_deflat_vctrs
+    result['nr_ests'] = loop["index"]
+    result['function_iters'] = int(np.sum(loop["iters_fine"]))
+    result['ests'] = loop["ests"][:, control] + tr1_cols[control]
     result['probe_loop_s'] = loop_s
     result['probes_solved'] = loop["solved"]
     mg_solver.sync_timer()

@@ -426,6 +426,85 @@ def meson_correlator(T, sink, source):
     return out
 
 
+def meson_fields(V, L, momenta):
+    """Phi[j, c, d, t, m, m'] = sum_x e^{-2 pi i p_j x / L} conj(V[idx(c,x,t), m]) V[idx(d,x,t), m'] for the columns of
+    V (2 L^2, k), idx(s,x,y) = s L^2 + y L + x: the meson fields of lma_two_point(), what Engine.meson_fields computes
+    one momentum at a time.  Evaluated in V's precision: a numpy.clongdouble V gives the extended-precision
+    statement (phases formed in long double), anything else complex128 with the engine's phase table."""
+    V = np.asarray(V)
+    if V.ndim != 2 or V.shape[0] != 2 * L * L:
+        raise Exception("meson_fields: V of shape %s, expected (%d, k)" % (V.shape, 2 * L * L))
+    idx = np.outer(np.asarray(momenta, dtype=np.int64), np.arange(L)) % L
+    if V.dtype == np.clongdouble:
+        j = np.arange(L)
+        ang = -2 * (4 * np.arctan(np.longdouble(1))) * j.astype(np.longdouble) / L
+        tab = (np.cos(ang) + 1j * np.sin(ang)).astype(np.clongdouble)
+        quarter = (4 * j) % L == 0
+        tab[quarter] = np.array([1, -1j, -1, 1j], dtype=np.clongdouble)[(4 * j[quarter]) // L]
+    else:
+        V = V.astype(np.complex128)
+        tab = _phase_table(L)
+    Vr = V.reshape(2, L, L, V.shape[1])                                   # [s][t][x][m]
+    out = np.zeros((len(momenta), 2, 2, L, V.shape[1], V.shape[1]), dtype=V.dtype)
+    for j in range(len(momenta)):
+        ph = tab[idx[j]]
+        for c in range(2):
+            left = np.conj(Vr[c]).transpose(0, 2, 1)                      # [t][m][x]
+            for d in range(2):
+                out[j, c, d] = np.matmul(left, ph[None, :, None] * Vr[d])
+    return out
+
+
+def low_mode_inverse(V, QV):
+    """G = (V^H Q V)^-1 made Hermitian, Q V = gamma_3 A V given: the low-mode inverse of lma_two_point(), with which
+    A_L^-1 = V G V^H gamma_3.  For exact eigenvectors of Q it is diag(1 / lambda)."""
+    V = np.asarray(V, dtype=np.complex128)
+    QV = np.asarray(QV, dtype=np.complex128)
+    if V.ndim != 2 or V.shape != QV.shape:
+        raise Exception("low_mode_inverse: V %s and QV %s, expected two equal (n, k)" % (V.shape, QV.shape))
+    G = np.linalg.inv(V.conj().T @ QV)
+    return 0.5 * (G + G.conj().T)
+
+
+def low_mode_two_point(Phi, G):
+    """E_L[j, a, b, c, d, t, t0] = g_a g_b sum_{m,m'} Phi[j, c, d, t, m, m'] conj(Psi[j, a, b, t0, m, m']) with
+    Psi = G Phi G^H and g = (+1, -1): the pair sums of two_point() with A_L^-1 = V G V^H gamma_3 in place of A^-1,
+    for every source timeslice t0, from the meson fields Phi[j, c, d, t, m, m'] of V.  Any G, Hermitian or not."""
+    Phi = np.asarray(Phi, dtype=np.complex128)
+    G = np.asarray(G, dtype=np.complex128)
+    if Phi.ndim != 6 or Phi.shape[1:3] != (2, 2) or Phi.shape[4] != Phi.shape[5] or G.shape != Phi.shape[4:]:
+        raise Exception("low_mode_two_point: Phi of shape %s and G of shape %s, expected (M, 2, 2, L, k, k) and (k, k)"
+                        % (Phi.shape, G.shape))
+    M, L, k = Phi.shape[0], Phi.shape[3], Phi.shape[4]
+    g = np.array([1.0, -1.0])
+    out = np.empty((M, 2, 2, 2, 2, L, L), dtype=np.complex128)
+    for j in range(M):
+        Psi = np.matmul(np.matmul(G, Phi[j]), G.conj().T)                # [a][b][t0][m][m']
+        E = Phi[j].reshape(4 * L, k * k) @ Psi.reshape(4 * L, k * k).conj().T          # [(c,d,t)][(a,b,t0)]
+        E = E.reshape(2, 2, L, 2, 2, L).transpose(3, 4, 0, 1, 2, 5)      # [a][b][c][d][t][t0]
+        out[j] = E * (g[:, None] * g[None, :])[:, :, None, None, None, None]
+    return out
+
+
+def low_mode_solutions(V, G, sources):
+    """z_L = A_L^-1 eta = V G V^H gamma_3 eta for sources eta of shape (..., 2 L^2) (slice_sources' layout (2 M, nb, n)
+    included), gamma_3 = +1 / -1 on the first / second half of the index."""
+    V = np.asarray(V, dtype=np.complex128)
+    eta = np.asarray(sources, dtype=np.complex128)
+    n = V.shape[0]
+    if eta.shape[-1] != n:
+        raise Exception("low_mode_solutions: sources of length %d, expected %d" % (eta.shape[-1], n))
+    g3 = np.where(np.arange(n) < n // 2, 1.0, -1.0)
+    c = (eta * g3) @ V.conj()                                             # [...][m] = V^H gamma_3 eta
+    return (c @ np.asarray(G, dtype=np.complex128).T) @ V.T
+
+
+def register_low_modes(mg_solver, G):
+    """Hand the low-mode inverse of the registered deflation vectors to every engine handle (None clears)."""
+    for eng in _engines(mg_solver):
+        eng.set_low_mode_inverse(G)
+
+
 def trace_params_from_params(params, example):
     """utils.py:73-125: whitelist copy into the dictionary the estimators read."""
     if example not in ("mlmc", "hutchinson"):

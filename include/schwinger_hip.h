@@ -206,6 +206,11 @@ int sw_hier_end(sw_engine* h, int hid);
 
 /* Deflation vectors U (utils.py:145-155), row-major complex128[n0*k], reference ordering, k <= SW_MAX_DEFL. */
 int sw_set_deflation(sw_engine* h, int k, const double* U);
+/* Low-mode inverse G of the registered deflation vectors (build-only: low-mode averaged two-point functions), row-major
+ * complex128[k*k]: the low-mode part of the propagator is A_L^-1 = U G U^H gamma_3, G meant to be (U^H gamma_3 A U)^-1
+ * made Hermitian (any G keeps SW_MODE_TWO_POINT_LMA unbiased).  k must equal the registered deflation rank; k = 0
+ * clears; every sw_set_deflation drops it. */
+int sw_set_low_mode_inverse(sw_engine* h, int k, const double* G);
 /* MLMC-level deflation vectors V_l of the difference operator at `level` of hid 0
  * (utils.py:141-157,260-266), row-major complex128[n_l*k]; k = 0 clears. */
 int sw_set_level_deflation(sw_engine* h, int level, int k, const double* V);
@@ -332,6 +337,16 @@ int sw_apply_slice_sources(sw_engine* h, int nb, const int8_t* probes, double* o
  * sum_x e^{-2 pi i p_j x / L} conj(Z[2 j0 + a][k][idx(c,x,t)]) Z[2 j + b][k][idx(d,x,t)], j0 = the registered
  * momentum 0. */
 int sw_apply_pair_dots(sw_engine* h, int nb, const double* Z, double* out);
+/* Meson fields of the registered deflation vectors U (sw_set_deflation; k of them) for ONE spatial momentum p in [0, L)
+ * (build-only): out[c][d][t][m][m'] = sum_x e^{-2 pi i p x / L} conj(U[idx(c,x,t)][m]) U[idx(d,x,t)][m'], complex128
+ * [2][2][L][k][k] (at most 537 MB at k = 256, L = 128: one momentum per call).  Level 0 of hid 0, lattice set
+ * (sw_set_lattice); fp64 MFMA, every entry summed in a fixed order (two calls agree bit for bit).  Fails without
+ * vectors and with p out of range. */
+int sw_meson_fields(sw_engine* h, int p, double* out);
+/* Y = U G U^H X with the registered vectors and low-mode inverse (sw_set_low_mode_inverse) on nb host vectors in the
+ * reference layout: the low-mode chain of SW_MODE_TWO_POINT_LMA alone (projection dots, G, expansion), without the
+ * gamma_3 sign of its sources. */
+int sw_apply_low_mode(sw_engine* h, int nb, const double* X, double* Y);
 /* X = one multigrid cycle applied to B starting at level0 (MG.one_mg_step, multigrid.py:369-447). */
 int sw_vcycle(sw_engine* h, int hid, int level0, int nb, const double* B, double* X);
 /* ONE operation of the complex64 cycle (option "precond_f32") alone on host vectors, for the per-kernel parity
@@ -428,6 +443,16 @@ int sw_solve(sw_engine* h, int hid, int level0, int nb, const double* B, double*
                                   sw_hutch_fetch returns x^H d -- the SW_MODE_MLMC value of the probe with the same
                                   vectors and no perm / rhsmap -- when the first registered momentum is 0 */
 #define SW_MODE_MLMC_DEFL_LOOPS_SKIP 10 /* the same on SW_MODE_MLMC_LOOPS_SKIP's difference, level 0 only */
+#define SW_MODE_TWO_POINT_LMA 11 /* SW_MODE_TWO_POINT's stochastic remainder under low-mode averaging, level 0 (build-only):
+                                  R_k = T(z_k, z_k) - T(z_L, z_L) with the sources, the one solve z = A^-1 eta and the
+                                  pair sum T of SW_MODE_TWO_POINT and z_L^(j,a) = A_L^-1 eta^(j,a) = g_a U G (U^H eta^(j,a)),
+                                  g = (+1, -1), for the registered vectors and low-mode inverse.  E[R_k] = E[T_k] - E_L
+                                  with E_L the pair sum of A_L^-1 in place of A^-1, exactly, for any U and G.  Needs
+                                  sw_set_two_point, sw_set_deflation and sw_set_low_mode_inverse.  A buffer of its own
+                                  (sw_hutch_fetch_two_point_lma; sw_hutch_fetch_two_point keeps returning the last
+                                  SW_MODE_TWO_POINT batch); sw_hutch_fetch returns sum_t sum_ac R[j0][a][a][c][c][t] and
+                                  the iteration counts of SW_MODE_TWO_POINT.  With G = 0 the batch equals the
+                                  SW_MODE_TWO_POINT batch bit for bit. */
 /* One batch of probes x_k in {-1,+1}^n (int8, nb*n, reference ordering) at `level`
  * (build-only extension: entries +-2 encode +-i, i.e. Z4 probes {1,i,-1,-i}):
  *   HUTCHINSON: e_k = x^H A^-1 Pperm^T (x - U U^H x)
@@ -473,6 +498,8 @@ int sw_hutch_fetch_mlmc_loops(sw_engine* h, double* out);
  * every noise k of the batch.  The results of the modes 4, 5 and 6 live in buffers of their own: each fetch
  * returns its own mode's last batch whatever ran since. */
 int sw_hutch_fetch_two_point(sw_engine* h, double* out);
+/* After a SW_MODE_TWO_POINT_LMA batch: out complex128[nmom][2][2][2][2][L][nb], the remainders R_k[j][a][b][c][d][t]. */
+int sw_hutch_fetch_two_point_lma(sw_engine* h, double* out);
 
 /* ---- multi-GPU: the one collective of the path ------------------------------------ */
 /* One process per GPU, one engine per process; the probe loop shards by probe and needs a single
@@ -509,6 +536,8 @@ int sw_timers_reset(sw_engine* h);
 #define SW_KCLASS_TP_SOURCES 17     /* k_slice_sources (SW_MODE_TWO_POINT); in sw_timers: other */
 #define SW_KCLASS_TP_DOTS 18        /* k_slice_pair_dots, k_pair_total (SW_MODE_TWO_POINT); in sw_timers: dots */
 #define SW_KCLASS_SLICE_CDOTS 19    /* k_slice_cdots (SW_MODE_MLMC_LOOPS, sw_coarsest_loops); in sw_timers: dots */
+#define SW_KCLASS_MESON_FIELD 20    /* k_meson_field (sw_meson_fields); in sw_timers: dots; sw_kernel_work counts
+                                       8 * 4 * L^2 * ld^2 flops per launch, ld = the rank rounded up to 16 */
 int sw_kernel_stats(sw_engine* h, int which, double* total_ms, int64_t* launches);
 /* Floating-point operations issued by the launches of an MFMA kernel class since the last reset
  * (profiling on): 8 flops per complex multiply-add over every (row tile, k-step, probe). */
