@@ -64,9 +64,11 @@ enum TimerCat { T_MVM = 0, T_DEFL, T_P, T_R, T_AXPY, T_DOTS, T_COARSEST, T_OTHER
                 T_TP_SOURCES,   // k_slice_sources of SW_MODE_TWO_POINT
                 T_TP_DOTS,      // k_slice_pair_dots / k_pair_total of SW_MODE_TWO_POINT
                 T_SLICE_CDOTS,  // k_slice_cdots of SW_MODE_MLMC_LOOPS / sw_coarsest_loops
-                T_MESON_FIELD,  // k_meson_field of sw_meson_fields
+                T_MESON_FIELD,  // k_meson_field of sw_meson_fields / sw_low_mode_two_point
+                T_LM_CONTRACT,  // k_cgemm_nt / k_lm_two_point_reduce of sw_low_mode_two_point
                 T_NCAT };
-// classes >= T_STENCIL are folded into the mvm / coarsest (two-point: other / dots; slice cdots, meson fields: dots) buckets by
+// classes >= T_STENCIL are folded into the mvm / coarsest (two-point: other / dots; slice cdots, meson fields and
+// their contraction: dots) buckets by
 // sw_timers and reported separately by sw_kernel_stats
 
 struct EllOp {
@@ -4933,32 +4935,83 @@ int sw_set_loop_momenta(sw_engine* h, int nmom, const int32_t* p) {
   return 0;
 }
 
-// Meson fields of the registered deflation vectors for the momentum p: out[c][d][t][m][m'], complex128
-// [2][2][L][kd][kd], k_meson_field on the engine's U; tables of its own (no momentum registration is touched).
+// Meson fields of the registered deflation vectors for the momentum p into a device buffer of the caller's scope:
+// phi[c][d][t][m][m'], [2][2][L][kd][kd], k_meson_field on the engine's U; tables of its own (no momentum registration
+// is touched).  The caller has checked the vectors and p.
+static int meson_fields_dev(sw_engine* h, int p, DevBuf<cplx>& phi) {
+  const int32_t p32 = p;
+  HIPCHK(hipSetDevice(h->device));
+  SWCHK(stream_sync(h));
+  SWCHK(upload_slice_tables(h, 1, &p32, &h->lm_mom, &h->lm_phase, &h->lm_slicerow));
+  Level& lv = h->hier[0].lv[0];
+  const int L = lv.L, kd = h->kd, ld = defl_ld(kd);
+  SWCHK(dev_realloc(h, &phi.p, (size_t)4 * L * kd * kd));
+  if (h->profiling) h->twork[T_MESON_FIELD] += 32.0 * (double)L * (double)L * (double)ld * (double)ld;
+  const dim3 grid(L, 4, (ld / 16 + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK);
+  if (p == 0)
+    return launch(h, T_MESON_FIELD, swk::k_meson_field<false>, grid, dim3(SW_BLOCK), (const cplx*)h->U, ld, kd,
+                  (const int*)h->lm_slicerow, (const cplx*)h->lm_phase, p, L, phi.p);
+  return launch(h, T_MESON_FIELD, swk::k_meson_field<true>, grid, dim3(SW_BLOCK), (const cplx*)h->U, ld, kd,
+                (const int*)h->lm_slicerow, (const cplx*)h->lm_phase, p, L, phi.p);
+}
+
+// out[c][d][t][m][m'], complex128 [2][2][L][kd][kd]: the meson fields of meson_fields_dev on the host.
 int sw_meson_fields(sw_engine* h, int p, double* out) {
   SWCHK(check_hier(h, 0, 0, false));
   if (!out) return sw_fail(h, "null output");
   if (h->kd <= 0 || !h->U) return sw_fail(h, "no deflation vectors registered (sw_set_deflation)");
   const int32_t p32 = p;
   SWCHK(check_momenta(h, "meson fields", 1, &p32));
-  HIPCHK(hipSetDevice(h->device));
-  SWCHK(stream_sync(h));
-  SWCHK(upload_slice_tables(h, 1, &p32, &h->lm_mom, &h->lm_phase, &h->lm_slicerow));
-  Level& lv = h->hier[0].lv[0];
-  const int L = lv.L, kd = h->kd, ld = defl_ld(kd);
-  const size_t cnt = (size_t)4 * L * kd * kd;
   DevBuf<cplx> phi(h);
-  SWCHK(dev_realloc(h, &phi.p, cnt));
-  if (h->profiling) h->twork[T_MESON_FIELD] += 32.0 * (double)L * (double)L * (double)ld * (double)ld;
-  const dim3 grid(L, 4, (ld / 16 + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK);
-  if (p == 0)
-    SWCHK(launch(h, T_MESON_FIELD, swk::k_meson_field<false>, grid, dim3(SW_BLOCK), (const cplx*)h->U, ld, kd,
-                 (const int*)h->lm_slicerow, (const cplx*)h->lm_phase, p, L, phi.p));
-  else
-    SWCHK(launch(h, T_MESON_FIELD, swk::k_meson_field<true>, grid, dim3(SW_BLOCK), (const cplx*)h->U, ld, kd,
-                 (const int*)h->lm_slicerow, (const cplx*)h->lm_phase, p, L, phi.p));
+  SWCHK(meson_fields_dev(h, p, phi));
   SWCHK(stream_sync(h));
+  const size_t cnt = (size_t)4 * h->hier[0].lv[0].L * h->kd * h->kd;
   HIPCHK(hipMemcpy(out, phi.p, cnt * sizeof(cplx), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// One launch of an instantiation of k_cgemm_nt: nz batches (kchunk = 0) or K splits of kchunk elements.
+typedef void (*cgemm_nt_kernel)(const cplx*, int, size_t, const cplx*, int, size_t, cplx*, int, size_t, int, int, int,
+                                int);
+static int cgemm_nt(sw_engine* h, cgemm_nt_kernel kern, const cplx* A, int lda, size_t sA, const cplx* B, int ldb, size_t sB, cplx* C,
+                    int ldc, size_t sC, int M, int N, int K, int nz, int kchunk) {
+  return launch(h, T_LM_CONTRACT, kern, dim3((N + 63) / 64, (M + 63) / 64, nz),
+                dim3(SW_BLOCK), A, lda, sA, B, ldb, sB, C, ldc, sC, M, N, K, kchunk);
+}
+
+// The low-mode two-point functions of the momentum p for every source timeslice, contracted on the device:
+// out[a][b][c][d][t][t0] = g_a g_b sum_{m,m'} Phi[c][d][t][m][m'] conj(Psi[a][b][t0][m][m']), Psi = G Phi G^H, complex128
+// [2][2][2][2][L][L].  Phi by meson_fields_dev; W^T[s] = conj(G) Phi[s]^T and Psi[s] = G (W^T[s])^T as two products
+// batched over the 4 L slices s; the (4 L x kd^2)(kd^2 x 4 L) contraction with split K into partial sums, added in a
+// fixed order by k_lm_two_point_reduce.  The number of splits follows from L and kd alone: about 1024 workgroups, at
+// most 64 splits, whole steps of 16 per split.  All buffers live for this call only.
+int sw_low_mode_two_point(sw_engine* h, int p, double* out) {
+  SWCHK(check_hier(h, 0, 0, false));
+  if (!out) return sw_fail(h, "null output");
+  SWCHK(low_mode_ready(h));
+  const int32_t p32 = p;
+  SWCHK(check_momenta(h, "low-mode two-point functions", 1, &p32));
+  DevBuf<cplx> phi(h), wt(h), psi(h), part(h), res(h);
+  SWCHK(meson_fields_dev(h, p, phi));
+  const int L = h->hier[0].lv[0].L, kd = h->kd, ld = defl_ld(kd), R = 4 * L, K = kd * kd;
+  const size_t per = (size_t)kd * kd, total = (size_t)R * R;
+  const int tiles = ((R + 63) / 64) * ((R + 63) / 64), steps = (K + 15) / 16;
+  const int want = std::min(steps, std::min(64, std::max(1, 1024 / tiles)));
+  const int kchunk = 16 * ((steps + want - 1) / want), nsplit = (K + kchunk - 1) / kchunk;
+  SWCHK(dev_realloc(h, &wt.p, R * per));
+  SWCHK(dev_realloc(h, &psi.p, R * per));
+  SWCHK(dev_realloc(h, &part.p, nsplit * total));
+  SWCHK(dev_realloc(h, &res.p, total));
+  if (h->profiling)
+    h->twork[T_LM_CONTRACT] += 8.0 * (2.0 * R * (double)ld * ld * ld + (double)R * R * (double)kd * kd);
+  const cplx* G = h->lm_G;
+  SWCHK(cgemm_nt(h, swk::k_cgemm_nt<true, false>, G, kd, 0, phi.p, kd, per, wt.p, kd, per, kd, kd, kd, R, 0));
+  SWCHK(cgemm_nt(h, swk::k_cgemm_nt<false, false>, G, kd, 0, wt.p, kd, per, psi.p, kd, per, kd, kd, kd, R, 0));
+  SWCHK(cgemm_nt(h, swk::k_cgemm_nt<false, true>, phi.p, K, 0, psi.p, K, 0, part.p, R, total, R, R, K, nsplit, kchunk));
+  SWCHK(launch(h, T_LM_CONTRACT, swk::k_lm_two_point_reduce, dim3((unsigned)((total + SW_BLOCK - 1) / SW_BLOCK)),
+               dim3(SW_BLOCK), (const cplx*)part.p, nsplit, L, res.p));
+  SWCHK(stream_sync(h));
+  HIPCHK(hipMemcpy(out, res.p, total * sizeof(cplx), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -5808,7 +5861,7 @@ int sw_timers(sw_engine* h, double t[8]) {
               h->tacc[T_MFMA_OP2] + h->tacc[T_SCHUR] + h->tacc[T_SCHUR_OP];
   t[T_COARSEST] += h->tacc[T_MFMA_DENSE];
   t[T_OTHER] += h->tacc[T_TP_SOURCES];
-  t[T_DOTS] += h->tacc[T_TP_DOTS] + h->tacc[T_SLICE_CDOTS] + h->tacc[T_MESON_FIELD];
+  t[T_DOTS] += h->tacc[T_TP_DOTS] + h->tacc[T_SLICE_CDOTS] + h->tacc[T_MESON_FIELD] + h->tacc[T_LM_CONTRACT];
   return 0;
 }
 int sw_timers_reset(sw_engine* h) {

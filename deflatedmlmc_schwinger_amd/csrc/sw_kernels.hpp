@@ -3878,4 +3878,120 @@ __global__ __launch_bounds__(SW_BLOCK) void k_sub_inplace(cplx* __restrict__ a, 
   for (; i < count; i += stride) a[i] = csub(a[i], b[i]);
 }
 
+// Complex "NT" product of two operands whose summed index is contiguous in memory (sw_low_mode_two_point):
+//   C[z][i][j] = sum_{n in the K range of z} opA(A[z][i][n]) opB(B[z][j][n]),  i < M, j < N,  op = conj where CONJ* is set,
+// A[z] = A + z sA with row stride lda, B[z] = B + z sB with row stride ldb, C[z] = C + z sC with row stride ldc.
+// kchunk = 0: a batched product, z = blockIdx.z the batch index, every z sums n = 0 .. K-1.  kchunk > 0 (a multiple of
+// 16): split K, z the split, n in [z kchunk, min(K, (z + 1) kchunk)), with sA = sB = 0 and C[z] the partial sums of
+// split z (added in a fixed order by k_lm_two_point_reduce: no atomics).
+// v_mfma_f64_16x16x4_f64, four real MFMAs per complex one, operand lanes as k_meson_field (lane l: row l&15 of its
+// operand, K element l>>4 of the MFMA's four; D[(l>>4)+4r][l&15]).  The order of the K sum is fixed but not natural:
+// in the step of 16 elements at k0, MFMA i (i < 4) sums the elements k0 + 4 (l>>4) + i, so a lane loads the 64
+// contiguous bytes k0 + 4 (l>>4) .. + 3 of its row, for A and B alike.  A wave owns 2 x 2 output tiles (32 x 32): every
+// loaded element serves two column / row tiles, and the products ar br, ai bi, ar bi, ai br of a tile accumulate in
+// four accumulators of their own (16 independent chains per wave), combined once at the end.  A workgroup is 2 x 2
+// waves, 64 x 64 of C; grid = (ceil(N / 64), ceil(M / 64), batches or splits).  Rows beyond M / N and K elements
+// beyond the range enter as exact zeros (their addresses are clamped to the last row, never read past K), and only
+// i < M, j < N are stored.  No LDS, no barrier; two calls agree bit for bit.
+template <bool CONJA, bool CONJB>
+__global__ __launch_bounds__(SW_BLOCK, 2) void k_cgemm_nt(const cplx* __restrict__ A, int lda, size_t sA,
+                                                       const cplx* __restrict__ B, int ldb, size_t sB,
+                                                       cplx* __restrict__ C, int ldc, size_t sC, int M, int N, int K,
+                                                       int kchunk) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 15, kq = lane >> 4;
+  const int z = blockIdx.z;
+  const int i0 = blockIdx.y * 64 + (wave >> 1) * 32, j0 = blockIdx.x * 64 + (wave & 1) * 32;
+  if (i0 >= M || j0 >= N) return;
+  const int kb = z * kchunk, ke = kchunk > 0 ? min(K, kb + kchunk) : K;
+  const cplx* __restrict__ pa[2];
+  const cplx* __restrict__ pb[2];
+  bool oka[2], okb[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int ia = i0 + 16 * u + r, jb = j0 + 16 * u + r;
+    oka[u] = ia < M;
+    okb[u] = jb < N;
+    pa[u] = A + z * sA + (size_t)min(ia, M - 1) * lda;
+    pb[u] = B + z * sB + (size_t)min(jb, N - 1) * ldb;
+  }
+  sw_double4 rr[2][2], ii[2][2], ri[2][2], ir[2][2];   // sums of ar br, ai bi, ar bi, ai br
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+#pragma unroll
+    for (int v = 0; v < 2; ++v) rr[u][v] = ii[u][v] = ri[u][v] = ir[u][v] = sw_double4{0.0, 0.0, 0.0, 0.0};
+  for (int k0 = kb; k0 < ke; k0 += 16) {
+    const int kk = k0 + 4 * kq;
+    cplx a[2][4], b[2][4];
+    if (k0 + 16 <= ke) {
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          a[u][i] = pa[u][kk + i];
+          b[u][i] = pb[u][kk + i];
+        }
+    } else {
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const bool in = kk + i < ke;
+          a[u][i] = in ? pa[u][kk + i] : cmake(0.0, 0.0);
+          b[u][i] = in ? pb[u][kk + i] : cmake(0.0, 0.0);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        if (!oka[u]) a[u][i] = cmake(0.0, 0.0);
+        if (!okb[u]) b[u][i] = cmake(0.0, 0.0);
+      }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int v = 0; v < 2; ++v) {
+          rr[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u][i].x, b[v][i].x, rr[u][v], 0, 0, 0);
+          ii[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u][i].y, b[v][i].y, ii[u][v], 0, 0, 0);
+          ri[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u][i].x, b[v][i].y, ri[u][v], 0, 0, 0);
+          ir[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u][i].y, b[v][i].x, ir[u][v], 0, 0, 0);
+        }
+  }
+  // (ar + s ai i)(br + s' bi i), s / s' = -1 on a conjugated operand: re = rr - s s' ii, im = s' ri + s ir
+  constexpr double sa = CONJA ? -1.0 : 1.0, sb = CONJB ? -1.0 : 1.0;
+  cplx* __restrict__ c = C + z * sC;
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+#pragma unroll
+    for (int v = 0; v < 2; ++v) {
+      const int col = j0 + 16 * v + r;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int row = i0 + 16 * u + kq + 4 * q;
+        if (row < M && col < N)
+          c[(size_t)row * ldc + col] =
+              cmake(rr[u][v][q] - sa * sb * ii[u][v][q], sb * ri[u][v][q] + sa * ir[u][v][q]);
+      }
+    }
+}
+
+// E_L of one momentum from the split-K partial sums of k_cgemm_nt: part[s][(c,d,t)][(a,b,t0)], s < nsplit, added in the
+// order s = 0, 1, ... (the same for every call), times g_a g_b (g = +1, -1), written transposed as
+// out[a][b][c][d][t][t0], the layout of utils.low_mode_two_point.  One thread per entry, (a,b,t0) fastest.
+__global__ __launch_bounds__(SW_BLOCK) void k_lm_two_point_reduce(const cplx* __restrict__ part, int nsplit, int L,
+                                                                  cplx* __restrict__ out) {
+  const size_t total = (size_t)16 * L * L;
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  cplx s = part[idx];
+  for (int k = 1; k < nsplit; ++k) s = cadd(s, part[(size_t)k * total + idx]);
+  const int q = (int)(idx % (size_t)(4 * L)), rw = (int)(idx / (size_t)(4 * L));
+  const int ab = q / L, t0 = q % L, cd = rw / L, t = rw % L;
+  if ((ab == 1) || (ab == 2)) s = cmake(-s.x, -s.y);
+  out[(((size_t)ab * 4 + cd) * L + t) * L + t0] = s;
+}
+
 }  // namespace swk

@@ -62,6 +62,7 @@ KCLASS_TP_SOURCES = 17     # sw_kernel_stats classes of the two-point kernels
 KCLASS_TP_DOTS = 18
 KCLASS_SLICE_CDOTS = 19    # ... and of k_slice_cdots (MLMC loops)
 KCLASS_MESON_FIELD = 20    # ... and of k_meson_field (low-mode averaging)
+KCLASS_LM_CONTRACT = 21    # ... and of k_cgemm_nt / k_lm_two_point_reduce (low_mode_two_point)
 MAX_SHIFTS = 128
 MAX_MOMENTA = 8
 # operations of Engine.apply_op32 (SW_OP32_* of the header): one kernel of the complex64 cycle at a time
@@ -223,6 +224,7 @@ def load_library():
     sig("sw_hutch_fetch_mlmc_loops", i32, vp, vp)
     sig("sw_level_deflation_loops", i32, vp, i32, i32, dbl, i32, vp)
     sig("sw_meson_fields", i32, vp, i32, vp)
+    sig("sw_low_mode_two_point", i32, vp, i32, vp)
     sig("sw_set_low_mode_inverse", i32, vp, i32, vp)
     sig("sw_apply_low_mode", i32, vp, i32, vp, vp)
     sig("sw_hutch_fetch_two_point_lma", i32, vp, vp)
@@ -250,7 +252,7 @@ EXPORTED_SYMBOLS = (
     "sw_set_loop_momenta", "sw_hutch_fetch_loops", "sw_apply_slice_dots",
     "sw_set_two_point", "sw_hutch_fetch_two_point", "sw_apply_slice_sources", "sw_apply_pair_dots",
     "sw_apply_slice_cdots", "sw_coarsest_loops", "sw_hutch_fetch_mlmc_loops", "sw_level_deflation_loops",
-    "sw_meson_fields", "sw_set_low_mode_inverse", "sw_apply_low_mode", "sw_hutch_fetch_two_point_lma",
+    "sw_meson_fields", "sw_low_mode_two_point", "sw_set_low_mode_inverse", "sw_apply_low_mode", "sw_hutch_fetch_two_point_lma",
 )
 
 
@@ -493,6 +495,15 @@ class Engine:
         L = int(round((self._n(0, 0) // 2) ** 0.5))
         out = np.zeros((2, 2, L, int(k), int(k)), dtype=np.complex128)
         self._chk(self._lib.sw_meson_fields(self._h, int(p), _ptr(out)), "sw_meson_fields")
+        return out
+
+    def low_mode_two_point(self, p):
+        """E_L[a, b, c, d, t, t0] of the momentum p from the registered vectors and low-mode inverse, contracted on the
+        device: utils.low_mode_two_point(meson_fields(p, k)[None], G)[0] without the fields leaving the device, shape
+        (2, 2, 2, 2, L, L)."""
+        L = int(round((self._n(0, 0) // 2) ** 0.5))
+        out = np.zeros((2, 2, 2, 2, L, L), dtype=np.complex128)
+        self._chk(self._lib.sw_low_mode_two_point(self._h, int(p), _ptr(out)), "sw_low_mode_two_point")
         return out
 
     def apply_low_mode(self, X):

@@ -5,6 +5,7 @@ behind ``matvec`` / ``one_mg_step`` / ``solve`` / ``diff_op`` runs in the HIP li
 :mod:`deflatedmlmc_schwinger_amd.engine`.  Setup (ARPACK test vectors, Galerkin products,
 dense inverse) stays on the host exactly as in the reference and is uploaded once.
 """
+import gc
 import os
 import time
 
@@ -21,6 +22,15 @@ from .utils import CustomTimer, defl_setup_of
 
 REF_HID = 0      # reference hierarchy (MLMC level operators)
 SOLVER_HID = 1   # level-0 preconditioner hierarchy
+
+
+def _finalise_dropped_engines():
+    """Run the cyclic collector on the calling thread before a host thread starts next to GPU work.  Engine handles
+    that earlier flows dropped (an MG and its engines form reference cycles) are destroyed when the collector runs,
+    on whichever thread triggers it; a host thread that allocates as steadily as the ARPACK loop of
+    reference_hierarchy would otherwise end up destroying streams, events and device blocks of those handles while
+    this thread drives the device."""
+    gc.collect()
 
 
 def collective_reference_hierarchy(A, dof, aggrs, max_levels, acc_eigvs, params, tv=None,
@@ -266,6 +276,7 @@ class MG:
             return tv0
         tv0 = comm.compute_on_root(root_job)
         tvs = tv if tv is not None else [tv0]
+        _finalise_dropped_engines()
         self._pending_pool = ThreadPoolExecutor(max_workers=1)
         self._pending = self._pending_pool.submit(_hier.reference_hierarchy, self._A0, dof, aggrs, max_levels,
                                                   acc_eigvs, params, tvs, None, False)
@@ -349,6 +360,7 @@ class MG:
                 _, tv0 = self.device_eigenpairs(int(dof[1] / 2), tolx, log=log)
                 self.setup_log["eigs_level0"] = {"seconds": round(time.time() - t1, 4), "steps": log}
                 tvs = [tv0]
+            _finalise_dropped_engines()
             with ThreadPoolExecutor(max_workers=1) as pool:
                 fut = pool.submit(_hier.reference_hierarchy, self._A0, dof, aggrs, max_levels, acc_eigvs,
                                   params, tvs, None, False)

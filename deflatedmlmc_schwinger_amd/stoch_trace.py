@@ -20,7 +20,7 @@ from .multigrid import MG
 from .utils import (_engines, deflation_pre_computations, displacements_of, draw_probes, flopsV_manual,
                     loops_of, mlmc_defl_setup_of, probe_batch, probe_batch_generated, register_loop_momenta,
                     register_shifts, register_two_point, two_point_of, low_mode_inverse, low_mode_two_point,
-                    register_low_modes)
+                    register_low_modes, low_mode_contraction_of)
 
 DEFAULT_BATCH = 256
 NR_ROUGH_PROBES = 5
@@ -530,7 +530,10 @@ def lma_two_point(A, params):
     Hermitian.  Its pair sums E_L[p][a][b][c][d][t][t0] are exact, from the device meson fields of V, for every source
     timeslice; the noises estimate only the remainder R_k = T(z_k, z_k) - T(z_L, z_L), z_L = A_L^-1 eta_k, whose
     expectation is E[T] - E_L(t0) for any V and G.  Keys, sources, probe loop and stopping rule are two_point()'s; the
-    level tolerances are relative to E_L(t0) plus the rough remainder, i.e. to the full correlator.
+    level tolerances are relative to E_L(t0) plus the rough remainder, i.e. to the full correlator.  The build-only key
+    low_mode_contraction says where E_L is contracted from the fields: "host" (the default: the fields are read back
+    and contracted in NumPy) or "device" (Engine.low_mode_two_point, the fields never leave the device; the two differ
+    in rounding only).
 
     Returns two_point()'s keys with two_point = E_L(t0) + the remainder's mean, plus two_point_low (E_L, all t0),
     two_point_rest (the remainder's mean), two_point_rest_devs and nr_deflat_vctrs; two_point_ests are the per-noise
@@ -539,6 +542,7 @@ def lma_two_point(A, params):
     if sel is None:
         raise Exception("lma_two_point() needs the key source_timeslice")
     t0, momenta = sel
+    contraction = low_mode_contraction_of(params)
     nr_deflat_vctrs = int(params['nr_deflat_vctrs'])
     if nr_deflat_vctrs <= 0:
         raise Exception("lma_two_point() needs nr_deflat_vctrs > 0 (two_point() is the estimator without low modes)")
@@ -564,7 +568,10 @@ def lma_two_point(A, params):
     register_low_modes(mg_solver, G)
     low = np.empty(shape + (L,), dtype=np.complex128)
     for j, p in enumerate(momenta):
-        low[j] = low_mode_two_point(eng.meson_fields(p, nr_deflat_vctrs)[None], G)[0]
+        if contraction == "device":
+            low[j] = eng.low_mode_two_point(p)
+        else:
+            low[j] = low_mode_two_point(eng.meson_fields(p, nr_deflat_vctrs)[None], G)[0]
     print(" done. Time : " + str(time.time() - t1) + " seconds")
     register_two_point(mg_solver, t0, momenta)
     tr1_cols = obs.columns(low[None, ..., t0])[0]

@@ -63,10 +63,23 @@ _BUILD_KEYS = ('batch', 'device', 'engines', 'cache_dir', 'report_path', 'probe_
                'solver_restart', 'stochastic_coarsest', 'stop_factor', 'ref_direct_max_n', 'ref_coarsest',
                'ref_coarse_dofs', 'setup_eigs', 'defer_coarse_levels',
                'verbose', 'probe_rounds_max', 'mlmc_defl_setup', 'defl_setup', 'x_displacements',
-               'timeslice_loops', 'source_timeslice', 'two_point_momenta')
+               'timeslice_loops', 'source_timeslice', 'two_point_momenta', 'low_mode_contraction')
 # where the eigenpairs of the MLMC difference operators come from: host ARPACK (the reference's path) or
 # the block eigensolver on the GPU (setup_gpu.device_diff_eigenpairs)
 MLMC_DEFL_SETUPS = ("host", "device")
+
+
+# where lma_two_point() contracts the meson fields into E_L: NumPy on the host from the read-back fields, or the
+# engine's MFMA products with the fields staying on the device (Engine.low_mode_two_point)
+LOW_MODE_CONTRACTIONS = ("host", "device")
+
+
+def low_mode_contraction_of(params):
+    """The build-only key low_mode_contraction ("host" when absent); any other value raises."""
+    how = params.get('low_mode_contraction', "host") if hasattr(params, "get") else "host"
+    if how not in LOW_MODE_CONTRACTIONS:
+        raise Exception("low_mode_contraction: %r is not one of %s" % (how, list(LOW_MODE_CONTRACTIONS)))
+    return how
 
 
 def mlmc_defl_setup_of(params):
@@ -484,6 +497,33 @@ def low_mode_two_point(Phi, G):
         E = E.reshape(2, 2, L, 2, 2, L).transpose(3, 4, 0, 1, 2, 5)      # [a][b][c][d][t][t0]
         out[j] = E * (g[:, None] * g[None, :])[:, :, None, None, None, None]
     return out
+
+
+def lma_correlator(result, sink, source):
+    """The source-averaged correlator of a lma_two_point() result, shape (M, L), as a function of the distance
+    Delta = (t - t0) mod L:
+
+        C_low[j][Delta]  = (1 / L) sum_t0 meson_correlator(two_point_low[..., t0], sink, source)[j][(t0 + Delta) mod L]
+        C_rest[j][Delta] = meson_correlator(two_point_rest, sink, source)[j][(source_timeslice + Delta) mod L]
+
+    and C_low + C_rest is returned.  The low-mode part is exact for every source timeslice and is averaged over all of
+    them; the remainder was estimated from the one source timeslice of the run.  Averaging over t0 relies on the
+    translation invariance of the ENSEMBLE average, as every low-mode averaging does: on a single configuration the
+    correlators from different t0 differ, and only their ensemble means coincide.  Raises on a result without
+    two_point_low (two_point() has no low part)."""
+    for key in ('two_point_low', 'two_point_rest', 'source_timeslice'):
+        if key not in result:
+            raise Exception("lma_correlator: the result has no %r (it takes the result of lma_two_point())" % key)
+    low = np.asarray(result['two_point_low'])
+    if low.ndim != 7 or low.shape[-1] != low.shape[-2]:
+        raise Exception("lma_correlator: two_point_low of shape %s, expected (M, 2, 2, 2, 2, L, L)" % (low.shape,))
+    L = low.shape[-1]
+    t0 = int(result['source_timeslice'])
+    shift = (np.arange(L)[:, None] + np.arange(L)[None, :]) % L           # [t0][Delta] -> t
+    per_source = meson_correlator(np.moveaxis(low, -1, 0), sink, source)   # [t0][j][t]
+    c_low = per_source[np.arange(L)[:, None], :, shift].mean(axis=0).T    # [t0][Delta][j] -> [j][Delta]
+    c_rest = meson_correlator(result['two_point_rest'], sink, source)[:, shift[t0]]
+    return c_low + c_rest
 
 
 def low_mode_solutions(V, G, sources):

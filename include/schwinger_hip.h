@@ -343,6 +343,14 @@ int sw_apply_pair_dots(sw_engine* h, int nb, const double* Z, double* out);
  * (sw_set_lattice); fp64 MFMA, every entry summed in a fixed order (two calls agree bit for bit).  Fails without
  * vectors and with p out of range. */
 int sw_meson_fields(sw_engine* h, int p, double* out);
+/* The low-mode two-point functions of ONE momentum p for every source timeslice, contracted on the device from the
+ * meson fields Phi of sw_meson_fields (same kernel, never copied to the host) and the registered low-mode inverse G:
+ * out[a][b][c][d][t][t0] = g_a g_b sum_{m,m'} Phi[c][d][t][m][m'] conj(Psi[a][b][t0][m][m']), Psi = G Phi G^H,
+ * g = (+1, -1), complex128 [2][2][2][2][L][L] -- utils.low_mode_two_point of one momentum.  fp64 MFMA, split-K partial
+ * sums added in a fixed order, no atomics (two calls agree bit for bit).  About 3 * 64 * L * k^2 bytes of device
+ * scratch for the call (1.6 GB at k = 256, L = 128), released on return; no registration, mode buffer or fetch is
+ * touched.  Fails as sw_meson_fields does, and without a low-mode inverse (sw_set_low_mode_inverse). */
+int sw_low_mode_two_point(sw_engine* h, int p, double* out);
 /* Y = U G U^H X with the registered vectors and low-mode inverse (sw_set_low_mode_inverse) on nb host vectors in the
  * reference layout: the low-mode chain of SW_MODE_TWO_POINT_LMA alone (projection dots, G, expansion), without the
  * gamma_3 sign of its sources. */
@@ -538,6 +546,8 @@ int sw_timers_reset(sw_engine* h);
 #define SW_KCLASS_SLICE_CDOTS 19    /* k_slice_cdots (SW_MODE_MLMC_LOOPS, sw_coarsest_loops); in sw_timers: dots */
 #define SW_KCLASS_MESON_FIELD 20    /* k_meson_field (sw_meson_fields); in sw_timers: dots; sw_kernel_work counts
                                        8 * 4 * L^2 * ld^2 flops per launch, ld = the rank rounded up to 16 */
+#define SW_KCLASS_LM_CONTRACT 21    /* k_cgemm_nt, k_lm_two_point_reduce (sw_low_mode_two_point); in sw_timers: dots;
+                                       sw_kernel_work counts 8 * (2 * 4L * ld^3 + (4L)^2 * k^2) flops per call */
 int sw_kernel_stats(sw_engine* h, int which, double* total_ms, int64_t* launches);
 /* Floating-point operations issued by the launches of an MFMA kernel class since the last reset
  * (profiling on): 8 flops per complex multiply-add over every (row tile, k-step, probe). */
