@@ -802,6 +802,15 @@ static int pick_ge(int v, F&& f) {
   return rc;
 }
 
+// One launch of k_slice_dots / k_slice_cdots for the registered momenta: f(momenta per pass, phased) with the
+// no-phase instantiation for the single momentum 0, else the smallest instantiation that holds them all (none of
+// them spills)
+template <class F>
+static int pick_momenta(sw_engine* h, F&& f) {
+  if (h->momenta.size() == 1 && h->momenta[0] == 0) return f(IntC<1>{}, std::false_type{});
+  return pick_ge<1, 2, 4, 8>((int)h->momenta.size(), [&](auto NP) { return f(NP, std::true_type{}); });
+}
+
 // ---------------------------------------------------------------------------------------------
 // CSR -> grouped ELL / MFMA block-row form: packed on the host (sw_pack.hpp), uploaded here
 // ---------------------------------------------------------------------------------------------
@@ -3571,6 +3580,9 @@ int sw_set_option(sw_engine* h, const char* name, double value) {
 // the 64 x 64 dense algebra in between (Rayleigh-Ritz, Cholesky-QR).
 static int solve_dev(sw_engine* h, int hid, int level0, const cplx* B, cplx* X, double tol, int maxiter,
                      int nbp, int* total);
+static int diff_levels(sw_engine* h, int level, int skip, int* fine_hid, int* lcoarse);
+static int diff_apply(sw_engine* h, int fine_hid, int level, int lcoarse, const cplx* x, int nbp, cplx* z, cplx* ca,
+                      cplx* cb, double tol, int maxiter, int count_nb, const cplx** y, int* total_f);
 static int eig_check(sw_engine* h, int a) {
   if (h->eig_n <= 0 || !h->eig_buf[0]) return sw_fail(h, "sw_eig_begin has not been called");
   if (a < 0 || a > 2) return sw_fail(h, "block buffer index %d out of 0..2", a);
@@ -3684,11 +3696,10 @@ int sw_eig_solve(sw_engine* h, int src, int dst, int mode, double tol, int maxit
 }
 
 // dst = (A_l^-1 - P A_c^-1 R) Gamma src on all columns (64 per pass), l = the level of sw_eig_begin on hierarchy 0:
-// the MLMC difference operator of utils.py:141-143 / multigrid.py:461-549, built exactly as the probe body
-// of sw_hutch_run builds it (fine solve on the solver hierarchy at level 0 when it is ready, R / P of
-// hierarchy 0, coarse solve on hierarchy 0, direct or dense at the coarsest level).  Gamma = gamma_3 (g3 = 1)
-// or the identity (g3 = 0); skip = 1: A_0^-1 - P_0 P_1 A_2^-1 R_1 R_0.  The third eigen buffer and two
-// coarse blocks of the eigen state are the scratch; the probe workspace is not touched.
+// the MLMC difference operator of utils.py:141-143 / multigrid.py:461-549 through diff_apply, the helper the probe
+// body of sw_hutch_run applies too.  Gamma = gamma_3 (g3 = 1) or the identity (g3 = 0); skip = 1: A_0^-1 - P_0 P_1
+// A_2^-1 R_1 R_0.  The third eigen buffer and two coarse blocks of the eigen state are the scratch; the probe
+// workspace is not touched.
 int sw_eig_apply_diff(sw_engine* h, int src, int dst, int skip, int g3, double tol, int maxiter,
                       int32_t* iters_max) {
   SWCHK(eig_check(h, src));
@@ -3703,21 +3714,15 @@ int sw_eig_apply_diff(sw_engine* h, int src, int dst, int skip, int g3, double t
   const int level = h->eig_level;
   if (skip && (level != 0 || H0.nlevels < 3))
     return sw_fail(h, "level skipping is defined for level 0 of a hierarchy with at least three levels");
-  const int lcoarse = level + (skip ? 2 : 1);
-  if (lcoarse >= H0.nlevels) return sw_fail(h, "no coarse level %d", lcoarse);
+  int fine_hid, lcoarse;
+  SWCHK(diff_levels(h, level, skip, &fine_hid, &lcoarse));
   Level& lv = H0.lv[level];
   const int n = lv.n;
-  const int n1 = H0.lv[level + 1].n;
-  const int fine_hid = (level == 0 && h->hier[h->solver_hid].ready) ? h->solver_hid : 0;
-  if (fine_hid != 0 && h->hier[fine_hid].lv[0].n != n)
-    return sw_fail(h, "solver hierarchy level-0 size mismatch");
   // two coarse blocks of the level below (with skip the level two below is smaller and fits in them)
   for (int q = 0; q < 2; ++q)
-    if (!h->eig_cs[q]) SWCHK(dev_realloc(h, &h->eig_cs[q], (size_t)n1 * 64));
+    if (!h->eig_cs[q]) SWCHK(dev_realloc(h, &h->eig_cs[q], (size_t)H0.lv[level + 1].n * 64));
   int worst = 0;
   for (int g = 0; g < h->eig_w / 64; ++g) {
-    cplx* ca = h->eig_cs[0];
-    cplx* cb = h->eig_cs[1];
     const size_t go = (size_t)g * n * 64;   // this group of 64 columns
     cplx* t = h->eig_buf[3 - src - dst] + go;
     cplx* d = h->eig_buf[dst] + go;
@@ -3728,25 +3733,11 @@ int sw_eig_apply_diff(sw_engine* h, int src, int dst, int skip, int g3, double t
                    dim3(SW_BLOCK), x, (const signed char*)h->eig_sign, d, n, 64));
       x = d;
     }
-    // xc = R x (skip: R_1 R_0 x)
-    SWCHK(launch_ell(h, lv.R, 0, x, nullptr, ca, 64, T_R));
-    const cplx* xc = ca;
-    cplx* y = cb;
-    if (skip) {
-      SWCHK(launch_ell(h, H0.lv[1].R, 0, ca, nullptr, cb, 64, T_R));
-      xc = cb;
-      y = ca;
-    }
-    // t = A_l^-1 x
-    int total_f = 0, total_c = 0;
-    SWCHK(solve_dev(h, fine_hid, level, x, t, tol, maxiter, 64, &total_f));
-    // y = A_c^-1 xc
-    SWCHK(solve_dev(h, 0, lcoarse, xc, y, tol, maxiter, 64, &total_c));
-    // dst = t - P y (skip: t - P_0 P_1 y)
-    if (skip) {
-      SWCHK(launch_ell(h, H0.lv[1].P, 0, y, nullptr, cb, 64, T_P));
-      y = cb;
-    }
+    // t = A_l^-1 x, y = the coarse solution on the level below, dst = t - P y
+    const cplx* y;
+    int total_f = 0;
+    SWCHK(diff_apply(h, fine_hid, level, lcoarse, x, 64, t, h->eig_cs[0], h->eig_cs[1], tol, maxiter, 0, &y,
+                     &total_f));
     SWCHK(launch_ell(h, lv.P, 1, y, t, d, 64, T_P));
     SWCHK(stream_sync(h));
     worst = std::max(worst, total_f);
@@ -5044,34 +5035,24 @@ static int slice_dots(sw_engine* h, Level& lv, const int8_t* probes, int nb, con
   SWCHK(loop_buffer(h, mlmc, L, nbp, &out));
   SWCHK(launch(h, T_OTHER, swk::k_probe_codes, dim3((n + 63) / 64, nbp / 64), dim3(SW_BLOCK), probes, nb, n,
                (const int*)lv.rowmap, h->pb_codes, nbp));
-  const dim3 grid(L, nbp / 64);
-  if (M == 1 && h->momenta[0] == 0) {
-    SWCHK(launch(h, T_DOTS, swk::k_slice_dots<1, false>, grid, dim3(SW_BLOCK), (const int8_t*)h->pb_codes, Z,
-                 (const int*)h->slicerow, (const cplx*)h->loop_phase, (const int*)h->loop_mom, L, nbp, M, out));
-  } else {
-    // momenta per pass: the smallest instantiation that holds them all (none of them spills)
-    SWCHK(pick_ge<1, 2, 4, 8>(M, [&](auto NPc) {
-      return launch(h, T_DOTS, swk::k_slice_dots<decltype(NPc)::value, true>, grid, dim3(SW_BLOCK),
-                    (const int8_t*)h->pb_codes, Z, (const int*)h->slicerow, (const cplx*)h->loop_phase,
-                    (const int*)h->loop_mom, L, nbp, M, out);
-    }));
-  }
+  SWCHK(pick_momenta(h, [&](auto NP, auto PH) {
+    return launch(h, T_DOTS, swk::k_slice_dots<decltype(NP)::value, decltype(PH)::value>, dim3(L, nbp / 64),
+                  dim3(SW_BLOCK), (const int8_t*)h->pb_codes, Z, (const int*)h->slicerow, (const cplx*)h->loop_phase,
+                  (const int*)h->loop_mom, L, nbp, M, out);
+  }));
   if (!total) return 0;
   return launch(h, T_DOTS, swk::k_slice_total, dim3(nbp / 64), dim3(SW_BLOCK), (const cplx*)out, L, nbp, total);
 }
 
 // out[p][a][b][t][col] = sum_x e^{-2 pi i p x / L} conj(U_col[idx(a,x,t)]) V_col[idx(b,x,t)] for the registered
 // momenta, U and V two blocks [n_0][nbp] of the lattice level (k_slice_cdots: same grid, same choice of momenta
-// per pass as slice_dots; none of the instantiations spills)
+// per pass as slice_dots)
 static int slice_cdots_into(sw_engine* h, Level& lv0, const cplx* U, const cplx* V, int nbp, cplx* out) {
   const int M = (int)h->momenta.size(), L = lv0.L;
-  const dim3 grid(L, nbp / 64);
-  if (M == 1 && h->momenta[0] == 0)
-    return launch(h, T_SLICE_CDOTS, swk::k_slice_cdots<1, false>, grid, dim3(SW_BLOCK), U, V,
-                  (const int*)h->slicerow, (const cplx*)h->loop_phase, (const int*)h->loop_mom, L, nbp, M, out);
-  return pick_ge<1, 2, 4, 8>(M, [&](auto NPc) {
-    return launch(h, T_SLICE_CDOTS, swk::k_slice_cdots<decltype(NPc)::value, true>, grid, dim3(SW_BLOCK), U, V,
-                  (const int*)h->slicerow, (const cplx*)h->loop_phase, (const int*)h->loop_mom, L, nbp, M, out);
+  return pick_momenta(h, [&](auto NP, auto PH) {
+    return launch(h, T_SLICE_CDOTS, swk::k_slice_cdots<decltype(NP)::value, decltype(PH)::value>, dim3(L, nbp / 64),
+                  dim3(SW_BLOCK), U, V, (const int*)h->slicerow, (const cplx*)h->loop_phase, (const int*)h->loop_mom, L,
+                  nbp, M, out);
   });
 }
 
@@ -5160,10 +5141,111 @@ static int prolong_to_lattice(sw_engine* h, int level, const cplx* X, cplx* s0, 
   return 0;
 }
 
+// rows of the loop buffers [p][a][b][t]
+static size_t loop_rows(sw_engine* h) { return h->momenta.size() * 4 * (size_t)h->hier[0].lv[0].L; }
+
+// Iteration counts of an outer solve on (H, level) for the first nb columns, once the stream has drained: 1 on the
+// coarsest and on a directly solved level, the solver's own counts elsewhere
+static int record_level_iters(sw_engine* h, Hier& H, int level, int total, std::vector<int32_t>& dst, int nb) {
+  SWCHK(stream_sync(h));
+  if ((level == H.nlevels - 1 && H.nlevels > 1) || level_is_direct(h, H, level)) {
+    dst.assign(nb, 1);
+    return 0;
+  }
+  return record_iters(h, &H.lv[level].sws, total, dst, nb);
+}
+
+// The two solves of the MLMC difference operator d = A_l^-1 x - P A_c^-1 R x of level `level` of hierarchy 0 (skip:
+// A_0^-1 x - P_0 P_1 A_2^-1 R_1 R_0 x; utils.py:288-341): the fine one on the solver hierarchy at level 0 when it is
+// ready, the coarse one on hierarchy 0 at lcoarse = level + 1 (skip: + 2).  Refused before anything is allocated or
+// launched; every user of the operator goes through this pair of functions.
+static int diff_levels(sw_engine* h, int level, int skip, int* fine_hid, int* lcoarse) {
+  *lcoarse = level + (skip ? 2 : 1);
+  if (*lcoarse >= h->hier[0].nlevels) return sw_fail(h, "no coarse level %d", *lcoarse);
+  *fine_hid = (level == 0 && h->hier[h->solver_hid].ready) ? h->solver_hid : 0;
+  if (*fine_hid != 0 && h->hier[*fine_hid].lv[0].n != h->hier[0].lv[level].n)
+    return sw_fail(h, "solver hierarchy level-0 size mismatch");
+  return 0;
+}
+
+// The operator on the block x [n_level][nbp] up to its last step: z = A_l^-1 x and *y = A_c^-1 R x on level + 1
+// (skip: P_1 A_2^-1 R_1 R_0 x).  The caller finishes d = z - P_l y: launch_ell(P_l, 1, y, z, d) in one launch, or
+// w = P_l y and two dots (modes 1 / 2).  ca, cb: two coarse blocks [n_{level+1}][nbp] (with skip the level two below
+// is smaller and fits in them), *y is one of them.  count_nb > 0: the stream is drained after each solve and the
+// iteration counts of the first count_nb columns go to last_iters_f / last_iters_c; without it nothing here waits for
+// the device.  total_f (optional) = the fine solve's iteration total.
+static int diff_apply(sw_engine* h, int fine_hid, int level, int lcoarse, const cplx* x, int nbp, cplx* z, cplx* ca,
+                      cplx* cb, double tol, int maxiter, int count_nb, const cplx** y, int* total_f) {
+  Hier& H0 = h->hier[0];
+  const bool skip = lcoarse == level + 2;
+  // xc = R x (skip: R_1 R_0 x)             utils.py:298-304
+  SWCHK(launch_ell(h, H0.lv[level].R, 0, x, nullptr, ca, nbp, T_R));
+  const cplx* xc = ca;
+  cplx* yc = cb;
+  if (skip) {
+    SWCHK(launch_ell(h, H0.lv[1].R, 0, ca, nullptr, cb, nbp, T_R));
+    xc = cb;
+    yc = ca;
+  }
+  int tf = 0, tc = 0;
+  SWCHK(solve_dev(h, fine_hid, level, x, z, tol, maxiter, nbp, &tf));
+  if (count_nb) SWCHK(record_level_iters(h, h->hier[fine_hid], level, tf, h->last_iters_f, count_nb));
+  // y = A_c^-1 xc                           utils.py:306-329
+  SWCHK(solve_dev(h, 0, lcoarse, xc, yc, tol, maxiter, nbp, &tc));
+  if (count_nb) SWCHK(record_level_iters(h, H0, lcoarse, tc, h->last_iters_c, count_nb));
+  if (skip) {
+    SWCHK(launch_ell(h, H0.lv[1].P, 0, yc, nullptr, cb, nbp, T_P));
+    yc = cb;
+  }
+  *y = yc;
+  if (total_f) *total_f = tf;
+  return 0;
+}
+
+// The frame of the column-blocked sums sum_j S_q(Pi u_j, Pi v_j) of sw_coarsest_loops and sw_level_deflation_loops:
+// 64 columns per pass, prolonged to the lattice level and reduced with k_slice_cdots; the passes are added in
+// ascending order on the device and the 64 columns of the sum by one host loop in ascending order, so two calls agree
+// bit for bit.  The probe workspace and the loop buffers of the modes are not touched.
+struct BlockSums {
+  size_t rows;
+  DevBuf<cplx> s[4], acc, part;
+  explicit BlockSums(sw_engine* h)
+      : rows(loop_rows(h)), s{DevBuf<cplx>(h), DevBuf<cplx>(h), DevBuf<cplx>(h), DevBuf<cplx>(h)}, acc(h), part(h) {}
+};
+// scratch for blocks of `level` and the zeroed sum
+static int sums_begin(sw_engine* h, BlockSums& S, int level) {
+  int nmax = 0;
+  for (int l = 0; l < h->hier[0].nlevels; ++l) nmax = std::max(nmax, h->hier[0].lv[l].n);
+  if (level > 0)
+    for (auto& b : S.s) SWCHK(dev_realloc(h, &b.p, (size_t)nmax * 64));
+  SWCHK(dev_realloc(h, &S.acc.p, S.rows * 64));
+  SWCHK(dev_realloc(h, &S.part.p, S.rows * 64));
+  return zero_vec(h, S.acc, (int)S.rows, 64);
+}
+// acc += S_q(Pi U, Pi V) of the blocks U, V [n_level][64]
+static int sums_add(sw_engine* h, BlockSums& S, int level, const cplx* U, const cplx* V) {
+  const cplx *u, *v;
+  SWCHK(prolong_to_lattice(h, level, U, S.s[0], S.s[1], 64, &u));
+  SWCHK(prolong_to_lattice(h, level, V, S.s[2], S.s[3], 64, &v));
+  SWCHK(slice_cdots_into(h, h->hier[0].lv[0], u, v, 64, S.part));
+  return vec_add(h, S.acc, S.part, S.acc, (int)S.rows, 64);
+}
+// out[p][a][b][t] = the sum over the 64 columns
+static int sums_finish(sw_engine* h, BlockSums& S, double* out) {
+  SWCHK(stream_sync(h));
+  std::vector<std::complex<double>> ha(S.rows * 64);
+  HIPCHK(hipMemcpy(ha.data(), S.acc.p, ha.size() * sizeof(cplx), hipMemcpyDeviceToHost));
+  for (size_t r = 0; r < S.rows; ++r) {
+    std::complex<double> sum(0.0, 0.0);
+    for (int c = 0; c < 64; ++c) sum += ha[r * 64 + c];
+    out[2 * r] = sum.real();
+    out[2 * r + 1] = sum.imag();
+  }
+  return 0;
+}
+
 // The exact coarsest term of the MLMC loops: out[p][a][b][t] = sum_j S_q(Pi e_j, Pi A_c^-1 e_j), Pi = P_0 ... P_{M-2},
-// on 64-column blocks of the identity and of the coarsest inverse, both prolonged to the lattice level and reduced
-// with k_slice_cdots; the blocks are added in ascending order and the 64 columns of the sum by one host loop in
-// ascending order, so two calls agree bit for bit.
+// on 64-column blocks of the identity and of the coarsest inverse (BlockSums).
 int sw_coarsest_loops(sw_engine* h, double* out) {
   SWCHK(check_hier(h, 0, 0, true));
   if (!out) return sw_fail(h, "null output");
@@ -5172,20 +5254,12 @@ int sw_coarsest_loops(sw_engine* h, double* out) {
   if (H0.nlevels < 2) return sw_fail(h, "the coarsest loops need at least two levels");
   HIPCHK(hipSetDevice(h->device));
   const int last = H0.nlevels - 1;
-  Level& lv0 = H0.lv[0];
-  Level& lc = H0.lv[last];
-  const int nc = lc.n, nbp = 64, L = lv0.L;
-  const size_t rows = h->momenta.size() * 4 * (size_t)L;
-  int nmax = 0;
-  for (int l = 0; l < H0.nlevels; ++l) nmax = std::max(nmax, H0.lv[l].n);
-  DevBuf<cplx> E(h), Y(h), s[4] = {DevBuf<cplx>(h), DevBuf<cplx>(h), DevBuf<cplx>(h), DevBuf<cplx>(h)}, acc(h),
-      part(h);
+  const int nc = H0.lv[last].n, nbp = 64;
+  DevBuf<cplx> E(h), Y(h);
+  BlockSums S(h);
   SWCHK(dev_realloc(h, &E.p, (size_t)nc * nbp));
   SWCHK(dev_realloc(h, &Y.p, (size_t)nc * nbp));
-  for (auto& b : s) SWCHK(dev_realloc(h, &b.p, (size_t)nmax * nbp));
-  SWCHK(dev_realloc(h, &acc.p, rows * nbp));
-  SWCHK(dev_realloc(h, &part.p, rows * nbp));
-  SWCHK(zero_vec(h, acc, (int)rows, nbp));
+  SWCHK(sums_begin(h, S, last));
   std::vector<std::complex<double>> he((size_t)nc * nbp);
   for (int j0 = 0; j0 < nc; j0 += 64) {
     std::fill(he.begin(), he.end(), std::complex<double>(0.0, 0.0));
@@ -5193,30 +5267,14 @@ int sw_coarsest_loops(sw_engine* h, double* out) {
     SWCHK(stream_sync(h));                 // the previous block's reads of E are done
     HIPCHK(hipMemcpy(E.p, he.data(), he.size() * sizeof(cplx), hipMemcpyHostToDevice));
     SWCHK(apply_coarsest(h, H0, E, Y, nbp));
-    const cplx *u, *v;
-    SWCHK(prolong_to_lattice(h, last, E, s[0], s[1], nbp, &u));
-    SWCHK(prolong_to_lattice(h, last, Y, s[2], s[3], nbp, &v));
-    SWCHK(slice_cdots_into(h, lv0, u, v, nbp, part));
-    SWCHK(vec_add(h, acc, part, acc, (int)rows, nbp));
+    SWCHK(sums_add(h, S, last, E, Y));
   }
-  SWCHK(stream_sync(h));
-  std::vector<std::complex<double>> ha(rows * nbp);
-  HIPCHK(hipMemcpy(ha.data(), acc.p, ha.size() * sizeof(cplx), hipMemcpyDeviceToHost));
-  for (size_t r = 0; r < rows; ++r) {
-    std::complex<double> sum(0.0, 0.0);
-    for (int c = 0; c < nbp; ++c) sum += ha[r * nbp + c];
-    out[2 * r] = sum.real();
-    out[2 * r + 1] = sum.imag();
-  }
-  return 0;
+  return sums_finish(h, S, out);
 }
 
 // The deflated part of a level's term of the MLMC loops: out[p][a][b][t] = sum_j S_q(Pi V_j, Pi D V_j) over the
-// vectors V_j registered at `level` (sw_set_level_deflation), D the level's difference operator built as the probe
-// body of sw_hutch_run builds it (fine solve on the solver hierarchy at level 0 when it is ready, R / P of hierarchy
-// 0, coarse solve on hierarchy 0), Pi = P_0 ... P_{level-1}.  64 columns of V per pass; the passes are added in
-// ascending order on the device and the 64 columns by one host loop in ascending order (as sw_coarsest_loops), so
-// two calls agree bit for bit.  The probe workspace and the loop buffers of the modes are not touched.
+// vectors V_j registered at `level` (sw_set_level_deflation), D the level's difference operator through diff_apply,
+// Pi = P_0 ... P_{level-1}; 64 columns of V per pass (BlockSums).
 int sw_level_deflation_loops(sw_engine* h, int level, int skip, double tol, int maxiter, double* out) {
   SWCHK(check_hier(h, 0, level, true));
   if (!out) return sw_fail(h, "null output");
@@ -5225,71 +5283,35 @@ int sw_level_deflation_loops(sw_engine* h, int level, int skip, double tol, int 
   if (h->momenta.empty()) return sw_fail(h, "no momenta registered (sw_set_loop_momenta)");
   Hier& H0 = h->hier[0];
   if (skip && level != 0) return sw_fail(h, "level skipping is defined for level 0 only");
-  const int lcoarse = level + (skip ? 2 : 1);
-  if (lcoarse >= H0.nlevels) return sw_fail(h, "no coarse level %d", lcoarse);
+  int fine_hid, lcoarse;
+  SWCHK(diff_levels(h, level, skip, &fine_hid, &lcoarse));
   const int k = h->lkd[level];
   if (k <= 0 || !h->lV[level]) return sw_fail(h, "no deflation vectors registered at level %d", level);
   HIPCHK(hipSetDevice(h->device));
-  Level& lv0 = H0.lv[0];
   Level& lv = H0.lv[level];
-  const int n = lv.n, n1 = H0.lv[level + 1].n, nbp = 64, L = lv0.L, ld = defl_ld(k);
-  const int fine_hid = (level == 0 && h->hier[h->solver_hid].ready) ? h->solver_hid : 0;
-  if (fine_hid != 0 && h->hier[fine_hid].lv[0].n != n) return sw_fail(h, "solver hierarchy level-0 size mismatch");
-  const size_t rows = h->momenta.size() * 4 * (size_t)L;
-  DevBuf<cplx> X(h), Z(h), Dv(h), ca(h), cb(h), s[4] = {DevBuf<cplx>(h), DevBuf<cplx>(h), DevBuf<cplx>(h), DevBuf<cplx>(h)},
-      acc(h), part(h);
+  const int n = lv.n, n1 = H0.lv[level + 1].n, nbp = 64, ld = defl_ld(k);
+  DevBuf<cplx> X(h), Z(h), Dv(h), ca(h), cb(h);
+  BlockSums S(h);
   SWCHK(dev_realloc(h, &X.p, (size_t)n * nbp));
   SWCHK(dev_realloc(h, &Z.p, (size_t)n * nbp));
   SWCHK(dev_realloc(h, &Dv.p, (size_t)n * nbp));
   // two coarse blocks of the level below (with skip the level two below is smaller and fits in them)
   SWCHK(dev_realloc(h, &ca.p, (size_t)n1 * nbp));
   SWCHK(dev_realloc(h, &cb.p, (size_t)n1 * nbp));
-  int nmax = 0;
-  for (int l = 0; l < H0.nlevels; ++l) nmax = std::max(nmax, H0.lv[l].n);
-  if (level > 0)
-    for (auto& b : s) SWCHK(dev_realloc(h, &b.p, (size_t)nmax * nbp));
-  SWCHK(dev_realloc(h, &acc.p, rows * nbp));
-  SWCHK(dev_realloc(h, &part.p, rows * nbp));
-  SWCHK(zero_vec(h, acc, (int)rows, nbp));
+  SWCHK(sums_begin(h, S, level));
   for (int j0 = 0; j0 < k; j0 += 64) {
     // x = the columns [j0, j0 + 64) of V, zero beyond the last vector (a zero column adds exact zeros)
     const int nc = std::min(64, k - j0);
     SWCHK(zero_vec(h, X, n, nbp));
     HIPCHK(hipMemcpy2DAsync(X.p, (size_t)nbp * sizeof(cplx), h->lV[level] + j0, (size_t)ld * sizeof(cplx),
                             (size_t)nc * sizeof(cplx), (size_t)n, hipMemcpyDeviceToDevice, h->stream));
-    // xc = R x (skip: R_1 R_0 x), z = A_l^-1 x, y = A_c^-1 xc, d = z - P y (skip: z - P_0 P_1 y)
-    SWCHK(launch_ell(h, lv.R, 0, X, nullptr, ca, nbp, T_R));
-    const cplx* xc = ca;
-    cplx* y = cb;
-    if (skip) {
-      SWCHK(launch_ell(h, H0.lv[1].R, 0, ca, nullptr, cb, nbp, T_R));
-      xc = cb;
-      y = ca;
-    }
-    int total_f = 0, total_c = 0;
-    SWCHK(solve_dev(h, fine_hid, level, X, Z, tol, maxiter, nbp, &total_f));
-    SWCHK(solve_dev(h, 0, lcoarse, xc, y, tol, maxiter, nbp, &total_c));
-    if (skip) {
-      SWCHK(launch_ell(h, H0.lv[1].P, 0, y, nullptr, cb, nbp, T_P));
-      y = cb;
-    }
+    // d = z - P y
+    const cplx* y;
+    SWCHK(diff_apply(h, fine_hid, level, lcoarse, X, nbp, Z, ca, cb, tol, maxiter, 0, &y, nullptr));
     SWCHK(launch_ell(h, lv.P, 1, y, Z, Dv, nbp, T_P));
-    const cplx *u, *v;
-    SWCHK(prolong_to_lattice(h, level, X, s[0], s[1], nbp, &u));
-    SWCHK(prolong_to_lattice(h, level, Dv, s[2], s[3], nbp, &v));
-    SWCHK(slice_cdots_into(h, lv0, u, v, nbp, part));
-    SWCHK(vec_add(h, acc, part, acc, (int)rows, nbp));
+    SWCHK(sums_add(h, S, level, X, Dv));
   }
-  SWCHK(stream_sync(h));
-  std::vector<std::complex<double>> ha(rows * nbp);
-  HIPCHK(hipMemcpy(ha.data(), acc.p, ha.size() * sizeof(cplx), hipMemcpyDeviceToHost));
-  for (size_t r = 0; r < rows; ++r) {
-    std::complex<double> sum(0.0, 0.0);
-    for (int c = 0; c < nbp; ++c) sum += ha[r * nbp + c];
-    out[2 * r] = sum.real();
-    out[2 * r + 1] = sum.imag();
-  }
-  return 0;
+  return sums_finish(h, S, out);
 }
 
 // ---- one-end-trick two-point functions from timeslice sources ------------------------------------------
@@ -5596,8 +5618,8 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
   const bool skip = (mode == SW_MODE_MLMC_SKIP || mode == SW_MODE_MLMC_LOOPS_SKIP ||
                      mode == SW_MODE_MLMC_DEFL_LOOPS_SKIP);
   if (skip && level != 0) return sw_fail(h, "level skipping is defined for level 0 only");
-  const int lcoarse = level + (skip ? 2 : 1);
-  if (lcoarse >= H0.nlevels) return sw_fail(h, "no coarse level %d", lcoarse);
+  int diff_hid, lcoarse;   // diff_hid = fine_hid: the same choice
+  SWCHK(diff_levels(h, level, skip, &diff_hid, &lcoarse));
   // x_def = Bblock_perm * Pperm^T * x0      utils.py:288-290
   const cplx* xdef = h->pb_x0;
   if (h->lkd[level] > 0) {
@@ -5610,31 +5632,13 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
     SWCHK(launch_ell(h, h->rhsmap[level], 0, xdef, nullptr, h->pb_rhs, nbp, T_OTHER));
     xdef = h->pb_rhs;
   }
-  int total_f = 0, total_c = 0;
-  SWCHK(solve_dev(h, fine_hid, level, xdef, h->pb_z, tol, maxiter, nbp, &total_f));
-  SWCHK(stream_sync(h));
-  if (level_is_direct(h, h->hier[fine_hid], level)) h->last_iters_f.assign(nb, 1);
-  else SWCHK(record_iters(h, &h->hier[fine_hid].lv[level].sws, total_f, h->last_iters_f, nb));
-  // xc = R x_def  (skip: R1 R0)             utils.py:298-304
-  SWCHK(launch_ell(h, lv.R, 0, xdef, nullptr, h->pb_xc, nbp, T_R));
-  const cplx* xc = h->pb_xc;
-  if (skip) {
-    SWCHK(launch_ell(h, H0.lv[1].R, 0, h->pb_xc, nullptr, h->pb_xc2, nbp, T_R));
-    xc = h->pb_xc2;
-  }
-  // y = A_c^-1 xc                            utils.py:306-329
-  SWCHK(solve_dev(h, 0, lcoarse, xc, h->pb_y, tol, maxiter, nbp, &total_c));
-  SWCHK(stream_sync(h));
-  if (lcoarse == H0.nlevels - 1 || level_is_direct(h, H0, lcoarse)) h->last_iters_c.assign(nb, 1);
-  else SWCHK(record_iters(h, &H0.lv[lcoarse].sws, total_c, h->last_iters_c, nb));
+  // z = A_l^-1 x_def, y = the coarse solution on level + 1 (iteration counts recorded after each solve)
+  const cplx* y;
+  SWCHK(diff_apply(h, diff_hid, level, lcoarse, xdef, nbp, h->pb_z, h->pb_xc, h->pb_y, tol, maxiter, nb, &y,
+                   nullptr));
   if (mloops) {
-    // d = z - P y on level `level` (skip: z - P0 P1 y), one launch with the prolongation
-    const cplx* yc = h->pb_y;
-    if (skip) {
-      SWCHK(launch_ell(h, H0.lv[1].P, 0, h->pb_y, nullptr, h->pb_w2, nbp, T_P));
-      yc = h->pb_w2;
-    }
-    SWCHK(launch_ell(h, lv.P, 1, yc, h->pb_z, h->pb_w, nbp, T_P));
+    // d = z - P y on level `level`, one launch with the prolongation
+    SWCHK(launch_ell(h, lv.P, 1, y, h->pb_z, h->pb_w, nbp, T_P));
     Level& lv0 = H0.lv[0];
     if (level == 0) {
       // the probe is the int8 codes themselves: mode 5's reduction on d, one pass
@@ -5651,22 +5655,13 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
     h->mloop_nb = nb;
     return 0;
   }
-  // w = P y (skip: P0 P1 y)                  utils.py:337-341
-  const cplx* w;
-  if (skip) {
-    SWCHK(launch_ell(h, H0.lv[1].P, 0, h->pb_y, nullptr, h->pb_w2, nbp, T_P));
-    SWCHK(launch_ell(h, lv.P, 0, h->pb_w2, nullptr, h->pb_w, nbp, T_P));
-  } else {
-    SWCHK(launch_ell(h, lv.P, 0, h->pb_y, nullptr, h->pb_w, nbp, T_P));
-  }
-  w = h->pb_w;
-  // e = x0^H z - x0^H w                      utils.py:336,353-355
+  // w = P y, e = x0^H z - x0^H w            utils.py:336-355
+  SWCHK(launch_ell(h, lv.P, 0, y, nullptr, h->pb_w, nbp, T_P));
   SWCHK(dot_into(h, h->pb_x0, h->pb_z, n, nbp, h->pb_est + nbp));
-  SWCHK(dot_into(h, h->pb_x0, w, n, nbp, h->pb_est + 2 * nbp));
+  SWCHK(dot_into(h, h->pb_x0, h->pb_w, n, nbp, h->pb_est + 2 * nbp));
   SWCHK(launch(h, T_OTHER, swk::k_est_combine, dim3((nbp + 255) / 256), dim3(256), (const cplx*)(h->pb_est + nbp),
                (const cplx*)(h->pb_est + 2 * nbp), nbp, h->pb_est));
-  SWCHK(stream_sync(h));
-  return 0;
+  return stream_sync(h);
 }
 
 // ---- the one collective of the path: trace-sum / variance statistics over the ranks (RCCL over xGMI)
