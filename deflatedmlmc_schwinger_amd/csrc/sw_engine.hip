@@ -66,9 +66,10 @@ enum TimerCat { T_MVM = 0, T_DEFL, T_P, T_R, T_AXPY, T_DOTS, T_COARSEST, T_OTHER
                 T_SLICE_CDOTS,  // k_slice_cdots of SW_MODE_MLMC_LOOPS / sw_coarsest_loops
                 T_MESON_FIELD,  // k_meson_field of sw_meson_fields / sw_low_mode_two_point
                 T_LM_CONTRACT,  // k_cgemm_nt / k_lm_two_point_reduce of sw_low_mode_two_point
+                T_LINK_DOTS,    // k_slice_link_dots of SW_MODE_HUTCHINSON_LINK_LOOPS
                 T_NCAT };
-// classes >= T_STENCIL are folded into the mvm / coarsest (two-point: other / dots; slice cdots, meson fields and
-// their contraction: dots) buckets by
+// classes >= T_STENCIL are folded into the mvm / coarsest (two-point: other / dots; slice cdots, meson fields,
+// their contraction and the link dots: dots) buckets by
 // sw_timers and reported separately by sw_kernel_stats
 
 struct EllOp {
@@ -334,6 +335,11 @@ struct sw_engine {
   cplx* pb_mlest = nullptr;
   size_t pb_mlest_cap = 0;
   int mloop_nb = 0, mloop_nbp = 0;
+  // point-split link loops (SW_MODE_HUTCHINSON_LINK_LOOPS, sw_apply_slice_link_dots): the same momenta and tables,
+  // the four branches [d][momentum][a][b][t][probe] in a buffer of their own
+  cplx* pb_klest = nullptr;
+  size_t pb_klest_cap = 0;
+  int link_nb = 0, link_nbp = 0;
   // one-end-trick two-point functions (sw_set_two_point, SW_MODE_TWO_POINT): a registration of its own (source
   // timeslice, momenta, the index of momentum 0, tables as for the loops), the sources and solutions [n][2 M nq]
   // and the pair sums T[momentum][a][b][c][d][t][noise]
@@ -2580,7 +2586,7 @@ int sw_hier_begin(sw_engine* h, int hid, int nlevels) {
     h->shifts.clear();
     h->shift_nb = 0;
     h->momenta.clear();
-    h->loop_nb = h->mloop_nb = 0;
+    h->loop_nb = h->mloop_nb = h->link_nb = 0;
     h->tp_momenta.clear();
     h->tp_nb = 0;
     h->lm_k = 0;
@@ -4913,7 +4919,7 @@ int sw_set_loop_momenta(sw_engine* h, int nmom, const int32_t* p) {
   SWCHK(check_hier(h, 0, 0, false));
   if (nmom < 0 || nmom > SW_MAX_MOMENTA)
     return sw_fail(h, "%d momenta: at most %d per registration", nmom, SW_MAX_MOMENTA);
-  h->loop_nb = h->mloop_nb = 0;
+  h->loop_nb = h->mloop_nb = h->link_nb = 0;
   if (nmom == 0) {
     h->momenta.clear();
     return 0;
@@ -5124,6 +5130,75 @@ int sw_hutch_fetch_mlmc_loops(sw_engine* h, double* out) {
   HIPCHK(hipSetDevice(h->device));
   SWCHK(stream_sync(h));
   return fetch_loops(h, true, h->mloop_nb, out);
+}
+
+// ---- point-split link loops: a probe entry at n paired with the solution at n +- mu through the link --------
+// what SW_MODE_HUTCHINSON_LINK_LOOPS and sw_apply_slice_link_dots need beyond a momentum registration: links
+static int link_loops_ready(sw_engine* h) {
+  if (h->momenta.empty()) return sw_fail(h, "no momenta registered (sw_set_loop_momenta)");
+  Level& lv = h->hier[0].lv[0];
+  if (!lv.stencil || !lv.U1 || !lv.U2) return sw_fail(h, "link loops need a lattice level 0 with links (sw_set_lattice)");
+  return 0;
+}
+
+// link[d][p][a][b][t][col], d = (F_x, B_x, F_t, B_t), for the registered momenta from the codes k_probe_codes left
+// in pb_codes (slice_dots of the same probes ran before, or probes != NULL: written here) and Z [n_0][nbp]:
+// k_slice_link_dots, one workgroup per (timeslice, 64 probes, branch), the momenta per pass chosen as slice_dots
+// does.  The buffer is the mode's own; only a completed batch marks it fetchable.
+static int slice_link_dots(sw_engine* h, Level& lv, const int8_t* probes, int nb, const cplx* Z, int nbp) {
+  const int M = (int)h->momenta.size();
+  const int L = lv.L, n = lv.n;
+  SWCHK(ensure_probe_ws(h, nbp));
+  h->link_nb = 0;
+  const size_t need = (size_t)4 * M * 4 * (size_t)L * nbp;
+  if (h->pb_klest_cap < need) {
+    SWCHK(dev_realloc(h, &h->pb_klest, need));
+    h->pb_klest_cap = need;
+  }
+  h->link_nbp = nbp;
+  if (probes)
+    SWCHK(launch(h, T_OTHER, swk::k_probe_codes, dim3((n + 63) / 64, nbp / 64), dim3(SW_BLOCK), probes, nb, n,
+                 (const int*)lv.rowmap, h->pb_codes, nbp));
+  return pick_momenta(h, [&](auto NP, auto PH) {
+    return launch(h, T_LINK_DOTS, swk::k_slice_link_dots<decltype(NP)::value, decltype(PH)::value>,
+                  dim3(L, nbp / 64, 4), dim3(SW_BLOCK), (const int8_t*)h->pb_codes, Z, (const int*)h->slicerow,
+                  (const cplx*)h->loop_phase, (const int*)h->loop_mom, (const cplx*)lv.U1, (const cplx*)lv.U2, L, nbp,
+                  M, 0, h->pb_klest);
+  });
+}
+
+static int fetch_link_loops(sw_engine* h, int nb, double* out) {
+  const size_t rows = 4 * h->momenta.size() * 4 * (size_t)h->hier[0].lv[0].L;
+  HIPCHK(hipMemcpy2D(out, sizeof(cplx) * nb, h->pb_klest, sizeof(cplx) * h->link_nbp, sizeof(cplx) * nb, rows,
+                     hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The kernel alone on host inputs (reference ordering): out[d][p][a][b][t][k] with z_k = Z_k.
+int sw_apply_slice_link_dots(sw_engine* h, int nb, const int8_t* probes, const double* Z, double* out) {
+  SWCHK(check_hier(h, 0, 0, false));
+  if (nb <= 0 || !probes || !Z || !out) return sw_fail(h, "bad arguments");
+  SWCHK(link_loops_ready(h));
+  HIPCHK(hipSetDevice(h->device));
+  Level& lv = h->hier[0].lv[0];
+  const int nbp = pad64(nb);
+  cplx *a, *b;
+  SWCHK(io_vectors(h, lv, nbp, &a, &b));
+  SWCHK(pack_host(h, lv, nb, Z, a, nbp));
+  DevBuf<int8_t> pr(h);
+  SWCHK(upload(h, &pr.p, probes, (size_t)nb * lv.n));
+  SWCHK(slice_link_dots(h, lv, pr, nb, a, nbp));
+  SWCHK(stream_sync(h));
+  return fetch_link_loops(h, nb, out);
+}
+
+int sw_hutch_fetch_link_loops(sw_engine* h, double* out) {
+  if (!h) return 1;
+  if (!out) return sw_fail(h, "null output");
+  if (h->link_nb <= 0 || !h->pb_klest) return sw_fail(h, "no link-loop batch to fetch");
+  HIPCHK(hipSetDevice(h->device));
+  SWCHK(stream_sync(h));
+  return fetch_link_loops(h, h->link_nb, out);
 }
 
 // X (level `level` of hierarchy 0, [n_level][nbp]) prolonged to the lattice level through P_{level-1} ... P_0,
@@ -5470,6 +5545,10 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
     if (level != 0) return sw_fail(h, "timeslice-loop Hutchinson mode runs at level 0");
     if (h->momenta.empty()) return sw_fail(h, "no momenta registered (sw_set_loop_momenta)");
   }
+  if (mode == SW_MODE_HUTCHINSON_LINK_LOOPS) {
+    if (level != 0) return sw_fail(h, "link-loop Hutchinson mode runs at level 0");
+    SWCHK(link_loops_ready(h));
+  }
   const bool lma = mode == SW_MODE_TWO_POINT_LMA;
   if (mode == SW_MODE_TWO_POINT || lma) {
     if (level != 0) return sw_fail(h, "two-point mode runs at level 0");
@@ -5592,6 +5671,25 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
     SWCHK(slice_dots(h, lv, h->pb_probes, nb, h->pb_z, nbp, h->pb_est));
     SWCHK(stream_sync(h));
     h->loop_nb = nb;
+    SWCHK(record_iters(h, &h->hier[fine_hid].lv[0].sws, total, h->last_iters_f, nb));
+    h->last_iters_c.assign(nb, 0);
+    return 0;
+  }
+  if (mode == SW_MODE_HUTCHINSON_LINK_LOOPS) {
+    // SW_MODE_HUTCHINSON_LOOPS' body (its local loops land in its buffer, bit for bit), then the four link
+    // branches of the same z and the same codes into the buffer of this mode
+    const cplx* rhs = h->pb_x0;
+    if (h->kd > 0) {
+      SWCHK(deflate(h, h->U, h->kd, nullptr, h->pb_x0, h->pb_rhs, n, nbp));
+      rhs = h->pb_rhs;
+    }
+    int total = 0;
+    SWCHK(solve_dev(h, fine_hid, 0, rhs, h->pb_z, tol, maxiter, nbp, &total));
+    SWCHK(slice_dots(h, lv, h->pb_probes, nb, h->pb_z, nbp, h->pb_est));
+    SWCHK(slice_link_dots(h, lv, nullptr, nb, h->pb_z, nbp));
+    SWCHK(stream_sync(h));
+    h->loop_nb = nb;
+    h->link_nb = nb;
     SWCHK(record_iters(h, &h->hier[fine_hid].lv[0].sws, total, h->last_iters_f, nb));
     h->last_iters_c.assign(nb, 0);
     return 0;
@@ -5856,7 +5954,8 @@ int sw_timers(sw_engine* h, double t[8]) {
               h->tacc[T_MFMA_OP2] + h->tacc[T_SCHUR] + h->tacc[T_SCHUR_OP];
   t[T_COARSEST] += h->tacc[T_MFMA_DENSE];
   t[T_OTHER] += h->tacc[T_TP_SOURCES];
-  t[T_DOTS] += h->tacc[T_TP_DOTS] + h->tacc[T_SLICE_CDOTS] + h->tacc[T_MESON_FIELD] + h->tacc[T_LM_CONTRACT];
+  t[T_DOTS] += h->tacc[T_TP_DOTS] + h->tacc[T_SLICE_CDOTS] + h->tacc[T_MESON_FIELD] + h->tacc[T_LM_CONTRACT] +
+               h->tacc[T_LINK_DOTS];
   return 0;
 }
 int sw_timers_reset(sw_engine* h) {

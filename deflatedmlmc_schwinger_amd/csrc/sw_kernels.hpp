@@ -3522,6 +3522,128 @@ __global__ __launch_bounds__(SW_BLOCK) void k_slice_total(const cplx* __restrict
   }
 }
 
+// Point-split link loops (SW_MODE_HUTCHINSON_LINK_LOOPS): the probe entry at one end of a link paired with the
+// solution at the other end through the link, per timeslice and momentum.  With n = (x, t) the site that owns the
+// link, n + x^ = ((x + 1) mod L, t), n + t^ = (x, (t + 1) mod L), U_x = U1, U_t = U2 (natural site order t L + x),
+// the four branches d = 0..3 = (F_x, B_x, F_t, B_t) are
+//   F_mu[p][a][b][t] = sum_x e^{-2 pi i p x / L} U_mu(n)       conj(x_k[idx(a,n)])      z_k[idx(b,n+mu)]
+//   B_mu[p][a][b][t] = sum_x e^{-2 pi i p x / L} conj(U_mu(n)) conj(x_k[idx(a,n+mu)])   z_k[idx(b,n)]
+// grid = (L timeslices, nbp / 64, 4 branches); lane = probe.  k_slice_dots' skeleton: the four waves take x = wave,
+// wave + 4, ...; per site a lane reads the two code bytes of the left site and z_0, z_1 of the right site (both
+// through slicerow; the wrap in x or t is one conditional subtraction on a wave-uniform index) and forms
+// conj(code_a) z_b by swap and sign flip.  The link is the same in all lanes (a uniform load); it is folded,
+// conjugated for B, into the momentum's phase once per site and momentum, so the per-lane work is that of
+// k_slice_dots<NP, true>: one complex multiply-add per accumulator.  PHASE = false (only p = 0 registered, NP = 1):
+// no table, the link is the only factor.  The branch is blockIdx.z: every select on it is wave-uniform.  This pass
+// takes the momenta j0 .. j0 + NP - 1 of the nmom registered (mom[] padded to SW_MAX_MOMENTA); the waves combine
+// through LDS in the fixed order w0 + w1 + w2 + w3 and wave 0 writes
+// out[(((d * nmom + j) * 4 + a * 2 + b) * L + t) * nbp + col]: no partials, no atomics, bit-identical between runs.
+template <int NP, bool PHASE = true>
+__global__ __launch_bounds__(SW_BLOCK) void k_slice_link_dots(const int8_t* __restrict__ codes,
+                                                              const cplx* __restrict__ Z,
+                                                              const int* __restrict__ slicerow,
+                                                              const cplx* __restrict__ phase,
+                                                              const int* __restrict__ mom,
+                                                              const cplx* __restrict__ U1,
+                                                              const cplx* __restrict__ U2, int L, int nbp, int nmom,
+                                                              int j0, cplx* __restrict__ out) {
+  constexpr int NA = 4 * NP;
+  __shared__ __attribute__((aligned(16))) cplx tab[PHASE ? SW_SHIFT_MAX_L : 1];
+  __shared__ __attribute__((aligned(16))) cplx red[NA][64];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int t = blockIdx.x, d = blockIdx.z;
+  const bool in_t = d >= 2, back = (d & 1) != 0;
+  const size_t col = (size_t)blockIdx.y * 64 + lane;
+  int idx[NP] = {}, step[NP] = {};
+  if constexpr (PHASE) {
+    for (int i = threadIdx.x; i < L; i += SW_BLOCK) tab[i] = phase[i];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      const int p = mom[j0 + j];            // in [0, L), L <= 1024: the products below stay far inside int
+      idx[j] = (p * wave) % L;
+      step[j] = (p * SW_WAVES_PER_BLOCK) % L;
+    }
+    __syncthreads();
+  }
+  double ar[NA], ai[NA];
+#pragma unroll
+  for (int i = 0; i < NA; ++i) ar[i] = ai[i] = 0.0;
+  const int tn = in_t ? (t + 1 == L ? 0 : t + 1) : t;        // timeslice of n + mu
+  const int dx = in_t ? 0 : 1;
+  const int* __restrict__ sr_own = slicerow + (size_t)t * L * 2;
+  const int* __restrict__ sr_nb = slicerow + (size_t)tn * L * 2;
+  // the codes come from the left site, z from the right one: F = (n, n + mu), B = (n + mu, n)
+  const int* __restrict__ sr_c = back ? sr_nb : sr_own;
+  const int* __restrict__ sr_z = back ? sr_own : sr_nb;
+  const cplx* __restrict__ U = (in_t ? U2 : U1) + (size_t)t * L;
+  const double usign = back ? -1.0 : 1.0;
+#pragma unroll 2
+  for (int x = wave; x < L; x += SW_WAVES_PER_BLOCK) {
+    int xn = x + dx;
+    xn = xn >= L ? xn - L : xn;
+    const int xc = back ? xn : x, xz = back ? x : xn;
+    const size_t c0 = (size_t)sr_c[2 * xc] * nbp + col, c1 = (size_t)sr_c[2 * xc + 1] * nbp + col;
+    const size_t r0 = (size_t)sr_z[2 * xz] * nbp + col, r1 = (size_t)sr_z[2 * xz + 1] * nbp + col;
+    const int c[2] = {(int)codes[c0], (int)codes[c1]};
+    const cplx z[2] = {Z[r0], Z[r1]};
+    const cplx lk = U[x];
+    const cplx u = cmake(lk.x, usign * lk.y);
+    double pr[4], pi[4];                    // conj(code_a) z_b at [a * 2 + b]
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      const bool rot = (c[a] & 1) == 0;     // +-2: multiply by -+i
+      const bool neg = c[a] < 0;
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const double ur = rot ? z[b].y : z[b].x;
+        const double ui = rot ? -z[b].x : z[b].y;
+        pr[a * 2 + b] = neg ? -ur : ur;
+        pi[a * 2 + b] = neg ? -ui : ui;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      cplx w = u;
+      if constexpr (PHASE) {
+        w = cmul(tab[idx[j]], u);
+        idx[j] += step[j];
+        idx[j] = idx[j] >= L ? idx[j] - L : idx[j];
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        ar[j * 4 + q] += w.x * pr[q] - w.y * pi[q];
+        ai[j * 4 + q] += w.x * pi[q] + w.y * pr[q];
+      }
+    }
+  }
+  for (int w = 1; w < SW_WAVES_PER_BLOCK; ++w) {
+    __syncthreads();                        // wave 0 has taken the previous wave's block
+    if (wave == w) {
+#pragma unroll
+      for (int i = 0; i < NA; ++i) red[i][lane] = cmake(ar[i], ai[i]);
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+      for (int i = 0; i < NA; ++i) {
+        const cplx v = red[i][lane];
+        ar[i] += v.x;
+        ai[i] += v.y;
+      }
+    }
+  }
+  if (wave == 0) {
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      if (j0 + j < nmom) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          out[((((size_t)d * nmom + j0 + j) * 4 + q) * L + t) * nbp + col] = cmake(ar[j * 4 + q], ai[j * 4 + q]);
+      }
+    }
+  }
+}
+
 // The slice reduction with a complex left operand (SW_MODE_MLMC_LOOPS, sw_coarsest_loops): out[p][a][b][t][k] =
 // sum_x e^{-2 pi i p x / L} conj(U_k[idx(a,x,t)]) V_k[idx(b,x,t)] for two blocks U, V [row][col] of the lattice
 // level -- the prolonged probe and the prolonged difference of a coarse MLMC level, which are no int8 codes.

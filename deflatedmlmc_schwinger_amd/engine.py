@@ -27,12 +27,14 @@ MODE_MLMC_LOOPS_SKIP = 8
 MODE_MLMC_DEFL_LOOPS = 9
 MODE_MLMC_DEFL_LOOPS_SKIP = 10
 MODE_TWO_POINT_LMA = 11
+MODE_HUTCHINSON_LINK_LOOPS = 12
 # estimator method -> (mode, mode of the level-skipping form at level 0); "mlmc_defl_loops" is "mlmc_loops" deflated
 _METHOD_MODES = {"hutchinson": (MODE_HUTCHINSON, MODE_HUTCHINSON),
                  "mlmc": (MODE_MLMC, MODE_MLMC_SKIP),
                  "level": (MODE_LEVEL, MODE_LEVEL),
                  "shifts": (MODE_HUTCHINSON_SHIFTS, MODE_HUTCHINSON_SHIFTS),
                  "loops": (MODE_HUTCHINSON_LOOPS, MODE_HUTCHINSON_LOOPS),
+                 "link_loops": (MODE_HUTCHINSON_LINK_LOOPS, MODE_HUTCHINSON_LINK_LOOPS),
                  "two_point": (MODE_TWO_POINT, MODE_TWO_POINT),
                  "two_point_lma": (MODE_TWO_POINT_LMA, MODE_TWO_POINT_LMA),
                  "mlmc_loops": (MODE_MLMC_LOOPS, MODE_MLMC_LOOPS_SKIP),
@@ -40,6 +42,7 @@ _METHOD_MODES = {"hutchinson": (MODE_HUTCHINSON, MODE_HUTCHINSON),
 # the modes whose batches leave a resolved result beside the scalar estimates -> the Engine method that fetches it
 RESOLVED_FETCH = {MODE_HUTCHINSON_SHIFTS: "hutch_fetch_shifts",
                   MODE_HUTCHINSON_LOOPS: "hutch_fetch_loops",
+                  MODE_HUTCHINSON_LINK_LOOPS: "hutch_fetch_link_resolved",
                   MODE_TWO_POINT: "hutch_fetch_two_point",
                   MODE_TWO_POINT_LMA: "hutch_fetch_two_point_lma",
                   MODE_MLMC_LOOPS: "hutch_fetch_mlmc_loops",
@@ -63,6 +66,7 @@ KCLASS_TP_DOTS = 18
 KCLASS_SLICE_CDOTS = 19    # ... and of k_slice_cdots (MLMC loops)
 KCLASS_MESON_FIELD = 20    # ... and of k_meson_field (low-mode averaging)
 KCLASS_LM_CONTRACT = 21    # ... and of k_cgemm_nt / k_lm_two_point_reduce (low_mode_two_point)
+KCLASS_LINK_DOTS = 22      # ... and of k_slice_link_dots (link loops)
 MAX_SHIFTS = 128
 MAX_MOMENTA = 8
 # operations of Engine.apply_op32 (SW_OP32_* of the header): one kernel of the complex64 cycle at a time
@@ -228,6 +232,8 @@ def load_library():
     sig("sw_set_low_mode_inverse", i32, vp, i32, vp)
     sig("sw_apply_low_mode", i32, vp, i32, vp, vp)
     sig("sw_hutch_fetch_two_point_lma", i32, vp, vp)
+    sig("sw_hutch_fetch_link_loops", i32, vp, vp)
+    sig("sw_apply_slice_link_dots", i32, vp, i32, vp, vp, vp)
     _lib = lib
     return lib
 
@@ -253,6 +259,7 @@ EXPORTED_SYMBOLS = (
     "sw_set_two_point", "sw_hutch_fetch_two_point", "sw_apply_slice_sources", "sw_apply_pair_dots",
     "sw_apply_slice_cdots", "sw_coarsest_loops", "sw_hutch_fetch_mlmc_loops", "sw_level_deflation_loops",
     "sw_meson_fields", "sw_low_mode_two_point", "sw_set_low_mode_inverse", "sw_apply_low_mode", "sw_hutch_fetch_two_point_lma",
+    "sw_hutch_fetch_link_loops", "sw_apply_slice_link_dots",
 )
 
 
@@ -778,6 +785,40 @@ class Engine:
         out = np.zeros(self._loop_shape(p.shape[0]), dtype=np.complex128)
         self._chk(self._lib.sw_apply_slice_dots(self._h, p.shape[0], _ptr(p), _ptr(Z2), _ptr(out)),
                   "sw_apply_slice_dots")
+        return np.ascontiguousarray(np.moveaxis(out, -1, 0))
+
+    def hutch_batch_link_loops(self, level, probes, tol, maxiter=1000):
+        """One MODE_HUTCHINSON_LINK_LOOPS batch: (link[nb, 4, nmom, 2, 2, L], iters_fine[nb], iters_coarse[nb]), the
+        branches d = (F_x, B_x, F_t, B_t) of every probe:
+        F_mu[k, p, a, b, t] = sum_x e^{-2 pi i p x / L} U_mu(n) conj(x_k[idx(a,n)]) z_k[idx(b,n+mu)],
+        B_mu[k, p, a, b, t] = sum_x e^{-2 pi i p x / L} conj(U_mu(n)) conj(x_k[idx(a,n+mu)]) z_k[idx(b,n)], n = (x, t).
+        hutch_fetch_loops() then returns the local loops of the same batch."""
+        _, itf, itc = self.hutch_batch(MODE_HUTCHINSON_LINK_LOOPS, level, probes, tol, maxiter)
+        self._nb_uploaded = itf.size
+        return self.hutch_fetch_link_loops(), itf, itc
+
+    def hutch_fetch_link_resolved(self):
+        """Everything a MODE_HUTCHINSON_LINK_LOOPS batch resolves, shape (nb, 5, nmom, 2, 2, L): [:, 0] the local
+        loops (hutch_fetch_loops), [:, 1:] the four link branches (hutch_fetch_link_loops)."""
+        return np.concatenate([self.hutch_fetch_loops()[:, None], self.hutch_fetch_link_loops()], axis=1)
+
+    def hutch_fetch_link_loops(self):
+        """Link branches of the last MODE_HUTCHINSON_LINK_LOOPS batch, shape (nb, 4, nmom, 2, 2, L)."""
+        out = np.zeros((4,) + self._loop_shape(getattr(self, "_nb_uploaded", 0)), dtype=np.complex128)
+        self._chk(self._lib.sw_hutch_fetch_link_loops(self._h, _ptr(out)), "sw_hutch_fetch_link_loops")
+        return np.ascontiguousarray(np.moveaxis(out, -1, 0))
+
+    def apply_slice_link_dots(self, probes, Z):
+        """The link-dot kernel alone: out[k, d, p, a, b, t], the four branches of hutch_batch_link_loops with
+        z_k = Z[k], for the registered momenta; probes int8 (nb, n) codes, Z complex (nb, n), both in the reference
+        ordering idx(s,x,y) = s L^2 + y L + x."""
+        p = self._probes(probes)
+        Z2, _ = self._io(Z, self._n(0, 0))
+        if p.shape != Z2.shape:
+            raise EngineError("probes %s and Z %s differ in shape" % (p.shape, Z2.shape))
+        out = np.zeros((4,) + self._loop_shape(p.shape[0]), dtype=np.complex128)
+        self._chk(self._lib.sw_apply_slice_link_dots(self._h, p.shape[0], _ptr(p), _ptr(Z2), _ptr(out)),
+                  "sw_apply_slice_link_dots")
         return np.ascontiguousarray(np.moveaxis(out, -1, 0))
 
     def hutch_batch_mlmc_loops(self, level, probes, tol, maxiter=1000, skip=False, deflated=False):

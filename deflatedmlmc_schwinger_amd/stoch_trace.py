@@ -20,7 +20,7 @@ from .multigrid import MG
 from .utils import (_engines, deflation_pre_computations, displacements_of, draw_probes, flopsV_manual,
                     loops_of, mlmc_defl_setup_of, probe_batch, probe_batch_generated, register_loop_momenta,
                     register_shifts, register_two_point, two_point_of, low_mode_inverse, low_mode_two_point,
-                    register_low_modes, low_mode_contraction_of)
+                    register_low_modes, low_mode_contraction_of, link_loops_of)
 
 DEFAULT_BATCH = 256
 NR_ROUGH_PROBES = 5
@@ -229,8 +229,10 @@ def two_point_columns(T, zero):
     return np.concatenate([T.reshape(T.shape[0], -1), total[:, None]], axis=1)
 
 
-def _setup_solver(A, params, announce=True, defer_coarse=False):
+def _setup_solver(A, params, announce=True, defer_coarse=False, lattice=None):
     mg_solver = MG(A)
+    if lattice is not None:
+        mg_solver._lat = lattice       # hierarchy.detect_lattice(A), which the caller already ran
     if defer_coarse and "defer_coarse_levels" not in params:
         # build-only: the flow uses level 0 only until its work model at the very end (MG.finish_setup)
         params = dict(params, defer_coarse_levels=True)
@@ -360,6 +362,38 @@ class _Loops(_Observable):
         result['converged'] = loop["converged"][:control].reshape(shape)
 
 
+class _LinkLoops(_Loops):
+    """link_loops: per probe the local loops l[p][a][b][t] and the four link branches [d][p][a][b][t] as
+    one array [5][p][a][b][t] (index 0: local), flattened, plus _Loops' control column, the scalar total of the local
+    loops at p = 0, whose series is the plain Hutchinson series."""
+    what = "link loops"
+    method = "link_loops"
+    one_rank = "link loops (link_loops) run on one rank"
+
+    def columns(self, rows):
+        rows = np.asarray(rows, dtype=np.complex128)
+        total = loop_columns(rows[:, 0], self.zero)[:, -1]
+        return np.concatenate([rows.reshape(rows.shape[0], -1), total[:, None]], axis=1)
+
+    def tr1_columns(self, tr1):
+        local, link = tr1
+        self.tr1 = np.concatenate([np.asarray(local, dtype=np.complex128)[None],
+                                   np.asarray(link, dtype=np.complex128)], axis=0)
+        return self.columns(self.tr1[None])[0]
+
+    def fill(self, result, loop, tr1_cols, rough, level_tols):
+        control, shape = rough.size - 1, self.tr1.shape
+        avgs = (loop["avgs"][:control] + tr1_cols[:control]).reshape(shape)
+        devs = loop["devs"][:control].reshape(shape)
+        ests = loop["ests"][:, :control].reshape((-1,) + shape) + self.tr1[None]
+        conv = loop["converged"][:control].reshape(shape)
+        result['momenta'] = list(self.momenta)
+        result['loops'], result['link_loops'] = avgs[0], avgs[1:]
+        result['loop_devs'], result['link_loop_devs'] = devs[0], devs[1:]
+        result['loop_ests'], result['link_loop_ests'] = ests[:, 0], ests[:, 1:]
+        result['converged'], result['link_converged'] = conv[0], conv[1:]
+
+
 class _TwoPoint(_Observable):
     """two_point(): the pair sums T[j][a][b][c][d][t], flattened, plus one control column, the pion total."""
     what = "two-point functions"
@@ -415,14 +449,20 @@ def _estimate_stage(mg_solver, params, n, obs, tr1_cols=None):
 # compute tr(A^{-1}) via (deflated) Hutchinson                      stoch_trace.py:33-179
 def hutchinson(A, params):
     """The build-only keys x_displacements (Tr(A^-1 D_s) at every listed displacement; DESIGN.md, "Displaced
-    traces") and timeslice_loops (the spin- and momentum-resolved loops l[p][a][b][t] of every timeslice; DESIGN.md
-    4c) resolve the estimate, from one deflation projection and one solve per probe: the reference's result keys
-    are then those of the control column, and the stopping rule runs on its series alone."""
+    traces"), timeslice_loops (the spin- and momentum-resolved loops l[p][a][b][t] of every timeslice; DESIGN.md
+    4c) and link_loops (those loops plus the four point-split link branches, from which utils.conserved_current
+    forms the conserved vector current) resolve the estimate, from one deflation projection and one
+    solve per probe: the reference's result keys are then those of the control column, and the stopping rule runs on
+    its series alone."""
     if two_point_of(params) is not None:
         raise Exception("source_timeslice belongs to two_point(), not to hutchinson()")
-    momenta = loops_of(params)
-    displaced = displacements_of(params) if momenta is None else None
-    if momenta is not None:
+    link = link_loops_of(params)
+    momenta = loops_of(params) if link is None else None
+    displaced = displacements_of(params) if momenta is None and link is None else None
+    lattice = None
+    if link is not None:
+        obs = _LinkLoops(link)
+    elif momenta is not None:
         obs = _Loops(momenta)
     elif displaced is not None:
         obs = _Displaced(displaced)
@@ -430,7 +470,13 @@ def hutchinson(A, params):
         obs = _Observable()
     if obs.one_rank and _dist.default_comm().world > 1:
         raise Exception(obs.one_rank)
-    mg_solver, nr_levels = _setup_solver(A, params, defer_coarse=True)
+    if link is not None:
+        # the branches pair sites through the links: the operator has to be the lattice stencil the engine detects
+        from .hierarchy import detect_lattice
+        lattice = A if isinstance(A, tuple) else (None if A is None else detect_lattice(A))
+        if lattice is None:
+            raise Exception("link_loops needs a lattice operator (a U(1) Wilson stencil with its links)")
+    mg_solver, nr_levels = _setup_solver(A, params, defer_coarse=True, lattice=lattice)
     N = A.shape[0]
 
     print("\nResetting timer to zero ...", end='')
@@ -677,6 +723,8 @@ def mlmc(A, params):
     if loops_of(params) is not None:
         raise Exception("timeslice_loops is implemented for hutchinson() only: the MLMC coarse terms need a "
                         "timeslice projection per level (mlmc_loops() has it)")
+    if link_loops_of(params) is not None:
+        raise Exception("link_loops is implemented for hutchinson() only: the MLMC levels have no links")
     if displacements_of(params) is not None:
         raise Exception("x_displacements is implemented for hutchinson() only: the MLMC difference levels "
                         "need their own displaced right-hand sides")
@@ -794,6 +842,8 @@ def _mlmc_loops_checks(params, deflated=False):
         raise Exception("source_timeslice belongs to two_point(), not to %s()" % who)
     if has and params.get('x_displacements') is not None:
         raise Exception("x_displacements does not combine with the MLMC loops")
+    if has and params.get('link_loops') is not None:
+        raise Exception("link_loops is implemented for hutchinson() only: %s() refuses the key" % who)
     momenta = loops_of(params)
     if momenta is None:
         raise Exception("%s() needs the key timeslice_loops" % who)

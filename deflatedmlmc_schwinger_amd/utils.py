@@ -63,7 +63,7 @@ _BUILD_KEYS = ('batch', 'device', 'engines', 'cache_dir', 'report_path', 'probe_
                'solver_restart', 'stochastic_coarsest', 'stop_factor', 'ref_direct_max_n', 'ref_coarsest',
                'ref_coarse_dofs', 'setup_eigs', 'defer_coarse_levels',
                'verbose', 'probe_rounds_max', 'mlmc_defl_setup', 'defl_setup', 'x_displacements',
-               'timeslice_loops', 'source_timeslice', 'two_point_momenta', 'low_mode_contraction')
+               'timeslice_loops', 'source_timeslice', 'two_point_momenta', 'low_mode_contraction', 'link_loops')
 # where the eigenpairs of the MLMC difference operators come from: host ARPACK (the reference's path) or
 # the block eigensolver on the GPU (setup_gpu.device_diff_eigenpairs)
 MLMC_DEFL_SETUPS = ("host", "device")
@@ -171,6 +171,113 @@ def loops_of(params):
     if 0 not in momenta:
         raise Exception("timeslice_loops has to contain the momentum 0 (its scalar total is the control series)")
     return momenta
+
+
+def link_loops_of(params):
+    """The build-only key link_loops: None when absent, else the validated list of spatial momenta p of the
+    point-split link loops, checked exactly as timeslice_loops: integers in [0, L), L = latt_dims[0], no
+    duplicates, at most MAX_MOMENTA, 0 among them (the scalar total of the local loops at p = 0 is the control
+    series).  The key combines with neither x_displacements, timeslice_loops, source_timeslice nor
+    two_point_momenta -- the local loops are part of its result anyway."""
+    if not hasattr(params, "get") or params.get('link_loops') is None:
+        return None
+    for other in ('x_displacements', 'timeslice_loops', 'source_timeslice', 'two_point_momenta'):
+        if params.get(other) is not None:
+            raise Exception("link_loops does not combine with %s" % other)
+    L = int(params['latt_dims'][0])
+    momenta = []
+    for p in params['link_loops']:
+        if isinstance(p, bool) or int(p) != p:
+            raise Exception("link_loops: %r is not an integer" % (p,))
+        p = int(p)
+        if not 0 <= p < L:
+            raise Exception("link_loops: momentum %d outside [0, %d)" % (p, L))
+        if p in momenta:
+            raise Exception("link_loops: momentum %d listed twice" % p)
+        momenta.append(p)
+    if len(momenta) > MAX_MOMENTA:
+        raise Exception("link_loops: %d momenta, at most %d" % (len(momenta), MAX_MOMENTA))
+    if 0 not in momenta:
+        raise Exception("link_loops has to contain the momentum 0 (its scalar total is the control series)")
+    return momenta
+
+
+LINK_BRANCHES = ('Fx', 'Bx', 'Ft', 'Bt')
+
+
+def slice_link_dots(X, Z, U1, U2, L, momenta):
+    """The four link branches d = (F_x, B_x, F_t, B_t) for a batch, out[k, d, p, a, b, t]:
+
+        F_mu = sum_x e^{-2 pi i p x / L} U_mu(n)       conj(X[k, idx(a,n)])    Z[k, idx(b,n+mu)]
+        B_mu = sum_x e^{-2 pi i p x / L} conj(U_mu(n)) conj(X[k, idx(a,n+mu)]) Z[k, idx(b,n)]
+
+    with n = (x, t) the site that owns the link (its phase, its timeslice), n + x^ = ((x+1) mod L, t), n + t^ =
+    (x, (t+1) mod L), idx(s,x,y) = s L^2 + y L + x and U_x = U1, U_t = U2 in natural site order t L + x.  X, Z:
+    complex arrays (nb, 2 L^2) (probes as the vectors they stand for: probes_as_complex); phases as the engine's
+    table -- the reduction of MODE_HUTCHINSON_LINK_LOOPS, what Engine.apply_slice_link_dots computes."""
+    X = np.atleast_2d(np.asarray(X))
+    Z = np.atleast_2d(np.asarray(Z))
+    if X.shape != Z.shape or X.shape[1] != 2 * L * L:
+        raise Exception("slice_link_dots: X %s and Z %s, expected two equal (nb, %d)" % (X.shape, Z.shape, 2 * L * L))
+    U = [np.asarray(u, dtype=np.complex128).reshape(-1) for u in (U1, U2)]
+    if any(u.size != L * L for u in U):
+        raise Exception("slice_link_dots: links of %d and %d entries, expected %d each" % (U[0].size, U[1].size, L * L))
+    ph = _phase_table(L)[np.outer(np.asarray(momenta, dtype=np.int64), np.arange(L)) % L]
+    Xc, Zr = X.reshape(-1, 2, L, L).conj(), Z.reshape(-1, 2, L, L)         # [k][s][t][x]
+    out = np.empty((X.shape[0], 4, len(momenta), 2, 2, L), dtype=np.complex128)
+    for mu, axis in enumerate((3, 2)):                                    # n + mu: one step along x / along t
+        u = U[mu].reshape(L, L)                                           # [t][x]
+        fwd = u * Xc[:, :, None] * np.roll(Zr, -1, axis=axis)[:, None]    # [k][a][b][t][x]
+        bwd = u.conj() * np.roll(Xc, -1, axis=axis)[:, :, None] * Zr[:, None]
+        out[:, 2 * mu] = np.moveaxis(fwd @ ph.T, -1, 1)
+        out[:, 2 * mu + 1] = np.moveaxis(bwd @ ph.T, -1, 1)
+    return out
+
+
+def link_sliced_tr1(Vx, Sy, g3, U1, U2, L, momenta):
+    """The deflated part of the link loops, shape (4, nmom, 2, 2, L): the four branches of slice_link_dots with
+    sum_i v_i w_i^H / |lambda_i| = A^-1 W W^H in place of A^-1 (I - W W^H), (lambda_i, v_i) eigenpairs of gamma_3 A
+    (Sy, columns of Vx), w_i = gamma_3 v_i sgn(lambda_i) -- as sliced_tr1.  g3: the diagonal of gamma_3, or a (sparse)
+    matrix."""
+    Vx = np.asarray(Vx, dtype=np.complex128)
+    Sy = np.asarray(Sy, dtype=float)
+    if Vx.shape[0] != 2 * L * L:
+        raise Exception("link_sliced_tr1: vectors of length %d, expected %d" % (Vx.shape[0], 2 * L * L))
+    W = (np.asarray(g3)[:, None] * Vx if np.ndim(g3) == 1 else np.asarray(g3 * Vx)) * np.sign(Sy)[None, :]
+    return slice_link_dots(W.T, (Vx / np.abs(Sy)[None, :]).T, U1, U2, L, momenta).sum(axis=0)
+
+
+def _link_branch(link, branch, who):
+    link = np.asarray(link)
+    if link.ndim < 5 or link.shape[-5] != 4 or link.shape[-3:-1] != (2, 2):
+        raise Exception("%s: link loops of shape %s, expected (..., 4, nmom, 2, 2, L)" % (who, link.shape))
+    if branch not in LINK_BRANCHES:
+        raise Exception("%s: unknown branch %r (one of %s)" % (who, branch, list(LINK_BRANCHES)))
+    return link[..., LINK_BRANCHES.index(branch), :, :, :, :]
+
+
+def link_loop_gamma(link, branch, which):
+    """sum_ab Gamma[a][b] link[..., d, :, a, b, :] of one branch d = 'Fx', 'Bx', 'Ft' or 'Bt' of the link loops
+    (..., 4, nmom, 2, 2, L), Gamma = '1', 'g3', 's1' or 's2' as loop_gamma: shape (..., nmom, L)."""
+    if which not in _PAULI:
+        raise Exception("link_loop_gamma: unknown spin matrix %r (one of %s)" % (which, sorted(_PAULI)))
+    return loop_gamma(_link_branch(link, branch, "link_loop_gamma"), which)
+
+
+def conserved_current(link, mu):
+    """The conserved (point-split) vector current per timeslice and momentum from the link loops (..., 4, nmom, 2, 2, L):
+
+        J_mu(t, p) = sum_ab ( H+_mu[a][b] F_mu[p][a][b][t] - H-_mu[a][b] B_mu[p][a][b][t] ),    mu = 'x' or 't',
+
+    H+-_mu = 1 -+ sigma_mu the hop matrices of the operator (hierarchy._HOP, no 1/2); shape (..., nmom, L).  For the
+    exact inverse it obeys (1 - e^{-2 pi i p / L}) J_x(t, p) + J_t(t, p) - J_t(t - 1, p) = 0 on every configuration."""
+    from .hierarchy import _HOP
+    if mu not in ('x', 't'):
+        raise Exception("conserved_current: unknown direction %r (one of ['t', 'x'])" % (mu,))
+    F = _link_branch(link, 'F' + mu, "conserved_current")
+    B = _link_branch(link, 'B' + mu, "conserved_current")
+    hp, hm = _HOP["+x" if mu == 'x' else "+y"], _HOP["-x" if mu == 'x' else "-y"]
+    return sum(hp[a, b] * F[..., a, b, :] - hm[a, b] * B[..., a, b, :] for a in range(2) for b in range(2))
 
 
 def slice_phases(L, momenta):
@@ -646,10 +753,12 @@ def deflation_pre_computations(A, nr_deflat_vctrs, tolx, method, timer, params, 
             for eng in _engines(mg_solver):
                 eng.set_deflation(None)
             disp = displacements_of(params)
-            momenta = loops_of(params)
+            link = link_loops_of(params)
+            momenta = loops_of(params) if link is None else link
             if momenta is not None:
                 L = int(params['latt_dims'][0])
-                return (None, np.zeros((len(momenta), 2, 2, L), dtype=np.complex128))
+                zero = np.zeros((len(momenta), 2, 2, L), dtype=np.complex128)
+                return (None, zero if link is None else (zero, np.zeros((4,) + zero.shape, dtype=np.complex128)))
             return (None, 0.0 if disp is None else np.zeros(len(disp[0]), dtype=np.complex128))
         for eng in _engines(mg_solver):
             eng.set_level_deflation(level_nr, None)
@@ -657,7 +766,8 @@ def deflation_pre_computations(A, nr_deflat_vctrs, tolx, method, timer, params, 
 
     lev0 = mg_solver.ml.levels[0]
     displaced = displacements_of(params) if method == "hutchinson" else None
-    momenta = loops_of(params) if method == "hutchinson" else None
+    link = link_loops_of(params) if method == "hutchinson" else None
+    momenta = (loops_of(params) if link is None else link) if method == "hutchinson" else None
     if method == "hutchinson":
         pre = params.get("deflation_eigenpairs") if hasattr(params, "get") else None
         how = defl_setup_of(params)
@@ -729,6 +839,14 @@ def deflation_pre_computations(A, nr_deflat_vctrs, tolx, method, timer, params, 
             mg_solver.solve_tol = params['function_params']['tol']
             for eng in _engines(mg_solver):
                 eng.set_deflation(np.asarray(Ux))
+            if link is not None:
+                # the link loops project as the timeslice loops do; tr1 = (the local array, the four link branches)
+                lat = getattr(mg_solver, "lattice", None)
+                if lat is None:
+                    raise Exception("link_loops needs a lattice operator (the links of hierarchy.detect_lattice)")
+                L = int(lat[0])
+                return (Ux, (sliced_tr1(Vx, Sy, lev0.g3, L, link),
+                             link_sliced_tr1(Vx, Sy, lev0.g3, lat[2], lat[3], L, link)))
             if momenta is not None:
                 return (Ux, sliced_tr1(Vx, Sy, lev0.g3, int(params['latt_dims'][0]), momenta))
             return (Ux, displaced_tr1(Vx, Sy, lev0.g3, Vx.shape[0], displaced[1]))
@@ -818,6 +936,8 @@ def probe_batch(mg_solver, params, method, probes, level=0, deflated=False):
     one row per probe from one projection and one solve per probe, on the first engine handle:
     shifts    : ests[nb, S], e[k, j] = (D_{s_j}^T x_k)^H A^-1 (x_k - W W^H x_k) at every registered shift
     loops     : loops[nb, nmom, 2, 2, L] (MODE_HUTCHINSON_LOOPS)
+    link_loops: rows[nb, 5, nmom, 2, 2, L] (MODE_HUTCHINSON_LINK_LOOPS): [:, 0] the local loops, [:, 1:] the four
+                link branches (F_x, B_x, F_t, B_t)
     mlmc_loops: loops[nb, nmom, 2, 2, L], the term of `level` (MODE_MLMC_LOOPS, _SKIP at level 0 with
                 mg_solver.skip_level; deflated: MODE_MLMC_DEFL_LOOPS / _SKIP, the level's registered projection)
     two_point : T[nb, nmom, 2, 2, 2, 2, L], the probes being the noises: 2 nmom solves per noise, no deflation;

@@ -310,6 +310,10 @@ int sw_apply_shift_dots(sw_engine* h, int nb, const int8_t* probes, const double
  * conj(x_k[idx(a,x,t)]) Z_k[idx(b,x,t)] for the registered momenta, idx(s,x,y) = s L^2 + y L + x; probes
  * int8[nb*n] (codes +-1, +-2 = +-i), Z complex128[nb*n], out complex128[nmom*2*2*L*nb]. */
 int sw_apply_slice_dots(sw_engine* h, int nb, const int8_t* probes, const double* Z, double* out);
+/* The link-dot kernel of SW_MODE_HUTCHINSON_LINK_LOOPS alone: out[d][p][a][b][t][k], the four branches of that mode
+ * with z_k = Z_k, for the registered momenta; probes int8[nb*n], Z complex128[nb*n], out complex128[4*nmom*2*2*L*nb].
+ * The refusals of the mode. */
+int sw_apply_slice_link_dots(sw_engine* h, int nb, const int8_t* probes, const double* Z, double* out);
 /* The slice-dot kernel with a complex left operand (SW_MODE_MLMC_LOOPS on coarse levels, sw_coarsest_loops) alone:
  * out[p][a][b][t][k] = sum_x e^{-2 pi i p x / L} conj(U_k[idx(a,x,t)]) V_k[idx(b,x,t)] for the registered momenta;
  * U, V complex128[nb*n] of the lattice level, out complex128[nmom*2*2*L*nb]. */
@@ -461,6 +465,16 @@ int sw_solve(sw_engine* h, int hid, int level0, int nb, const double* B, double*
                                   SW_MODE_TWO_POINT batch); sw_hutch_fetch returns sum_t sum_ac R[j0][a][a][c][c][t] and
                                   the iteration counts of SW_MODE_TWO_POINT.  With G = 0 the batch equals the
                                   SW_MODE_TWO_POINT batch bit for bit. */
+#define SW_MODE_HUTCHINSON_LINK_LOOPS 12 /* SW_MODE_HUTCHINSON_LOOPS plus the point-split link loops, level 0 (build-only):
+                                  projection, solve and local loops exactly as mode 5 -- sw_hutch_fetch and
+                                  sw_hutch_fetch_loops return what a mode-5 batch on the same probes returns, bit for
+                                  bit -- and, from the same z_k and codes, the four link branches d = (F_x, B_x, F_t, B_t)
+                                  F_mu,k[p][a][b][t] = sum_x e^{-2 pi i p x / L} U_mu(n) conj(x_k[idx(a,n)]) z_k[idx(b,n+mu)],
+                                  B_mu,k[p][a][b][t] = sum_x e^{-2 pi i p x / L} conj(U_mu(n)) conj(x_k[idx(a,n+mu)]) z_k[idx(b,n)],
+                                  n = (x,t) the site that owns the link, n+x^ = ((x+1) mod L, t), n+t^ = (x, (t+1) mod L),
+                                  U_x = U1, U_t = U2 of sw_set_lattice, for the momenta of sw_set_loop_momenta.  A
+                                  buffer of its own (sw_hutch_fetch_link_loops).  Refused at a level other than 0,
+                                  without momenta and when level 0 is no lattice level with links. */
 /* One batch of probes x_k in {-1,+1}^n (int8, nb*n, reference ordering) at `level`
  * (build-only extension: entries +-2 encode +-i, i.e. Z4 probes {1,i,-1,-i}):
  *   HUTCHINSON: e_k = x^H A^-1 Pperm^T (x - U U^H x)
@@ -502,6 +516,10 @@ int sw_hutch_fetch_loops(sw_engine* h, double* out);
 /* After a SW_MODE_MLMC_LOOPS / _SKIP batch: out complex128[nmom][2][2][L][nb], the level loops of every probe of the
  * batch (a buffer of its own: sw_hutch_fetch_loops keeps returning the last SW_MODE_HUTCHINSON_LOOPS batch). */
 int sw_hutch_fetch_mlmc_loops(sw_engine* h, double* out);
+/* After a SW_MODE_HUTCHINSON_LINK_LOOPS batch: out complex128[4][nmom][2][2][L][nb], the link branches
+ * F/B_k[d][p][a][b][t] of every probe of the batch (a buffer of its own: batches of other modes leave it intact, and
+ * sw_hutch_fetch_loops returns the local loops of the same batch). */
+int sw_hutch_fetch_link_loops(sw_engine* h, double* out);
 /* After a SW_MODE_TWO_POINT batch: out complex128[nmom][2][2][2][2][L][nb], the pair sums T_k[j][a][b][c][d][t] of
  * every noise k of the batch.  The results of the modes 4, 5 and 6 live in buffers of their own: each fetch
  * returns its own mode's last batch whatever ran since. */
@@ -548,6 +566,7 @@ int sw_timers_reset(sw_engine* h);
                                        8 * 4 * L^2 * ld^2 flops per launch, ld = the rank rounded up to 16 */
 #define SW_KCLASS_LM_CONTRACT 21    /* k_cgemm_nt, k_lm_two_point_reduce (sw_low_mode_two_point); in sw_timers: dots;
                                        sw_kernel_work counts 8 * (2 * 4L * ld^3 + (4L)^2 * k^2) flops per call */
+#define SW_KCLASS_LINK_DOTS 22      /* k_slice_link_dots (SW_MODE_HUTCHINSON_LINK_LOOPS); in sw_timers: dots */
 int sw_kernel_stats(sw_engine* h, int which, double* total_ms, int64_t* launches);
 /* Floating-point operations issued by the launches of an MFMA kernel class since the last reset
  * (profiling on): 8 flops per complex multiply-add over every (row tile, k-step, probe). */
