@@ -67,9 +67,11 @@ enum TimerCat { T_MVM = 0, T_DEFL, T_P, T_R, T_AXPY, T_DOTS, T_COARSEST, T_OTHER
                 T_MESON_FIELD,  // k_meson_field of sw_meson_fields / sw_low_mode_two_point
                 T_LM_CONTRACT,  // k_cgemm_nt / k_lm_two_point_reduce of sw_low_mode_two_point
                 T_LINK_DOTS,    // k_slice_link_dots of SW_MODE_HUTCHINSON_LINK_LOOPS
+                T_3PT_SOURCES,  // k_seq_sources / k_pair_slice_total of SW_MODE_THREE_POINT
+                T_3PT_DOTS,     // k_slice_seq_dots of SW_MODE_THREE_POINT
                 T_NCAT };
-// classes >= T_STENCIL are folded into the mvm / coarsest (two-point: other / dots; slice cdots, meson fields,
-// their contraction and the link dots: dots) buckets by
+// classes >= T_STENCIL are folded into the mvm / coarsest (two-point and three-point: other / dots; slice cdots,
+// meson fields, their contraction and the link dots: dots) buckets by
 // sw_timers and reported separately by sw_kernel_stats
 
 struct EllOp {
@@ -367,6 +369,20 @@ struct sw_engine {
   cplx *lma_est = nullptr, *lma_tmp = nullptr;
   size_t lma_est_cap = 0, lma_tmp_cap = 0;
   int lma_nb = 0, lma_nq = 0;
+  // three-point functions (sw_set_three_point, SW_MODE_THREE_POINT): a registration of its own (source and sink
+  // timeslice, sink spin matrix and momentum, insertion momenta; t3_jz = the index of momentum 0 or -1; t3_mom0 =
+  // a zero momentum table for the stage-1 sources), three blocks [n][2 nq] -- the sources of either stage, z and
+  // zeta -- and the sums S[branch][momentum][a][b][f][c][t][noise]
+  std::vector<int32_t> t3_momenta;
+  int t3_t0 = 0, t3_tf = 0, t3_gamma = 0, t3_pf = 0, t3_jz = -1;
+  int *t3_mom = nullptr, *t3_mom0 = nullptr;
+  cplx* t3_phase = nullptr;
+  int* t3_slicerow = nullptr;
+  cplx *t3_rhs = nullptr, *t3_z = nullptr, *t3_zeta = nullptr;
+  size_t t3_ws_cap = 0;
+  cplx* t3_est = nullptr;
+  size_t t3_est_cap = 0;
+  int t3_nb = 0, t3_nq = 0;        // noises and row stride of the last three-point batch (0: nothing to fetch)
   std::vector<int32_t> last_iters_f, last_iters_c;
   // profiling
   bool profiling = false;
@@ -2591,6 +2607,8 @@ int sw_hier_begin(sw_engine* h, int hid, int nlevels) {
     h->tp_nb = 0;
     h->lm_k = 0;
     h->lma_nb = 0;
+    h->t3_momenta.clear();
+    h->t3_nb = 0;
   }
   return 0;
 }
@@ -5533,6 +5551,164 @@ int sw_hutch_fetch_two_point_lma(sw_engine* h, double* out) {
   return fetch_pair_sums(h, h->lma_est, h->lma_nq, h->lma_nb, out);
 }
 
+// ---- three-point functions: sequential one-end-trick solves and a local or point-split insertion ---------
+// (g3 Gf g3)^H for Gf = 1, g3, s1, s2 as k_seq_sources takes it: bit 0 = the rows select the other spin, bits 1-2 /
+// 3-4 = the entry of row 0 / row 1 as a power of i:  1, diag(1,-1), -s1, -s2 = [[0, i], [-i, 0]]
+static const int kSeqGammaCode[4] = {0, 2 << 3, 1 | (2 << 1) | (2 << 3), 1 | (1 << 1) | (3 << 3)};
+
+int sw_set_three_point(sw_engine* h, int t0, int tf, int sink_gamma, int pf, int nmom, const int32_t* q) {
+  SWCHK(check_hier(h, 0, 0, false));
+  if (nmom < 0 || nmom > SW_MAX_MOMENTA)
+    return sw_fail(h, "%d momenta: at most %d per registration", nmom, SW_MAX_MOMENTA);
+  h->t3_nb = 0;
+  if (nmom == 0) {
+    h->t3_momenta.clear();
+    return 0;
+  }
+  SWCHK(check_momenta(h, "three-point functions", nmom, q));
+  Level& lv = h->hier[0].lv[0];
+  const int L = lv.L;
+  if (!lv.U1 || !lv.U2) return sw_fail(h, "three-point functions need a lattice level 0 with links (sw_set_lattice)");
+  if (t0 < 0 || t0 >= L) return sw_fail(h, "source timeslice %d outside [0,%d)", t0, L);
+  if (tf < 0 || tf >= L) return sw_fail(h, "sink timeslice %d outside [0,%d)", tf, L);
+  if (tf == t0) return sw_fail(h, "sink timeslice %d equals the source timeslice", tf);
+  if (pf < 0 || pf >= L) return sw_fail(h, "sink momentum %d outside [0,%d)", pf, L);
+  if (sink_gamma < 0 || sink_gamma > 3) return sw_fail(h, "unknown sink spin matrix code %d (0..3 = 1, g3, s1, s2)", sink_gamma);
+  HIPCHK(hipSetDevice(h->device));
+  SWCHK(stream_sync(h));
+  SWCHK(upload_slice_tables(h, nmom, q, &h->t3_mom, &h->t3_phase, &h->t3_slicerow));
+  const std::vector<int> zero(SW_MAX_MOMENTA, 0);
+  SWCHK(upload(h, &h->t3_mom0, zero.data(), zero.size()));
+  h->t3_momenta.assign(q, q + nmom);
+  h->t3_t0 = t0;
+  h->t3_tf = tf;
+  h->t3_gamma = sink_gamma;
+  h->t3_pf = pf;
+  h->t3_jz = -1;
+  for (int j = 0; j < nmom; ++j)
+    if (q[j] == 0) h->t3_jz = j;
+  return 0;
+}
+
+// what SW_MODE_THREE_POINT and its stateless entries need: a registration on a lattice level 0 with links
+static int three_point_ready(sw_engine* h) {
+  if (h->t3_momenta.empty()) return sw_fail(h, "no three-point registration (sw_set_three_point)");
+  Level& lv = h->hier[0].lv[0];
+  if (!lv.stencil || !lv.U1 || !lv.U2)
+    return sw_fail(h, "three-point functions need a lattice level 0 with links (sw_set_lattice)");
+  return 0;
+}
+
+// the three blocks [n][2 nq] of a three-point batch: sources (either stage), z, zeta
+static int ensure_three_point_ws(sw_engine* h, size_t cnt) {
+  if (h->t3_ws_cap >= cnt && h->t3_rhs) return 0;
+  SWCHK(dev_realloc(h, &h->t3_rhs, cnt));
+  SWCHK(dev_realloc(h, &h->t3_z, cnt));
+  SWCHK(dev_realloc(h, &h->t3_zeta, cnt));
+  h->t3_ws_cap = cnt;
+  return 0;
+}
+
+// S = the sequential sources of Z [n][2 nq] through the registered sink; total (optional) = c_k of Z
+static int seq_sources(sw_engine* h, Level& lv, const cplx* Z, int nb, int nq, cplx* S, cplx* total) {
+  SWCHK(launch(h, T_3PT_SOURCES, swk::k_seq_sources, dim3((lv.n + 15) / 16, 2 * nq / 64), dim3(SW_BLOCK), Z, nb, lv.n,
+               (const int*)lv.rowmap, (const int*)h->t3_slicerow, (const cplx*)h->t3_phase, lv.L, h->t3_tf, h->t3_pf,
+               kSeqGammaCode[h->t3_gamma], nq, S));
+  if (!total) return 0;
+  return launch(h, T_3PT_SOURCES, swk::k_pair_slice_total, dim3(nq / 64), dim3(SW_BLOCK), Z,
+                (const int*)h->t3_slicerow, lv.L, h->t3_tf, nq, total);
+}
+
+// t3_est[d][j][a][b][f][c][t][k] from Zeta and Z [n][2 nq]: the table-free instantiation for a registered momentum
+// 0, the phased one over the others
+static int seq_dots(sw_engine* h, Level& lv, const cplx* Zeta, const cplx* Z, int nq) {
+  const int M = (int)h->t3_momenta.size(), L = lv.L, jz = h->t3_jz;
+  h->t3_nb = 0;   // t3_est is rewritten: only a completed three-point batch sets it again
+  h->t3_nq = nq;
+  const size_t need = (size_t)5 * M * 16 * L * nq;
+  if (h->t3_est_cap < need) {
+    SWCHK(dev_realloc(h, &h->t3_est, need));
+    h->t3_est_cap = need;
+  }
+  if (jz >= 0)
+    SWCHK(launch(h, T_3PT_DOTS, swk::k_slice_seq_dots<false>, dim3(L, nq / 64, 5), dim3(SW_BLOCK), Zeta, Z,
+                 (const int*)h->t3_slicerow, (const cplx*)h->t3_phase, (const int*)h->t3_mom, (const cplx*)lv.U1,
+                 (const cplx*)lv.U2, jz, 1, M, L, nq, h->t3_est));
+  const int nz = M - (jz >= 0 ? 1 : 0);
+  if (nz > 0)
+    SWCHK(launch(h, T_3PT_DOTS, swk::k_slice_seq_dots<true>, dim3(L, nq / 64, 5 * nz), dim3(SW_BLOCK), Zeta, Z,
+                 (const int*)h->t3_slicerow, (const cplx*)h->t3_phase, (const int*)h->t3_mom, (const cplx*)lv.U1,
+                 (const cplx*)lv.U2, jz, nz, M, L, nq, h->t3_est));
+  return 0;
+}
+
+static int fetch_three_point(sw_engine* h, int nb, double* out) {
+  const size_t rows = 5 * h->t3_momenta.size() * 16 * (size_t)h->hier[0].lv[0].L;
+  HIPCHK(hipMemcpy2D(out, sizeof(cplx) * nb, h->t3_est, sizeof(cplx) * h->t3_nq, sizeof(cplx) * nb, rows,
+                     hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// host vectors [2][nb][n] (reference ordering) <-> a block [n][2 nq]
+static int pack_pair(sw_engine* h, Level& lv, int nb, int nq, const double* X, cplx* dst) {
+  const size_t per = (size_t)nb * lv.n;
+  SWCHK(ensure_stage(h, per * 2 * sizeof(cplx)));
+  HIPCHK(hipMemcpyAsync(h->stage, X, per * 2 * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
+  for (int g = 0; g < 2; ++g)
+    SWCHK(launch(h, T_OTHER, swk::k_pack_c, dim3((lv.n + 63) / 64, nq / 64), dim3(SW_BLOCK),
+                 (const cplx*)h->stage + (size_t)g * per, nb, lv.n, (const int*)lv.rowmap, dst + (size_t)g * nq,
+                 2 * nq));
+  return stream_sync(h);   // the stage is free for the next block
+}
+
+static int three_point_args(sw_engine* h, int nb, const void* a, const void* b, const void* out) {
+  SWCHK(check_hier(h, 0, 0, false));
+  SWCHK(three_point_ready(h));
+  if (nb <= 0 || !a || !b || !out) return sw_fail(h, "bad arguments");
+  return 0;
+}
+
+// k_seq_sources alone on host solutions Z[a][k][n] (reference ordering): out[a][k][n] = s_k^a.
+int sw_apply_seq_sources(sw_engine* h, int nb, const double* Z, double* out) {
+  SWCHK(three_point_args(h, nb, Z, Z, out));
+  HIPCHK(hipSetDevice(h->device));
+  Level& lv = h->hier[0].lv[0];
+  const int nq = pad64(nb);
+  SWCHK(ensure_three_point_ws(h, (size_t)lv.n * 2 * nq));
+  SWCHK(pack_pair(h, lv, nb, nq, Z, h->t3_z));
+  SWCHK(seq_sources(h, lv, h->t3_z, nb, nq, h->t3_rhs, nullptr));
+  const size_t per = (size_t)nb * lv.n;
+  for (int g = 0; g < 2; ++g)
+    SWCHK(launch(h, T_OTHER, swk::k_unpack_c, dim3((lv.n + 63) / 64, nq / 64), dim3(SW_BLOCK),
+                 (const cplx*)(h->t3_rhs + (size_t)g * nq), 2 * nq, lv.n, (const int*)lv.rowmap,
+                 (cplx*)h->stage + (size_t)g * per, nb));
+  HIPCHK(hipMemcpyAsync(out, h->stage, per * 2 * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
+  return stream_sync(h);
+}
+
+// k_slice_seq_dots alone on host fields Zeta, Z [a][k][n] (reference ordering): out[d][j][a][b][f][c][t][k].
+int sw_apply_seq_dots(sw_engine* h, int nb, const double* Zeta, const double* Z, double* out) {
+  SWCHK(three_point_args(h, nb, Zeta, Z, out));
+  HIPCHK(hipSetDevice(h->device));
+  Level& lv = h->hier[0].lv[0];
+  const int nq = pad64(nb);
+  SWCHK(ensure_three_point_ws(h, (size_t)lv.n * 2 * nq));
+  SWCHK(pack_pair(h, lv, nb, nq, Zeta, h->t3_zeta));
+  SWCHK(pack_pair(h, lv, nb, nq, Z, h->t3_z));
+  SWCHK(seq_dots(h, lv, h->t3_zeta, h->t3_z, nq));
+  SWCHK(stream_sync(h));
+  return fetch_three_point(h, nb, out);
+}
+
+int sw_hutch_fetch_three_point(sw_engine* h, double* out) {
+  if (!h) return 1;
+  if (!out) return sw_fail(h, "null output");
+  if (h->t3_nb <= 0 || !h->t3_est) return sw_fail(h, "no three-point batch to fetch");
+  HIPCHK(hipSetDevice(h->device));
+  SWCHK(stream_sync(h));
+  return fetch_three_point(h, h->t3_nb, out);
+}
+
 int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
   SWCHK(check_hier(h, 0, level, true));
   if (h->pb_level != level || h->pb_nb <= 0) return sw_fail(h, "no probes uploaded for level %d", level);
@@ -5554,6 +5730,10 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
     if (level != 0) return sw_fail(h, "two-point mode runs at level 0");
     if (h->tp_momenta.empty()) return sw_fail(h, "no two-point registration (sw_set_two_point)");
     if (lma) SWCHK(low_mode_ready(h));
+  }
+  if (mode == SW_MODE_THREE_POINT) {
+    if (level != 0) return sw_fail(h, "three-point mode runs at level 0");
+    SWCHK(three_point_ready(h));
   }
   // the deflated level loops: modes 7 / 8 with the level's registered projection on the right-hand side
   const bool dloops = (mode == SW_MODE_MLMC_DEFL_LOOPS || mode == SW_MODE_MLMC_DEFL_LOOPS_SKIP);
@@ -5612,6 +5792,34 @@ int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
     h->last_iters_f.assign(nb, 0);
     for (int g = 0; g < G; ++g)
       for (int k = 0; k < nb; ++k) h->last_iters_f[k] = std::max(h->last_iters_f[k], all[(size_t)g * nbp + k]);
+    h->last_iters_c.assign(nb, 0);
+    return 0;
+  }
+  if (mode == SW_MODE_THREE_POINT) {
+    // stage 1: the two spin sources of every noise at momentum 0 and their solutions z (no deflation); stage 2: the
+    // sequential sources through the sink, written over the stage-1 sources, and their solutions zeta to the same
+    // tol; then the field x field sums of zeta and z.  pb_est = c_k, the pion two-point value at the sink slice.
+    const int ncols = 2 * nbp;
+    SWCHK(ensure_three_point_ws(h, (size_t)n * ncols));
+    h->t3_nb = 0;
+    SWCHK(launch(h, T_3PT_SOURCES, swk::k_slice_sources, dim3((n + 15) / 16, ncols / 64), dim3(SW_BLOCK),
+                 (const int8_t*)h->pb_probes, nb, n, (const int*)lv.rowmap, (const cplx*)h->t3_phase,
+                 (const int*)h->t3_mom0, lv.L, h->t3_t0, nbp, ncols, h->t3_rhs));
+    const int hid = h->hier[h->solver_hid].ready ? h->solver_hid : 0;
+    if (hid != 0 && h->hier[hid].lv[0].n != n) return sw_fail(h, "solver hierarchy level-0 size mismatch");
+    // iterations of a noise = the largest count among its two columns, stage 1 plus stage 2
+    std::vector<int32_t> all, sum(nb, 0);
+    for (int stage = 0; stage < 2; ++stage) {
+      int total = 0;
+      SWCHK(solve_dev(h, hid, 0, h->t3_rhs, stage == 0 ? h->t3_z : h->t3_zeta, tol, maxiter, ncols, &total));
+      if (stage == 0) SWCHK(seq_sources(h, lv, h->t3_z, nb, nbp, h->t3_rhs, h->pb_est));
+      else SWCHK(seq_dots(h, lv, h->t3_zeta, h->t3_z, nbp));
+      SWCHK(stream_sync(h));
+      SWCHK(record_iters(h, &h->hier[hid].lv[0].sws, total, all, ncols));
+      for (int k = 0; k < nb; ++k) sum[k] += std::max(all[k], all[(size_t)nbp + k]);
+    }
+    h->t3_nb = nb;
+    h->last_iters_f = sum;
     h->last_iters_c.assign(nb, 0);
     return 0;
   }
@@ -5953,9 +6161,9 @@ int sw_timers(sw_engine* h, double t[8]) {
   t[T_MVM] += h->tacc[T_STENCIL] + h->tacc[T_STENCIL_RES] + h->tacc[T_STENCIL_SM] + h->tacc[T_MFMA_OP] +
               h->tacc[T_MFMA_OP2] + h->tacc[T_SCHUR] + h->tacc[T_SCHUR_OP];
   t[T_COARSEST] += h->tacc[T_MFMA_DENSE];
-  t[T_OTHER] += h->tacc[T_TP_SOURCES];
+  t[T_OTHER] += h->tacc[T_TP_SOURCES] + h->tacc[T_3PT_SOURCES];
   t[T_DOTS] += h->tacc[T_TP_DOTS] + h->tacc[T_SLICE_CDOTS] + h->tacc[T_MESON_FIELD] + h->tacc[T_LM_CONTRACT] +
-               h->tacc[T_LINK_DOTS];
+               h->tacc[T_LINK_DOTS] + h->tacc[T_3PT_DOTS];
   return 0;
 }
 int sw_timers_reset(sw_engine* h) {

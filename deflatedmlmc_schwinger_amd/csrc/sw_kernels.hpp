@@ -3903,6 +3903,201 @@ __global__ __launch_bounds__(SW_BLOCK) void k_pair_total(const cplx* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------
+// Three-point functions (SW_MODE_THREE_POINT): per noise k the one-end-trick solutions z^a = A^-1 eta^a of the two
+// spin sources on the timeslice t0, the sequential sources through the sink
+//   s^a[idx(e,x,t)] = delta_t,tf e^{+2 pi i pf x / L} sum_c ((g3 Gf g3)^H)[e][c] z^a[idx(c,x,tf)],
+// their solutions zeta^a = A^-1 s^a, and the field x field sums per timeslice, insertion momentum q_j and branch
+// d = (local, F_x, B_x, F_t, B_t), with n = (x, t) the site that owns the link as in k_slice_link_dots:
+//   S[0][j][a][b][f][c][t] = sum_x omega^(q_j x)               conj(zeta^a[idx(f,n)])    z^b[idx(c,n)]
+//   S[F_mu]                = sum_x omega^(q_j x) U_mu(n)       conj(zeta^a[idx(f,n)])    z^b[idx(c,n+mu)]
+//   S[B_mu]                = sum_x omega^(q_j x) conj(U_mu(n)) conj(zeta^a[idx(f,n+mu)]) z^b[idx(c,n)].
+// z, s and zeta are blocks [row][2 nq], nq = the noise count padded to 64; spin group a owns the columns
+// [a nq, (a + 1) nq).  slicerow and the phase table omega^i = e^{-2 pi i i / L} are those of k_slice_dots.
+// ------------------------------------------------------------------------------------------
+// grid = (ceil(n / 16), 2 nq / 64); lane = noise.  Each wave writes four rows (reference index i = idx(e,x,t)) of
+// its 64 columns: zero off the sink slice, and on it the entry of (g3 Gf g3)^H -- one of +-1, +-i, the other entry of
+// the row being 0 -- times z of the spin it selects, times conj(omega^(pf x mod L)).  `code` holds the matrix:
+// bit 0 = the rows select the other spin (sigma_1, sigma_2), bits 1-2 / 3-4 = the entry of row 0 / row 1 as a power
+// of i; the row is the same in all lanes, so every select on it is wave-uniform.  pf = 0 reads no table and does no
+// multiplication.  Columns of padded noises (k >= nb) stay exactly zero.
+__global__ __launch_bounds__(SW_BLOCK) void k_seq_sources(const cplx* __restrict__ Z, int nb, int n,
+                                                          const int* __restrict__ rowmap,
+                                                          const int* __restrict__ slicerow,
+                                                          const cplx* __restrict__ phase, int L, int tf, int pf,
+                                                          int code, int nq, cplx* __restrict__ out) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int ncols = 2 * nq;
+  const int c0 = blockIdx.y * 64;
+  const int k = c0 - (c0 / nq) * nq + lane;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int i = blockIdx.x * 16 + wave * 4 + r;
+    if (i >= n) return;
+    const int e = i / (L * L), rem = i - e * L * L;
+    const int t = rem / L, x = rem - t * L;
+    cplx v = cmake(0.0, 0.0);
+    if (t == tf && k < nb) {
+      const int c = e ^ (code & 1);
+      const int m = (code >> (1 + 2 * e)) & 3;
+      const cplx u = Z[(size_t)slicerow[((size_t)tf * L + x) * 2 + c] * ncols + c0 + lane];
+      const double ur = (m & 1) ? -u.y : u.x;
+      const double ui = (m & 1) ? u.x : u.y;
+      v = (m & 2) ? cmake(-ur, -ui) : cmake(ur, ui);
+      if (pf != 0) {
+        const cplx w = phase[(pf * x) % L];
+        v = cmulc(w, v);
+      }
+    }
+    const size_t row = rowmap ? (size_t)rowmap[i] : (size_t)i;
+    out[row * ncols + c0 + lane] = v;
+  }
+}
+
+// est[k] = sum_{a,c,x} |z^a[idx(c,x,tf)]|^2: the pion two-point value of noise k at the sink slice, the jump of the
+// conserved charge across it.  grid = (nq / 64); the four waves take x = wave, wave + 4, ... and combine through LDS
+// in the fixed order w0 + w1 + w2 + w3: no atomics, bit-identical between runs.
+__global__ __launch_bounds__(SW_BLOCK) void k_pair_slice_total(const cplx* __restrict__ Z,
+                                                               const int* __restrict__ slicerow, int L, int tf,
+                                                               int nq, cplx* __restrict__ est) {
+  __shared__ double red[3][64];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const size_t col = (size_t)blockIdx.x * 64 + lane;
+  const size_t ncols = 2 * (size_t)nq;
+  const int* __restrict__ sr = slicerow + (size_t)tf * L * 2;
+  double s = 0.0;
+  for (int x = wave; x < L; x += SW_WAVES_PER_BLOCK) {
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const size_t r = (size_t)sr[2 * x + c] * ncols + col;
+      const cplx u0 = Z[r], u1 = Z[r + nq];
+      s += u0.x * u0.x + u0.y * u0.y;
+      s += u1.x * u1.x + u1.y * u1.y;
+    }
+  }
+  if (wave > 0) red[wave - 1][lane] = s;
+  __syncthreads();
+  if (wave == 0) {
+    s += red[0][lane];
+    s += red[1][lane];
+    s += red[2][lane];
+    est[col] = cmake(s, 0.0);
+  }
+}
+
+// grid = (L timeslices, nq / 64, 5 branches x momenta of the launch); lane = noise.  k_slice_pair_dots' skeleton with
+// two different buffers and a neighbour: one workgroup owns one (t, noise group, momentum j, branch d) completely,
+// blockIdx.z = d * nz + (index among the launch's momenta), every select on d wave-uniform.  Its four waves take the
+// sites x = wave, wave + 4, ...; per site a lane reads u[a][f] = zeta^a_f at the left site and z^b_c at the right
+// site (16 bytes each; F = (n, n + mu), B = (n + mu, n), local = (n, n); the rows through slicerow of (t, x),
+// (t, (x + 1) mod L) or ((t + 1) mod L, x)), multiplies the four z by the one uniform factor of the site -- the link,
+// conjugated for B, times omega^(q_j x mod L) from the table staged in LDS -- and adds the 16 products conj(u) v to
+// 16 complex accumulators held in registers.  PHASE = false serves a registered momentum 0 (jz >= 0: that index):
+// no table, the link is the only factor and the local branch multiplies nothing; it runs with nz = 1.  PHASE = true
+// runs over the other momenta (the index skips jz when jz >= 0).  The waves combine through LDS in the fixed order
+// w0 + w1 + w2 + w3 and wave 0 writes out[((((d * M + j) * 16 + a * 8 + b * 4 + f * 2 + c) * L + t) * nq + k]: no
+// partials, no atomics, bit-identical between runs.  A padded noise column only ever touches its own lane's sums.
+template <bool PHASE>
+__global__ __launch_bounds__(SW_BLOCK) void k_slice_seq_dots(const cplx* __restrict__ Zeta,
+                                                             const cplx* __restrict__ Z,
+                                                             const int* __restrict__ slicerow,
+                                                             const cplx* __restrict__ phase,
+                                                             const int* __restrict__ mom,
+                                                             const cplx* __restrict__ U1,
+                                                             const cplx* __restrict__ U2, int jz, int nz, int M,
+                                                             int L, int nq, cplx* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) cplx tab[PHASE ? SW_SHIFT_MAX_L : 1];
+  __shared__ __attribute__((aligned(16))) cplx red[16][64];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int t = blockIdx.x;
+  const int k = blockIdx.y * 64 + lane;
+  const int d = (int)blockIdx.z / nz, jl = (int)blockIdx.z - d * nz;
+  const int j = PHASE ? jl + ((jz >= 0 && jl >= jz) ? 1 : 0) : jz;
+  const bool local = d == 0, in_t = d >= 3, back = d == 2 || d == 4;
+  int idx = 0, step = 0;
+  if constexpr (PHASE) {
+    for (int i = threadIdx.x; i < L; i += SW_BLOCK) tab[i] = phase[i];
+    const int p = mom[j];                       // in [0, L), L <= 1024: the products below stay far inside int
+    idx = (p * wave) % L;
+    step = (p * SW_WAVES_PER_BLOCK) % L;
+    __syncthreads();
+  }
+  double ar[16], ai[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) ar[i] = ai[i] = 0.0;
+  const int tn = in_t ? (t + 1 == L ? 0 : t + 1) : t;          // timeslice of n + mu
+  const int dx = (local || in_t) ? 0 : 1;
+  const int* __restrict__ sr_own = slicerow + (size_t)t * L * 2;
+  const int* __restrict__ sr_nb = slicerow + (size_t)tn * L * 2;
+  const int* __restrict__ sr_u = back ? sr_nb : sr_own;        // the left factor's site
+  const int* __restrict__ sr_v = back ? sr_own : sr_nb;        // the right factor's site
+  const cplx* __restrict__ U = (in_t ? U2 : U1) + (size_t)t * L;
+  const double usign = back ? -1.0 : 1.0;
+  const size_t ncols = 2 * (size_t)nq;
+  for (int x = wave; x < L; x += SW_WAVES_PER_BLOCK) {
+    int xn = x + dx;
+    xn = xn >= L ? xn - L : xn;
+    const int xu = back ? xn : x, xv = back ? x : xn;
+    const size_t u0 = (size_t)sr_u[2 * xu] * ncols + k, u1 = (size_t)sr_u[2 * xu + 1] * ncols + k;
+    const size_t v0 = (size_t)sr_v[2 * xv] * ncols + k, v1 = (size_t)sr_v[2 * xv + 1] * ncols + k;
+    const cplx u[4] = {Zeta[u0], Zeta[u1], Zeta[u0 + nq], Zeta[u1 + nq]};   // [a][f]
+    const cplx s[4] = {Z[v0], Z[v1], Z[v0 + nq], Z[v1 + nq]};               // [b][c]
+    cplx w = cmake(1.0, 0.0);
+    if (!local) {
+      const cplx lk = U[x];
+      w = cmake(lk.x, usign * lk.y);
+    }
+    if constexpr (PHASE) {
+      const cplx e = tab[idx];
+      idx += step;
+      idx = idx >= L ? idx - L : idx;
+      w = local ? e : cmul(e, w);
+    }
+    cplx v[4];
+    if (PHASE || !local) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[q] = cmake(w.x * s[q].x - w.y * s[q].y, w.x * s[q].y + w.y * s[q].x);
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[q] = s[q];
+    }
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int f = 0; f < 2; ++f)
+#pragma unroll
+          for (int c = 0; c < 2; ++c) {
+            const cplx uu = u[a * 2 + f], vv = v[b * 2 + c];
+            const int i = a * 8 + b * 4 + f * 2 + c;
+            ar[i] += uu.x * vv.x + uu.y * vv.y;
+            ai[i] += uu.x * vv.y - uu.y * vv.x;
+          }
+  }
+  for (int w = 1; w < SW_WAVES_PER_BLOCK; ++w) {
+    __syncthreads();                          // wave 0 has taken the previous wave's block
+    if (wave == w) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) red[i][lane] = cmake(ar[i], ai[i]);
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const cplx q = red[i][lane];
+        ar[i] += q.x;
+        ai[i] += q.y;
+      }
+    }
+  }
+  if (wave == 0) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      out[((((size_t)d * M + j) * 16 + i) * L + t) * nq + k] = cmake(ar[i], ai[i]);
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // Low-mode averaging of the two-point functions (sw_meson_fields, SW_MODE_TWO_POINT_LMA).
 // ------------------------------------------------------------------------------------------
 // Meson fields of the registered deflation vectors for one momentum p:

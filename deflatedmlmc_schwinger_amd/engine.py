@@ -28,6 +28,7 @@ MODE_MLMC_DEFL_LOOPS = 9
 MODE_MLMC_DEFL_LOOPS_SKIP = 10
 MODE_TWO_POINT_LMA = 11
 MODE_HUTCHINSON_LINK_LOOPS = 12
+MODE_THREE_POINT = 13
 # estimator method -> (mode, mode of the level-skipping form at level 0); "mlmc_defl_loops" is "mlmc_loops" deflated
 _METHOD_MODES = {"hutchinson": (MODE_HUTCHINSON, MODE_HUTCHINSON),
                  "mlmc": (MODE_MLMC, MODE_MLMC_SKIP),
@@ -37,6 +38,7 @@ _METHOD_MODES = {"hutchinson": (MODE_HUTCHINSON, MODE_HUTCHINSON),
                  "link_loops": (MODE_HUTCHINSON_LINK_LOOPS, MODE_HUTCHINSON_LINK_LOOPS),
                  "two_point": (MODE_TWO_POINT, MODE_TWO_POINT),
                  "two_point_lma": (MODE_TWO_POINT_LMA, MODE_TWO_POINT_LMA),
+                 "three_point": (MODE_THREE_POINT, MODE_THREE_POINT),
                  "mlmc_loops": (MODE_MLMC_LOOPS, MODE_MLMC_LOOPS_SKIP),
                  "mlmc_defl_loops": (MODE_MLMC_DEFL_LOOPS, MODE_MLMC_DEFL_LOOPS_SKIP)}
 # the modes whose batches leave a resolved result beside the scalar estimates -> the Engine method that fetches it
@@ -45,6 +47,7 @@ RESOLVED_FETCH = {MODE_HUTCHINSON_SHIFTS: "hutch_fetch_shifts",
                   MODE_HUTCHINSON_LINK_LOOPS: "hutch_fetch_link_resolved",
                   MODE_TWO_POINT: "hutch_fetch_two_point",
                   MODE_TWO_POINT_LMA: "hutch_fetch_two_point_lma",
+                  MODE_THREE_POINT: "hutch_fetch_three_point_resolved",
                   MODE_MLMC_LOOPS: "hutch_fetch_mlmc_loops",
                   MODE_MLMC_LOOPS_SKIP: "hutch_fetch_mlmc_loops",
                   MODE_MLMC_DEFL_LOOPS: "hutch_fetch_mlmc_loops",
@@ -67,6 +70,9 @@ KCLASS_SLICE_CDOTS = 19    # ... and of k_slice_cdots (MLMC loops)
 KCLASS_MESON_FIELD = 20    # ... and of k_meson_field (low-mode averaging)
 KCLASS_LM_CONTRACT = 21    # ... and of k_cgemm_nt / k_lm_two_point_reduce (low_mode_two_point)
 KCLASS_LINK_DOTS = 22      # ... and of k_slice_link_dots (link loops)
+KCLASS_3PT_SOURCES = 23    # ... and of k_seq_sources / k_pair_slice_total and the stage-1 sources (three-point functions)
+KCLASS_3PT_DOTS = 24       # ... and of k_slice_seq_dots
+SINK_GAMMAS = ('1', 'g3', 's1', 's2')      # the sink spin matrix codes of set_three_point
 MAX_SHIFTS = 128
 MAX_MOMENTA = 8
 # operations of Engine.apply_op32 (SW_OP32_* of the header): one kernel of the complex64 cycle at a time
@@ -234,6 +240,10 @@ def load_library():
     sig("sw_hutch_fetch_two_point_lma", i32, vp, vp)
     sig("sw_hutch_fetch_link_loops", i32, vp, vp)
     sig("sw_apply_slice_link_dots", i32, vp, i32, vp, vp, vp)
+    sig("sw_set_three_point", i32, vp, i32, i32, i32, i32, i32, vp)
+    sig("sw_hutch_fetch_three_point", i32, vp, vp)
+    sig("sw_apply_seq_sources", i32, vp, i32, vp, vp)
+    sig("sw_apply_seq_dots", i32, vp, i32, vp, vp, vp)
     _lib = lib
     return lib
 
@@ -260,6 +270,7 @@ EXPORTED_SYMBOLS = (
     "sw_apply_slice_cdots", "sw_coarsest_loops", "sw_hutch_fetch_mlmc_loops", "sw_level_deflation_loops",
     "sw_meson_fields", "sw_low_mode_two_point", "sw_set_low_mode_inverse", "sw_apply_low_mode", "sw_hutch_fetch_two_point_lma",
     "sw_hutch_fetch_link_loops", "sw_apply_slice_link_dots",
+    "sw_set_three_point", "sw_hutch_fetch_three_point", "sw_apply_seq_sources", "sw_apply_seq_dots",
 )
 
 
@@ -328,6 +339,7 @@ class Engine:
         if hid == 0:
             self._nshifts = 0          # the engine drops its shift registration with hierarchy 0
             self._nmom = 0             # ... and its loop momenta
+            self._t3_nmom = 0          # ... and its three-point registration
 
     def set_lattice(self, hid, L, mass, U1, U2):
         U1, U2 = _c128(U1), _c128(U2)
@@ -910,6 +922,67 @@ class Engine:
                               % (Z.shape, 2 * getattr(self, "_tp_nmom", 0), self._n(0, 0)))
         out = np.zeros(self._two_point_shape(Z.shape[1]), dtype=np.complex128)
         self._chk(self._lib.sw_apply_pair_dots(self._h, Z.shape[1], _ptr(Z), _ptr(out)), "sw_apply_pair_dots")
+        return np.ascontiguousarray(np.moveaxis(out, -1, 0))
+
+    def set_three_point(self, t0, tf, sink='g3', pf=0, momenta=(0,)):
+        """Source and sink timeslice, sink spin matrix ('1', 'g3', 's1', 's2' or its code 0..3), sink momentum and
+        insertion momenta of MODE_THREE_POINT (momenta None or an empty list clears)."""
+        m = np.ascontiguousarray([] if momenta is None else momenta, dtype=np.int32)
+        code = SINK_GAMMAS.index(sink) if sink in SINK_GAMMAS else sink
+        if isinstance(code, str):
+            raise EngineError("unknown sink spin matrix %r (one of %s)" % (sink, list(SINK_GAMMAS)))
+        self._chk(self._lib.sw_set_three_point(self._h, int(t0), int(tf), int(code), int(pf), m.size,
+                                               _ptr(m) if m.size else None), "sw_set_three_point")
+        self._t3_nmom = int(m.size)
+
+    def _three_point_shape(self, nb):
+        n = self._n(0, 0)
+        L = int(round((n // 2) ** 0.5))
+        return (5, getattr(self, "_t3_nmom", 0), 2, 2, 2, 2, L, nb)
+
+    def hutch_batch_three_point(self, level, probes, tol, maxiter=1000):
+        """One MODE_THREE_POINT batch, the probes being the noises: (S[nb, 5, nmom, 2, 2, 2, 2, L], c[nb],
+        iters_fine[nb], iters_coarse[nb]); S[k, d, j, a, b, f, c, t] over the branches d = (local, F_x, B_x, F_t, B_t),
+        c[k] = sum_{a,c,x} |z_k^a[idx(c,x,tf)]|^2, iters_fine[k] the largest stage-1 plus the largest stage-2 count."""
+        c, itf, itc = self.hutch_batch(MODE_THREE_POINT, level, probes, tol, maxiter)
+        self._nb_uploaded = itf.size
+        return self.hutch_fetch_three_point(), c, itf, itc
+
+    def hutch_fetch_three_point(self):
+        """Sums of the last MODE_THREE_POINT batch, shape (nb, 5, nmom, 2, 2, 2, 2, L)."""
+        out = np.zeros(self._three_point_shape(getattr(self, "_nb_uploaded", 0)), dtype=np.complex128)
+        self._chk(self._lib.sw_hutch_fetch_three_point(self._h, _ptr(out)), "sw_hutch_fetch_three_point")
+        return np.ascontiguousarray(np.moveaxis(out, -1, 0))
+
+    def hutch_fetch_three_point_resolved(self):
+        """Everything a MODE_THREE_POINT batch resolves, one row per noise: the flattened S followed by c_k."""
+        S = self.hutch_fetch_three_point()
+        c, _, _ = self.hutch_fetch()
+        return np.concatenate([S.reshape(S.shape[0], -1), c[:, None]], axis=1)
+
+    def _pair_fields(self, Z, what):
+        Z = _c128(Z)
+        if Z.ndim != 3 or Z.shape[0] != 2 or Z.shape[2] != self._n(0, 0):
+            raise EngineError("%s of shape %s, expected (2, nb, %d)" % (what, Z.shape, self._n(0, 0)))
+        return Z
+
+    def apply_seq_sources(self, Z):
+        """The sequential-source kernel alone: Z complex (2, nb, n) = z_k^a in the reference ordering; returns s of
+        the same shape for the registration of set_three_point (utils.seq_sources)."""
+        Z = self._pair_fields(Z, "Z")
+        out = np.zeros_like(Z)
+        self._chk(self._lib.sw_apply_seq_sources(self._h, Z.shape[1], _ptr(Z), _ptr(out)), "sw_apply_seq_sources")
+        return out
+
+    def apply_seq_dots(self, Zeta, Z):
+        """The field x field reduction alone: Zeta, Z complex (2, nb, n); returns S[k, d, j, a, b, f, c, t]
+        (utils.seq_dots with the links of the lattice level)."""
+        Zeta, Z = self._pair_fields(Zeta, "Zeta"), self._pair_fields(Z, "Z")
+        if Zeta.shape != Z.shape:
+            raise EngineError("Zeta %s and Z %s differ in shape" % (Zeta.shape, Z.shape))
+        out = np.zeros(self._three_point_shape(Z.shape[1]), dtype=np.complex128)
+        self._chk(self._lib.sw_apply_seq_dots(self._h, Z.shape[1], _ptr(Zeta), _ptr(Z), _ptr(out)),
+                  "sw_apply_seq_dots")
         return np.ascontiguousarray(np.moveaxis(out, -1, 0))
 
     def probes_upload(self, level, probes):

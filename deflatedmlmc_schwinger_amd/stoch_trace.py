@@ -20,7 +20,8 @@ from .multigrid import MG
 from .utils import (_engines, deflation_pre_computations, displacements_of, draw_probes, flopsV_manual,
                     loops_of, mlmc_defl_setup_of, probe_batch, probe_batch_generated, register_loop_momenta,
                     register_shifts, register_two_point, two_point_of, low_mode_inverse, low_mode_two_point,
-                    register_low_modes, low_mode_contraction_of, link_loops_of)
+                    register_low_modes, low_mode_contraction_of, link_loops_of, three_point_of,
+                    register_three_point, refuse_three_point)
 
 DEFAULT_BATCH = 256
 NR_ROUGH_PROBES = 5
@@ -454,6 +455,7 @@ def hutchinson(A, params):
     forms the conserved vector current) resolve the estimate, from one deflation projection and one
     solve per probe: the reference's result keys are then those of the control column, and the stopping rule runs on
     its series alone."""
+    refuse_three_point(params, "hutchinson()")
     if two_point_of(params) is not None:
         raise Exception("source_timeslice belongs to two_point(), not to hutchinson()")
     link = link_loops_of(params)
@@ -540,6 +542,7 @@ def two_point(A, params):
     Returns two_point (the mean, [p][a][b][c][d][t]), two_point_devs, two_point_ests (per noise), converged,
     momenta, source_timeslice, nr_ests, function_iters (a noise counts the largest iteration number among its
     2 M solves), ests (the control series), probe_loop_s and probes_solved."""
+    refuse_three_point(params, "two_point()")
     sel = two_point_of(params)
     if sel is None:
         raise Exception("two_point() needs the key source_timeslice")
@@ -570,6 +573,81 @@ def two_point(A, params):
     return result
 
 
+class _ThreePoint(_Observable):
+    """three_point(): the sums S[d][j][a][b][f][c][t], flattened, plus one control column, c_k = the pion two-point value
+    at the sink slice (real and positive) -- a batch's row as Engine.hutch_fetch_three_point_resolved returns it."""
+    what = "three-point functions"
+    method = "three_point"
+    one_rank = "three-point functions (sink_timeslice) run on one rank"
+
+    @staticmethod
+    def columns(rows):
+        return np.asarray(rows, dtype=np.complex128)
+
+    def control(self, rough):
+        return rough.size - 1
+
+
+def three_point(A, params):
+    """Three-point functions source -> insertion at t -> sink at tf from sequential one-end-trick solves (DESIGN.md
+    4j).  The build-only keys source_timeslice = t0, sink_timeslice = tf != t0, sink_gamma (default 'g3'),
+    sink_momentum (default 0) and three_point_momenta = [q_0, ...] (default [0]) select the chain: per noise k the two
+    spin sources of two_point() at momentum 0 give z_k^a, the sequential sources through the sink (utils.seq_sources)
+    give zeta_k^a, 2 + 2 solves without deflation to the same tolerance, and
+
+        S_k[d][j][a][b][f][c][t],  d = (local, F_x, B_x, F_t, B_t)        (utils.seq_dots)
+
+    is what utils.three_point_correlator (a local insertion, any source matrix) and utils.three_point_current (the
+    conserved vector current) contract.  No fermion-loop sign is applied.  The columns of the probe loop are the
+    flattened S plus one control column, c_k = sum_{a,c,x} |z_k^a[idx(c,x,tf)]|^2 -- the pion two-point value
+    C_2(tf) of the noise, real and positive, the denominator of the usual ratio C_3 / C_2 -- and the stopping rule runs
+    on it alone.  `batch` counts noises; each solve is 2 batch columns wide.  One rank; the operator has to be the
+    lattice stencil the engine detects (the link branches need its links).
+
+    Returns three_point (the mean, [d][j][a][b][f][c][t]), three_point_devs, three_point_ests (per noise),
+    three_point_converged, sink_two_point (mean and deviation of c_k), momenta, source_timeslice, sink_timeslice,
+    sink_gamma, sink_momentum, and the reference's keys from the control series: trace (= the mean of c_k), std_dev,
+    nr_ests, function_iters (a noise counts its largest stage-1 plus its largest stage-2 iteration number), ests,
+    rough_trace, level_tol, probe_loop_s and probes_solved."""
+    sel = three_point_of(params)
+    if sel is None:
+        raise Exception("three_point() needs the keys source_timeslice and sink_timeslice")
+    obs = _ThreePoint()
+    if _dist.default_comm().world > 1:
+        raise Exception(obs.one_rank)
+    from .hierarchy import detect_lattice
+    lattice = A if isinstance(A, tuple) else (None if A is None else detect_lattice(A))
+    if lattice is None:
+        raise Exception("three_point() needs a lattice operator (a U(1) Wilson stencil with its links)")
+    mg_solver, nr_levels = _setup_solver(A, params, defer_coarse=True, lattice=lattice)
+    shape = (5, len(sel['momenta']), 2, 2, 2, 2, int(params['latt_dims'][0]))
+    register_three_point(mg_solver, sel)
+    rough, level_tols, control, loop, loop_s = _estimate_stage(mg_solver, params, A.shape[0], obs)
+
+    mg_solver.finish_setup()
+    result = dict()
+    result['three_point'] = loop["avgs"][:control].reshape(shape)
+    result['three_point_devs'] = loop["devs"][:control].reshape(shape)
+    result['three_point_ests'] = loop["ests"][:, :control].reshape((-1,) + shape)
+    result['three_point_converged'] = loop["converged"][:control].reshape(shape)
+    result['sink_two_point'] = (loop["avg"], loop["dev"])
+    result['momenta'] = list(sel['momenta'])
+    result['source_timeslice'], result['sink_timeslice'] = sel['t0'], sel['tf']
+    result['sink_gamma'], result['sink_momentum'] = sel['sink'], sel['pf']
+    result['trace'] = loop["avg"]
+    result['std_dev'] = loop["dev"]
+    result['nr_ests'] = loop["index"]
+    result['function_iters'] = int(np.sum(loop["iters_fine"]))
+    result['ests'] = loop["ests"][:, control]       # (nr_ests + 1,): c_k per noise
+    result['rough_trace'] = rough[control]
+    result['level_tol'] = level_tols[control]
+    result['probe_loop_s'] = loop_s
+    result['probes_solved'] = loop["solved"]
+    mg_solver.sync_timer()
+    print(mg_solver.timer)
+    return result
+
+
 def lma_two_point(A, params):
     """two_point() with low-mode averaging: the nr_deflat_vctrs > 0 lowest eigenvectors V of gamma_3 A
     (hutchinson()'s deflation step) give the low-mode inverse A_L^-1 = V G V^H gamma_3, G = (V^H gamma_3 A V)^-1 made
@@ -584,6 +662,7 @@ def lma_two_point(A, params):
     Returns two_point()'s keys with two_point = E_L(t0) + the remainder's mean, plus two_point_low (E_L, all t0),
     two_point_rest (the remainder's mean), two_point_rest_devs and nr_deflat_vctrs; two_point_ests are the per-noise
     remainders plus E_L(t0)."""
+    refuse_three_point(params, "lma_two_point()")
     sel = two_point_of(params)
     if sel is None:
         raise Exception("lma_two_point() needs the key source_timeslice")
@@ -718,6 +797,7 @@ def _mlmc_work_model(output_params, mg_solver):
 
 # compute tr(A^{-1}) via multigrid multilevel Monte Carlo          stoch_trace.py:185-471
 def mlmc(A, params):
+    refuse_three_point(params, "mlmc()")
     if two_point_of(params) is not None:
         raise Exception("source_timeslice belongs to two_point(), not to mlmc()")
     if loops_of(params) is not None:
@@ -838,6 +918,7 @@ def _mlmc_loops_checks(params, deflated=False):
     """The validation of mlmc_loops() (deflated: of deflated_mlmc_loops()), before any setup: (momenta, skip_level)."""
     who = "deflated_mlmc_loops" if deflated else "mlmc_loops"
     has = hasattr(params, "get")
+    refuse_three_point(params, who + "()")
     if has and params.get('source_timeslice') is not None:
         raise Exception("source_timeslice belongs to two_point(), not to %s()" % who)
     if has and params.get('x_displacements') is not None:

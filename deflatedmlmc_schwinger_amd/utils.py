@@ -63,7 +63,8 @@ _BUILD_KEYS = ('batch', 'device', 'engines', 'cache_dir', 'report_path', 'probe_
                'solver_restart', 'stochastic_coarsest', 'stop_factor', 'ref_direct_max_n', 'ref_coarsest',
                'ref_coarse_dofs', 'setup_eigs', 'defer_coarse_levels',
                'verbose', 'probe_rounds_max', 'mlmc_defl_setup', 'defl_setup', 'x_displacements',
-               'timeslice_loops', 'source_timeslice', 'two_point_momenta', 'low_mode_contraction', 'link_loops')
+               'timeslice_loops', 'source_timeslice', 'two_point_momenta', 'low_mode_contraction', 'link_loops',
+               'sink_timeslice', 'sink_gamma', 'sink_momentum', 'three_point_momenta')
 # where the eigenpairs of the MLMC difference operators come from: host ARPACK (the reference's path) or
 # the block eigensolver on the GPU (setup_gpu.device_diff_eigenpairs)
 MLMC_DEFL_SETUPS = ("host", "device")
@@ -546,6 +547,166 @@ def meson_correlator(T, sink, source):
     return out
 
 
+def _momentum_list(key, given, L):
+    momenta = []
+    for p in given:
+        if isinstance(p, bool) or int(p) != p:
+            raise Exception("%s: %r is not an integer" % (key, p))
+        p = int(p)
+        if not 0 <= p < L:
+            raise Exception("%s: momentum %d outside [0, %d)" % (key, p, L))
+        if p in momenta:
+            raise Exception("%s: momentum %d listed twice" % (key, p))
+        momenta.append(p)
+    if not momenta or len(momenta) > MAX_MOMENTA:
+        raise Exception("%s: %d momenta, between 1 and %d" % (key, len(momenta), MAX_MOMENTA))
+    return momenta
+
+
+def three_point_of(params):
+    """The build-only keys of three_point(): None when sink_timeslice is absent, else the validated
+    dict(t0, tf, sink, pf, momenta) -- source_timeslice and sink_timeslice different integers in [0, L), L =
+    latt_dims[0]; sink_gamma one of '1', 'g3', 's1', 's2' (default 'g3'); sink_momentum an integer in [0, L) (default
+    0); three_point_momenta ([0] when absent) at most MAX_MOMENTA different integers in [0, L), which need not contain
+    0.  The keys combine with none of x_displacements, timeslice_loops, link_loops and two_point_momenta."""
+    has = hasattr(params, "get")
+    if not has or params.get('sink_timeslice') is None:
+        for key in ('sink_gamma', 'sink_momentum', 'three_point_momenta'):
+            if has and params.get(key) is not None:
+                raise Exception("%s needs sink_timeslice" % key)
+        return None
+    for other in ('x_displacements', 'timeslice_loops', 'link_loops', 'two_point_momenta'):
+        if params.get(other) is not None:
+            raise Exception("sink_timeslice does not combine with %s" % other)
+    if params.get('source_timeslice') is None:
+        raise Exception("sink_timeslice needs source_timeslice")
+    L = int(params['latt_dims'][0])
+    got = {}
+    for key, name in (('source_timeslice', 't0'), ('sink_timeslice', 'tf'), ('sink_momentum', 'pf')):
+        v = params.get(key)
+        v = 0 if v is None else v          # only sink_momentum can be absent here
+        if isinstance(v, bool) or int(v) != v:
+            raise Exception("%s: %r is not an integer" % (key, v))
+        if not 0 <= int(v) < L:
+            raise Exception("%s: %d outside [0, %d)" % (key, int(v), L))
+        got[name] = int(v)
+    if got['tf'] == got['t0']:
+        raise Exception("sink_timeslice: %d equals source_timeslice" % got['tf'])
+    sink = params.get('sink_gamma')
+    sink = 'g3' if sink is None else sink
+    if sink not in _PAULI:
+        raise Exception("sink_gamma: unknown spin matrix %r (one of %s)" % (sink, sorted(_PAULI)))
+    given = params.get('three_point_momenta')
+    got['sink'] = sink
+    got['momenta'] = _momentum_list('three_point_momenta', [0] if given is None else given, L)
+    return got
+
+
+def refuse_three_point(params, who):
+    """sink_timeslice selects three_point(): every other flow raises on it."""
+    if hasattr(params, "get") and params.get('sink_timeslice') is not None:
+        raise Exception("sink_timeslice belongs to three_point(), not to %s" % who)
+
+
+def seq_sources(Z, L, tf, sink, pf):
+    """The sequential sources of three_point(): out[a, k, idx(e,x,t)] = delta_{t,tf} e^{+2 pi i pf x / L} sum_c
+    ((g3 Gf g3)^H)[e][c] Z[a, k, idx(c,x,tf)], Gf = `sink` out of '1', 'g3', 's1', 's2'; Z of shape (2, nb, 2 L^2), the
+    solutions z_k^a of the two spin sources.  Every row of (g3 Gf g3)^H holds one entry out of +-1, +-i, so the
+    matrix acts as a selection with a quarter turn; the phase is the conjugated entry of the engine's table, and
+    pf = 0 multiplies nothing -- what Engine.apply_seq_sources computes."""
+    if sink not in _PAULI:
+        raise Exception("seq_sources: unknown spin matrix %r (one of %s)" % (sink, sorted(_PAULI)))
+    Z = np.asarray(Z, dtype=np.complex128)
+    if Z.ndim != 3 or Z.shape[0] != 2 or Z.shape[2] != 2 * L * L:
+        raise Exception("seq_sources: Z of shape %s, expected (2, nb, %d)" % (Z.shape, 2 * L * L))
+    g3 = _PAULI['g3']
+    Mx = (g3 @ _PAULI[sink] @ g3).conj().T
+    Zr = Z.reshape(2, Z.shape[1], 2, L, L)                                # [a][k][c][t][x]
+    out = np.zeros_like(Zr)
+    ph = np.conj(_phase_table(L)[(int(pf) * np.arange(L)) % L])
+    for e in range(2):
+        c = int(np.flatnonzero(Mx[e])[0])
+        v = Mx[e, c] * Zr[:, :, c, tf, :]
+        out[:, :, e, tf, :] = v if pf == 0 else ph * v
+    return out.reshape(Z.shape)
+
+
+def seq_dots(Zeta, Z, U1, U2, L, momenta):
+    """The field x field sums of three_point() for a batch, out[k, d, j, a, b, f, c, t] over the branches d = (local,
+    F_x, B_x, F_t, B_t):
+
+        S[0]    = sum_x e^{-2 pi i q_j x / L}               conj(Zeta[a, k, idx(f,n)])    Z[b, k, idx(c,n)]
+        S[F_mu] = sum_x e^{-2 pi i q_j x / L} U_mu(n)       conj(Zeta[a, k, idx(f,n)])    Z[b, k, idx(c,n+mu)]
+        S[B_mu] = sum_x e^{-2 pi i q_j x / L} conj(U_mu(n)) conj(Zeta[a, k, idx(f,n+mu)]) Z[b, k, idx(c,n)]
+
+    with n = (x, t) the site that owns the link, n + mu and the links as in slice_link_dots; Zeta, Z of shape
+    (2, nb, 2 L^2); phases as the engine's table -- what Engine.apply_seq_dots computes."""
+    Zeta, Z = np.asarray(Zeta), np.asarray(Z)
+    if Zeta.shape != Z.shape or Z.ndim != 3 or Z.shape[0] != 2 or Z.shape[2] != 2 * L * L:
+        raise Exception("seq_dots: Zeta %s and Z %s, expected two equal (2, nb, %d)" % (Zeta.shape, Z.shape, 2 * L * L))
+    U = [np.asarray(u, dtype=np.complex128).reshape(-1) for u in (U1, U2)]
+    if any(u.size != L * L for u in U):
+        raise Exception("seq_dots: links of %d and %d entries, expected %d each" % (U[0].size, U[1].size, L * L))
+    ph = _phase_table(L)[np.outer(np.asarray(momenta, dtype=np.int64), np.arange(L)) % L]
+    nb = Z.shape[1]
+    Zc, Zr = Zeta.reshape(2, nb, 2, L, L).conj(), Z.reshape(2, nb, 2, L, L)      # [a][k][f][t][x], [b][k][c][t][x]
+    out = np.empty((nb, 5, len(momenta), 2, 2, 2, 2, L), dtype=Z.dtype if Z.dtype.kind == 'c' else np.complex128)
+    out[:, 0] = np.einsum('jx,akftx,bkctx->kjabfct', ph, Zc, Zr)
+    for mu, axis in enumerate((4, 3)):                                   # n + mu: one step along x / along t
+        u = U[mu].reshape(L, L).astype(out.dtype)                        # [t][x]
+        out[:, 1 + 2 * mu] = np.einsum('jx,tx,akftx,bkctx->kjabfct', ph, u, Zc, np.roll(Zr, -1, axis=axis))
+        out[:, 2 + 2 * mu] = np.einsum('jx,tx,akftx,bkctx->kjabfct', ph, u.conj(), np.roll(Zc, -1, axis=axis), Zr)
+    return out
+
+
+def _three_point_sums(S, who):
+    S = np.asarray(S)
+    if S.ndim < 7 or S.shape[-7] != 5 or S.shape[-5:-1] != (2, 2, 2, 2):
+        raise Exception("%s: S of shape %s, expected (..., 5, nmom, 2, 2, 2, 2, L)" % (who, S.shape))
+    return S
+
+
+def _source_weights(source, who):
+    if source not in _PAULI:
+        raise Exception("%s: unknown spin matrix %r (one of %s)" % (who, source, sorted(_PAULI)))
+    return _PAULI[source] @ _PAULI['g3']                                  # (Gamma_i g3)[b][a]
+
+
+def three_point_correlator(S, insertion, source):
+    """C3_Gamma(t, q_j) = sum_abfc (Gamma_i g3)[b][a] g_f Gamma[f][c] S[..., 0, j, a, b, f, c, t], Gamma = `insertion`,
+    Gamma_i = `source` out of '1', 'g3', 's1', 's2', g = (+1, -1): the three-point function sum_{x,y,w} e^{-2 pi i q x / L}
+    e^{-2 pi i pf w / L} tr[Gamma_i A^-1(y,t0; w,tf) Gamma_f A^-1(w,tf; x,t) Gamma A^-1(x,t; y,t0)] from the local
+    sums of three_point() (S of shape (..., 5, nmom, 2, 2, 2, 2, L)); shape (..., nmom, L).  No fermion-loop sign."""
+    S = _three_point_sums(S, "three_point_correlator")
+    if insertion not in _PAULI:
+        raise Exception("three_point_correlator: unknown spin matrix %r (one of %s)" % (insertion, sorted(_PAULI)))
+    W = _source_weights(source, "three_point_correlator")
+    G = _PAULI['g3'] @ _PAULI[insertion]                                  # g_f Gamma[f][c]
+    return np.einsum('ba,fc,...jabfct->...jt', W, G, S[..., 0, :, :, :, :, :, :])
+
+
+def three_point_current(S, mu, source=None):
+    """The conserved vector current inserted into the three-point function, from the link sums of three_point():
+
+        J_mu[a][b](t, q_j) = sum_fc g_f ( H+_mu[f][c] S[F_mu] - H-_mu[f][c] S[B_mu] )[j][a][b][f][c][t],  mu = 'x' or 't',
+
+    H+-_mu the hop matrices of the operator (hierarchy._HOP).  source None: J itself, shape (..., nmom, 2, 2, L);
+    else C3_{J_mu}(t, q_j) = sum_ab (Gamma_i g3)[b][a] J_mu[a][b], shape (..., nmom, L).  Per noise and exactly,
+    W[a][b](t) = (1 - e^{-2 pi i q / L}) J_x(t) + J_t(t) - J_t(t - 1) vanishes off the source and the sink slice."""
+    from .hierarchy import _HOP
+    S = _three_point_sums(S, "three_point_current")
+    if mu not in ('x', 't'):
+        raise Exception("three_point_current: unknown direction %r (one of ['t', 'x'])" % (mu,))
+    d = 1 if mu == 'x' else 3
+    g3 = _PAULI['g3']
+    hp, hm = g3 @ _HOP["+x" if mu == 'x' else "+y"], g3 @ _HOP["-x" if mu == 'x' else "-y"]
+    J = (np.einsum('fc,...jabfct->...jabt', hp, S[..., d, :, :, :, :, :, :])
+         - np.einsum('fc,...jabfct->...jabt', hm, S[..., d + 1, :, :, :, :, :, :]))
+    if source is None:
+        return J
+    return np.einsum('ba,...jabt->...jt', _source_weights(source, "three_point_current"), J)
+
+
 def meson_fields(V, L, momenta):
     """Phi[j, c, d, t, m, m'] = sum_x e^{-2 pi i p_j x / L} conj(V[idx(c,x,t), m]) V[idx(d,x,t), m'] for the columns of
     V (2 L^2, k), idx(s,x,y) = s L^2 + y L + x: the meson fields of lma_two_point(), what Engine.meson_fields computes
@@ -976,6 +1137,15 @@ def register_two_point(mg_solver, t0, momenta):
     """Hand the source timeslice and momenta of two_point() to every engine handle (momenta None clears)."""
     for eng in _engines(mg_solver):
         eng.set_two_point(t0, momenta)
+
+
+def register_three_point(mg_solver, sel):
+    """Hand the registration of three_point() -- three_point_of's dict, None clears -- to every engine handle."""
+    for eng in _engines(mg_solver):
+        if sel is None:
+            eng.set_three_point(0, 1, 'g3', 0, None)
+        else:
+            eng.set_three_point(sel['t0'], sel['tf'], sel['sink'], sel['pf'], sel['momenta'])
 
 
 def probe_batch_generated(mg_solver, params, method, level, first_probe, count, kind="z2",

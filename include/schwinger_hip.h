@@ -232,6 +232,12 @@ int sw_set_loop_momenta(sw_engine* h, int nmom, const int32_t* p);
  * functions).  A registration of its own, independent of sw_set_loop_momenta; the same checks, plus 0 <= t0 < L
  * and 0 among the momenta (its solutions are the conjugated factor of every momentum); nmom = 0 clears. */
 int sw_set_two_point(sw_engine* h, int t0, int nmom, const int32_t* p);
+/* Source timeslice t0, sink timeslice tf, sink spin matrix (0..3 = 1, gamma_3, sigma_1, sigma_2), sink momentum pf
+ * and insertion momenta q_j of SW_MODE_THREE_POINT (build-only: three-point functions from sequential one-end-trick
+ * solves).  A registration of its own beside sw_set_two_point; the momentum checks of sw_set_loop_momenta (the list
+ * need not contain 0), plus 0 <= t0, tf < L, tf != t0, 0 <= pf < L, a known matrix code and a lattice level 0 with
+ * links (the condition of SW_MODE_HUTCHINSON_LINK_LOOPS); nmom = 0 clears. */
+int sw_set_three_point(sw_engine* h, int t0, int tf, int sink_gamma, int pf, int nmom, const int32_t* q);
 /* Outer flexible-GMRES restart length (<= SW_MAX_KRYLOV) and the hierarchy used to
  * precondition level-0 solves (0 or 1). */
 int sw_set_solver(sw_engine* h, int restart, int solver_hid);
@@ -341,6 +347,15 @@ int sw_apply_slice_sources(sw_engine* h, int nb, const int8_t* probes, double* o
  * sum_x e^{-2 pi i p_j x / L} conj(Z[2 j0 + a][k][idx(c,x,t)]) Z[2 j + b][k][idx(d,x,t)], j0 = the registered
  * momentum 0. */
 int sw_apply_pair_dots(sw_engine* h, int nb, const double* Z, double* out);
+/* The sequential-source kernel of SW_MODE_THREE_POINT alone on host solutions: Z complex128[2][nb][n] (spin group a,
+ * noise k, reference ordering), out complex128[2][nb][n], out[a][k][idx(e,x,t)] = delta_{t,tf} e^{+2 pi i pf x / L}
+ * sum_c ((g3 Gf g3)^H)[e][c] Z[a][k][idx(c,x,tf)] for the registration of sw_set_three_point.  The refusals of the
+ * mode. */
+int sw_apply_seq_sources(sw_engine* h, int nb, const double* Z, double* out);
+/* The field x field reduction of SW_MODE_THREE_POINT alone on host fields: Zeta, Z complex128[2][nb][n] as above,
+ * out complex128[5][nmom][2][2][2][2][L][nb] = S[d][j][a][b][f][c][t][k] of that mode with zeta = Zeta, z = Z.  The
+ * refusals of the mode. */
+int sw_apply_seq_dots(sw_engine* h, int nb, const double* Zeta, const double* Z, double* out);
 /* Meson fields of the registered deflation vectors U (sw_set_deflation; k of them) for ONE spatial momentum p in [0, L)
  * (build-only): out[c][d][t][m][m'] = sum_x e^{-2 pi i p x / L} conj(U[idx(c,x,t)][m]) U[idx(d,x,t)][m'], complex128
  * [2][2][L][k][k] (at most 537 MB at k = 256, L = 128: one momentum per call).  Level 0 of hid 0, lattice set
@@ -475,6 +490,22 @@ int sw_solve(sw_engine* h, int hid, int level0, int nb, const double* B, double*
                                   U_x = U1, U_t = U2 of sw_set_lattice, for the momenta of sw_set_loop_momenta.  A
                                   buffer of its own (sw_hutch_fetch_link_loops).  Refused at a level other than 0,
                                   without momenta and when level 0 is no lattice level with links. */
+#define SW_MODE_THREE_POINT 13  /* three-point functions source -> insertion at t -> sink at tf, level 0 (build-only), for
+                                  the registration of sw_set_three_point.  Per noise k, xi_k(y) = the code of probe k
+                                  at idx(0,y,t0) as in SW_MODE_TWO_POINT:
+                                  eta_k^a[idx(a',y,t)] = delta_aa' delta_{t,t0} xi_k(y),  z_k^a = A^-1 eta_k^a  (stage 1),
+                                  s_k^a[idx(e,x,t)] = delta_{t,tf} e^{+2 pi i pf x / L} sum_c ((g3 Gf g3)^H)[e][c] z_k^a[idx(c,x,tf)],
+                                  zeta_k^a = A^-1 s_k^a  (stage 2, the same tol; no deflation in either stage), and for
+                                  the branches d = (local, F_x, B_x, F_t, B_t), n = (x,t), n+mu as in mode 12:
+                                  S_k[0][j][a][b][f][c][t] = sum_x e^{-2 pi i q_j x / L} conj(zeta^a[idx(f,n)]) z^b[idx(c,n)],
+                                  S_k[F_mu] = sum_x e^{-2 pi i q_j x / L} U_mu(n) conj(zeta^a[idx(f,n)]) z^b[idx(c,n+mu)],
+                                  S_k[B_mu] = sum_x e^{-2 pi i q_j x / L} conj(U_mu(n)) conj(zeta^a[idx(f,n+mu)]) z^b[idx(c,n)].
+                                  Buffers of its own (sw_hutch_fetch_three_point; the last batches of the modes 4, 5,
+                                  6, 11 and 12 stay fetchable, and the reverse).  sw_hutch_fetch returns c_k =
+                                  sum_{a,c,x} |z_k^a[idx(c,x,tf)]|^2, the pion two-point value at the sink slice, and
+                                  per noise the largest stage-1 column count plus the largest stage-2 column count.
+                                  Refused before any launch at a level other than 0, without a registration and when
+                                  level 0 is no lattice level with links. */
 /* One batch of probes x_k in {-1,+1}^n (int8, nb*n, reference ordering) at `level`
  * (build-only extension: entries +-2 encode +-i, i.e. Z4 probes {1,i,-1,-i}):
  *   HUTCHINSON: e_k = x^H A^-1 Pperm^T (x - U U^H x)
@@ -526,6 +557,9 @@ int sw_hutch_fetch_link_loops(sw_engine* h, double* out);
 int sw_hutch_fetch_two_point(sw_engine* h, double* out);
 /* After a SW_MODE_TWO_POINT_LMA batch: out complex128[nmom][2][2][2][2][L][nb], the remainders R_k[j][a][b][c][d][t]. */
 int sw_hutch_fetch_two_point_lma(sw_engine* h, double* out);
+/* After a SW_MODE_THREE_POINT batch: out complex128[5][nmom][2][2][2][2][L][nb], the sums S_k[d][j][a][b][f][c][t] of
+ * every noise k of the batch ("no three-point batch to fetch" otherwise). */
+int sw_hutch_fetch_three_point(sw_engine* h, double* out);
 
 /* ---- multi-GPU: the one collective of the path ------------------------------------ */
 /* One process per GPU, one engine per process; the probe loop shards by probe and needs a single
@@ -567,6 +601,9 @@ int sw_timers_reset(sw_engine* h);
 #define SW_KCLASS_LM_CONTRACT 21    /* k_cgemm_nt, k_lm_two_point_reduce (sw_low_mode_two_point); in sw_timers: dots;
                                        sw_kernel_work counts 8 * (2 * 4L * ld^3 + (4L)^2 * k^2) flops per call */
 #define SW_KCLASS_LINK_DOTS 22      /* k_slice_link_dots (SW_MODE_HUTCHINSON_LINK_LOOPS); in sw_timers: dots */
+#define SW_KCLASS_3PT_SOURCES 23    /* k_seq_sources, k_pair_slice_total and the stage-1 k_slice_sources
+                                       (SW_MODE_THREE_POINT); in sw_timers: other */
+#define SW_KCLASS_3PT_DOTS 24       /* k_slice_seq_dots (SW_MODE_THREE_POINT); in sw_timers: dots */
 int sw_kernel_stats(sw_engine* h, int which, double* total_ms, int64_t* launches);
 /* Floating-point operations issued by the launches of an MFMA kernel class since the last reset
  * (profiling on): 8 flops per complex multiply-add over every (row tile, k-step, probe). */
