@@ -3998,32 +3998,37 @@ int sw_vcycle(sw_engine* h, int hid, int level0, int nb, const double* B, double
   return unpack_host(h, lv, nb, b, X, nbp);
 }
 
-// One operation of the complex64 cycle alone on host vectors (the per-kernel parity tests): fp64 in, cast to
-// complex64 (k_cast), ONE launch through the launcher vcycle32 / vcycle32_even use -- with the kernel category
-// they pass, so the options pick the variant exactly as in the cycle --, cast back (exact), fp64 out.  Rows the
-// operation does not write come back zero (in place: as they went in).
-int sw_apply_op32(sw_engine* h, int hid, int level, int which, int mode, int nb, const double* X, const double* B,
-                  double w_re, double w_im, int flags, double* Y, int32_t* info) {
+// What sw_apply_op32 and sw_apply_op64 share: the argument checks, the operator behind a `which` code with the
+// kernel category the cycles launch it under, and `info`.  f32: the complex64 entry point (its mirrors are made
+// here; it has the lattice level's even-odd kernels and no lattice operator, the fp64 one the reverse).
+struct OpSel {
+  const EllOp* op = nullptr;
+  int cat = T_MVM;
+  bool inplace = false, square = false, smoother = false, transfer = false, up = false;
+};
+static int select_op(sw_engine* h, const char* fn, bool f32, int hid, int level, int which, int mode, int nb,
+                     const double* X, const double* B, const double* Y, int flags, int32_t* info, OpSel* s) {
   SWCHK(check_hier(h, hid, level, true));
-  const bool inplace = (flags & SW_OP32_INPLACE) != 0;
-  const bool square = which == SW_OP32_A || (which >= SW_OP32_EO0 && which <= SW_OP32_EO0 + 4);
-  const bool smoother = which == SW_OP32_EO_SMOOTH || which == SW_OP32_EO_SMOOTH_REDUCED;
+  const bool inplace = s->inplace = (flags & SW_OP32_INPLACE) != 0;
+  const bool square = s->square = which == SW_OP32_A || (which >= SW_OP32_EO0 && which <= SW_OP32_EO0 + 4);
+  const bool smoother = s->smoother = which == SW_OP32_EO_SMOOTH || which == SW_OP32_EO_SMOOTH_REDUCED;
   if (which < 0 || which > SW_OP32_EO_SMOOTH_REDUCED || nb <= 0 || !X || !Y || (flags & ~SW_OP32_INPLACE))
-    return sw_fail(h, "sw_apply_op32: bad arguments");
+    return sw_fail(h, "%s: bad arguments", fn);
+  if (!f32 && (which == SW_OP32_SCHUR || smoother))
+    return sw_fail(h, "%s: operation %d (the lattice level's even-odd kernels) is not available here", fn, which);
   if (!(mode == 0 || (square && (mode == 1 || mode == 3))))
-    return sw_fail(h, "sw_apply_op32: operation %d has no mode %d", which, mode);
+    return sw_fail(h, "%s: operation %d has no mode %d", fn, which, mode);
   if (inplace && !(square && mode == 1))
-    return sw_fail(h, "sw_apply_op32: the in-place form is Y = X - op X (mode 1) of a square operator");
-  if (!B && ((mode != 0 && !inplace) || smoother)) return sw_fail(h, "sw_apply_op32: operation %d needs B", which);
+    return sw_fail(h, "%s: the in-place form is Y = X - op X (mode 1) of a square operator", fn);
+  if (!B && ((mode != 0 && !inplace) || smoother)) return sw_fail(h, "%s: operation %d needs B", fn, which);
   HIPCHK(hipSetDevice(h->device));
   Hier& H = h->hier[hid];
   const int last = H.nlevels - 1;
-  const bool transfer = which >= SW_OP32_R && which <= SW_OP32_RE;
+  const bool transfer = s->transfer = which >= SW_OP32_R && which <= SW_OP32_RE;
   if (transfer && level >= last) return sw_fail(h, "no transfer at the coarsest level");
   if (which == SW_OP32_COARSEST && level != last)
-    return sw_fail(h, "sw_apply_op32: the coarsest inverse acts on level %d", last);
+    return sw_fail(h, "%s: the coarsest inverse acts on level %d", fn, last);
   Level& lv = H.lv[level];
-  Level& lc = H.lv[transfer ? level + 1 : level];
   const bool on_stencil = which == SW_OP32_RE || which == SW_OP32_SCHUR || smoother;
   if (on_stencil && !(lv.stencil && lv.U1 && !lv.w_eo.empty()))
     return sw_fail(h, "level %d is not a lattice level with the even-odd smoother", level);
@@ -4037,15 +4042,19 @@ int sw_apply_op32(sw_engine* h, int hid, int level, int which, int mode, int nb,
     op = &lv.eo_op[which - SW_OP32_EO0];
     if (which == SW_OP32_EO0 + 4) cat = T_COARSEST;
   }
-  if (which == SW_OP32_A && lv.stencil) return sw_fail(h, "level %d is the lattice level: no complex64 operator", level);
+  if (which == SW_OP32_A && lv.stencil) {
+    if (f32) return sw_fail(h, "level %d is the lattice level: no complex64 operator", level);
+    if (!lv.U1) return sw_fail(h, "level %d: the lattice level has no gauge links", level);
+    if (inplace) return sw_fail(h, "%s: the stencil reads its neighbours' rows: no in-place form", fn);
+    op = nullptr;
+  }
   if (op && !op->set) return sw_fail(h, "level %d: operation %d has no operator", level, which);
-  const int nbp = pad64(nb);
-  SWCHK(ensure_f32(h, H));
+  if (f32) SWCHK(ensure_f32(h, H));
   if (which == SW_OP32_RE || which == SW_OP32_P_EVEN) {
     SWCHK(ensure_even_orders(h, H));
     if (which == SW_OP32_RE) {
       if (!lv.Re.set) return sw_fail(h, "level %d has no even-column restrictor", level);
-      SWCHK(mirror_op32(h, lv.Re));
+      if (f32) SWCHK(mirror_op32(h, lv.Re));
       op = &lv.Re;
       cat = T_R;
     } else if (!(lv.P.order_even && h->p_even)) {
@@ -4058,8 +4067,28 @@ int sw_apply_op32(sw_engine* h, int hid, int level, int which, int mode, int nb,
     info[2] = (op && op->cols) ? op->G : 0;
     info[3] = (op && op->cols) ? op->K : 0;
   }
+  s->op = op;
+  s->cat = cat;
+  s->up = which == SW_OP32_P || which == SW_OP32_P_EVEN;
+  return 0;
+}
+
+// One operation of the complex64 cycle alone on host vectors (the per-kernel parity tests): fp64 in, cast to
+// complex64 (k_cast), ONE launch through the launcher vcycle32 / vcycle32_even use -- with the kernel category
+// they pass, so the options pick the variant exactly as in the cycle --, cast back (exact), fp64 out.  Rows the
+// operation does not write come back zero (in place: as they went in).
+int sw_apply_op32(sw_engine* h, int hid, int level, int which, int mode, int nb, const double* X, const double* B,
+                  double w_re, double w_im, int flags, double* Y, int32_t* info) {
+  OpSel sel;
+  SWCHK(select_op(h, "sw_apply_op32", true, hid, level, which, mode, nb, X, B, Y, flags, info, &sel));
+  const bool inplace = sel.inplace, smoother = sel.smoother, up = sel.up;
+  const EllOp* op = sel.op;
+  const int cat = sel.cat;
+  Hier& H = h->hier[hid];
+  Level& lv = H.lv[level];
+  Level& lc = H.lv[sel.transfer ? level + 1 : level];
+  const int nbp = pad64(nb);
   // input on `lin`, output on `lout` (they differ for the transfers only)
-  const bool up = which == SW_OP32_P || which == SW_OP32_P_EVEN;
   Level& lin = up ? lc : lv;
   Level& lout = up ? lv : lc;
   SWCHK(ensure_level_ws32(h, lin, nbp));
@@ -4099,6 +4128,38 @@ int sw_apply_op32(sw_engine* h, int hid, int level, int which, int mode, int nb,
   if (which == SW_OP32_EO_SMOOTH_REDUCED)      // half vectors: the odd sites' rows were never the smoother's
     HIPCHK(hipMemsetAsync(d + cout / 2, 0, (cout / 2) * sizeof(cplx), h->stream));
   return unpack_host(h, lout, nb, d, Y, nbp);
+}
+
+// The fp64 twin: ONE launch through the launcher the fp64 cycle uses for the operation (launch_ell with the
+// cycle's kernel category, launch_stencil on the lattice level), no casts, so use_mfma, mfma_ops, mfma_3m, the
+// tile, stage, map and stencil options and the batch width pick the kernel variant exactly as in the cycle.  The
+// coarsest inverse is the dense operator itself (H.cinv), not the even-odd direct path of apply_coarsest.
+int sw_apply_op64(sw_engine* h, int hid, int level, int which, int mode, int nb, const double* X, const double* B,
+                  double w_re, double w_im, int flags, double* Y, int32_t* info) {
+  OpSel sel;
+  SWCHK(select_op(h, "sw_apply_op64", false, hid, level, which, mode, nb, X, B, Y, flags, info, &sel));
+  Hier& H = h->hier[hid];
+  Level& lv = H.lv[level];
+  Level& lc = H.lv[sel.transfer ? level + 1 : level];
+  Level& lin = sel.up ? lc : lv;
+  Level& lout = sel.up ? lv : lc;
+  const int nbp = pad64(nb);
+  SWCHK(ensure_level_ws(h, lin, nbp));
+  SWCHK(ensure_level_ws(h, lout, nbp));
+  // three distinct buffers also where input and output live on the same level
+  cplx* x = lin.b;
+  cplx* y = sel.inplace ? x : lout.x;
+  const cplx* b = sel.inplace ? x : nullptr;
+  SWCHK(pack_host(h, lin, nb, X, x, nbp));
+  if (mode != 0 && !sel.inplace) {
+    SWCHK(pack_host(h, lout, nb, B, lout.r, nbp));
+    b = lout.r;
+  }
+  if (!sel.inplace) HIPCHK(hipMemsetAsync(y, 0, (size_t)lout.n * nbp * sizeof(cplx), h->stream));
+  const cplx w{w_re, w_im};
+  if (!sel.op) SWCHK(launch_stencil<cplx, cplx>(h, lv, mode == 3 ? 2 : mode, x, b, y, nbp, w));
+  else SWCHK(launch_ell(h, *sel.op, mode, x, b, y, nbp, sel.cat, w, which == SW_OP32_P_EVEN));
+  return unpack_host(h, lout, nb, y, Y, nbp);
 }
 
 // ---------------------------------------------------------------------------------------------

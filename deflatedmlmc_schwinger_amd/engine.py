@@ -75,7 +75,8 @@ KCLASS_3PT_DOTS = 24       # ... and of k_slice_seq_dots
 SINK_GAMMAS = ('1', 'g3', 's1', 's2')      # the sink spin matrix codes of set_three_point
 MAX_SHIFTS = 128
 MAX_MOMENTA = 8
-# operations of Engine.apply_op32 (SW_OP32_* of the header): one kernel of the complex64 cycle at a time
+# operations of Engine.apply_op32 / apply_op64 (SW_OP32_* of the header): one kernel of the complex64 / fp64
+# cycle at a time
 OP32_A = 0
 OP32_R = 1
 OP32_P = 2
@@ -185,6 +186,7 @@ def load_library():
     sig("sw_apply_deflation", i32, vp, i32, i32, i32, vp, vp)
     sig("sw_vcycle", i32, vp, i32, i32, i32, vp, vp)
     sig("sw_apply_op32", i32, vp, i32, i32, i32, i32, i32, vp, vp, dbl, dbl, i32, vp, vp)
+    sig("sw_apply_op64", i32, vp, i32, i32, i32, i32, i32, vp, vp, dbl, dbl, i32, vp, vp)
     sig("sw_solve", i32, vp, i32, i32, i32, vp, vp, dbl, i32, vp, vp)
     sig("sw_hutch_batch", i32, vp, i32, i32, i32, vp, dbl, i32, vp, vp)
     sig("sw_probes_upload", i32, vp, i32, i32, vp)
@@ -255,7 +257,7 @@ EXPORTED_SYMBOLS = (
     "sw_get_level_bsr", "sw_setup_testvectors", "sw_setup_transfer",
     "sw_setup_galerkin", "sw_get_level_dense", "sw_setup_invert_coarsest", "sw_setup_direct_level", "sw_setup_level_inverse", "sw_setup_arnoldi", "sw_hier_end", "sw_set_deflation", "sw_set_level_deflation", "sw_set_perm", "sw_set_rhsmap", "sw_set_solver", "sw_set_option", "sw_get_option",
     "sw_pool_trim", "sw_get_coarsest_inv", "sw_eig_begin", "sw_eig_begin_wide", "sw_eig_load", "sw_eig_solve", "sw_eig_apply_diff", "sw_eig_gram", "sw_eig_rotate", "sw_eig_fetch", "sw_eig_end",
-    "sw_apply_dirac", "sw_restrict", "sw_prolong", "sw_coarsest", "sw_apply_deflation", "sw_vcycle", "sw_apply_op32", "sw_solve",
+    "sw_apply_dirac", "sw_restrict", "sw_prolong", "sw_coarsest", "sw_apply_deflation", "sw_vcycle", "sw_apply_op32", "sw_apply_op64", "sw_solve",
     "sw_hutch_batch", "sw_probes_upload", "sw_probes_upload_slot", "sw_probes_select",
     "sw_kernel_stats", "sw_kernel_work", "sw_hutch_run", "sw_sync", "sw_hutch_fetch",
     "sw_comm_unique_id", "sw_comm_init", "sw_allreduce_stats", "sw_comm_destroy",
@@ -688,6 +690,16 @@ class Engine:
         B - op X (1) or X + w (B - op X) (3) in complex64 through the cycle's own launcher, widened to complex128;
         in_place: mode 1 with B = Y = X on the device.  Returns (Y, info) with info = (row tiles, k-steps, ELL
         group size G, ELL entries per row K) of the operator applied."""
+        return self._apply_op(self._lib.sw_apply_op32, "sw_apply_op32", hid, level, which, X, B, mode, w, in_place)
+
+    def apply_op64(self, hid, level, which, X, B=None, mode=0, w=0.0, in_place=False):
+        """One operation of the fp64 cycle alone (sw_apply_op64): as apply_op32 without the casts, through the fp64
+        cycle's launcher; OP32_A also on the lattice level (the Wilson stencil), no Schur / even-odd smoother codes."""
+        return self._apply_op(self._lib.sw_apply_op64, "sw_apply_op64", hid, level, which, X, B, mode, w, in_place)
+
+    def _apply_op(self, fn, name, hid, level, which, X, B, mode, w, in_place):
+        if which in (OP32_R, OP32_P, OP32_P_EVEN, OP32_RE) and not 0 <= level < len(self.level_sizes[hid]) - 1:
+            raise EngineError("%s: no transfer from level %d" % (name, level))
         n_in = self._n(hid, level + 1) if which in (OP32_P, OP32_P_EVEN) else self._n(hid, level)
         n_out = self._n(hid, level + 1) if which in (OP32_R, OP32_RE) else self._n(hid, level)
         X2, single = self._io(X, n_in)
@@ -699,9 +711,9 @@ class Engine:
         Y = np.empty((X2.shape[0], n_out), dtype=np.complex128)
         info = np.zeros(4, dtype=np.int32)
         w = complex(w)
-        self._chk(self._lib.sw_apply_op32(self._h, hid, level, int(which), int(mode), X2.shape[0], _ptr(X2),
-                                          _ptr(B2) if B2 is not None else None, w.real, w.imag,
-                                          OP32_INPLACE if in_place else 0, _ptr(Y), _ptr(info)), "sw_apply_op32")
+        self._chk(fn(self._h, hid, level, int(which), int(mode), X2.shape[0], _ptr(X2),
+                     _ptr(B2) if B2 is not None else None, w.real, w.imag, OP32_INPLACE if in_place else 0, _ptr(Y),
+                     _ptr(info)), name)
         return (Y[0] if single else Y), tuple(int(v) for v in info)
 
     def solve(self, hid, level0, B, tol, maxiter=1000):

@@ -417,6 +417,15 @@ int sw_vcycle(sw_engine* h, int hid, int level0, int nb, const double* B, double
 #define SW_OP32_INPLACE 1
 int sw_apply_op32(sw_engine* h, int hid, int level, int which, int mode, int nb, const double* X, const double* B,
                   double w_re, double w_im, int flags, double* Y, int32_t* info);
+/* The fp64 twin of sw_apply_op32 (test-only): ONE operation of the fp64 cycle on host vectors, with no casts,
+ * through the launcher and kernel category that cycle uses, so use_mfma, mfma_ops, mfma_3m, the tile, stage, block
+ * map, dense_lds, ell_order, p_even and stencil options and the batch width select the kernel variant as they do
+ * there.  Same `which` codes, modes, flags, zeroed output and info.  SW_OP32_A also acts on the lattice level
+ * (the Wilson stencil; mode 3 is its fused step Y = X + w (B - A X), no in-place form); w is taken in full double
+ * precision.  SW_OP32_COARSEST is the dense inverse itself, not the even-odd direct path a directly solved
+ * coarsest level takes in the cycle.  SW_OP32_SCHUR and the two SW_OP32_EO_SMOOTH codes are refused. */
+int sw_apply_op64(sw_engine* h, int hid, int level, int which, int mode, int nb, const double* X, const double* B,
+                  double w_re, double w_im, int flags, double* Y, int32_t* info);
 /* Solve A_level0 X = B to ||r|| < tol*||b|| per right-hand side (MG.solve -> pyamg fgmres,
  * multigrid.py:347-366).  iters[nb], relres[nb] may be NULL.  Non-convergence within
  * maxiter is NOT an error (the reference discards exitCode); it is visible in relres. */
