@@ -1566,6 +1566,16 @@ static bool f32_capable(const Hier& H, int level);
 // z_j = M v_j, w_j = A z_j (v_0 = R, v_j = w_{j-1}) without orthogonalisation, one multigram pass over
 // [R, w_0 .. w_{L-1}] whose SW_TAIL_GRAM tail `tg` (tolerances, iteration base, counter, first_cycle set by
 // the caller) solves for y, then X += sum_j y_j z_j
+// (the cycle's BLAS-1 half, after its operator applications: pu = [R, w_0 .. w_{L-1}], pz = [z_0 .. z_{L-1}])
+static int gram_cycle_update(sw_engine* h, const PtrList& pu, const PtrList& pz, int L, int n, int nbp, cplx* X,
+                             KrylovWS& ws, swk::FgTail tg) {
+  tg.kind = SW_TAIL_GRAM;
+  tg.s = ws.sc;
+  tg.j = L;
+  tg.h1 = ws.gram;
+  SWCHK(multigram(h, pu, L + 1, n, nbp, ws.gram, &tg));
+  return multiaxpy(h, pz, L, ws.sc.ys, 1.0, X, X, n, nbp, nullptr);
+}
 static int gram_cycle(sw_engine* h, const KrylovSys& sys, const cplx* R, cplx* X, int L, KrylovWS& ws, int nbp,
                       swk::FgTail tg) {
   const size_t vec = (size_t)sys.n * nbp;
@@ -1579,12 +1589,7 @@ static int gram_cycle(sw_engine* h, const KrylovSys& sys, const cplx* R, cplx* X
     pu.p[j + 1] = w;
     pz.p[j] = z;
   }
-  tg.kind = SW_TAIL_GRAM;
-  tg.s = ws.sc;
-  tg.j = L;
-  tg.h1 = ws.gram;
-  SWCHK(multigram(h, pu, L + 1, sys.n, nbp, ws.gram, &tg));
-  return multiaxpy(h, pz, L, ws.sc.ys, 1.0, X, X, sys.n, nbp, nullptr);
+  return gram_cycle_update(h, pu, pz, L, sys.n, nbp, X, ws, tg);
 }
 
 // The K-cycle's inner iteration -- L steps of flexible GMRES from a zero guess, preconditioned by the cycle
@@ -2159,6 +2164,11 @@ static int read_slot(sw_engine* h, const int* slot, int* count) {
   *count = *h->h_notconv;
   return 0;
 }
+// y = H(0:k,0:k)^-1 g(0:k) and ys = svec y per probe, at the end of a restart cycle of k columns
+static int launch_fg_solve(sw_engine* h, const swk::FgScalars& sc, int k) {
+  const int tb = 256;
+  return launch(h, T_OTHER, swk::k_fg_solve, dim3((sc.nbp + tb - 1) / tb), dim3(tb), sc, k);
+}
 static swk::FgTail tail_begin(const KrylovWS& ws, int first_cycle) {
   swk::FgTail t{};
   t.kind = SW_TAIL_BEGIN;
@@ -2214,7 +2224,6 @@ static int fgmres_loop(sw_engine* h, Hier& H, int level, const KrylovSys& sys, c
   const int check_from = (outer && h->lazy_sync) ? std::max(0, h->sync_hint[hid_idx][level] - 2) : 0;
   const int n = sys.n;
   const size_t vec = (size_t)n * nbp;
-  const int tb = 256, tg = (nbp + tb - 1) / tb;
   const double tol_stop = outer ? tol * h->stop_factor : tol;
   // complex64 directions: the input copy of each Krylov vector is written by its producer
   const bool z32 = (bool)sys.precond32;
@@ -2332,7 +2341,7 @@ static int fgmres_loop(sw_engine* h, Hier& H, int level, const KrylovSys& sys, c
       }
     }
     const int k = j;  // columns built in this cycle
-    SWCHK(launch(h, T_OTHER, swk::k_fg_solve, dim3(tg), dim3(tb), ws.sc, k));
+    SWCHK(launch_fg_solve(h, ws.sc, k));
     if (z32) {
       swk::PtrListT<cplxf> pz;
       for (int q = 0; q < k; ++q) pz.p[q] = ws.Z32 + vec * q;
@@ -2411,21 +2420,28 @@ static int fgmres(sw_engine* h, Hier& H, int level, const cplx* B, cplx* X, doub
 // ---------------------------------------------------------------------------------------------
 // host <-> device vector movement in the reference layout
 // ---------------------------------------------------------------------------------------------
-static int pack_host(sw_engine* h, Level& lv, int nb, const double* Xhost, cplx* dst, int nbp) {
-  const size_t bytes = (size_t)nb * lv.n * sizeof(cplx);
+// host (nb, n) <-> device [n][nbp] (pad columns zero), rows through `rowmap` when there is one
+static int pack_rows(sw_engine* h, int n, const int* rowmap, int nb, const double* Xhost, cplx* dst, int nbp) {
+  const size_t bytes = (size_t)nb * n * sizeof(cplx);
   SWCHK(ensure_stage(h, bytes));
   HIPCHK(hipMemcpyAsync(h->stage, Xhost, bytes, hipMemcpyHostToDevice, h->stream));
-  return launch(h, T_OTHER, swk::k_pack_c, dim3((lv.n + 63) / 64, nbp / 64), dim3(SW_BLOCK), (const cplx*)h->stage,
-                nb, lv.n, (const int*)lv.rowmap, dst, nbp);
+  return launch(h, T_OTHER, swk::k_pack_c, dim3((n + 63) / 64, nbp / 64), dim3(SW_BLOCK), (const cplx*)h->stage,
+                nb, n, rowmap, dst, nbp);
 }
-static int unpack_host(sw_engine* h, Level& lv, int nb, const cplx* src, double* Yhost, int nbp) {
-  const size_t bytes = (size_t)nb * lv.n * sizeof(cplx);
+static int unpack_rows(sw_engine* h, int n, const int* rowmap, int nb, const cplx* src, double* Yhost, int nbp) {
+  const size_t bytes = (size_t)nb * n * sizeof(cplx);
   SWCHK(ensure_stage(h, bytes));
-  SWCHK(launch(h, T_OTHER, swk::k_unpack_c, dim3((lv.n + 63) / 64, nbp / 64), dim3(SW_BLOCK), src, nbp, lv.n,
-               (const int*)lv.rowmap, (cplx*)h->stage, nb));
+  SWCHK(launch(h, T_OTHER, swk::k_unpack_c, dim3((n + 63) / 64, nbp / 64), dim3(SW_BLOCK), src, nbp, n, rowmap,
+               (cplx*)h->stage, nb));
   HIPCHK(hipMemcpyAsync(Yhost, h->stage, bytes, hipMemcpyDeviceToHost, h->stream));
   SWCHK(stream_sync(h));
   return 0;
+}
+static int pack_host(sw_engine* h, Level& lv, int nb, const double* Xhost, cplx* dst, int nbp) {
+  return pack_rows(h, lv.n, (const int*)lv.rowmap, nb, Xhost, dst, nbp);
+}
+static int unpack_host(sw_engine* h, Level& lv, int nb, const cplx* src, double* Yhost, int nbp) {
+  return unpack_rows(h, lv.n, (const int*)lv.rowmap, nb, src, Yhost, nbp);
 }
 
 static int check_hier(sw_engine* h, int hid, int level, bool need_ready) {
@@ -2444,6 +2460,135 @@ static int io_vectors(sw_engine* h, Level& lv, int nbp, cplx** a, cplx** b) {
   // the cycle never uses lv.b / lv.x of its own start level, so they are free for I/O
   *a = lv.b;
   *b = lv.x;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// What the sw_krylov_* entry points share (one operation of the Krylov solver alone on host data, for the
+// per-kernel tests): small per-probe arrays host [rows][nb] <-> device [rows][nbp] with the pad columns zero
+// (cx: complex entries, otherwise the real parts alone), a Krylov workspace with the life of one call, and the
+// row blocking the production helper is about to choose.
+// ---------------------------------------------------------------------------------------------
+static int put_cols(sw_engine* h, cplx* dst, const double* src, int rows, int nb, int nbp, bool cx = true) {
+  std::vector<cplx> t((size_t)rows * nbp, cplx{0.0, 0.0});
+  for (int r = 0; r < rows; ++r)
+    for (int c = 0; c < nb; ++c) {
+      const size_t i = (size_t)r * nb + c;
+      t[(size_t)r * nbp + c] = cx ? cplx{src[2 * i], src[2 * i + 1]} : cplx{src[i], 0.0};
+    }
+  HIPCHK(hipMemcpyAsync(dst, t.data(), t.size() * sizeof(cplx), hipMemcpyHostToDevice, h->stream));
+  return stream_sync(h);
+}
+static int get_cols(sw_engine* h, const cplx* src, double* dst, int rows, int nb, int nbp, bool cx = true) {
+  std::vector<cplx> t((size_t)rows * nbp);
+  HIPCHK(hipMemcpyAsync(t.data(), src, t.size() * sizeof(cplx), hipMemcpyDeviceToHost, h->stream));
+  SWCHK(stream_sync(h));
+  for (int r = 0; r < rows; ++r)
+    for (int c = 0; c < nb; ++c) {
+      const size_t i = (size_t)r * nb + c;
+      const cplx v = t[(size_t)r * nbp + c];
+      if (cx) { dst[2 * i] = v.x; dst[2 * i + 1] = v.y; }
+      else dst[i] = v.x;
+    }
+  return 0;
+}
+static int put_ints(sw_engine* h, int* dst, const int32_t* src, int nb, int nbp) {
+  std::vector<int> t((size_t)nbp, 0);
+  for (int c = 0; c < nb; ++c) t[c] = src[c];
+  HIPCHK(hipMemcpyAsync(dst, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  return stream_sync(h);
+}
+static int get_ints(sw_engine* h, const int* src, int32_t* dst, int nb) {
+  std::vector<int> t((size_t)nb);
+  HIPCHK(hipMemcpyAsync(t.data(), src, t.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  SWCHK(stream_sync(h));
+  for (int c = 0; c < nb; ++c) dst[c] = t[c];
+  return 0;
+}
+struct KrylovScope {
+  sw_engine* h;
+  KrylovWS ws;
+  explicit KrylovScope(sw_engine* h_) : h(h_) {}
+  KrylovScope(const KrylovScope&) = delete;
+  KrylovScope& operator=(const KrylovScope&) = delete;
+  ~KrylovScope() {
+    std::string first;
+    first.swap(h->err);
+    (void)free_krylov(h, ws);
+    h->err.swap(first);
+  }
+};
+// info = {row blocks P, rows per block, 1 when the reduction is completed in the launch, groups of row blocks}
+static void blocking_info(sw_engine* h, int n, int nbp, bool reduce, int32_t* info) {
+  if (!info) return;
+  int P = 0, rpb = 0;
+  row_blocking(n, nbp, reduce, &P, &rpb);
+  info[0] = P;
+  info[1] = rpb;
+  info[2] = (reduce && fused_ok(h, P, nbp)) ? 1 : 0;
+  info[3] = (P + SW_RED_GROUP - 1) / SW_RED_GROUP;
+}
+// cnt host vectors (nb, n) -> device [cnt][n][nbp]
+static int pack_vectors(sw_engine* h, int n, int nb, int nbp, int cnt, const double* src, cplx* dst) {
+  for (int k = 0; k < cnt; ++k)
+    SWCHK(pack_rows(h, n, nullptr, nb, src + (size_t)k * nb * n * 2, dst + (size_t)n * nbp * k, nbp));
+  return 0;
+}
+// ... in storage C: the fp64 block itself, or its complex64 copy (k_cast: rounded to nearest) in `v32`
+template <class C>
+static int stored_as(sw_engine* h, cplx* v64, size_t count, DevBuf<cplxf>& v32, C** out) {
+  if constexpr (std::is_same<C, cplx>::value) {
+    *out = v64;
+  } else {
+    SWCHK(dev_realloc(h, &v32.p, count));
+    SWCHK(cast_vec(h, (const cplx*)v64, v32.p, count));
+    *out = v32.p;
+  }
+  return 0;
+}
+template <class CV>
+static int krylov_multidot(sw_engine* h, int n, int nb, int nbp, int K, const double* V, const double* W,
+                           const cplx* svec, cplx* out, cplx* coef) {
+  const size_t vec = (size_t)n * nbp;
+  DevBuf<cplx> v64(h);
+  DevBuf<cplxf> v32(h);
+  SWCHK(dev_realloc(h, &v64.p, vec * (K + 1)));       // (the K vectors and W in one block)
+  SWCHK(pack_vectors(h, n, nb, nbp, K, V, v64.p));
+  SWCHK(pack_vectors(h, n, nb, nbp, 1, W, v64.p + vec * K));
+  CV* v = nullptr;
+  SWCHK(stored_as<CV>(h, v64.p, vec * (K + 1), v32, &v));
+  swk::PtrListT<CV> pl;
+  for (int k = 0; k < K; ++k) pl.p[k] = v + vec * k;
+  SWCHK(multidot(h, pl, K, (const CV*)(v + vec * K), n, nbp, out, svec, coef));
+  return stream_sync(h);
+}
+template <class CV, class CW>
+static int krylov_multiaxpy(sw_engine* h, int n, int nb, int nbp, int K, const double* V, const cplx* coef,
+                            double sign, double* W, cplx* nrm, double* W32) {
+  const size_t vec = (size_t)n * nbp;
+  DevBuf<cplx> v64(h), w64(h);
+  DevBuf<cplxf> v32(h), w32s(h), wcopy(h);
+  SWCHK(dev_realloc(h, &v64.p, vec * K));
+  SWCHK(dev_realloc(h, &w64.p, vec));
+  CV* v = nullptr;
+  CW* w = nullptr;
+  SWCHK(pack_vectors(h, n, nb, nbp, K, V, v64.p));
+  SWCHK(pack_vectors(h, n, nb, nbp, 1, W, w64.p));
+  SWCHK(stored_as<CV>(h, v64.p, vec * K, v32, &v));
+  SWCHK(stored_as<CW>(h, w64.p, vec, w32s, &w));
+  if (W32) {
+    SWCHK(dev_realloc(h, &wcopy.p, vec));
+    HIPCHK(hipMemsetAsync(wcopy.p, 0xFF, vec * sizeof(cplxf), h->stream));
+  }
+  swk::PtrListT<CV> pl;
+  for (int k = 0; k < K; ++k) pl.p[k] = v + vec * k;
+  SWCHK(multiaxpy(h, pl, K, coef, sign, (const CW*)w, w, n, nbp, nrm, W32 ? wcopy.p : nullptr));   // in place
+  if constexpr (!std::is_same<CW, cplx>::value) SWCHK(cast_vec(h, (const cplxf*)w, w64.p, vec));
+  SWCHK(unpack_rows(h, n, nullptr, nb, w64.p, W, nbp));
+  if (W32) {
+    SWCHK(cast_vec(h, (const cplxf*)wcopy.p, w64.p, vec));
+    SWCHK(unpack_rows(h, n, nullptr, nb, w64.p, W32, nbp));
+  }
   return 0;
 }
 
@@ -4160,6 +4305,184 @@ int sw_apply_op64(sw_engine* h, int hid, int level, int which, int mode, int nb,
   if (!sel.op) SWCHK(launch_stencil<cplx, cplx>(h, lv, mode == 3 ? 2 : mode, x, b, y, nbp, w));
   else SWCHK(launch_ell(h, *sel.op, mode, x, b, y, nbp, sel.cat, w, which == SW_OP32_P_EVEN));
   return unpack_host(h, lout, nb, y, Y, nbp);
+}
+
+// ---------------------------------------------------------------------------------------------
+// One operation of the Krylov solver alone on host data (test-only, no hierarchy needed): each entry runs the
+// production host helper -- multidot, multigram + multiaxpy as gram_cycle_update, multiaxpy, launch_tail,
+// launch_fg_solve --, so row_blocking, fused_ok, red_args, the KT / NV instantiation and the options fused_reduce
+// and dot_blocks choose the launch exactly as in a solve.  Vectors in the (nb, n) host layout, per-probe arrays
+// [rows][nb]; on the device the pad columns up to nbp are zero.  Output buffers start as NaN patterns: an entry
+// a kernel does not write shows.
+// ---------------------------------------------------------------------------------------------
+static_assert(SW_KRYLOV_BEGIN == SW_TAIL_BEGIN && SW_KRYLOV_HESS == SW_TAIL_HESS &&
+                  SW_KRYLOV_VERIFY == SW_TAIL_VERIFY && SW_KRYLOV_SOLVE > SW_TAIL_GRAM,
+              "the operation codes of sw_krylov_scalars are the tail kinds");
+int sw_krylov_multidot(sw_engine* h, int n, int nb, int K, int storage, const double* V, const double* W,
+                       const double* svec, double* out, double* coef, int32_t* info) {
+  if (!h) return 1;
+  if (K < 1 || K > SW_MAXK) return sw_fail(h, "sw_krylov_multidot: K=%d out of [1,%d]", K, SW_MAXK);
+  if (n <= 0 || nb <= 0 || !V || !W || !out || (svec && !coef))
+    return sw_fail(h, "sw_krylov_multidot: bad arguments");
+  if (storage != SW_KRYLOV_C128 && storage != SW_KRYLOV_C64)
+    return sw_fail(h, "sw_krylov_multidot: unsupported storage %d", storage);
+  HIPCHK(hipSetDevice(h->device));
+  const int nbp = pad64(nb);
+  DevBuf<cplx> d(h);       // out [K][nbp], coef [K][nbp], svec [K][nbp]
+  const size_t cnt = (size_t)K * nbp;
+  SWCHK(dev_realloc(h, &d.p, 3 * cnt));
+  HIPCHK(hipMemsetAsync(d.p, 0xFF, 2 * cnt * sizeof(cplx), h->stream));
+  if (svec) SWCHK(put_cols(h, d.p + 2 * cnt, svec, K, nb, nbp, false));
+  const cplx* sv = svec ? d.p + 2 * cnt : nullptr;
+  cplx* cf = svec ? d.p + cnt : nullptr;
+  blocking_info(h, n, nbp, true, info);
+  if (storage == SW_KRYLOV_C64) SWCHK(krylov_multidot<cplxf>(h, n, nb, nbp, K, V, W, sv, d.p, cf));
+  else SWCHK(krylov_multidot<cplx>(h, n, nb, nbp, K, V, W, sv, d.p, cf));
+  // (out comes back at the padded width: its pad columns are part of what is checked)
+  SWCHK(get_cols(h, d.p, out, K, nbp, nbp));
+  if (svec) SWCHK(get_cols(h, d.p + cnt, coef, K, nb, nbp));
+  return 0;
+}
+
+int sw_krylov_gram_cycle(sw_engine* h, int n, int nb, int NV, int flags, const double* U, const double* Z,
+                         double* X, double* normb, int32_t* iters, double tol, double tol_stop, int iter_base,
+                         double* gram, double* ys, double* relres, double* g, int32_t* notconv, int32_t* info) {
+  if (!h) return 1;
+  if (NV < 2 || NV > SW_GRAM_MAXL + 1)
+    return sw_fail(h, "sw_krylov_gram_cycle: %d vectors out of [2,%d]", NV, SW_GRAM_MAXL + 1);
+  const bool with_tail = !(flags & SW_KRYLOV_NOTAIL);
+  if (n <= 0 || nb <= 0 || !U || !gram || (flags & ~(SW_KRYLOV_INIT | SW_KRYLOV_NOTAIL)) ||
+      (with_tail && (!Z || !X || !normb || !iters || !ys || !relres || !g || !notconv)))
+    return sw_fail(h, "sw_krylov_gram_cycle: bad arguments");
+  HIPCHK(hipSetDevice(h->device));
+  const int nbp = pad64(nb), L = NV - 1, K = NV * (NV + 1) / 2;
+  const size_t vec = (size_t)n * nbp;
+  blocking_info(h, n, nbp, true, info);
+  KrylovScope ks(h);
+  KrylovWS& ws = ks.ws;
+  SWCHK(ensure_krylov(h, ws, L, n, nbp, false));
+  DevBuf<cplx> rx(h);      // r0, X
+  SWCHK(dev_realloc(h, &rx.p, 2 * vec));
+  cplx* r0 = rx.p;
+  cplx* x = rx.p + vec;
+  SWCHK(pack_vectors(h, n, nb, nbp, 1, U, r0));
+  SWCHK(pack_vectors(h, n, nb, nbp, L, U + (size_t)nb * n * 2, ws.V));
+  PtrList pu, pz;
+  pu.p[0] = r0;
+  for (int j = 0; j < L; ++j) {
+    pu.p[j + 1] = ws.V + vec * j;
+    pz.p[j] = ws.Z + vec * j;
+  }
+  HIPCHK(hipMemsetAsync(ws.gram, 0xFF, (size_t)K * nbp * sizeof(cplx), h->stream));
+  if (!with_tail) {
+    SWCHK(multigram(h, pu, NV, n, nbp, ws.gram, nullptr));
+    return get_cols(h, ws.gram, gram, K, nb, nbp);
+  }
+  SWCHK(pack_vectors(h, n, nb, nbp, L, Z, ws.Z));
+  SWCHK(pack_vectors(h, n, nb, nbp, 1, X, x));
+  SWCHK(put_cols(h, ws.sc.normb, normb, 1, nb, nbp, false));
+  SWCHK(put_ints(h, ws.sc.iters, iters, nb, nbp));
+  HIPCHK(hipMemsetAsync(ws.sc.ys, 0xFF, (size_t)L * nbp * sizeof(cplx), h->stream));
+  HIPCHK(hipMemsetAsync(ws.sc.relres, 0xFF, (size_t)nbp * sizeof(cplx), h->stream));
+  HIPCHK(hipMemsetAsync(ws.sc.g, 0xFF, (size_t)nbp * sizeof(cplx), h->stream));
+  SWCHK(reset_slots(h));
+  swk::FgTail tg{};
+  tg.tol = tol;
+  tg.tol_stop = tol_stop;
+  tg.iter_base = iter_base;
+  tg.first_cycle = (flags & SW_KRYLOV_INIT) ? 1 : 0;
+  SWCHK(take_slot(h, &tg.notconv));
+  SWCHK(gram_cycle_update(h, pu, pz, L, n, nbp, x, ws, tg));
+  int left = 0;
+  SWCHK(read_slot(h, tg.notconv, &left));
+  *notconv = left;
+  SWCHK(get_cols(h, ws.gram, gram, K, nb, nbp));
+  SWCHK(get_cols(h, ws.sc.ys, ys, L, nb, nbp));
+  SWCHK(get_cols(h, ws.sc.relres, relres, 1, nb, nbp, false));
+  SWCHK(get_cols(h, ws.sc.g, g, 1, nb, nbp, false));
+  SWCHK(get_cols(h, ws.sc.normb, normb, 1, nb, nbp, false));
+  SWCHK(get_ints(h, ws.sc.iters, iters, nb));
+  return unpack_rows(h, n, nullptr, nb, x, X, nbp);
+}
+
+int sw_krylov_multiaxpy(sw_engine* h, int n, int nb, int K, int storage_v, int storage_w, int flags,
+                        const double* V, const double* coef, double sign, double* W, double* nrm, double* W32,
+                        int32_t* info) {
+  if (!h) return 1;
+  if (K < 1 || K > SW_MAXK) return sw_fail(h, "sw_krylov_multiaxpy: K=%d out of [1,%d]", K, SW_MAXK);
+  const bool norm = (flags & SW_KRYLOV_NORM) != 0, w32 = (flags & SW_KRYLOV_W32) != 0;
+  if (n <= 0 || nb <= 0 || !V || !coef || !W || (flags & ~(SW_KRYLOV_NORM | SW_KRYLOV_W32)) || (norm && !nrm) ||
+      (w32 && !W32))
+    return sw_fail(h, "sw_krylov_multiaxpy: bad arguments");
+  // the storage pairs fgmres_loop instantiates: the fp64 basis and the iterate (V, W fp64), the complex64 basis
+  // of f32_krylov (both complex64), complex64 directions into the fp64 iterate
+  const bool v32 = storage_v == SW_KRYLOV_C64, wc32 = storage_w == SW_KRYLOV_C64;
+  if ((storage_v != SW_KRYLOV_C128 && !v32) || (storage_w != SW_KRYLOV_C128 && !wc32) || (!v32 && wc32))
+    return sw_fail(h, "sw_krylov_multiaxpy: unsupported storage pair V %d, W %d", storage_v, storage_w);
+  if (w32 && wc32) return sw_fail(h, "sw_krylov_multiaxpy: the complex64 copy goes with an fp64 W");
+  HIPCHK(hipSetDevice(h->device));
+  const int nbp = pad64(nb);
+  DevBuf<cplx> d(h);       // coef [K][nbp], nrm [nbp]
+  const size_t cnt = (size_t)K * nbp;
+  SWCHK(dev_realloc(h, &d.p, cnt + nbp));
+  SWCHK(put_cols(h, d.p, coef, K, nb, nbp));
+  HIPCHK(hipMemsetAsync(d.p + cnt, 0xFF, (size_t)nbp * sizeof(cplx), h->stream));
+  cplx* nr = norm ? d.p + cnt : nullptr;
+  blocking_info(h, n, nbp, norm, info);
+  double* c32 = w32 ? W32 : nullptr;
+  if (v32 && wc32) SWCHK(krylov_multiaxpy<cplxf, cplxf>(h, n, nb, nbp, K, V, d.p, sign, W, nr, c32));
+  else if (v32) SWCHK(krylov_multiaxpy<cplxf, cplx>(h, n, nb, nbp, K, V, d.p, sign, W, nr, c32));
+  else SWCHK(krylov_multiaxpy<cplx, cplx>(h, n, nb, nbp, K, V, d.p, sign, W, nr, c32));
+  if (norm) SWCHK(get_cols(h, nr, nrm, 1, nb, nbp, false));
+  return 0;
+}
+
+int sw_krylov_scalars(sw_engine* h, int m, int nb, int op, int j, int flag, double tol, double tol_stop,
+                      int iter_base, const double* h1, const double* h2, const double* nrm, double* state,
+                      int32_t* iters, int32_t* notconv) {
+  if (!h) return 1;
+  if (m < 1 || m > SW_MAXM) return sw_fail(h, "sw_krylov_scalars: restart %d out of [1,%d]", m, SW_MAXM);
+  if (nb <= 0 || !state || !iters || !notconv) return sw_fail(h, "sw_krylov_scalars: bad arguments");
+  const bool hess = op == SW_TAIL_HESS, solve = op == SW_KRYLOV_SOLVE;
+  if (!(op == SW_TAIL_BEGIN || hess || op == SW_TAIL_VERIFY || solve))
+    return sw_fail(h, "sw_krylov_scalars: unknown operation %d", op);
+  if ((hess && (j < 0 || j >= m || !h1)) || (solve && (j < 0 || j > m)))
+    return sw_fail(h, "sw_krylov_scalars: column %d out of range", j);
+  if (!solve && !nrm && !(hess && flag)) return sw_fail(h, "sw_krylov_scalars: operation %d needs nrm", op);
+  HIPCHK(hipSetDevice(h->device));
+  const int nbp = pad64(nb);
+  KrylovScope ks(h);
+  KrylovWS& ws = ks.ws;
+  SWCHK(ensure_krylov(h, ws, m, 0, nbp, false));
+  // the packed state: H, cs, sn, g, y, normb, relres, svec, ys, each [rows][nb] complex
+  struct Part { cplx* p; int rows; };
+  const Part parts[] = {{ws.sc.H, (m + 1) * m}, {ws.sc.cs, m}, {ws.sc.sn, m}, {ws.sc.g, m + 1}, {ws.sc.y, m},
+                        {ws.sc.normb, 1},       {ws.sc.relres, 1}, {ws.sc.svec, m + 1}, {ws.sc.ys, m}};
+  size_t off = 0;
+  for (const Part& q : parts) {
+    SWCHK(put_cols(h, q.p, state + off, q.rows, nb, nbp));
+    off += (size_t)q.rows * nb * 2;
+  }
+  SWCHK(put_ints(h, ws.sc.iters, iters, nb, nbp));
+  if (h1) SWCHK(put_cols(h, ws.h1, h1, m + 2, nb, nbp));
+  if (h2) SWCHK(put_cols(h, ws.h2, h2, m + 2, nb, nbp));
+  if (nrm) SWCHK(put_cols(h, ws.nrm, nrm, 1, nb, nbp, false));
+  SWCHK(reset_slots(h));
+  int* slot = nullptr;
+  SWCHK(take_slot(h, &slot));
+  if (solve) SWCHK(launch_fg_solve(h, ws.sc, j));
+  else if (op == SW_TAIL_BEGIN) SWCHK(launch_tail(h, tail_begin(ws, flag ? 1 : 0)));
+  else if (hess) SWCHK(launch_tail(h, tail_hess(ws, j, h2 != nullptr, flag != 0, tol, tol_stop, iter_base, slot)));
+  else SWCHK(launch_tail(h, tail_verify(ws, tol, tol_stop, slot)));
+  int left = 0;
+  SWCHK(read_slot(h, slot, &left));
+  *notconv = left;
+  off = 0;
+  for (const Part& q : parts) {
+    SWCHK(get_cols(h, q.p, state + off, q.rows, nb, nbp));
+    off += (size_t)q.rows * nb * 2;
+  }
+  return get_ints(h, ws.sc.iters, iters, nb);
 }
 
 // ---------------------------------------------------------------------------------------------

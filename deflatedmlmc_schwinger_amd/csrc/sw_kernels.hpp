@@ -2511,7 +2511,17 @@ __global__ __launch_bounds__(SW_BLOCK) void k_gram(PtrList U, int n, int nbp, in
 #pragma unroll
     for (int a = 0; a < NV; ++a)
 #pragma unroll
-      for (int b = a; b < NV; ++b) cfmac(acc[k++], u[a], u[b]);
+      for (int b = a; b < NV; ++b) {
+        if (b == a) {
+          // |u_a|^2 is real: the two fused multiply-adds of cfmac's real part; its imaginary part would leave
+          // fma(-y, x, fl(x y)), the rounding error of x y, where exactly 0 belongs
+          acc[k].x = fma(u[a].x, u[a].x, acc[k].x);
+          acc[k].x = fma(u[a].y, u[a].y, acc[k].x);
+          ++k;
+        } else {
+          cfmac(acc[k++], u[a], u[b]);
+        }
+      }
   }
   if (wave > 0) {
 #pragma unroll

@@ -88,6 +88,15 @@ OP32_SCHUR = 11
 OP32_EO_SMOOTH = 12
 OP32_EO_SMOOTH_REDUCED = 13
 OP32_INPLACE = 1
+# Engine.krylov_* (SW_KRYLOV_* of the header): one operation of the Krylov solver alone
+KRYLOV_C128, KRYLOV_C64 = 0, 1
+KRYLOV_INIT, KRYLOV_NOTAIL = 1, 2
+KRYLOV_NORM, KRYLOV_W32 = 1, 2
+KRYLOV_BEGIN, KRYLOV_HESS, KRYLOV_VERIFY, KRYLOV_SOLVE = 1, 2, 3, 5
+# the packed FGMRES state of sw_krylov_scalars: (key, rows of nb complex entries for restart length m)
+KRYLOV_STATE = (("H", lambda m: (m + 1) * m), ("cs", lambda m: m), ("sn", lambda m: m), ("g", lambda m: m + 1),
+                ("y", lambda m: m), ("normb", lambda m: 1), ("relres", lambda m: 1), ("svec", lambda m: m + 1),
+                ("ys", lambda m: m))
 PROBES_Z2 = 1
 PROBES_Z4 = 2
 PROBE_KINDS = {"z2": PROBES_Z2, "z4": PROBES_Z4}
@@ -187,6 +196,11 @@ def load_library():
     sig("sw_vcycle", i32, vp, i32, i32, i32, vp, vp)
     sig("sw_apply_op32", i32, vp, i32, i32, i32, i32, i32, vp, vp, dbl, dbl, i32, vp, vp)
     sig("sw_apply_op64", i32, vp, i32, i32, i32, i32, i32, vp, vp, dbl, dbl, i32, vp, vp)
+    sig("sw_krylov_multidot", i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp)
+    sig("sw_krylov_gram_cycle", i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, dbl, dbl, i32, vp, vp, vp, vp,
+        P(i32), vp)
+    sig("sw_krylov_multiaxpy", i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, dbl, vp, vp, vp, vp)
+    sig("sw_krylov_scalars", i32, vp, i32, i32, i32, i32, i32, dbl, dbl, i32, vp, vp, vp, vp, vp, P(i32))
     sig("sw_solve", i32, vp, i32, i32, i32, vp, vp, dbl, i32, vp, vp)
     sig("sw_hutch_batch", i32, vp, i32, i32, i32, vp, dbl, i32, vp, vp)
     sig("sw_probes_upload", i32, vp, i32, i32, vp)
@@ -258,6 +272,7 @@ EXPORTED_SYMBOLS = (
     "sw_setup_galerkin", "sw_get_level_dense", "sw_setup_invert_coarsest", "sw_setup_direct_level", "sw_setup_level_inverse", "sw_setup_arnoldi", "sw_hier_end", "sw_set_deflation", "sw_set_level_deflation", "sw_set_perm", "sw_set_rhsmap", "sw_set_solver", "sw_set_option", "sw_get_option",
     "sw_pool_trim", "sw_get_coarsest_inv", "sw_eig_begin", "sw_eig_begin_wide", "sw_eig_load", "sw_eig_solve", "sw_eig_apply_diff", "sw_eig_gram", "sw_eig_rotate", "sw_eig_fetch", "sw_eig_end",
     "sw_apply_dirac", "sw_restrict", "sw_prolong", "sw_coarsest", "sw_apply_deflation", "sw_vcycle", "sw_apply_op32", "sw_apply_op64", "sw_solve",
+    "sw_krylov_multidot", "sw_krylov_gram_cycle", "sw_krylov_multiaxpy", "sw_krylov_scalars",
     "sw_hutch_batch", "sw_probes_upload", "sw_probes_upload_slot", "sw_probes_select",
     "sw_kernel_stats", "sw_kernel_work", "sw_hutch_run", "sw_sync", "sw_hutch_fetch",
     "sw_comm_unique_id", "sw_comm_init", "sw_allreduce_stats", "sw_comm_destroy",
@@ -715,6 +730,120 @@ class Engine:
                      _ptr(B2) if B2 is not None else None, w.real, w.imag, OP32_INPLACE if in_place else 0, _ptr(Y),
                      _ptr(info)), name)
         return (Y[0] if single else Y), tuple(int(v) for v in info)
+
+    # -- one operation of the Krylov solver alone (sw_krylov_*, test-only; no hierarchy needed) -----------------
+    # vectors (nb, n) or stacks (K, nb, n), per-probe arrays (rows, nb); info = (row blocks P, rows per block,
+    # 1 when the reduction was completed in the launch, groups of 32 row blocks)
+    def krylov_multidot(self, V, W, svec=None, c64=False):
+        """out[k] = V_k^H W through multidot (k_multidot<KT, complex128 or complex64>).  Returns (out[K, nb],
+        coef[K, nb] = svec^2 out or None, largest |pad column entry| of out, info)."""
+        V, W = _c128(V), _c128(W)
+        K, nb, n = V.shape
+        if W.shape != (nb, n):
+            raise EngineError("W must be %d x %d" % (nb, n))
+        nbp = (nb + 63) // 64 * 64
+        out = np.empty((K, nbp), dtype=np.complex128)
+        coef = sv = None
+        if svec is not None:
+            sv = np.ascontiguousarray(svec, dtype=np.float64)
+            if sv.shape != (K, nb):
+                raise EngineError("svec must be %d x %d" % (K, nb))
+            coef = np.empty((K, nb), dtype=np.complex128)
+        info = np.zeros(4, dtype=np.int32)
+        self._chk(self._lib.sw_krylov_multidot(self._h, n, nb, K, KRYLOV_C64 if c64 else KRYLOV_C128, _ptr(V), _ptr(W),
+                                               _ptr(sv) if sv is not None else None, _ptr(out),
+                                               _ptr(coef) if coef is not None else None, _ptr(info)),
+                  "sw_krylov_multidot")
+        pad = out[:, nb:]
+        # (a NaN in the pad columns -- an entry no kernel wrote -- must not pass for zero)
+        pad_max = float(np.nan_to_num(np.abs(pad), nan=np.inf).max()) if pad.size else 0.0
+        return np.ascontiguousarray(out[:, :nb]), coef, pad_max, tuple(int(v) for v in info)
+
+    def krylov_gram(self, U):
+        """All inner products of the NV vectors U[NV, nb, n] through multigram without a tail (k_gram<NV>):
+        (gram[NV (NV + 1) / 2, nb], info)."""
+        U = _c128(U)
+        NV, nb, n = U.shape
+        gram = np.empty((max(NV * (NV + 1) // 2, 1), nb), dtype=np.complex128)
+        info = np.zeros(4, dtype=np.int32)
+        self._chk(self._lib.sw_krylov_gram_cycle(self._h, n, nb, NV, KRYLOV_NOTAIL, _ptr(U), None, None, None, None,
+                                                 0.0, 0.0, 0, _ptr(gram), None, None, None, None, _ptr(info)),
+                  "sw_krylov_gram_cycle")
+        return gram, tuple(int(v) for v in info)
+
+    def krylov_gram_cycle(self, U, Z, X, normb, iters, tol, tol_stop, iter_base=0, init=False):
+        """The BLAS-1 half of a Gram-matrix restart cycle (gram_cycle after its operator applications): multigram
+        over U = [r0, w_0 .. w_{L-1}] with the Gram tail, then X += sum_j ys_j z_j.  Returns a dict: gram, ys,
+        relres, g, normb, iters, notconv, X, info."""
+        U, Z, X = _c128(U), _c128(Z), _c128(X).copy()
+        NV, nb, n = U.shape
+        L = NV - 1
+        if Z.shape != (L, nb, n) or X.shape != (nb, n):
+            raise EngineError("Z must be %d x %d x %d and X %d x %d" % (L, nb, n, nb, n))
+        normb = np.array(normb, dtype=np.float64).reshape(nb).copy()
+        iters = np.array(iters, dtype=np.int32).reshape(nb).copy()
+        gram = np.empty((max(NV * (NV + 1) // 2, 1), nb), dtype=np.complex128)
+        ys = np.empty((max(L, 1), nb), dtype=np.complex128)
+        relres, g = np.empty(nb), np.empty(nb)
+        notconv = C.c_int32(0)
+        info = np.zeros(4, dtype=np.int32)
+        self._chk(self._lib.sw_krylov_gram_cycle(self._h, n, nb, NV, KRYLOV_INIT if init else 0, _ptr(U), _ptr(Z),
+                                                 _ptr(X), _ptr(normb), _ptr(iters), float(tol), float(tol_stop),
+                                                 int(iter_base), _ptr(gram), _ptr(ys), _ptr(relres), _ptr(g),
+                                                 C.byref(notconv), _ptr(info)), "sw_krylov_gram_cycle")
+        return dict(gram=gram, ys=ys, relres=relres, g=g, normb=normb, iters=iters, notconv=int(notconv.value), X=X,
+                    info=tuple(int(v) for v in info))
+
+    def krylov_multiaxpy(self, V, coef, sign, W, v_c64=False, w_c64=False, norm=False, w32=False):
+        """W + sign sum_k coef[k] V_k in place through multiaxpy (k_multiaxpy<KT, NORM, CV, CW>).  Returns (Wout,
+        |Wout|^2 per column or None, the complex64 copy widened or None, info)."""
+        V, W = _c128(V), _c128(W).copy()
+        K, nb, n = V.shape
+        coef = _c128(coef)
+        if W.shape != (nb, n) or coef.shape != (K, nb):
+            raise EngineError("W must be %d x %d and coef %d x %d" % (nb, n, K, nb))
+        nrm = np.empty(nb) if norm else None
+        W32 = np.empty_like(W) if w32 else None
+        info = np.zeros(4, dtype=np.int32)
+        self._chk(self._lib.sw_krylov_multiaxpy(self._h, n, nb, K, KRYLOV_C64 if v_c64 else KRYLOV_C128,
+                                                KRYLOV_C64 if w_c64 else KRYLOV_C128,
+                                                (KRYLOV_NORM if norm else 0) | (KRYLOV_W32 if w32 else 0), _ptr(V),
+                                                _ptr(coef), float(sign), _ptr(W), _ptr(nrm) if norm else None,
+                                                _ptr(W32) if w32 else None, _ptr(info)), "sw_krylov_multiaxpy")
+        return W, nrm, W32, tuple(int(v) for v in info)
+
+    def krylov_scalars(self, state, op, j=0, flag=0, tol=0.0, tol_stop=0.0, iter_base=0, h1=None, h2=None, nrm=None):
+        """One FGMRES scalar update (op = KRYLOV_BEGIN / HESS / VERIFY through k_fg_tail, KRYLOV_SOLVE = k_fg_solve
+        with k = j) on `state`, a dict of H[m + 1, m, nb], cs, sn, y, ys[m, nb], g, svec[m + 1, nb], normb,
+        relres[nb] (complex or real) and iters[nb].  Returns (new state, notconv)."""
+        m, nb = np.asarray(state["cs"]).shape
+        parts = []
+        for key, rows in KRYLOV_STATE:
+            a = _c128(state[key]).reshape(-1, nb)
+            if a.shape[0] != rows(m):
+                raise EngineError("state[%r] must have %d rows" % (key, rows(m)))
+            parts.append(a)
+        packed = np.ascontiguousarray(np.concatenate(parts, axis=0))
+        iters = np.array(state["iters"], dtype=np.int32).reshape(nb).copy()
+
+        def small(a, rows, dtype):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype)
+            if a.shape != (rows, nb):
+                raise EngineError("a %d x %d array is needed" % (rows, nb))
+            return a
+        h1, h2 = small(h1, m + 2, np.complex128), small(h2, m + 2, np.complex128)
+        nrm = small(None if nrm is None else np.asarray(nrm).reshape(1, nb), 1, np.float64)
+        notconv = C.c_int32(0)
+        self._chk(self._lib.sw_krylov_scalars(self._h, m, nb, int(op), int(j), int(flag), float(tol), float(tol_stop),
+                                              int(iter_base), *[_ptr(a) if a is not None else None for a in (h1, h2, nrm)],
+                                              _ptr(packed), _ptr(iters), C.byref(notconv)), "sw_krylov_scalars")
+        new, r = {"iters": iters}, 0
+        for key, rows in KRYLOV_STATE:
+            new[key] = packed[r:r + rows(m)].reshape(np.asarray(state[key]).shape).copy()
+            r += rows(m)
+        return new, int(notconv.value)
 
     def solve(self, hid, level0, B, tol, maxiter=1000):
         B2, single = self._io(B, self._n(hid, level0))

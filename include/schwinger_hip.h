@@ -426,6 +426,56 @@ int sw_apply_op32(sw_engine* h, int hid, int level, int which, int mode, int nb,
  * coarsest level takes in the cycle.  SW_OP32_SCHUR and the two SW_OP32_EO_SMOOTH codes are refused. */
 int sw_apply_op64(sw_engine* h, int hid, int level, int which, int mode, int nb, const double* X, const double* B,
                   double w_re, double w_im, int flags, double* Y, int32_t* info);
+/* ---- one operation of the Krylov solver alone (test-only) -----------------------------------
+ * The batched BLAS-1 kernels and the per-probe FGMRES scalar updates, one operation per call on host data, each
+ * through the host helper the solves use, so the row blocking, the in-launch or two-stage reduction (options
+ * fused_reduce, dot_blocks), and the KT / NV kernel instantiation are chosen exactly as in a solve.  No hierarchy
+ * is needed.  Vectors: n rows, nb columns, (nb, n) host layout as everywhere else, complex128; per-probe arrays
+ * [rows][nb], complex128 unless said to be real.  storage: SW_KRYLOV_C128, or SW_KRYLOV_C64 -- the operands are
+ * rounded to complex64 on the device and the complex64 instantiation runs.  info (may be NULL) receives {row
+ * blocks P, rows per block, 1 when the reduction was completed inside the launch, groups of 32 row blocks}. */
+#define SW_KRYLOV_C128 0
+#define SW_KRYLOV_C64 1
+/* out[K][nbp] = V_k^H W (k_multidot; nbp = nb rounded up to 64: the pad columns come back too and must be zero),
+ * V = K vectors one after the other; with svec[K][nb] (real) also coef[K][nb] = svec^2 out.  1 <= K <= 34. */
+int sw_krylov_multidot(sw_engine* h, int n, int nb, int K, int storage, const double* V, const double* W,
+                       const double* svec, double* out, double* coef, int32_t* info);
+/* The BLAS-1 half of a restart cycle in Gram-matrix form: U = the NV = L + 1 vectors [r0, w_0 .. w_{L-1}], Z the L
+ * directions; k_gram with the Gram tail (Cholesky solve per probe), then X += sum_j ys_j z_j (k_multiaxpy).
+ * In/out: X, normb[nb] (real), iters[nb]; out: gram[NV (NV + 1) / 2][nb] (entry (a, b), a <= b, at
+ * a NV - a (a - 1) / 2 + (b - a)), ys[L][nb], relres[nb], g[nb] (real: |r_L| / |b| and |r_0| / |b|), notconv = the
+ * probes left above tol_stop.  flags: SW_KRYLOV_INIT (r0 is the right-hand side: sets normb and iters),
+ * SW_KRYLOV_NOTAIL (the inner products alone: only U and gram are used).  2 <= NV <= 5; refused when the
+ * in-launch reduction is not available (fused_reduce off, or too many row blocks). */
+#define SW_KRYLOV_INIT 1
+#define SW_KRYLOV_NOTAIL 2
+int sw_krylov_gram_cycle(sw_engine* h, int n, int nb, int NV, int flags, const double* U, const double* Z,
+                         double* X, double* normb, int32_t* iters, double tol, double tol_stop, int iter_base,
+                         double* gram, double* ys, double* relres, double* g, int32_t* notconv, int32_t* info);
+/* W <- W + sign sum_k coef[k] V_k in place (k_multiaxpy).  flags: SW_KRYLOV_NORM (nrm[nb] (real) = |W|^2 of the
+ * values before they are narrowed to the storage of W), SW_KRYLOV_W32 (W32 = the complex64 copy of the new W,
+ * widened; fp64 W only).  Storage pairs (V, W): (C128, C128), (C64, C64), (C64, C128); others are refused. */
+#define SW_KRYLOV_NORM 1
+#define SW_KRYLOV_W32 2
+int sw_krylov_multiaxpy(sw_engine* h, int n, int nb, int K, int storage_v, int storage_w, int flags,
+                        const double* V, const double* coef, double sign, double* W, double* nrm, double* W32,
+                        int32_t* info);
+/* One per-probe scalar update of FGMRES(m) on an uploaded state (k_fg_tail, k_fg_solve).  state, in and out: H
+ * [(m + 1) m], cs [m], sn [m], g [m + 1], y [m], normb [1], relres [1], svec [m + 1], ys [m] rows of nb complex
+ * entries, one block after the other (H row-major: entry (i, j) in row i m + j); iters[nb] in and out.
+ *   SW_KRYLOV_BEGIN   start of a cycle from nrm[nb] (real) = |r|^2; flag: first cycle (fixes normb, iters, relres)
+ *   SW_KRYLOV_HESS    column j from the raw inner products h1[(m + 2)][nb], h2 (second Gram-Schmidt pass, or NULL)
+ *                     and nrm = |vtilde_{j+1}|^2; flag: the last-step form, |A ztilde_j|^2 in row j + 1 of h1, nrm unused
+ *   SW_KRYLOV_VERIFY  true-residual check from nrm = |b - A x|^2
+ *   SW_KRYLOV_SOLVE   y = H(0:j, 0:j)^-1 g(0:j), ys = svec y
+ * notconv = the probes HESS / VERIFY left above tol_stop. */
+#define SW_KRYLOV_BEGIN 1
+#define SW_KRYLOV_HESS 2
+#define SW_KRYLOV_VERIFY 3
+#define SW_KRYLOV_SOLVE 5
+int sw_krylov_scalars(sw_engine* h, int m, int nb, int op, int j, int flag, double tol, double tol_stop,
+                      int iter_base, const double* h1, const double* h2, const double* nrm, double* state,
+                      int32_t* iters, int32_t* notconv);
 /* Solve A_level0 X = B to ||r|| < tol*||b|| per right-hand side (MG.solve -> pyamg fgmres,
  * multigrid.py:347-366).  iters[nb], relres[nb] may be NULL.  Non-convergence within
  * maxiter is NOT an error (the reference discards exitCode); it is visible in relres. */
