@@ -69,9 +69,10 @@ enum TimerCat { T_MVM = 0, T_DEFL, T_P, T_R, T_AXPY, T_DOTS, T_COARSEST, T_OTHER
                 T_LINK_DOTS,    // k_slice_link_dots of SW_MODE_HUTCHINSON_LINK_LOOPS
                 T_3PT_SOURCES,  // k_seq_sources / k_pair_slice_total of SW_MODE_THREE_POINT
                 T_3PT_DOTS,     // k_slice_seq_dots of SW_MODE_THREE_POINT
+                T_SMEAR,        // k_smear_step / k_smear_fused of SW_MODE_TWO_POINT_SMEARED / sw_apply_smearing
                 T_NCAT };
 // classes >= T_STENCIL are folded into the mvm / coarsest (two-point and three-point: other / dots; slice cdots,
-// meson fields, their contraction and the link dots: dots) buckets by
+// meson fields, their contraction and the link dots: dots; smearing: other) buckets by
 // sw_timers and reported separately by sw_kernel_stats
 
 struct EllOp {
@@ -359,6 +360,15 @@ struct sw_engine {
   cplx *tp_rhs = nullptr, *tp_z = nullptr;
   size_t tp_ws_cap = 0;
   ResultBuf r_tp;
+  // smeared sources and sinks (sw_set_smearing, SW_MODE_TWO_POINT_SMEARED): a registration of its own -- kappa with
+  // the two coefficients of a step as the kernels take them, the source steps, the ascending sink steps, a
+  // (timeslice, x, spin) -> internal row table of its own -- and the pair sums
+  // T[sink level][momentum][a][b][c][d][t][noise]
+  double sm_kappa = 0.0, sm_c0 = 1.0, sm_c1 = 0.0;
+  int sm_source = 0;
+  std::vector<int32_t> sm_sink;
+  int* sm_slicerow = nullptr;
+  ResultBuf r_tps;
   // low-mode averaging (sw_set_low_mode_inverse, sw_meson_fields, SW_MODE_TWO_POINT_LMA): G [lm_k][lm_k] row-major
   // for the registered deflation vectors (lm_k = kd, 0: none), the tables of sw_meson_fields, the coefficients
   // c and c' [2][ld][columns], and the remainder R = T(z, z) - T(z_L, z_L) of the last batch with T(z_L, z_L)'s
@@ -426,7 +436,7 @@ struct sw_engine {
 // every fetchable result (a new definition of the reference hierarchy drops them all)
 static constexpr ResultBuf sw_engine::* kResults[] = {&sw_engine::r_shifts, &sw_engine::r_loops, &sw_engine::r_mloops,
                                                       &sw_engine::r_links,  &sw_engine::r_tp,    &sw_engine::r_lma,
-                                                      &sw_engine::r_t3};
+                                                      &sw_engine::r_t3,    &sw_engine::r_tps};
 
 // ---------------------------------------------------------------------------------------------
 // engine options (sw_set_option / sw_get_option): one entry per name.  Bool fields take value != 0, int
@@ -2770,6 +2780,7 @@ int sw_hier_begin(sw_engine* h, int hid, int nlevels) {
     h->tp_momenta.clear();
     h->lm_k = 0;
     h->t3_momenta.clear();
+    h->sm_sink.clear();
     for (auto r : kResults) (h->*r).drop();
   }
   return 0;
@@ -5307,10 +5318,10 @@ static int check_momenta(sw_engine* h, const char* what, int nmom, const int32_t
   }
   return 0;
 }
+static int upload_slicerow(sw_engine* h, int** d_slicerow);
 static int upload_slice_tables(sw_engine* h, int nmom, const int32_t* p, int** d_mom, cplx** d_phase,
                                int** d_slicerow) {
-  Level& lv = h->hier[0].lv[0];
-  const int L = lv.L, n = lv.n;
+  const int L = h->hier[0].lv[0].L;
   std::vector<int> mom(p, p + nmom);
   mom.resize(SW_MAX_MOMENTA, mom[0]);
   SWCHK(upload(h, d_mom, mom.data(), mom.size()));
@@ -5326,6 +5337,11 @@ static int upload_slice_tables(sw_engine* h, int nmom, const int32_t* p, int** d
     }
   }
   SWCHK(upload(h, d_phase, ph.data(), ph.size()));
+  return upload_slicerow(h, d_slicerow);
+}
+static int upload_slicerow(sw_engine* h, int** d_slicerow) {
+  Level& lv = h->hier[0].lv[0];
+  const int L = lv.L, n = lv.n;
   // reference index idx(a,x,t) = a L^2 + t L + x
   std::vector<int> sr((size_t)n);
   for (int t = 0; t < L; ++t)
@@ -5770,6 +5786,7 @@ int sw_set_two_point(sw_engine* h, int t0, int nmom, const int32_t* p) {
     return sw_fail(h, "%d momenta: at most %d per registration", nmom, SW_MAX_MOMENTA);
   h->r_tp.drop();
   h->r_lma.drop();
+  h->r_tps.drop();
   if (nmom == 0) {
     h->tp_momenta.clear();
     return 0;
@@ -5809,20 +5826,24 @@ static int slice_sources(sw_engine* h, Level& lv, const int8_t* probes, int nb, 
 
 // res[j][a][b][c][d][t][k] from the solutions Z [n][2 M nq]: the p = 0 instantiation for the registered
 // momentum 0, the phased one over the others; total (optional) = sum_t sum_ac T[j0][a][a][c][c][t][k]
-static int pair_dots(sw_engine* h, Level& lv, const cplx* Z, int nq, ResultBuf& res, cplx* total) {
+// (pair_dots_into: the same launches into `out`, M 16 L rows of a buffer the caller has begun)
+static int pair_dots_into(sw_engine* h, Level& lv, const cplx* Z, int nq, cplx* out, cplx* total) {
   const int M = (int)h->tp_momenta.size(), L = lv.L;
   const int ncols = 2 * M * nq;
-  SWCHK(result_begin(h, res, (size_t)M * 16 * L, nq));
   SWCHK(launch(h, T_TP_DOTS, swk::k_slice_pair_dots<false>, dim3(L, nq / 64, 1), dim3(SW_BLOCK), Z,
                (const int*)h->tp_slicerow, (const cplx*)h->tp_phase, (const int*)h->tp_mom, h->tp_j0, L, nq, ncols,
-               res.p));
+               out));
   if (M > 1)
     SWCHK(launch(h, T_TP_DOTS, swk::k_slice_pair_dots<true>, dim3(L, nq / 64, M - 1), dim3(SW_BLOCK), Z,
                  (const int*)h->tp_slicerow, (const cplx*)h->tp_phase, (const int*)h->tp_mom, h->tp_j0, L, nq,
-                 ncols, res.p));
+                 ncols, out));
   if (!total) return 0;
-  return launch(h, T_TP_DOTS, swk::k_pair_total, dim3(nq / 64), dim3(SW_BLOCK), (const cplx*)res.p, h->tp_j0, L,
-                nq, total);
+  return launch(h, T_TP_DOTS, swk::k_pair_total, dim3(nq / 64), dim3(SW_BLOCK), (const cplx*)out, h->tp_j0, L, nq,
+                total);
+}
+static int pair_dots(sw_engine* h, Level& lv, const cplx* Z, int nq, ResultBuf& res, cplx* total) {
+  SWCHK(result_begin(h, res, h->tp_momenta.size() * 16 * lv.L, nq));
+  return pair_dots_into(h, lv, Z, nq, res.p, total);
 }
 
 static int two_point_args(sw_engine* h, int nb, const void* in, const void* out) {
@@ -5877,6 +5898,95 @@ int sw_hutch_fetch_two_point(sw_engine* h, double* out) {
 
 int sw_hutch_fetch_two_point_lma(sw_engine* h, double* out) {
   return fetch_result(h, &sw_engine::r_lma, "no low-mode averaged two-point batch to fetch", out);
+}
+
+// ---- smeared sources and sinks: gauge-covariant Jacobi smearing of the two-point functions' quark fields -----
+int sw_set_smearing(sw_engine* h, double kappa, int source_steps, int nsink, const int32_t* sink_steps) {
+  SWCHK(check_hier(h, 0, 0, false));
+  if (nsink < 0 || nsink > SW_MAX_SINK_LEVELS)
+    return sw_fail(h, "%d sink smearing levels: at most %d per registration", nsink, SW_MAX_SINK_LEVELS);
+  h->r_tps.drop();
+  if (nsink == 0) {
+    h->sm_sink.clear();
+    return 0;
+  }
+  Level& lv = h->hier[0].lv[0];
+  if (!lv.stencil || !lv.U1 || !lv.U2 || lv.h_rowmap.empty())
+    return sw_fail(h, "smearing needs a lattice level 0 with links (sw_set_lattice)");
+  if (!sink_steps) return sw_fail(h, "null sink step list");
+  if (!(kappa > 0.0) || !std::isfinite(kappa))
+    return sw_fail(h, "smearing kappa %g has to be positive and finite", kappa);
+  if (source_steps < 0 || source_steps > SW_MAX_SMEARING_STEPS)
+    return sw_fail(h, "%d source smearing steps outside [0,%d]", source_steps, SW_MAX_SMEARING_STEPS);
+  for (int i = 0; i < nsink; ++i) {
+    if (sink_steps[i] < 0 || sink_steps[i] > SW_MAX_SMEARING_STEPS)
+      return sw_fail(h, "%d sink smearing steps outside [0,%d]", (int)sink_steps[i], SW_MAX_SMEARING_STEPS);
+    if (i > 0 && sink_steps[i] <= sink_steps[i - 1])
+      return sw_fail(h, "sink smearing steps have to ascend strictly (%d after %d)", (int)sink_steps[i],
+                     (int)sink_steps[i - 1]);
+  }
+  HIPCHK(hipSetDevice(h->device));
+  SWCHK(stream_sync(h));
+  SWCHK(upload_slicerow(h, &h->sm_slicerow));
+  h->sm_kappa = kappa;
+  // the two coefficients of a step (smear_site): each two roundings away from its exact value
+  h->sm_c0 = 1.0 / (1.0 + 2.0 * kappa);
+  h->sm_c1 = kappa / (1.0 + 2.0 * kappa);
+  h->sm_source = source_steps;
+  h->sm_sink.assign(sink_steps, sink_steps + nsink);
+  return 0;
+}
+
+static int smearing_ready(sw_engine* h) {
+  if (h->sm_sink.empty()) return sw_fail(h, "no smearing registration (sw_set_smearing)");
+  return 0;
+}
+static bool smear_has_fused(int L) { return L == 16 || L == 128; }
+
+// X [n][ncols] <- S^steps X on the nt timeslices from t_first on (both spins), in place: the fused kernel where L has
+// an instantiation and `fused`, else `steps` launches of k_smear_step alternating with `tmp` (as large as X; only
+// the rows of those lines are written) and, after an odd count, the copy back.  steps = 0: nothing is launched.
+static int smear(sw_engine* h, Level& lv, cplx* X, cplx* tmp, int ncols, int t_first, int nt, int steps, bool fused) {
+  if (steps == 0) return 0;
+  const dim3 grid(2 * nt, ncols / 64);
+  const int* sr = h->sm_slicerow;
+  const cplx* U = lv.U1;
+  if (fused && lv.L == 16)
+    return launch(h, T_SMEAR, swk::k_smear_fused<4>, grid, dim3(SW_BLOCK), X, sr, U, t_first, ncols, h->sm_c0,
+                  h->sm_c1, steps);
+  if (fused && lv.L == 128)
+    return launch(h, T_SMEAR, swk::k_smear_fused<32>, grid, dim3(SW_BLOCK), X, sr, U, t_first, ncols, h->sm_c0,
+                  h->sm_c1, steps);
+  cplx *a = X, *b = tmp;
+  for (int k = 0; k < steps; ++k, std::swap(a, b))
+    SWCHK(launch(h, T_SMEAR, swk::k_smear_step<false>, grid, dim3(SW_BLOCK), (const cplx*)a, b, sr, U, lv.L, t_first,
+                 ncols, h->sm_c0, h->sm_c1));
+  if (a == X) return 0;
+  return launch(h, T_SMEAR, swk::k_smear_step<true>, grid, dim3(SW_BLOCK), (const cplx*)tmp, X, sr, U, lv.L, t_first,
+                ncols, h->sm_c0, h->sm_c1);
+}
+
+// Y = S^steps X on nb host vectors (reference ordering), every timeslice: the smearing kernels alone.
+int sw_apply_smearing(sw_engine* h, int nb, int steps, int fused, const double* X, double* Y) {
+  SWCHK(check_hier(h, 0, 0, false));
+  SWCHK(smearing_ready(h));
+  if (nb <= 0 || !X || !Y) return sw_fail(h, "bad arguments");
+  if (steps < 0 || steps > SW_MAX_SMEARING_STEPS)
+    return sw_fail(h, "%d smearing steps outside [0,%d]", steps, SW_MAX_SMEARING_STEPS);
+  Level& lv = h->hier[0].lv[0];
+  if (fused && !smear_has_fused(lv.L))
+    return sw_fail(h, "no fused smearing kernel for L=%d (16 and 128 have one)", lv.L);
+  HIPCHK(hipSetDevice(h->device));
+  const int nbp = pad64(nb);
+  cplx *a, *b;
+  SWCHK(io_vectors(h, lv, nbp, &a, &b));
+  SWCHK(pack_host(h, lv, nb, X, a, nbp));
+  SWCHK(smear(h, lv, a, b, nbp, 0, lv.L, steps, fused != 0));
+  return unpack_host(h, lv, nb, a, Y, nbp);
+}
+
+int sw_hutch_fetch_two_point_smeared(sw_engine* h, double* out) {
+  return fetch_result(h, &sw_engine::r_tps, "no smeared two-point batch to fetch", out);
 }
 
 // ---- three-point functions: sequential one-end-trick solves and a local or point-split insertion ---------
@@ -6144,6 +6254,34 @@ static int body_two_point(sw_engine* h, const Batch& b) {
   return batch_tail(h, b, total, G, {&h->r_lma});
 }
 
+// SW_MODE_TWO_POINT_SMEARED: mode 6 with the sources smeared on their timeslice after the phase, and the solution
+// block smeared in place, on every timeslice, from one registered sink level to the next (the increments add up:
+// S_a S_b = S_{a+b}); the pair sums of level i land in slab i of the mode's buffer.  pb_est = the pion total of
+// slab 0, real and positive at any level.  The fused kernel where L has one, else the one-step chain with the
+// source block as its second buffer (the solve is over: the sources are no longer needed).
+static int body_two_point_smeared(sw_engine* h, const Batch& b) {
+  Level& lv = h->hier[0].lv[0];
+  const int n = lv.n, nb = b.nb, nbp = b.nbp, L = lv.L;
+  const int M = (int)h->tp_momenta.size(), G = 2 * M, ncols = G * nbp, nsink = (int)h->sm_sink.size();
+  const bool fused = smear_has_fused(L);
+  SWCHK(ensure_two_point_ws(h, (size_t)n * ncols));
+  SWCHK(slice_sources(h, lv, h->pb_probes, nb, nbp, h->tp_rhs));
+  SWCHK(smear(h, lv, h->tp_rhs, h->tp_z, ncols, h->tp_t0, 1, h->sm_source, fused));
+  int total = 0;
+  SWCHK(solve_dev(h, b.hid, 0, h->tp_rhs, h->tp_z, b.tol, b.maxiter, ncols, &total));
+  const size_t slab = (size_t)M * 16 * L;
+  SWCHK(result_begin(h, h->r_tps, nsink * slab, nbp));
+  int done = 0;
+  for (int i = 0; i < nsink; ++i) {
+    SWCHK(smear(h, lv, h->tp_z, h->tp_rhs, ncols, 0, L, h->sm_sink[i] - done, fused));
+    done = h->sm_sink[i];
+    SWCHK(pair_dots_into(h, lv, h->tp_z, nbp, h->r_tps.p + i * slab * nbp, nullptr));
+  }
+  SWCHK(launch(h, T_TP_DOTS, swk::k_pair_total, dim3(nbp / 64), dim3(SW_BLOCK), (const cplx*)h->r_tps.p, h->tp_j0, L,
+               nbp, h->pb_est));
+  return batch_tail(h, b, total, G, {&h->r_tps});
+}
+
 // Stage 1: the two spin sources of every noise at momentum 0 and their solutions z (no deflation); stage 2: the
 // sequential sources through the sink, written over the stage-1 sources, and their solutions zeta to the same tol;
 // then the field x field sums of zeta and z.  pb_est = c_k, the pion two-point value at the sink slice.  Iterations
@@ -6270,6 +6408,10 @@ static int two_point_lma_ready(sw_engine* h, int level) {
   SWCHK(two_point_ready(h, level));
   return low_mode_ready(h);
 }
+static int two_point_smeared_ready(sw_engine* h, int level) {
+  SWCHK(two_point_ready(h, level));
+  return smearing_ready(h);
+}
 static const ProbeMode kModes[] = {
     {SW_MODE_HUTCHINSON, "Hutchinson", 0, nullptr, body_hutchinson},
     {SW_MODE_MLMC, nullptr, 1, nullptr, body_mlmc},
@@ -6289,6 +6431,7 @@ static const ProbeMode kModes[] = {
      body_loops},
     {SW_MODE_THREE_POINT, "three-point", 0, [](sw_engine* h, int) { return three_point_ready(h); },
      body_three_point},
+    {SW_MODE_TWO_POINT_SMEARED, "smeared two-point", 0, two_point_smeared_ready, body_two_point_smeared},
 };
 
 int sw_hutch_run(sw_engine* h, int mode, int level, double tol, int maxiter) {
@@ -6507,7 +6650,7 @@ int sw_timers(sw_engine* h, double t[8]) {
   t[T_MVM] += h->tacc[T_STENCIL] + h->tacc[T_STENCIL_RES] + h->tacc[T_STENCIL_SM] + h->tacc[T_MFMA_OP] +
               h->tacc[T_MFMA_OP2] + h->tacc[T_SCHUR] + h->tacc[T_SCHUR_OP];
   t[T_COARSEST] += h->tacc[T_MFMA_DENSE];
-  t[T_OTHER] += h->tacc[T_TP_SOURCES] + h->tacc[T_3PT_SOURCES];
+  t[T_OTHER] += h->tacc[T_TP_SOURCES] + h->tacc[T_3PT_SOURCES] + h->tacc[T_SMEAR];
   t[T_DOTS] += h->tacc[T_TP_DOTS] + h->tacc[T_SLICE_CDOTS] + h->tacc[T_MESON_FIELD] + h->tacc[T_LM_CONTRACT] +
                h->tacc[T_LINK_DOTS] + h->tacc[T_3PT_DOTS];
   return 0;

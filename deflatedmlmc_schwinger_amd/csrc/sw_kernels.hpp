@@ -3913,6 +3913,108 @@ __global__ __launch_bounds__(SW_BLOCK) void k_pair_total(const cplx* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------
+// Gauge-covariant Jacobi (Wuppertal) smearing in the spatial direction (sw_set_smearing, SW_MODE_TWO_POINT_SMEARED):
+// on the line (spin s, timeslice t), with U = U1 in the natural site order t L + x,
+//   (H psi)(x) = U(x,t) psi(x+1) + conj(U(x-1,t)) psi(x-1)      (x +- 1 mod L),      S = (1 + kappa H) / (1 + 2 kappa).
+// A field is a block [row][column], lane = column; a line's rows come from slicerow[(t L + x) 2 + s].  line =
+// blockIdx.x -> s = line & 1, t = t_first + (line >> 1): the 2 lines of a source timeslice or all 2 L of the lattice.
+// ------------------------------------------------------------------------------------------
+// ONE site of ONE step, the arithmetic definition both kernels share: c = psi(x), p = psi(x+1), q = psi(x-1),
+// u = U(x), v = U(x-1), c0 = 1 / (1 + 2 kappa), c1 = kappa / (1 + 2 kappa) as the host rounded them.  Every operation
+// is spelled out (one multiplication, then fused multiply-adds in this order), so that no contraction choice of
+// the compiler can make two kernels differ:
+//   h.re = fma(u.re, p.re, fma(-u.im, p.im, fma(v.im, q.im, v.re * q.re)))
+//   h.im = fma(u.re, p.im, fma( u.im, p.re, fma(-v.im, q.re, v.re * q.im)))
+//   y    = fma(c1, h, c0 * c)                                                  per component
+__device__ __forceinline__ cplx smear_site(cplx c, cplx p, cplx q, cplx u, cplx v, double c0, double c1) {
+  double hr = v.x * q.x;
+  hr = __builtin_fma(v.y, q.y, hr);
+  hr = __builtin_fma(-u.y, p.y, hr);
+  hr = __builtin_fma(u.x, p.x, hr);
+  double hi = v.x * q.y;
+  hi = __builtin_fma(-v.y, q.x, hi);
+  hi = __builtin_fma(u.y, p.x, hi);
+  hi = __builtin_fma(u.x, p.y, hi);
+  return cmake(__builtin_fma(c1, hr, c0 * c.x), __builtin_fma(c1, hi, c0 * c.y));
+}
+
+// One step out of place, any L: Y = S X on the lines of the grid, rows off those lines untouched.  grid = (lines,
+// ncols / 64); the four waves take x = wave, wave + 4, ...; a lane reads its site and the two neighbours (the
+// neighbours' rows again through slicerow), the two links are the same in all lanes (uniform loads).  COPY: Y = X on
+// the same rows instead (what brings an odd chain of steps back into the buffer it started from).
+template <bool COPY>
+__global__ __launch_bounds__(SW_BLOCK) void k_smear_step(const cplx* __restrict__ X, cplx* __restrict__ Y,
+                                                         const int* __restrict__ slicerow,
+                                                         const cplx* __restrict__ U1, int L, int t_first, int ncols,
+                                                         double c0, double c1) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int s = blockIdx.x & 1, t = t_first + (int)(blockIdx.x >> 1);
+  const size_t col = (size_t)blockIdx.y * 64 + lane;
+  const int* __restrict__ sr = slicerow + (size_t)t * L * 2 + s;
+  const cplx* __restrict__ U = U1 + (size_t)t * L;
+  for (int x = wave; x < L; x += SW_WAVES_PER_BLOCK) {
+    const size_t r = (size_t)sr[2 * x] * ncols + col;
+    if constexpr (COPY) {
+      Y[r] = X[r];
+    } else {
+      const int xp = x + 1 == L ? 0 : x + 1, xm = x == 0 ? L - 1 : x - 1;
+      const cplx p = X[(size_t)sr[2 * xp] * ncols + col], q = X[(size_t)sr[2 * xm] * ncols + col];
+      Y[r] = smear_site(X[r], p, q, U[x], U[xm], c0, c1);
+    }
+  }
+}
+
+// `steps` steps with one read and one write of the field, in place, for a lattice of L = 4 SEG sites a side.  A
+// workgroup owns one line and one 64-column group; wave w holds the SEG sites x = w SEG .. (w + 1) SEG - 1 of its
+// 64 columns in registers (fully unrolled: no register array is indexed dynamically); the links are the same in all
+// lanes and their index is wave-uniform, so they come through the scalar path (the compiler keeps a line's links
+// in scalar registers and the lanes of a spare vector register across the steps).  Per step a wave publishes its
+// first and last site to LDS, ONE barrier, reads the last site of the wave to its left and the first of the wave to
+// its right (cyclic), and updates its segment in place from left to right with one saved old neighbour.  The
+// exchange buffer alternates between two halves, so a wave that runs ahead into step k + 1 writes the half nobody
+// reads before the next barrier.  Every site goes through smear_site with the operands of k_smear_step: the result
+// equals `steps` launches of it bit for bit.  No atomics, no scratch, no traffic to the field between the first
+// read and the last write.
+template <int SEG>
+__global__ __launch_bounds__(SW_BLOCK) void k_smear_fused(cplx* __restrict__ X, const int* __restrict__ slicerow,
+                                                          const cplx* __restrict__ U1, int t_first, int ncols,
+                                                          double c0, double c1, int steps) {
+  constexpr int L = SEG * SW_WAVES_PER_BLOCK;
+  __shared__ __attribute__((aligned(16))) cplx edge[2][SW_WAVES_PER_BLOCK][2][64];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int s = blockIdx.x & 1, t = t_first + (int)(blockIdx.x >> 1);
+  // a row's base is wave-uniform (scalar registers); a lane adds its column's byte offset, 32 bits: ncols < 2^28
+  const unsigned coff = (blockIdx.y * 64 + lane) * (unsigned)sizeof(cplx);
+  const int x0 = wave * SEG;
+  const int* __restrict__ sr = slicerow + ((size_t)t * L + x0) * 2 + s;
+  const cplx* __restrict__ lk = U1 + (size_t)t * L;
+  cplx v[SEG];
+#pragma unroll
+  for (int i = 0; i < SEG; ++i) v[i] = *(const cplx*)((const char*)(X + (size_t)sr[2 * i] * ncols) + coff);
+  const int wl = (wave + SW_WAVES_PER_BLOCK - 1) % SW_WAVES_PER_BLOCK, wr = (wave + 1) % SW_WAVES_PER_BLOCK;
+  const int xl = x0 == 0 ? L - 1 : x0 - 1;            // the site left of the segment: its link enters site x0
+  for (int k = 0; k < steps; ++k) {
+    const int half = k & 1;
+    edge[half][wave][0][lane] = v[0];
+    edge[half][wave][1][lane] = v[SEG - 1];
+    __syncthreads();
+    cplx left = edge[half][wl][1][lane];               // old psi(x0 - 1)
+    const cplx right = edge[half][wr][0][lane];        // old psi(x0 + SEG)
+    cplx ul = lk[xl];
+#pragma unroll
+    for (int i = 0; i < SEG; ++i) {
+      const cplx u = lk[x0 + i];
+      const cplx old = v[i];
+      v[i] = smear_site(old, i + 1 < SEG ? v[i + 1 < SEG ? i + 1 : i] : right, left, u, ul, c0, c1);
+      left = old;
+      ul = u;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < SEG; ++i) *(cplx*)((char*)(X + (size_t)sr[2 * i] * ncols) + coff) = v[i];
+}
+
+// ------------------------------------------------------------------------------------------
 // Three-point functions (SW_MODE_THREE_POINT): per noise k the one-end-trick solutions z^a = A^-1 eta^a of the two
 // spin sources on the timeslice t0, the sequential sources through the sink
 //   s^a[idx(e,x,t)] = delta_t,tf e^{+2 pi i pf x / L} sum_c ((g3 Gf g3)^H)[e][c] z^a[idx(c,x,tf)],

@@ -29,6 +29,7 @@ MODE_MLMC_DEFL_LOOPS_SKIP = 10
 MODE_TWO_POINT_LMA = 11
 MODE_HUTCHINSON_LINK_LOOPS = 12
 MODE_THREE_POINT = 13
+MODE_TWO_POINT_SMEARED = 14
 # estimator method -> (mode, mode of the level-skipping form at level 0); "mlmc_defl_loops" is "mlmc_loops" deflated
 _METHOD_MODES = {"hutchinson": (MODE_HUTCHINSON, MODE_HUTCHINSON),
                  "mlmc": (MODE_MLMC, MODE_MLMC_SKIP),
@@ -38,6 +39,7 @@ _METHOD_MODES = {"hutchinson": (MODE_HUTCHINSON, MODE_HUTCHINSON),
                  "link_loops": (MODE_HUTCHINSON_LINK_LOOPS, MODE_HUTCHINSON_LINK_LOOPS),
                  "two_point": (MODE_TWO_POINT, MODE_TWO_POINT),
                  "two_point_lma": (MODE_TWO_POINT_LMA, MODE_TWO_POINT_LMA),
+                 "two_point_smeared": (MODE_TWO_POINT_SMEARED, MODE_TWO_POINT_SMEARED),
                  "three_point": (MODE_THREE_POINT, MODE_THREE_POINT),
                  "mlmc_loops": (MODE_MLMC_LOOPS, MODE_MLMC_LOOPS_SKIP),
                  "mlmc_defl_loops": (MODE_MLMC_DEFL_LOOPS, MODE_MLMC_DEFL_LOOPS_SKIP)}
@@ -47,6 +49,7 @@ RESOLVED_FETCH = {MODE_HUTCHINSON_SHIFTS: "hutch_fetch_shifts",
                   MODE_HUTCHINSON_LINK_LOOPS: "hutch_fetch_link_resolved",
                   MODE_TWO_POINT: "hutch_fetch_two_point",
                   MODE_TWO_POINT_LMA: "hutch_fetch_two_point_lma",
+                  MODE_TWO_POINT_SMEARED: "hutch_fetch_two_point_smeared",
                   MODE_THREE_POINT: "hutch_fetch_three_point_resolved",
                   MODE_MLMC_LOOPS: "hutch_fetch_mlmc_loops",
                   MODE_MLMC_LOOPS_SKIP: "hutch_fetch_mlmc_loops",
@@ -72,6 +75,9 @@ KCLASS_LM_CONTRACT = 21    # ... and of k_cgemm_nt / k_lm_two_point_reduce (low_
 KCLASS_LINK_DOTS = 22      # ... and of k_slice_link_dots (link loops)
 KCLASS_3PT_SOURCES = 23    # ... and of k_seq_sources / k_pair_slice_total and the stage-1 sources (three-point functions)
 KCLASS_3PT_DOTS = 24       # ... and of k_slice_seq_dots
+KCLASS_SMEAR = 25          # ... and of k_smear_step / k_smear_fused (smeared two-point functions)
+MAX_SINK_LEVELS = 4        # SW_MAX_SINK_LEVELS, SW_MAX_SMEARING_STEPS
+MAX_SMEARING_STEPS = 1024
 SINK_GAMMAS = ('1', 'g3', 's1', 's2')      # the sink spin matrix codes of set_three_point
 MAX_SHIFTS = 128
 MAX_MOMENTA = 8
@@ -260,6 +266,9 @@ def load_library():
     sig("sw_hutch_fetch_three_point", i32, vp, vp)
     sig("sw_apply_seq_sources", i32, vp, i32, vp, vp)
     sig("sw_apply_seq_dots", i32, vp, i32, vp, vp, vp)
+    sig("sw_set_smearing", i32, vp, dbl, i32, i32, vp)
+    sig("sw_apply_smearing", i32, vp, i32, i32, i32, vp, vp)
+    sig("sw_hutch_fetch_two_point_smeared", i32, vp, vp)
     _lib = lib
     return lib
 
@@ -288,6 +297,7 @@ EXPORTED_SYMBOLS = (
     "sw_meson_fields", "sw_low_mode_two_point", "sw_set_low_mode_inverse", "sw_apply_low_mode", "sw_hutch_fetch_two_point_lma",
     "sw_hutch_fetch_link_loops", "sw_apply_slice_link_dots",
     "sw_set_three_point", "sw_hutch_fetch_three_point", "sw_apply_seq_sources", "sw_apply_seq_dots",
+    "sw_set_smearing", "sw_apply_smearing", "sw_hutch_fetch_two_point_smeared",
 )
 
 
@@ -1048,6 +1058,34 @@ class Engine:
             raise EngineError("Z of shape %s, expected (%d, nb, %d)"
                               % (Z.shape, 2 * getattr(self, "_tp_nmom", 0), self._n(0, 0)))
         return self._probe_rows("sw_apply_pair_dots", self._two_point_shape(Z.shape[1]), Z.shape[1], _ptr(Z))
+
+    def set_smearing(self, kappa, source_steps=0, sink_steps=(0,)):
+        """kappa, the source steps and the ascending sink levels of MODE_TWO_POINT_SMEARED (sink_steps None or an
+        empty list clears)."""
+        s = np.ascontiguousarray([] if sink_steps is None else sink_steps, dtype=np.int32)
+        self._chk(self._lib.sw_set_smearing(self._h, float(kappa), int(source_steps), s.size,
+                                            _ptr(s) if s.size else None), "sw_set_smearing")
+        self._sm_nsink = int(s.size)
+
+    def apply_smearing(self, X, steps, fused=False):
+        """The smearing kernels alone: S_steps X with the registered kappa on X complex (nb, n) or (n,), reference
+        ordering, every timeslice (utils.smear); fused: one launch of k_smear_fused instead of `steps` of
+        k_smear_step -- the same bits."""
+        X2, single = self._io(X, self._n(0, 0))
+        Y = np.empty_like(X2)
+        self._chk(self._lib.sw_apply_smearing(self._h, X2.shape[0], int(steps), int(bool(fused)), _ptr(X2), _ptr(Y)),
+                  "sw_apply_smearing")
+        return Y[0] if single else Y
+
+    def hutch_batch_two_point_smeared(self, level, probes, tol, maxiter=1000):
+        """One MODE_TWO_POINT_SMEARED batch: (T[nb, nsink, nmom, 2, 2, 2, 2, L], iters_fine[nb], iters_coarse[nb])."""
+        return self.hutch_batch_resolved(MODE_TWO_POINT_SMEARED, level, probes, tol, maxiter)
+
+    def hutch_fetch_two_point_smeared(self):
+        """Pair sums of the last MODE_TWO_POINT_SMEARED batch at every sink level, shape (nb, nsink, nmom, 2, 2, 2,
+        2, L)."""
+        return self._fetch_rows("sw_hutch_fetch_two_point_smeared",
+                                lambda nb: (getattr(self, "_sm_nsink", 0),) + self._two_point_shape(nb))
 
     def set_three_point(self, t0, tf, sink='g3', pf=0, momenta=(0,)):
         """Source and sink timeslice, sink spin matrix ('1', 'g3', 's1', 's2' or its code 0..3), sink momentum and

@@ -21,7 +21,7 @@ from .utils import (_engines, deflation_pre_computations, displacements_of, draw
                     loops_of, mlmc_defl_setup_of, probe_batch, probe_batch_generated, register_loop_momenta,
                     register_shifts, register_two_point, two_point_of, low_mode_inverse, low_mode_two_point,
                     register_low_modes, low_mode_contraction_of, link_loops_of, three_point_of,
-                    register_three_point, refuse_three_point)
+                    register_three_point, refuse_three_point, register_smearing, refuse_smearing, smearing_of)
 
 DEFAULT_BATCH = 256
 NR_ROUGH_PROBES = 5
@@ -411,6 +411,18 @@ class _TwoPoint(_Observable):
         return rough.size - 1
 
 
+class _TwoPointSmeared(_TwoPoint):
+    """two_point() with smearing_kappa: the pair sums T[i][j][a][b][c][d][t] of every sink level i, flattened, plus
+    the pion total of sink level 0 as the control column (real and positive at any source and sink level)."""
+    what = "smeared two-point functions"
+    method = "two_point_smeared"
+
+    def columns(self, T):
+        T = np.asarray(T, dtype=np.complex128)
+        total = two_point_columns(T[:, 0], self.zero)[:, -1]
+        return np.concatenate([T.reshape(T.shape[0], -1), total[:, None]], axis=1)
+
+
 class _TwoPointLMA(_TwoPoint):
     """lma_two_point(): the remainders R[j][a][b][c][d][t] = T(z, z) - T(z_L, z_L), flattened, plus their pion total;
     the exact low-mode part E_L(t0) enters as tr1_cols."""
@@ -456,6 +468,7 @@ def hutchinson(A, params):
     solve per probe: the reference's result keys are then those of the control column, and the stopping rule runs on
     its series alone."""
     refuse_three_point(params, "hutchinson()")
+    refuse_smearing(params, "hutchinson()")
     if two_point_of(params) is not None:
         raise Exception("source_timeslice belongs to two_point(), not to hutchinson()")
     link = link_loops_of(params)
@@ -539,6 +552,12 @@ def two_point(A, params):
     sum_t C_pi(t, 0), which is real and positive, and the stopping rule runs on it alone.  `batch` counts noises;
     the solve is 2 M batch columns wide.
 
+    With the build-only key smearing_kappa (source_smearing_steps, default 0, and sink_smearing_steps,
+    default [0], go with it) the quark fields are smeared with utils.smear: the sources on their timeslice after the
+    phase, the solutions on every timeslice at each listed sink level.  The arrays then carry a leading axis over the
+    sink levels, the control column is the pion total of the first level, and the result carries the three keys
+    back.  The operator has to be the lattice stencil the engine detects.
+
     Returns two_point (the mean, [p][a][b][c][d][t]), two_point_devs, two_point_ests (per noise), converged,
     momenta, source_timeslice, nr_ests, function_iters (a noise counts the largest iteration number among its
     2 M solves), ests (the control series), probe_loop_s and probes_solved."""
@@ -547,12 +566,23 @@ def two_point(A, params):
     if sel is None:
         raise Exception("two_point() needs the key source_timeslice")
     t0, momenta = sel
-    obs = _TwoPoint(momenta)
+    smearing = smearing_of(params)
+    obs = _TwoPoint(momenta) if smearing is None else _TwoPointSmeared(momenta)
     if _dist.default_comm().world > 1:
         raise Exception(obs.one_rank)
-    mg_solver, nr_levels = _setup_solver(A, params, defer_coarse=True)
+    lattice = None
+    if smearing is not None:
+        # H pairs sites through the links: the operator has to be the lattice stencil the engine detects
+        from .hierarchy import detect_lattice
+        lattice = A if isinstance(A, tuple) else (None if A is None else detect_lattice(A))
+        if lattice is None:
+            raise Exception("smearing_kappa needs a lattice operator (a U(1) Wilson stencil with its links)")
+    mg_solver, nr_levels = _setup_solver(A, params, defer_coarse=True, lattice=lattice)
     shape = (len(momenta), 2, 2, 2, 2, int(params['latt_dims'][0]))
     register_two_point(mg_solver, t0, momenta)
+    if smearing is not None:
+        shape = (len(smearing['sink']),) + shape
+        register_smearing(mg_solver, smearing)
     _, _, control, loop, loop_s = _estimate_stage(mg_solver, params, A.shape[0], obs)
 
     mg_solver.finish_setup()
@@ -563,6 +593,10 @@ def two_point(A, params):
     result['converged'] = loop["converged"][:control].reshape(shape)
     result['momenta'] = list(momenta)
     result['source_timeslice'] = t0
+    if smearing is not None:
+        result['smearing_kappa'] = smearing['kappa']
+        result['source_smearing_steps'] = smearing['source']
+        result['sink_smearing_steps'] = list(smearing['sink'])
     result['nr_ests'] = loop["index"]
     result['function_iters'] = int(np.sum(loop["iters_fine"]))
     result['ests'] = loop["ests"][:, control]       # (nr_ests + 1,): sum_t C_pi(t, 0) per noise
@@ -609,6 +643,7 @@ def three_point(A, params):
     sink_gamma, sink_momentum, and the reference's keys from the control series: trace (= the mean of c_k), std_dev,
     nr_ests, function_iters (a noise counts its largest stage-1 plus its largest stage-2 iteration number), ests,
     rough_trace, level_tol, probe_loop_s and probes_solved."""
+    refuse_smearing(params, "three_point()")
     sel = three_point_of(params)
     if sel is None:
         raise Exception("three_point() needs the keys source_timeslice and sink_timeslice")
@@ -663,6 +698,7 @@ def lma_two_point(A, params):
     two_point_rest (the remainder's mean), two_point_rest_devs and nr_deflat_vctrs; two_point_ests are the per-noise
     remainders plus E_L(t0)."""
     refuse_three_point(params, "lma_two_point()")
+    refuse_smearing(params, "lma_two_point()")
     sel = two_point_of(params)
     if sel is None:
         raise Exception("lma_two_point() needs the key source_timeslice")
@@ -798,6 +834,7 @@ def _mlmc_work_model(output_params, mg_solver):
 # compute tr(A^{-1}) via multigrid multilevel Monte Carlo          stoch_trace.py:185-471
 def mlmc(A, params):
     refuse_three_point(params, "mlmc()")
+    refuse_smearing(params, "mlmc()")
     if two_point_of(params) is not None:
         raise Exception("source_timeslice belongs to two_point(), not to mlmc()")
     if loops_of(params) is not None:

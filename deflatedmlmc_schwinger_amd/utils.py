@@ -64,7 +64,8 @@ _BUILD_KEYS = ('batch', 'device', 'engines', 'cache_dir', 'report_path', 'probe_
                'ref_coarse_dofs', 'setup_eigs', 'defer_coarse_levels',
                'verbose', 'probe_rounds_max', 'mlmc_defl_setup', 'defl_setup', 'x_displacements',
                'timeslice_loops', 'source_timeslice', 'two_point_momenta', 'low_mode_contraction', 'link_loops',
-               'sink_timeslice', 'sink_gamma', 'sink_momentum', 'three_point_momenta')
+               'sink_timeslice', 'sink_gamma', 'sink_momentum', 'three_point_momenta',
+               'smearing_kappa', 'source_smearing_steps', 'sink_smearing_steps')
 # where the eigenpairs of the MLMC difference operators come from: host ARPACK (the reference's path) or
 # the block eigensolver on the GPU (setup_gpu.device_diff_eigenpairs)
 MLMC_DEFL_SETUPS = ("host", "device")
@@ -545,6 +546,90 @@ def meson_correlator(T, sink, source):
                     if w != 0:
                         out = out + w * T[..., a, b, c, d, :]
     return out
+
+
+SMEARING_KEYS = ('smearing_kappa', 'source_smearing_steps', 'sink_smearing_steps')
+MAX_SINK_LEVELS = 4            # SW_MAX_SINK_LEVELS, SW_MAX_SMEARING_STEPS of the engine
+MAX_SMEARING_STEPS = 1024
+
+
+def smear(field, U1, L, kappa, steps):
+    """Gauge-covariant Jacobi (Wuppertal) smearing in the spatial direction, the NumPy definition of what
+    Engine.apply_smearing computes: S_steps field with S = (1 + kappa H) / (1 + 2 kappa) and, on every line (spin s,
+    timeslice t),
+
+        (H psi)(x, t) = U1(x, t) psi(x + 1, t) + conj(U1(x - 1, t)) psi(x - 1, t)            (x +- 1 mod L).
+
+    field: (..., 2 L^2) in the reference ordering idx(s,x,y) = s L^2 + y L + x, t = y, any leading axes; U1: the L^2
+    x-links in the natural site order t L + x.  The lines do not talk to each other, so a subset of nt timeslices may
+    be smeared alone: U1 the nt L links of those timeslices, field (..., 2 nt L) as [s][t][x].  S commutes with spin,
+    is Hermitian on each timeslice and gauge covariant, and leaves a constant field unchanged on unit links.  A field
+    (or links) of extended precision is smeared in that precision."""
+    field = np.asarray(field)
+    U1 = np.asarray(U1)
+    nt = U1.size // L
+    if nt == 0 or U1.size != nt * L or field.shape[-1] != 2 * nt * L:
+        raise Exception("smear: field of shape %s and %d links, expected (..., 2 nt %d) and nt %d links (nt = %d on the "
+                        "whole lattice)" % (field.shape, U1.size, L, L, L))
+    if isinstance(steps, bool) or int(steps) != steps or steps < 0:
+        raise Exception("smear: steps %r is not a non-negative integer" % (steps,))
+    wide = np.clongdouble in (field.dtype.type, U1.dtype.type)
+    ctype = np.clongdouble if wide else np.complex128
+    rtype = np.longdouble if wide else np.float64
+    psi = field.astype(ctype).reshape(field.shape[:-1] + (2, nt, L))      # [...][s][t][x]
+    U = U1.astype(ctype).reshape(nt, L)                                   # [t][x]
+    Ub = np.roll(U, 1, axis=-1).conj()                                    # conj(U1(x - 1, t))
+    kappa = rtype(kappa)
+    for _ in range(int(steps)):
+        H = U * np.roll(psi, -1, axis=-1) + Ub * np.roll(psi, 1, axis=-1)
+        psi = (psi + kappa * H) / (1 + 2 * kappa)
+    return psi.reshape(field.shape)
+
+
+def smearing_of(params):
+    """The build-only keys of the smeared two_point(): None when smearing_kappa is absent, else the validated
+    dict(kappa, source, sink) -- smearing_kappa positive and finite; source_smearing_steps (0 when absent) an integer
+    in [0, MAX_SMEARING_STEPS]; sink_smearing_steps ([0] when absent) between 1 and MAX_SINK_LEVELS strictly ascending
+    integers in that range, 0 meaning a local sink.  The keys need source_timeslice."""
+    has = hasattr(params, "get")
+    if not has or params.get('smearing_kappa') is None:
+        for key in SMEARING_KEYS[1:]:
+            if has and params.get(key) is not None:
+                raise Exception("%s needs smearing_kappa" % key)
+        return None
+    if params.get('source_timeslice') is None:
+        raise Exception("smearing_kappa needs source_timeslice")
+    kappa = params['smearing_kappa']
+    if isinstance(kappa, (bool, str)) or not np.isreal(kappa) or not np.isfinite(kappa) or not kappa > 0:
+        raise Exception("smearing_kappa: %r is not a positive finite number" % (kappa,))
+
+    def steps_of(key, v):
+        if isinstance(v, bool) or int(v) != v:
+            raise Exception("%s: %r is not an integer" % (key, v))
+        if not 0 <= int(v) <= MAX_SMEARING_STEPS:
+            raise Exception("%s: %d outside [0, %d]" % (key, int(v), MAX_SMEARING_STEPS))
+        return int(v)
+
+    given = params.get('source_smearing_steps')
+    source = steps_of('source_smearing_steps', 0 if given is None else given)
+    given = params.get('sink_smearing_steps')
+    given = [0] if given is None else given
+    if isinstance(given, (str, bytes)) or not hasattr(given, '__len__'):
+        raise Exception("sink_smearing_steps: %r is not a list" % (given,))
+    sink = [steps_of('sink_smearing_steps', v) for v in given]
+    if not sink or len(sink) > MAX_SINK_LEVELS:
+        raise Exception("sink_smearing_steps: %d levels, between 1 and %d" % (len(sink), MAX_SINK_LEVELS))
+    for a, b in zip(sink, sink[1:]):
+        if b <= a:
+            raise Exception("sink_smearing_steps: %d after %d, the levels have to ascend strictly" % (b, a))
+    return dict(kappa=float(kappa), source=source, sink=sink)
+
+
+def refuse_smearing(params, who):
+    """The smearing keys belong to two_point(): every other flow raises on them."""
+    for key in SMEARING_KEYS:
+        if hasattr(params, "get") and params.get(key) is not None:
+            raise Exception("%s belongs to two_point(), not to %s" % (key, who))
 
 
 def _momentum_list(key, given, L):
@@ -1137,6 +1222,15 @@ def register_two_point(mg_solver, t0, momenta):
     """Hand the source timeslice and momenta of two_point() to every engine handle (momenta None clears)."""
     for eng in _engines(mg_solver):
         eng.set_two_point(t0, momenta)
+
+
+def register_smearing(mg_solver, sel):
+    """Hand the registration of the smeared two_point() -- smearing_of's dict, None clears -- to every engine handle."""
+    for eng in _engines(mg_solver):
+        if sel is None:
+            eng.set_smearing(1.0, 0, None)
+        else:
+            eng.set_smearing(sel['kappa'], sel['source'], sel['sink'])
 
 
 def register_three_point(mg_solver, sel):

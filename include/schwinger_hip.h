@@ -34,6 +34,8 @@ extern "C" {
 #define SW_MAX_DEFL 256
 #define SW_MAX_SHIFTS 128
 #define SW_MAX_MOMENTA 8
+#define SW_MAX_SINK_LEVELS 4
+#define SW_MAX_SMEARING_STEPS 1024
 
 typedef struct sw_engine sw_engine;
 
@@ -232,6 +234,14 @@ int sw_set_loop_momenta(sw_engine* h, int nmom, const int32_t* p);
  * functions).  A registration of its own, independent of sw_set_loop_momenta; the same checks, plus 0 <= t0 < L
  * and 0 among the momenta (its solutions are the conjugated factor of every momentum); nmom = 0 clears. */
 int sw_set_two_point(sw_engine* h, int t0, int nmom, const int32_t* p);
+/* Gauge-covariant Jacobi (Wuppertal) smearing of SW_MODE_TWO_POINT_SMEARED (build-only): on every line (spin,
+ * timeslice t), (H psi)(x) = U1(x,t) psi(x+1) + conj(U1(x-1,t)) psi(x-1) (x +- 1 mod L) and S_n =
+ * [(1 + kappa H) / (1 + 2 kappa)]^n.  source_steps smear the sources on their timeslice (after the momentum phase);
+ * sink_steps[nsink] are the sink levels, each applied to every timeslice of every solution (0 = a local sink).  A
+ * registration of its own on a lattice level 0 with links (the condition of SW_MODE_HUTCHINSON_LINK_LOOPS): kappa > 0
+ * and finite, 0 <= steps <= SW_MAX_SMEARING_STEPS, 1 <= nsink <= SW_MAX_SINK_LEVELS, the sink steps strictly
+ * ascending; nsink = 0 clears. */
+int sw_set_smearing(sw_engine* h, double kappa, int source_steps, int nsink, const int32_t* sink_steps);
 /* Source timeslice t0, sink timeslice tf, sink spin matrix (0..3 = 1, gamma_3, sigma_1, sigma_2), sink momentum pf
  * and insertion momenta q_j of SW_MODE_THREE_POINT (build-only: three-point functions from sequential one-end-trick
  * solves).  A registration of its own beside sw_set_two_point; the momentum checks of sw_set_loop_momenta (the list
@@ -347,6 +357,11 @@ int sw_apply_slice_sources(sw_engine* h, int nb, const int8_t* probes, double* o
  * sum_x e^{-2 pi i p_j x / L} conj(Z[2 j0 + a][k][idx(c,x,t)]) Z[2 j + b][k][idx(d,x,t)], j0 = the registered
  * momentum 0. */
 int sw_apply_pair_dots(sw_engine* h, int nb, const double* Z, double* out);
+/* The smearing kernels alone on nb host vectors in the reference layout: Y = S_steps X with the registered kappa
+ * (sw_set_smearing), on every timeslice.  fused = 0: `steps` launches of the one-step kernel k_smear_step (any L);
+ * fused = 1: one launch of k_smear_fused, refused when L has no instantiation (16 and 128 have one).  The two agree
+ * bit for bit. */
+int sw_apply_smearing(sw_engine* h, int nb, int steps, int fused, const double* X, double* Y);
 /* The sequential-source kernel of SW_MODE_THREE_POINT alone on host solutions: Z complex128[2][nb][n] (spin group a,
  * noise k, reference ordering), out complex128[2][nb][n], out[a][k][idx(e,x,t)] = delta_{t,tf} e^{+2 pi i pf x / L}
  * sum_c ((g3 Gf g3)^H)[e][c] Z[a][k][idx(c,x,tf)] for the registration of sw_set_three_point.  The refusals of the
@@ -565,6 +580,16 @@ int sw_solve(sw_engine* h, int hid, int level0, int nb, const double* B, double*
                                   per noise the largest stage-1 column count plus the largest stage-2 column count.
                                   Refused before any launch at a level other than 0, without a registration and when
                                   level 0 is no lattice level with links. */
+#define SW_MODE_TWO_POINT_SMEARED 14 /* SW_MODE_TWO_POINT with smeared sources and sinks, level 0 (build-only), for the
+                                  registrations of sw_set_two_point and sw_set_smearing:
+                                  eta_k^(j,a) = S_n (e^{+2 pi i p_j y / L} xi_k) on the timeslice t0, z = A^-1 eta, and
+                                  for every registered sink level s_i the pair sums T^(i)_k of S_{s_i} z_k, the
+                                  solutions being smeared in place from one level to the next.  A buffer of its own
+                                  (sw_hutch_fetch_two_point_smeared); sw_hutch_fetch returns the pion total of sink
+                                  level 0 and the iteration counts of SW_MODE_TWO_POINT.  With source_steps = 0 and
+                                  the sink levels [0] the batch equals the SW_MODE_TWO_POINT batch bit for bit.
+                                  Refused before any launch at a level other than 0 and without either
+                                  registration. */
 /* One batch of probes x_k in {-1,+1}^n (int8, nb*n, reference ordering) at `level`
  * (build-only extension: entries +-2 encode +-i, i.e. Z4 probes {1,i,-1,-i}):
  *   HUTCHINSON: e_k = x^H A^-1 Pperm^T (x - U U^H x)
@@ -619,6 +644,10 @@ int sw_hutch_fetch_two_point_lma(sw_engine* h, double* out);
 /* After a SW_MODE_THREE_POINT batch: out complex128[5][nmom][2][2][2][2][L][nb], the sums S_k[d][j][a][b][f][c][t] of
  * every noise k of the batch ("no three-point batch to fetch" otherwise). */
 int sw_hutch_fetch_three_point(sw_engine* h, double* out);
+/* After a SW_MODE_TWO_POINT_SMEARED batch: out complex128[nsink][nmom][2][2][2][2][L][nb], the pair sums
+ * T^(i)_k[j][a][b][c][d][t] of every sink level i and noise k ("no smeared two-point batch to fetch" otherwise, and
+ * again after sw_set_smearing or sw_set_two_point). */
+int sw_hutch_fetch_two_point_smeared(sw_engine* h, double* out);
 
 /* ---- multi-GPU: the one collective of the path ------------------------------------ */
 /* One process per GPU, one engine per process; the probe loop shards by probe and needs a single
@@ -663,6 +692,8 @@ int sw_timers_reset(sw_engine* h);
 #define SW_KCLASS_3PT_SOURCES 23    /* k_seq_sources, k_pair_slice_total and the stage-1 k_slice_sources
                                        (SW_MODE_THREE_POINT); in sw_timers: other */
 #define SW_KCLASS_3PT_DOTS 24       /* k_slice_seq_dots (SW_MODE_THREE_POINT); in sw_timers: dots */
+#define SW_KCLASS_SMEAR 25          /* k_smear_step, k_smear_fused (SW_MODE_TWO_POINT_SMEARED, sw_apply_smearing); in
+                                       sw_timers: other */
 int sw_kernel_stats(sw_engine* h, int which, double* total_ms, int64_t* launches);
 /* Floating-point operations issued by the launches of an MFMA kernel class since the last reset
  * (profiling on): 8 flops per complex multiply-add over every (row tile, k-step, probe). */
