@@ -247,10 +247,36 @@ static void test_poly(std::mt19937& rng) {
   CHECK(!swp::product_form(w3, u2, b2) && u2.empty(), "zero weight accepted");
 }
 
+// laph_pack: every entry lands conjugated at [t][x][m], the padding in x (L % 4 != 0) and in m (nev % 16 != 0) is zero
+static void test_laph(std::mt19937& rng) {
+  std::uniform_real_distribution<double> U(-1.0, 1.0);
+  const int cases[][2] = {{16, 1}, {16, 5}, {16, 16}, {6, 3}, {9, 9}, {21, 17}, {128, 32}};
+  for (auto& cs : cases) {
+    const int L = cs[0], nev = cs[1];
+    std::vector<std::complex<double>> V((size_t)L * nev * L);
+    for (auto& v : V) v = {U(rng), U(rng)};
+    swp::LaphHost p;
+    swp::laph_pack(p, L, nev, V.data());
+    CHECK(p.Lp % 4 == 0 && p.Lp >= L && p.Lp < L + 4, "laph_pack: Lp %d for L %d", p.Lp, L);
+    CHECK(p.ld % 16 == 0 && p.ld >= nev && p.ld < nev + 16, "laph_pack: ld %d for nev %d", p.ld, nev);
+    CHECK(p.v.size() == (size_t)L * p.Lp * p.ld, "laph_pack: size");
+    size_t bad = 0;
+    for (int t = 0; t < L; ++t)
+      for (int x = 0; x < p.Lp; ++x)
+        for (int m = 0; m < p.ld; ++m) {
+          const std::complex<double> want =
+              (x < L && m < nev) ? std::conj(V[((size_t)t * nev + m) * L + x]) : std::complex<double>(0, 0);
+          bad += p.v[((size_t)t * p.Lp + x) * p.ld + m] != want;
+        }
+    CHECK(bad == 0, "laph_pack: %zu wrong entries (L %d, nev %d)", bad, L, nev);
+  }
+}
+
 int main() {
   std::mt19937 rng(20240);
   test_ell(rng);
   test_bsr(rng);
+  test_laph(rng);
   test_mt();
   test_poly(rng);
   if (fails) {

@@ -70,9 +70,12 @@ enum TimerCat { T_MVM = 0, T_DEFL, T_P, T_R, T_AXPY, T_DOTS, T_COARSEST, T_OTHER
                 T_3PT_SOURCES,  // k_seq_sources / k_pair_slice_total of SW_MODE_THREE_POINT
                 T_3PT_DOTS,     // k_slice_seq_dots of SW_MODE_THREE_POINT
                 T_SMEAR,        // k_smear_step / k_smear_fused of SW_MODE_TWO_POINT_SMEARED / sw_apply_smearing
+                T_LAPH,         // k_laph_project of sw_perambulators; SW_KCLASS_LAPH reports it with T_LAPH_SRC
+                T_LAPH_SRC,     // k_laph_sources (internal: no kernel class of its own)
                 T_NCAT };
 // classes >= T_STENCIL are folded into the mvm / coarsest (two-point and three-point: other / dots; slice cdots,
-// meson fields, their contraction and the link dots: dots; smearing: other) buckets by
+// meson fields, their contraction and the link dots: dots; smearing: other; distillation: the projection dots, the
+// sources other) buckets by
 // sw_timers and reported separately by sw_kernel_stats
 
 struct EllOp {
@@ -369,6 +372,11 @@ struct sw_engine {
   std::vector<int32_t> sm_sink;
   int* sm_slicerow = nullptr;
   ResultBuf r_tps;
+  // distillation (sw_set_distillation, sw_perambulators): a registration of its own -- the eigenvectors as
+  // swp::laph_pack lays them out, conj(V)[t][lh_Lp][lh_ld], and a (timeslice, x, spin) -> internal row table of its own
+  int lh_nev = 0, lh_Lp = 0, lh_ld = 0;
+  cplx* lh_V = nullptr;
+  int* lh_slicerow = nullptr;
   // low-mode averaging (sw_set_low_mode_inverse, sw_meson_fields, SW_MODE_TWO_POINT_LMA): G [lm_k][lm_k] row-major
   // for the registered deflation vectors (lm_k = kd, 0: none), the tables of sw_meson_fields, the coefficients
   // c and c' [2][ld][columns], and the remainder R = T(z, z) - T(z_L, z_L) of the last batch with T(z_L, z_L)'s
@@ -2781,6 +2789,7 @@ int sw_hier_begin(sw_engine* h, int hid, int nlevels) {
     h->lm_k = 0;
     h->t3_momenta.clear();
     h->sm_sink.clear();
+    h->lh_nev = 0;
     for (auto r : kResults) (h->*r).drop();
   }
   return 0;
@@ -5989,6 +5998,153 @@ int sw_hutch_fetch_two_point_smeared(sw_engine* h, double* out) {
   return fetch_result(h, &sw_engine::r_tps, "no smeared two-point batch to fetch", out);
 }
 
+// ---- distillation: perambulators between the Laplacian eigenvectors of the timeslices -----------------------
+int sw_set_distillation(sw_engine* h, int nev, const double* V) {
+  SWCHK(check_hier(h, 0, 0, false));
+  if (nev == 0) {
+    h->lh_nev = 0;
+    return 0;
+  }
+  Level& lv = h->hier[0].lv[0];
+  if (!lv.stencil || lv.h_rowmap.empty())
+    return sw_fail(h, "distillation needs a lattice level 0 (sw_set_lattice)");
+  const int L = lv.L;
+  if (nev < 1 || nev > std::min(L, SW_MAX_LAPH))
+    return sw_fail(h, "%d distillation vectors outside [1,%d]", nev, std::min(L, SW_MAX_LAPH));
+  if (!V) return sw_fail(h, "null eigenvectors");
+  swp::LaphHost p;
+  swp::laph_pack(p, L, nev, (const std::complex<double>*)V);
+  HIPCHK(hipSetDevice(h->device));
+  SWCHK(stream_sync(h));
+  h->lh_nev = 0;
+  SWCHK(upload_slicerow(h, &h->lh_slicerow));
+  SWCHK(upload(h, (std::complex<double>**)&h->lh_V, p.v.data(), p.v.size()));
+  h->lh_Lp = p.Lp;
+  h->lh_ld = p.ld;
+  h->lh_nev = nev;
+  return 0;
+}
+
+static int distillation_ready(sw_engine* h) {
+  if (h->lh_nev <= 0 || !h->lh_V) return sw_fail(h, "no distillation registration (sw_set_distillation)");
+  return 0;
+}
+// distinct source timeslices inside [0, L), in any order
+static int check_source_timeslices(sw_engine* h, int nsrc, const int32_t* t0) {
+  const int L = h->hier[0].lv[0].L;
+  if (nsrc < 1 || nsrc > L) return sw_fail(h, "%d source timeslices outside [1,%d]", nsrc, L);
+  if (!t0) return sw_fail(h, "null source timeslice list");
+  std::vector<char> seen(L, 0);
+  for (int s = 0; s < nsrc; ++s) {
+    if (t0[s] < 0 || t0[s] >= L) return sw_fail(h, "source timeslice %d outside [0,%d)", (int)t0[s], L);
+    if (seen[t0[s]]) return sw_fail(h, "source timeslice %d listed twice", (int)t0[s]);
+    seen[t0[s]] = 1;
+  }
+  return 0;
+}
+
+// rhs [n][ncols] = the eigenvector sources of the global columns [col_first, col_first + nvalid), pad columns zero
+static int laph_sources(sw_engine* h, Level& lv, const int* d_t0, int col_first, int nvalid, int ncols, cplx* rhs) {
+  return launch(h, T_LAPH_SRC, swk::k_laph_sources, dim3((lv.n + 15) / 16, ncols / 64), dim3(SW_BLOCK),
+                (const cplx*)h->lh_V, h->lh_ld, h->lh_Lp, h->lh_nev, d_t0, col_first, nvalid, lv.n,
+                (const int*)lv.rowmap, lv.L, ncols, rhs);
+}
+// out [L][2][nev][ncols] = the projection of the block Z [n][ncols] onto every timeslice's eigenvectors
+static int laph_project(sw_engine* h, Level& lv, const cplx* Z, int ncols, cplx* out) {
+  const int L = lv.L, ld = h->lh_ld;
+  if (h->profiling) h->twork[T_LAPH] += 8.0 * 2.0 * (double)L * (double)L * (double)ld * (double)ncols;
+  return pick<1, 2, 3, 4, 5, 6, 7, 8>(ld / 16, [&](auto NT) {
+    return launch(h, T_LAPH, swk::k_laph_project<decltype(NT)::value>, dim3(L, 2, ncols / 64), dim3(SW_BLOCK),
+                  (const cplx*)h->lh_V, ld, h->lh_Lp, h->lh_nev, Z, (const int*)h->lh_slicerow, L, ncols, out);
+  });
+}
+
+// tau[s][t][c][m][n][a] = sum_x conj(v_m(x,t)) z^(s,n,a)[idx(c,x,t)], z = A^-1 eta for the eigenvector sources of the
+// nsrc source timeslices: the 2 nev nsrc columns in blocks of at most 256 (padded to 64 with zero columns), each block
+// k_laph_sources -> solve_dev on the hierarchy of solve_hier (no deflation, no permutation) -> k_laph_project -> the
+// copy to `out`.  Stateless: no mode buffer and no probe slot is touched; the blocks live in the two-point workspace,
+// everything else for this call only.
+int sw_perambulators(sw_engine* h, int nsrc, const int32_t* t0, double tol, int maxiter, double* out,
+                     int32_t* iters) {
+  SWCHK(check_hier(h, 0, 0, true));
+  SWCHK(distillation_ready(h));
+  SWCHK(check_source_timeslices(h, nsrc, t0));
+  if (maxiter < 1) return sw_fail(h, "maxiter must be >= 1");
+  if (!out) return sw_fail(h, "null output");
+  int hid;
+  SWCHK(solve_hier(h, 0, &hid));
+  HIPCHK(hipSetDevice(h->device));
+  Level& lv = h->hier[0].lv[0];
+  const int n = lv.n, L = lv.L, nev = h->lh_nev, per = 2 * nev, total = per * nsrc;
+  const int bmax = std::min(256, pad64(total));
+  const size_t rows = (size_t)L * 2 * nev;
+  DevBuf<int> d_t0(h);
+  DevBuf<cplx> proj(h);
+  SWCHK(upload(h, &d_t0.p, (const int*)t0, (size_t)nsrc));
+  SWCHK(ensure_two_point_ws(h, (size_t)n * bmax));
+  SWCHK(dev_realloc(h, &proj.p, rows * bmax));
+  std::vector<int32_t> it;
+  for (int c0 = 0; c0 < total; c0 += 256) {
+    const int nvalid = std::min(256, total - c0), ncols = pad64(nvalid);
+    SWCHK(laph_sources(h, lv, d_t0, c0, nvalid, ncols, h->tp_rhs));
+    int tot = 0;
+    SWCHK(solve_dev(h, hid, 0, h->tp_rhs, h->tp_z, tol, maxiter, ncols, &tot));
+    SWCHK(record_level_iters(h, h->hier[hid], 0, tot, it, nvalid));
+    if (iters) std::copy(it.begin(), it.end(), iters + c0);
+    SWCHK(laph_project(h, lv, h->tp_z, ncols, proj));
+    SWCHK(stream_sync(h));
+    // the columns of one source timeslice are contiguous in `out`: one strided copy per timeslice the block touches
+    for (int c = c0; c < c0 + nvalid;) {
+      const int s = c / per, e = std::min(c0 + nvalid, (s + 1) * per);
+      HIPCHK(hipMemcpy2D((cplx*)out + (size_t)s * rows * per + (c - s * per), sizeof(cplx) * per, proj.p + (c - c0),
+                         sizeof(cplx) * ncols, sizeof(cplx) * (e - c), rows, hipMemcpyDeviceToHost));
+      c = e;
+    }
+  }
+  return 0;
+}
+
+// k_laph_sources alone: out complex128 [nsrc nev 2][n], the sources in the reference ordering, column (s, n, a).
+int sw_apply_laph_sources(sw_engine* h, int nsrc, const int32_t* t0, double* out) {
+  SWCHK(check_hier(h, 0, 0, false));
+  SWCHK(distillation_ready(h));
+  SWCHK(check_source_timeslices(h, nsrc, t0));
+  if (!out) return sw_fail(h, "null output");
+  HIPCHK(hipSetDevice(h->device));
+  Level& lv = h->hier[0].lv[0];
+  const int total = 2 * h->lh_nev * nsrc;
+  DevBuf<int> d_t0(h);
+  DevBuf<cplx> rhs(h);
+  SWCHK(upload(h, &d_t0.p, (const int*)t0, (size_t)nsrc));
+  SWCHK(dev_realloc(h, &rhs.p, (size_t)lv.n * 256));
+  for (int c0 = 0; c0 < total; c0 += 256) {
+    const int nvalid = std::min(256, total - c0), ncols = pad64(nvalid);
+    SWCHK(laph_sources(h, lv, d_t0, c0, nvalid, ncols, rhs));
+    SWCHK(unpack_host(h, lv, nvalid, rhs, out + (size_t)2 * c0 * lv.n, ncols));
+  }
+  return 0;
+}
+
+// k_laph_project alone on nb host vectors Z [nb][n] (reference ordering): out complex128 [L][2][nev][nb].
+int sw_apply_laph_project(sw_engine* h, int nb, const double* Z, double* out) {
+  SWCHK(check_hier(h, 0, 0, false));
+  SWCHK(distillation_ready(h));
+  if (nb <= 0 || !Z || !out) return sw_fail(h, "bad arguments");
+  HIPCHK(hipSetDevice(h->device));
+  Level& lv = h->hier[0].lv[0];
+  const int nbp = pad64(nb);
+  const size_t rows = (size_t)lv.L * 2 * h->lh_nev;
+  DevBuf<cplx> z(h), proj(h);
+  SWCHK(dev_realloc(h, &z.p, (size_t)lv.n * nbp));
+  SWCHK(dev_realloc(h, &proj.p, rows * nbp));
+  SWCHK(pack_host(h, lv, nb, Z, z, nbp));
+  SWCHK(laph_project(h, lv, z, nbp, proj));
+  SWCHK(stream_sync(h));
+  HIPCHK(hipMemcpy2D(out, sizeof(cplx) * nb, proj.p, sizeof(cplx) * nbp, sizeof(cplx) * nb, rows,
+                     hipMemcpyDeviceToHost));
+  return 0;
+}
+
 // ---- three-point functions: sequential one-end-trick solves and a local or point-split insertion ---------
 // (g3 Gf g3)^H for Gf = 1, g3, s1, s2 as k_seq_sources takes it: bit 0 = the rows select the other spin, bits 1-2 /
 // 3-4 = the entry of row 0 / row 1 as a power of i:  1, diag(1,-1), -s1, -s2 = [[0, i], [-i, 0]]
@@ -6650,9 +6806,9 @@ int sw_timers(sw_engine* h, double t[8]) {
   t[T_MVM] += h->tacc[T_STENCIL] + h->tacc[T_STENCIL_RES] + h->tacc[T_STENCIL_SM] + h->tacc[T_MFMA_OP] +
               h->tacc[T_MFMA_OP2] + h->tacc[T_SCHUR] + h->tacc[T_SCHUR_OP];
   t[T_COARSEST] += h->tacc[T_MFMA_DENSE];
-  t[T_OTHER] += h->tacc[T_TP_SOURCES] + h->tacc[T_3PT_SOURCES] + h->tacc[T_SMEAR];
+  t[T_OTHER] += h->tacc[T_TP_SOURCES] + h->tacc[T_3PT_SOURCES] + h->tacc[T_SMEAR] + h->tacc[T_LAPH_SRC];
   t[T_DOTS] += h->tacc[T_TP_DOTS] + h->tacc[T_SLICE_CDOTS] + h->tacc[T_MESON_FIELD] + h->tacc[T_LM_CONTRACT] +
-               h->tacc[T_LINK_DOTS] + h->tacc[T_3PT_DOTS];
+               h->tacc[T_LINK_DOTS] + h->tacc[T_3PT_DOTS] + h->tacc[T_LAPH];
   return 0;
 }
 int sw_timers_reset(sw_engine* h) {
@@ -6668,15 +6824,19 @@ int sw_timers_reset(sw_engine* h) {
 }
 int sw_kernel_stats(sw_engine* h, int which, double* total_ms, int64_t* launches) {
   if (!h || !total_ms || !launches) return 1;
-  if (which < 0 || which >= T_NCAT) return sw_fail(h, "kernel class %d out of range", which);
+  if (which < 0 || which >= T_LAPH_SRC) return sw_fail(h, "kernel class %d out of range", which);
   SWCHK(stream_sync(h));
   *total_ms = h->tacc[which];
   *launches = h->tcount[which];
+  if (which == T_LAPH) {
+    *total_ms += h->tacc[T_LAPH_SRC];
+    *launches += h->tcount[T_LAPH_SRC];
+  }
   return 0;
 }
 int sw_kernel_work(sw_engine* h, int which, double* work) {
   if (!h || !work) return 1;
-  if (which < 0 || which >= T_NCAT) return sw_fail(h, "kernel class %d out of range", which);
+  if (which < 0 || which >= T_LAPH_SRC) return sw_fail(h, "kernel class %d out of range", which);
   *work = h->twork[which];
   return 0;
 }

@@ -4423,4 +4423,91 @@ __global__ __launch_bounds__(SW_BLOCK) void k_lm_two_point_reduce(const cplx* __
   out[(((size_t)ab * 4 + cd) * L + t) * L + t0] = s;
 }
 
+// ------------------------------------------------------------------------------------------
+// Distillation (sw_set_distillation, sw_perambulators): the quark fields projected onto the nev lowest eigenvectors
+// v_m(., t) of the gauge-covariant spatial Laplacian of every timeslice.  The eigenvectors come packed by
+// swp::laph_pack: Vc[(t Lp + x) ld + m] = conj(v_m(x, t)), Lp = L rounded up to 4, ld = nev rounded up to 16, the
+// padding exact zeros.  Global column g = (s nev + n) 2 + a: source timeslice t0s[s], eigenvector n, spin a.
+// ------------------------------------------------------------------------------------------
+// The twin of k_slice_sources: grid = (ceil(n / 16), ncols / 64), lane = column; the launch writes the columns
+// [col_first, col_first + nvalid) of the global numbering into the block out [n][ncols].  Each wave writes four
+// rows of its 64 columns: zero, except on the L rows idx(a, y, t0s[s]) of column (s, n, a), which hold v_n(y, t0s[s])
+// -- the packed entry with its imaginary part negated back, so the source is the registered value exactly.  Pad
+// columns (>= nvalid) stay exactly zero.
+__global__ __launch_bounds__(SW_BLOCK) void k_laph_sources(const cplx* __restrict__ Vc, int ld, int Lp, int nev,
+                                                           const int* __restrict__ t0s, int col_first, int nvalid,
+                                                           int n, const int* __restrict__ rowmap, int L, int ncols,
+                                                           cplx* __restrict__ out) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int c = blockIdx.y * 64 + lane;
+  const bool valid = c < nvalid;
+  const int g = col_first + c, a = g & 1, m = (g >> 1) % nev;
+  const int t0 = valid ? t0s[(g >> 1) / nev] : 0;
+  const int first = a * L * L + t0 * L;         // idx(a, 0, t0)
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int i = blockIdx.x * 16 + wave * 4 + r;
+    if (i >= n) return;
+    cplx v = cmake(0.0, 0.0);
+    const int y = i - first;
+    if (valid && y >= 0 && y < L) {
+      const cplx e = Vc[((size_t)t0 * Lp + y) * ld + m];
+      v = cmake(e.x, -e.y);
+    }
+    const size_t row = rowmap ? (size_t)rowmap[i] : (size_t)i;
+    out[row * ncols + c] = v;
+  }
+}
+
+// out[t][c][m][col] = sum_x conj(v_m(x,t)) Z[row(c,x,t)][col], [L][2][nev][ncols], for a block Z [n][ncols]: per
+// (t, spin c) the product of the ld x L matrix conj(V) with the L x ncols slab of Z on v_mfma_f64_16x16x4_f64, K = x,
+// four real MFMAs per complex product (re += ar br, re += (-ai) bi, im += ar bi, im += ai br, a = the packed conj(v)),
+// operand lanes as k_meson_field: lane l holds A[l&15][l>>4] = Vc[t][x0 + (l>>4)][16 q + (l&15)],
+// B[l>>4][l&15] = Z[row(c, x0 + (l>>4), t)][col0 + (l&15)], D[(l>>4) + 4 r][l&15].
+// grid = (L, 2, ncols / 64): a wave owns 16 columns of one (t, c) and ALL the NT = ld / 16 row tiles (2 NT
+// accumulators of four doubles; NT <= 8: 128 registers), so every element of Z is loaded by exactly one wave of the
+// launch, once; the eigenvectors of the timeslice are shared by the four waves and by the two spins through the
+// cache.  Every output is summed by one wave in the order x = 0, 4, 8, ... (L not a multiple of 4: the missing rows
+// of Z enter as zeros against the packed zeros of Vc), written once: no partials, no atomics, no LDS, no barrier; a
+// column's value does not depend on the other columns of the launch, and two calls agree bit for bit.  The padding
+// rows m >= nev are not stored.
+template <int NT>
+__global__ __launch_bounds__(SW_BLOCK) void k_laph_project(const cplx* __restrict__ Vc, int ld, int Lp, int nev,
+                                                           const cplx* __restrict__ Z,
+                                                           const int* __restrict__ slicerow, int L, int ncols,
+                                                           cplx* __restrict__ out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int k = lane >> 4, c = lane & 15;
+  const int t = blockIdx.x, sp = blockIdx.y;
+  const size_t col = (size_t)blockIdx.z * 64 + wave * 16 + c;
+  const int* __restrict__ sr = slicerow + (size_t)t * L * 2 + sp;
+  const cplx* __restrict__ va = Vc + (size_t)t * Lp * ld + c;
+  sw_double4 re[NT], im[NT];
+#pragma unroll
+  for (int q = 0; q < NT; ++q) re[q] = im[q] = sw_double4{0.0, 0.0, 0.0, 0.0};
+  for (int x0 = 0; x0 < L; x0 += 4) {
+    const int x = x0 + k;                       // < Lp
+    cplx b = cmake(0.0, 0.0);
+    if (x < L) b = Z[(size_t)sr[2 * x] * ncols + col];
+    const cplx* __restrict__ ap = va + (size_t)x * ld;
+#pragma unroll
+    for (int q = 0; q < NT; ++q) {
+      const cplx a = ap[q * 16];
+      re[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, b.x, re[q], 0, 0, 0);
+      re[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(-a.y, b.y, re[q], 0, 0, 0);
+      im[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, b.y, im[q], 0, 0, 0);
+      im[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, b.x, im[q], 0, 0, 0);
+    }
+  }
+  cplx* __restrict__ o = out + ((size_t)t * 2 + sp) * nev * ncols + col;
+#pragma unroll
+  for (int q = 0; q < NT; ++q) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int m = q * 16 + k + 4 * r;
+      if (m < nev) o[(size_t)m * ncols] = cmake(re[q][r], im[q][r]);
+    }
+  }
+}
+
 }  // namespace swk

@@ -5,6 +5,7 @@
 //   MFMA block-row (k_bsr_mfma): per 16-row tile a sorted list of KS 4-column groups ("k-steps");
 //                               kcol[RT][KS] = first column of the group, vals[RT][KS][64] with
 //                               lane = (row & 15) + 16 * (col & 3)
+//   LapH eigenvectors (k_laph_project): conj(V)[t][x padded to 4][m padded to 16]
 // The block structures are those of SURVEY 3.4 (multigrid.py:192-280 products).
 #pragma once
 #include <algorithm>
@@ -198,6 +199,23 @@ inline void bsr_pack(BsrHost& out, int n, const int64_t* indptr, const int32_t* 
     }
   }
   out.KS = KS;
+}
+
+// Laplacian eigenvectors of sw_set_distillation in the layout of k_laph_project / k_laph_sources:
+// V [L][nev][L] (timeslice t, vector m, site x) -> out [L][Lp][ld], out[(t Lp + x) ld + m] = conj(V[t][m][x]),
+// Lp = L rounded up to the MFMA's 4 K elements, ld = nev rounded up to its 16 rows; the padding is exact zeros
+struct LaphHost {
+  int Lp = 0, ld = 0;
+  std::vector<std::complex<double>> v;
+};
+inline void laph_pack(LaphHost& out, int L, int nev, const std::complex<double>* V) {
+  out.Lp = (L + 3) / 4 * 4;
+  out.ld = (nev + 15) / 16 * 16;
+  out.v.assign((size_t)L * out.Lp * out.ld, std::complex<double>(0, 0));
+  for (int t = 0; t < L; ++t)
+    for (int m = 0; m < nev; ++m)
+      for (int x = 0; x < L; ++x)
+        out.v[((size_t)t * out.Lp + x) * out.ld + m] = std::conj(V[((size_t)t * nev + m) * L + x]);
 }
 
 }  // namespace swp

@@ -76,6 +76,8 @@ KCLASS_LINK_DOTS = 22      # ... and of k_slice_link_dots (link loops)
 KCLASS_3PT_SOURCES = 23    # ... and of k_seq_sources / k_pair_slice_total and the stage-1 sources (three-point functions)
 KCLASS_3PT_DOTS = 24       # ... and of k_slice_seq_dots
 KCLASS_SMEAR = 25          # ... and of k_smear_step / k_smear_fused (smeared two-point functions)
+KCLASS_LAPH = 26           # ... and of k_laph_sources / k_laph_project (distillation)
+MAX_LAPH = 128             # SW_MAX_LAPH
 MAX_SINK_LEVELS = 4        # SW_MAX_SINK_LEVELS, SW_MAX_SMEARING_STEPS
 MAX_SMEARING_STEPS = 1024
 SINK_GAMMAS = ('1', 'g3', 's1', 's2')      # the sink spin matrix codes of set_three_point
@@ -269,6 +271,10 @@ def load_library():
     sig("sw_set_smearing", i32, vp, dbl, i32, i32, vp)
     sig("sw_apply_smearing", i32, vp, i32, i32, i32, vp, vp)
     sig("sw_hutch_fetch_two_point_smeared", i32, vp, vp)
+    sig("sw_set_distillation", i32, vp, i32, vp)
+    sig("sw_perambulators", i32, vp, i32, vp, dbl, i32, vp, vp)
+    sig("sw_apply_laph_sources", i32, vp, i32, vp, vp)
+    sig("sw_apply_laph_project", i32, vp, i32, vp, vp)
     _lib = lib
     return lib
 
@@ -298,6 +304,7 @@ EXPORTED_SYMBOLS = (
     "sw_hutch_fetch_link_loops", "sw_apply_slice_link_dots",
     "sw_set_three_point", "sw_hutch_fetch_three_point", "sw_apply_seq_sources", "sw_apply_seq_dots",
     "sw_set_smearing", "sw_apply_smearing", "sw_hutch_fetch_two_point_smeared",
+    "sw_set_distillation", "sw_perambulators", "sw_apply_laph_sources", "sw_apply_laph_project",
 )
 
 
@@ -367,6 +374,7 @@ class Engine:
             self._nshifts = 0          # the engine drops its shift registration with hierarchy 0
             self._nmom = 0             # ... and its loop momenta
             self._t3_nmom = 0          # ... and its three-point registration
+            self._lh_nev = 0           # ... and its distillation vectors
 
     def set_lattice(self, hid, L, mass, U1, U2):
         U1, U2 = _c128(U1), _c128(U2)
@@ -1076,6 +1084,54 @@ class Engine:
         self._chk(self._lib.sw_apply_smearing(self._h, X2.shape[0], int(steps), int(bool(fused)), _ptr(X2), _ptr(Y)),
                   "sw_apply_smearing")
         return Y[0] if single else Y
+
+    def set_distillation(self, V):
+        """The Laplacian eigenvectors of perambulators(): V complex (L, nev, L) = v_m(x, t) at [t, m, x] (None or an
+        empty array clears).  Orthonormality is not checked: V defines the operator."""
+        if V is None or np.size(V) == 0:
+            self._chk(self._lib.sw_set_distillation(self._h, 0, None), "sw_set_distillation")
+            self._lh_nev = 0
+            return
+        V = _c128(V)
+        if V.ndim != 3 or V.shape[0] != V.shape[2]:
+            raise EngineError("set_distillation: V of shape %s, expected (L, nev, L)" % (V.shape,))
+        self._chk(self._lib.sw_set_distillation(self._h, V.shape[1], _ptr(V)), "sw_set_distillation")
+        self._lh_nev = int(V.shape[1])
+
+    def _t0s(self, t0s):
+        return np.ascontiguousarray(np.atleast_1d(t0s), dtype=np.int32).reshape(-1)
+
+    def perambulators(self, t0s, tol, maxiter=1000):
+        """(tau[nsrc, L, 2, nev, nev, 2], iters[nsrc, nev, 2]): tau[s, t, c, m, n, a] = sum_x conj(v_m(x, t))
+        z^(s,n,a)[idx(c, x, t)] for the solutions of the eigenvector sources on the timeslices t0s
+        (utils.perambulators_from_solutions of utils.laph_sources).  Stateless: no mode buffer is touched."""
+        t = self._t0s(t0s)
+        nev = getattr(self, "_lh_nev", 0)
+        L = int(round((self._n(0, 0) // 2) ** 0.5))
+        out = np.zeros((t.size, L, 2, nev, nev, 2), dtype=np.complex128)
+        iters = np.zeros((t.size, nev, 2), dtype=np.int32)
+        self._chk(self._lib.sw_perambulators(self._h, t.size, _ptr(t) if t.size else None, float(tol), int(maxiter),
+                                             _ptr(out) if out.size else None, _ptr(iters) if iters.size else None),
+                  "sw_perambulators")
+        return out, iters
+
+    def apply_laph_sources(self, t0s):
+        """k_laph_sources alone: the sources of perambulators(), shape (nsrc nev 2, n), reference ordering."""
+        t = self._t0s(t0s)
+        out = np.zeros((t.size * getattr(self, "_lh_nev", 0) * 2, self._n(0, 0)), dtype=np.complex128)
+        self._chk(self._lib.sw_apply_laph_sources(self._h, t.size, _ptr(t) if t.size else None,
+                                                  _ptr(out) if out.size else None), "sw_apply_laph_sources")
+        return out
+
+    def apply_laph_project(self, Z):
+        """k_laph_project alone on Z complex (nb, n), reference ordering: out[t, c, m, k] = sum_x conj(v_m(x, t))
+        Z[k, idx(c, x, t)], shape (L, 2, nev, nb)."""
+        Z2, _ = self._io(Z, self._n(0, 0))
+        L = int(round((self._n(0, 0) // 2) ** 0.5))
+        out = np.zeros((L, 2, getattr(self, "_lh_nev", 0), Z2.shape[0]), dtype=np.complex128)
+        self._chk(self._lib.sw_apply_laph_project(self._h, Z2.shape[0], _ptr(Z2), _ptr(out) if out.size else None),
+                  "sw_apply_laph_project")
+        return out
 
     def hutch_batch_two_point_smeared(self, level, probes, tol, maxiter=1000):
         """One MODE_TWO_POINT_SMEARED batch: (T[nb, nsink, nmom, 2, 2, 2, 2, L], iters_fine[nb], iters_coarse[nb])."""

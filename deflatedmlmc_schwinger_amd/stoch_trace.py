@@ -21,7 +21,9 @@ from .utils import (_engines, deflation_pre_computations, displacements_of, draw
                     loops_of, mlmc_defl_setup_of, probe_batch, probe_batch_generated, register_loop_momenta,
                     register_shifts, register_two_point, two_point_of, low_mode_inverse, low_mode_two_point,
                     register_low_modes, low_mode_contraction_of, link_loops_of, three_point_of,
-                    register_three_point, refuse_three_point, register_smearing, refuse_smearing, smearing_of)
+                    register_three_point, refuse_three_point, register_smearing, refuse_smearing, smearing_of,
+                    distillation_of, refuse_distillation, laplacian_eigenvectors, laph_elementals,
+                    distilled_pair_sums, distilled_loops, source_average)
 
 DEFAULT_BATCH = 256
 NR_ROUGH_PROBES = 5
@@ -469,6 +471,7 @@ def hutchinson(A, params):
     its series alone."""
     refuse_three_point(params, "hutchinson()")
     refuse_smearing(params, "hutchinson()")
+    refuse_distillation(params, "hutchinson()")
     if two_point_of(params) is not None:
         raise Exception("source_timeslice belongs to two_point(), not to hutchinson()")
     link = link_loops_of(params)
@@ -562,6 +565,7 @@ def two_point(A, params):
     momenta, source_timeslice, nr_ests, function_iters (a noise counts the largest iteration number among its
     2 M solves), ests (the control series), probe_loop_s and probes_solved."""
     refuse_three_point(params, "two_point()")
+    refuse_distillation(params, "two_point()")
     sel = two_point_of(params)
     if sel is None:
         raise Exception("two_point() needs the key source_timeslice")
@@ -607,6 +611,92 @@ def two_point(A, params):
     return result
 
 
+def distilled_two_point(A, params):
+    """Distillation: the quark fields projected onto the distillation_vectors = N lowest eigenvectors
+    of the gauge-covariant spatial Laplacian of every timeslice, box(t) = sum_m v_m v_m^H.  For every listed source
+    timeslice the engine solves the 2 N eigenvector sources and projects the solutions on the device
+    (Engine.perambulators); the perambulators tau(t, t0) are exact -- no noise, no stopping rule -- and every
+    connected correlator follows from them on the host:
+
+        two_point[s][p][a][b][c][d][t]   utils.distilled_pair_sums: two_point()'s pair sums with box(t) A^-1 box(t0) in
+                                         place of A^-1 (utils.meson_correlator applies unchanged)
+        two_point_avg[p][a][b][c][d][dt] their mean over the sources at t = t0 + dt mod L
+        loops[p][a][b][t]                utils.distilled_loops on the source timeslices, NaN elsewhere
+
+    Keys (utils.distillation_of): distillation_vectors, source_timeslices (a list, or "all"), two_point_momenta
+    (default [0]; need not contain 0), keep_perambulators (default True).  The sources go to the engine in chunks of
+    max(1, 256 // (2 N)) timeslices, one 256-column solve block each, and are contracted chunk by chunk: with
+    keep_perambulators false nothing of the size of all perambulators is retained.  One rank; the operator has to be the
+    lattice stencil the engine detects.
+
+    Returns two_point, two_point_avg, loops, perambulators ([s][t][c][m][n][a], or None), eigenvalues ([t][m]),
+    momenta, source_timeslices, distillation_vectors, function_iters (summed over all columns), solves and
+    solve_s."""
+    sel = distillation_of(params)
+    if sel is None:
+        raise Exception("distilled_two_point() needs the key distillation_vectors")
+    if _dist.default_comm().world > 1:
+        raise Exception("distilled two-point functions run on one rank")
+    # H pairs sites through the links: the operator has to be the lattice stencil the engine detects
+    from .hierarchy import detect_lattice
+    lattice = A if isinstance(A, tuple) else (None if A is None else detect_lattice(A))
+    if lattice is None:
+        raise Exception("distillation_vectors needs a lattice operator (a U(1) Wilson stencil with its links)")
+    nev, t0s, momenta = sel['nev'], sel['t0s'], sel['momenta']
+    L = int(params['latt_dims'][0])
+    mg_solver, nr_levels = _setup_solver(A, params, defer_coarse=True, lattice=lattice)
+    engs = _engines(mg_solver)
+    if not engs:
+        raise Exception("no GPU engine attached (run MG.setup first)")
+    eng = engs[0]
+    V, eigenvalues = laplacian_eigenvectors(lattice[2], L, nev)
+    eng.set_distillation(V)
+    M = laph_elementals(V, L, momenta)
+    n = 2 * L * L
+    tol, maxiter = params['function_params']['tol'], (n if n < 1000 else 1000)
+
+    print("\nResetting timer to zero ...", end='')
+    mg_solver.timer.reset()
+    eng.timers_reset()
+    print(" done")
+    print("\nComputing the perambulators ...", end='', flush=True)
+    T = np.zeros((len(t0s), len(momenta), 2, 2, 2, 2, L), dtype=np.complex128)
+    loops = np.full((len(momenta), 2, 2, L), np.nan + 0j, dtype=np.complex128)
+    kept = [] if sel['keep'] else None
+    iters, solve_s = 0, 0.0
+    chunk = max(1, 256 // (2 * nev))
+    for first in range(0, len(t0s), chunk):
+        part = t0s[first:first + chunk]
+        t1 = time.time()
+        tau, it = eng.perambulators(part, tol, maxiter)
+        solve_s += time.time() - t1
+        iters += int(np.sum(it))
+        T[first:first + len(part)] = distilled_pair_sums(tau, M, part)
+        lp = distilled_loops(tau, M, part)
+        loops[..., part] = lp[..., part]
+        if kept is not None:
+            kept.append(tau)
+    print(" done. Time : " + str(solve_s) + " seconds")
+    eng.set_distillation(None)
+
+    mg_solver.finish_setup()
+    result = dict()
+    result['two_point'] = T
+    result['two_point_avg'] = source_average(T, t0s)
+    result['loops'] = loops
+    result['perambulators'] = np.concatenate(kept, axis=0) if kept is not None else None
+    result['eigenvalues'] = eigenvalues
+    result['momenta'] = list(momenta)
+    result['source_timeslices'] = list(t0s)
+    result['distillation_vectors'] = nev
+    result['function_iters'] = iters
+    result['solves'] = 2 * nev * len(t0s)
+    result['solve_s'] = solve_s
+    mg_solver.sync_timer()
+    print(mg_solver.timer)
+    return result
+
+
 class _ThreePoint(_Observable):
     """three_point(): the sums S[d][j][a][b][f][c][t], flattened, plus one control column, c_k = the pion two-point value
     at the sink slice (real and positive) -- a batch's row as Engine.hutch_fetch_three_point_resolved returns it."""
@@ -644,6 +734,7 @@ def three_point(A, params):
     nr_ests, function_iters (a noise counts its largest stage-1 plus its largest stage-2 iteration number), ests,
     rough_trace, level_tol, probe_loop_s and probes_solved."""
     refuse_smearing(params, "three_point()")
+    refuse_distillation(params, "three_point()")
     sel = three_point_of(params)
     if sel is None:
         raise Exception("three_point() needs the keys source_timeslice and sink_timeslice")
@@ -699,6 +790,7 @@ def lma_two_point(A, params):
     remainders plus E_L(t0)."""
     refuse_three_point(params, "lma_two_point()")
     refuse_smearing(params, "lma_two_point()")
+    refuse_distillation(params, "lma_two_point()")
     sel = two_point_of(params)
     if sel is None:
         raise Exception("lma_two_point() needs the key source_timeslice")
@@ -835,6 +927,7 @@ def _mlmc_work_model(output_params, mg_solver):
 def mlmc(A, params):
     refuse_three_point(params, "mlmc()")
     refuse_smearing(params, "mlmc()")
+    refuse_distillation(params, "mlmc()")
     if two_point_of(params) is not None:
         raise Exception("source_timeslice belongs to two_point(), not to mlmc()")
     if loops_of(params) is not None:
@@ -956,6 +1049,7 @@ def _mlmc_loops_checks(params, deflated=False):
     who = "deflated_mlmc_loops" if deflated else "mlmc_loops"
     has = hasattr(params, "get")
     refuse_three_point(params, who + "()")
+    refuse_distillation(params, who + "()")
     if has and params.get('source_timeslice') is not None:
         raise Exception("source_timeslice belongs to two_point(), not to %s()" % who)
     if has and params.get('x_displacements') is not None:

@@ -65,7 +65,8 @@ _BUILD_KEYS = ('batch', 'device', 'engines', 'cache_dir', 'report_path', 'probe_
                'verbose', 'probe_rounds_max', 'mlmc_defl_setup', 'defl_setup', 'x_displacements',
                'timeslice_loops', 'source_timeslice', 'two_point_momenta', 'low_mode_contraction', 'link_loops',
                'sink_timeslice', 'sink_gamma', 'sink_momentum', 'three_point_momenta',
-               'smearing_kappa', 'source_smearing_steps', 'sink_smearing_steps')
+               'smearing_kappa', 'source_smearing_steps', 'sink_smearing_steps',
+               'distillation_vectors', 'source_timeslices', 'keep_perambulators')
 # where the eigenpairs of the MLMC difference operators come from: host ARPACK (the reference's path) or
 # the block eigensolver on the GPU (setup_gpu.device_diff_eigenpairs)
 MLMC_DEFL_SETUPS = ("host", "device")
@@ -630,6 +631,212 @@ def refuse_smearing(params, who):
     for key in SMEARING_KEYS:
         if hasattr(params, "get") and params.get(key) is not None:
             raise Exception("%s belongs to two_point(), not to %s" % (key, who))
+
+
+DISTILLATION_KEYS = ('distillation_vectors', 'source_timeslices', 'keep_perambulators')
+MAX_LAPH = 128                 # SW_MAX_LAPH of the engine
+LAPH_TIE = 1e-8                # moduli this close (relatively) to the largest are tied in the phase convention
+
+
+def laplacian_eigenvectors(U1, L, nev):
+    """(V, eigenvalues): on every timeslice t the nev eigenvectors of the largest eigenvalues of the Hermitian L x L
+    matrix of smear(),
+
+        (H_t psi)(x) = U1(x, t) psi(x + 1) + conj(U1(x - 1, t)) psi(x - 1)                   (x +- 1 mod L),
+
+    i.e. the lowest modes of the gauge-covariant spatial Laplacian 2 - H_t.  V[t, m, x] = v_m(x, t), orthonormal in x,
+    eigenvalues[t, m] descending in m.  U1: the L^2 x-links in the natural site order t L + x.  np.linalg.eigh per
+    timeslice; the phase of every vector is fixed by making its largest-modulus component real and positive, the
+    lowest x on ties.  In one dimension ties are the rule -- H_t is gauge equivalent to uniform links, so a
+    non-degenerate eigenvector has the same modulus at every site up to rounding -- hence moduli within the relative
+    LAPH_TIE of the largest count as tied: the result is a function of the links alone."""
+    U = np.asarray(U1, dtype=np.complex128).reshape(-1)
+    if U.size != L * L:
+        raise Exception("laplacian_eigenvectors: %d links, expected %d" % (U.size, L * L))
+    if isinstance(nev, bool) or int(nev) != nev or not 1 <= int(nev) <= L:
+        raise Exception("laplacian_eigenvectors: %r vectors outside [1, %d]" % (nev, L))
+    nev = int(nev)
+    U = U.reshape(L, L)
+    x = np.arange(L)
+    V = np.zeros((L, nev, L), dtype=np.complex128)
+    lam = np.zeros((L, nev))
+    for t in range(L):
+        H = np.zeros((L, L), dtype=np.complex128)
+        np.add.at(H, (x, (x + 1) % L), U[t])
+        np.add.at(H, ((x + 1) % L, x), U[t].conj())
+        w, Q = np.linalg.eigh(H)
+        w, Q = w[::-1][:nev], Q[:, ::-1][:, :nev].T                       # [m][x], descending
+        mod = np.abs(Q)
+        big = np.argmax(mod >= (1.0 - LAPH_TIE) * mod.max(axis=1, keepdims=True), axis=1)
+        pivot = Q[np.arange(nev), big]
+        V[t] = Q * (np.abs(pivot) / pivot)[:, None]
+        V[t, np.arange(nev), big] = np.abs(pivot)                         # exactly real
+        lam[t] = w
+    return V, lam
+
+
+def _check_laph(V, L, who):
+    V = np.asarray(V)
+    if V.ndim != 3 or V.shape[0] != L or V.shape[2] != L:
+        raise Exception("%s: V of shape %s, expected (%d, nev, %d)" % (who, V.shape, L, L))
+    return V
+
+
+def laph_sources(V, L, t0s):
+    """The eigenvector sources of perambulators(), the NumPy definition of what Engine.apply_laph_sources writes:
+    out[(s nev + n) 2 + a, idx(a', y, t)] = delta_aa' delta_{t, t0s[s]} V[t0s[s], n, y], shape (nsrc nev 2, 2 L^2)."""
+    V = _check_laph(V, L, "laph_sources")
+    nev = V.shape[1]
+    t0s = [int(t) for t in np.atleast_1d(t0s)]
+    out = np.zeros((len(t0s), nev, 2, 2 * L * L), dtype=V.dtype)
+    for s, t0 in enumerate(t0s):
+        for a in range(2):
+            first = a * L * L + t0 * L
+            out[s, :, a, first:first + L] = V[t0]
+    return out.reshape(len(t0s) * nev * 2, 2 * L * L)
+
+
+def perambulators_from_solutions(V, Z, L, nsrc=None):
+    """out[t, c, m, k] = sum_x conj(V[t, m, x]) Z[k, idx(c, x, t)], shape (L, 2, nev, nb): the NumPy definition of what
+    Engine.apply_laph_project computes, for Z of shape (nb, 2 L^2) in the reference ordering.  In np.longdouble when V
+    or Z comes in that precision.  nsrc given: Z holds the nsrc nev 2 solutions of laph_sources and the result comes in
+    the layout of Engine.perambulators, tau[s, t, c, m, n, a]."""
+    V = _check_laph(V, L, "perambulators_from_solutions")
+    Z = np.asarray(Z)
+    if Z.ndim != 2 or Z.shape[1] != 2 * L * L:
+        raise Exception("perambulators_from_solutions: Z of shape %s, expected (nb, %d)" % (Z.shape, 2 * L * L))
+    wide = np.clongdouble in (V.dtype.type, Z.dtype.type)
+    ctype = np.clongdouble if wide else np.complex128
+    Zr = Z.astype(ctype).reshape(Z.shape[0], 2, L, L)                      # [k][c][t][x]
+    out = np.einsum('tmx,kctx->tcmk', V.astype(ctype).conj(), Zr)
+    if nsrc is None:
+        return out
+    nev = V.shape[1]
+    if Z.shape[0] != nsrc * nev * 2:
+        raise Exception("perambulators_from_solutions: %d solutions, expected %d x %d x 2" % (Z.shape[0], nsrc, nev))
+    return np.ascontiguousarray(out.reshape(L, 2, nev, nsrc, nev, 2).transpose(3, 0, 1, 2, 4, 5))
+
+
+def laph_elementals(V, L, momenta):
+    """M[j, t, m, m'] = sum_x e^{-2 pi i p_j x / L} conj(V[t, m, x]) V[t, m', x]: the momentum projection in the
+    eigenvector basis of every timeslice, shape (nmom, L, nev, nev); the phases are the engine's table."""
+    V = _check_laph(V, L, "laph_elementals").astype(np.complex128)
+    tab = _phase_table(L)
+    ph = tab[np.outer(np.asarray(momenta, dtype=np.int64), np.arange(L)) % L]           # [j][x]
+    return np.einsum('tmx,jtnx->jtmn', V.conj(), ph[:, None, None, :] * V[None])
+
+
+def _check_tau(tau, M, t0s, who):
+    tau = np.asarray(tau, dtype=np.complex128)
+    M = np.asarray(M, dtype=np.complex128)
+    t0s = [int(t) for t in np.atleast_1d(t0s)]
+    if tau.ndim != 6 or tau.shape[0] != len(t0s) or tau.shape[2] != 2 or tau.shape[5] != 2 \
+            or tau.shape[3] != tau.shape[4]:
+        raise Exception("%s: tau of shape %s, expected (%d, L, 2, nev, nev, 2)" % (who, tau.shape, len(t0s)))
+    if M.ndim != 4 or M.shape[1:] != (tau.shape[1], tau.shape[3], tau.shape[3]):
+        raise Exception("%s: M of shape %s, expected (nmom, %d, %d, %d)"
+                        % (who, M.shape, tau.shape[1], tau.shape[3], tau.shape[3]))
+    return tau, M, t0s
+
+
+def distilled_pair_sums(tau, M, t0s):
+    """T[s, j, a, b, c, d, t] = sum conj(tau[s, t, c, m1, n1, a]) M[j, t, m1, m2] tau[s, t, d, m2, n2, b]
+    conj(M[j, t0s[s], n1, n2]): the pair sums of two_point() with box(t) A^-1 box(t0) in place of A^-1, from the
+    perambulators tau[s, t, c, m, n, a] and the elementals M of laph_elementals -- meson_correlator applies to it
+    unchanged.  Per (s, j) two batched matrix products X = M_t tau_db M_t0^H and one elementwise sum against conj(tau)."""
+    tau, M, t0s = _check_tau(tau, M, t0s, "distilled_pair_sums")
+    nsrc, L = tau.shape[:2]
+    T = np.zeros((nsrc, M.shape[0], 2, 2, 2, 2, L), dtype=np.complex128)
+    for s, t0 in enumerate(t0s):
+        ts = np.ascontiguousarray(tau[s].transpose(0, 1, 4, 2, 3))         # [t][c][a][m][n]
+        for j in range(M.shape[0]):
+            X = np.matmul(np.matmul(M[j][:, None, None], ts), M[j, t0].conj().T)       # [t][d][b][m1][n1]
+            T[s, j] = np.einsum('tcamn,tdbmn->abcdt', ts.conj(), X)
+    return T
+
+
+def distilled_loops(tau, M, t0s):
+    """loops[j, a, b, t] = sum_{m,n} M[j, t, n, m] tau(t, t)[b, m, n, a] on the source timeslices t = t0s[s], NaN on
+    every other timeslice: tr[Gamma e^{-ipx} box A^-1 box] per timeslice in the layout of the timeslice loops, so
+    loop_gamma applies to it unchanged."""
+    tau, M, t0s = _check_tau(tau, M, t0s, "distilled_loops")
+    L = tau.shape[1]
+    out = np.full((M.shape[0], 2, 2, L), np.nan + 0j, dtype=np.complex128)
+    for s, t0 in enumerate(t0s):
+        out[:, :, :, t0] = np.einsum('jnm,bmna->jab', M[:, t0], tau[s, t0])
+    return out
+
+
+def source_average(T, t0s):
+    """avg[..., dt] = the mean over the sources s of T[s, ..., (t0s[s] + dt) mod L]: the two_point_avg of
+    distilled_two_point(), every source's correlator shifted to its own origin."""
+    T = np.asarray(T)
+    t0s = [int(t) for t in np.atleast_1d(t0s)]
+    if T.ndim < 2 or T.shape[0] != len(t0s):
+        raise Exception("source_average: T of shape %s for %d sources" % (T.shape, len(t0s)))
+    return np.mean(np.stack([np.roll(T[s], -t0, axis=-1) for s, t0 in enumerate(t0s)]), axis=0)
+
+
+def distillation_of(params):
+    """The build-only keys of distilled_two_point(): None when distillation_vectors is absent, else the validated
+    dict(nev, t0s, momenta, keep) -- distillation_vectors an integer in [1, min(L, MAX_LAPH)], L = latt_dims[0];
+    source_timeslices a non-empty list of different integers in [0, L) or "all"; two_point_momenta ([0] when absent)
+    at most MAX_MOMENTA different integers in [0, L), which need not contain 0; keep_perambulators (True when absent)
+    a bool.  The keys combine with none of source_timeslice, sink_timeslice, x_displacements, timeslice_loops,
+    link_loops and the smearing keys."""
+    has = hasattr(params, "get")
+    if not has or params.get('distillation_vectors') is None:
+        for key in DISTILLATION_KEYS[1:]:
+            if has and params.get(key) is not None:
+                raise Exception("%s needs distillation_vectors" % key)
+        return None
+    for other in ('source_timeslice', 'sink_timeslice', 'x_displacements', 'timeslice_loops', 'link_loops') \
+            + SMEARING_KEYS:
+        if params.get(other) is not None:
+            raise Exception("distillation_vectors does not combine with %s" % other)
+    L = int(params['latt_dims'][0])
+    nev = params['distillation_vectors']
+    if isinstance(nev, (bool, str)) or int(nev) != nev:
+        raise Exception("distillation_vectors: %r is not an integer" % (nev,))
+    nev = int(nev)
+    if not 1 <= nev <= min(L, MAX_LAPH):
+        raise Exception("distillation_vectors: %d outside [1, %d]" % (nev, min(L, MAX_LAPH)))
+    given = params.get('source_timeslices')
+    if given is None:
+        raise Exception("distillation_vectors needs source_timeslices (a list, or \"all\")")
+    if isinstance(given, str):
+        if given != "all":
+            raise Exception("source_timeslices: %r is neither a list nor \"all\"" % (given,))
+        t0s = list(range(L))
+    else:
+        if isinstance(given, bytes) or not hasattr(given, '__len__'):
+            raise Exception("source_timeslices: %r is not a list" % (given,))
+        t0s = []
+        for t in given:
+            if isinstance(t, bool) or int(t) != t:
+                raise Exception("source_timeslices: %r is not an integer" % (t,))
+            t = int(t)
+            if not 0 <= t < L:
+                raise Exception("source_timeslices: %d outside [0, %d)" % (t, L))
+            if t in t0s:
+                raise Exception("source_timeslices: %d listed twice" % t)
+            t0s.append(t)
+        if not t0s:
+            raise Exception("source_timeslices: the list is empty")
+    given = params.get('two_point_momenta')
+    momenta = _momentum_list('two_point_momenta', [0] if given is None else given, L)
+    keep = params.get('keep_perambulators')
+    keep = True if keep is None else keep
+    if not isinstance(keep, (bool, np.bool_)):
+        raise Exception("keep_perambulators: %r is not a bool" % (keep,))
+    return dict(nev=nev, t0s=t0s, momenta=momenta, keep=bool(keep))
+
+
+def refuse_distillation(params, who):
+    """The distillation keys belong to distilled_two_point(): every other flow raises on them."""
+    for key in DISTILLATION_KEYS:
+        if hasattr(params, "get") and params.get(key) is not None:
+            raise Exception("%s belongs to distilled_two_point(), not to %s" % (key, who))
 
 
 def _momentum_list(key, given, L):

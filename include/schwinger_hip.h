@@ -36,6 +36,7 @@ extern "C" {
 #define SW_MAX_MOMENTA 8
 #define SW_MAX_SINK_LEVELS 4
 #define SW_MAX_SMEARING_STEPS 1024
+#define SW_MAX_LAPH 128
 
 typedef struct sw_engine sw_engine;
 
@@ -242,6 +243,12 @@ int sw_set_two_point(sw_engine* h, int t0, int nmom, const int32_t* p);
  * and finite, 0 <= steps <= SW_MAX_SMEARING_STEPS, 1 <= nsink <= SW_MAX_SINK_LEVELS, the sink steps strictly
  * ascending; nsink = 0 clears. */
 int sw_set_smearing(sw_engine* h, double kappa, int source_steps, int nsink, const int32_t* sink_steps);
+/* Distillation (build-only): the nev eigenvectors of every timeslice's gauge-covariant spatial Laplacian 2 - H_t (H_t as
+ * in sw_set_smearing) onto which sw_perambulators projects the quark fields, V complex128[L][nev][L] = v_m(x,t) at
+ * [t][m][x].  A registration of its own on a lattice level 0 of hid 0 (the condition of sw_meson_fields);
+ * 1 <= nev <= min(L, SW_MAX_LAPH); nev = 0 clears.  V is packed on the host into the kernels' layout (conjugated,
+ * [t][x][m], padded with zeros to 4 sites and 16 vectors).  Orthonormality is NOT checked: V defines the operator. */
+int sw_set_distillation(sw_engine* h, int nev, const double* V);
 /* Source timeslice t0, sink timeslice tf, sink spin matrix (0..3 = 1, gamma_3, sigma_1, sigma_2), sink momentum pf
  * and insertion momenta q_j of SW_MODE_THREE_POINT (build-only: three-point functions from sequential one-end-trick
  * solves).  A registration of its own beside sw_set_two_point; the momentum checks of sw_set_loop_momenta (the list
@@ -362,6 +369,24 @@ int sw_apply_pair_dots(sw_engine* h, int nb, const double* Z, double* out);
  * fused = 1: one launch of k_smear_fused, refused when L has no instantiation (16 and 128 have one).  The two agree
  * bit for bit. */
 int sw_apply_smearing(sw_engine* h, int nb, int steps, int fused, const double* X, double* Y);
+/* Perambulators of the registration of sw_set_distillation (build-only, stateless in the style of
+ * sw_level_deflation_loops): for the nsrc source timeslices t0[s] (distinct, each in [0, L), any order) and the
+ * sources eta^(s,n,a)[idx(a',y,t)] = delta_aa' delta_{t,t0[s]} v_n(y, t0[s]), z = A^-1 eta solved to `tol` on the
+ * hierarchy that solves level 0 (no deflation, no permutation),
+ *   out[s][t][c][m][n][a] = sum_x conj(v_m(x,t)) z^(s,n,a)[idx(c,x,t)],   complex128[nsrc][L][2][nev][nev][2],
+ * the 2 nev nsrc columns in blocks of at most 256 (padded to 64 with zero columns): k_laph_sources, the solve,
+ * k_laph_project (fp64 matrix cores, every output summed by one wave in the order x = 0, 4, 8, ...), the copy out.
+ * iters int32[nsrc][nev][2] (may be NULL): the iteration count of every column.  Refused before anything is allocated
+ * or launched without a registration, without a finalised hierarchy, on a bad timeslice list, maxiter < 1 or a null
+ * out.  No mode buffer and no probe slot is touched; two calls agree bit for bit. */
+int sw_perambulators(sw_engine* h, int nsrc, const int32_t* t0, double tol, int maxiter, double* out,
+                     int32_t* iters);
+/* k_laph_sources alone: out complex128[nsrc*nev*2][n], the sources of sw_perambulators in the reference ordering,
+ * column (s, n, a). */
+int sw_apply_laph_sources(sw_engine* h, int nsrc, const int32_t* t0, double* out);
+/* k_laph_project alone on nb host vectors Z complex128[nb][n] (reference ordering): out complex128[L][2][nev][nb],
+ * out[t][c][m][k] = sum_x conj(v_m(x,t)) Z[k][idx(c,x,t)]. */
+int sw_apply_laph_project(sw_engine* h, int nb, const double* Z, double* out);
 /* The sequential-source kernel of SW_MODE_THREE_POINT alone on host solutions: Z complex128[2][nb][n] (spin group a,
  * noise k, reference ordering), out complex128[2][nb][n], out[a][k][idx(e,x,t)] = delta_{t,tf} e^{+2 pi i pf x / L}
  * sum_c ((g3 Gf g3)^H)[e][c] Z[a][k][idx(c,x,tf)] for the registration of sw_set_three_point.  The refusals of the
@@ -694,6 +719,9 @@ int sw_timers_reset(sw_engine* h);
 #define SW_KCLASS_3PT_DOTS 24       /* k_slice_seq_dots (SW_MODE_THREE_POINT); in sw_timers: dots */
 #define SW_KCLASS_SMEAR 25          /* k_smear_step, k_smear_fused (SW_MODE_TWO_POINT_SMEARED, sw_apply_smearing); in
                                        sw_timers: other */
+#define SW_KCLASS_LAPH 26           /* k_laph_sources, k_laph_project (sw_perambulators, sw_apply_laph_*); in sw_timers
+                                       the sources count as other, the projection as dots; sw_kernel_work counts
+                                       8 * 2 L^2 * ld * ncols flops per projection launch, ld = nev rounded up to 16 */
 int sw_kernel_stats(sw_engine* h, int which, double* total_ms, int64_t* launches);
 /* Floating-point operations issued by the launches of an MFMA kernel class since the last reset
  * (profiling on): 8 flops per complex multiply-add over every (row tile, k-step, probe). */
