@@ -71,11 +71,12 @@ enum TimerCat { T_MVM = 0, T_DEFL, T_P, T_R, T_AXPY, T_DOTS, T_COARSEST, T_OTHER
                 T_3PT_DOTS,     // k_slice_seq_dots of SW_MODE_THREE_POINT
                 T_SMEAR,        // k_smear_step / k_smear_fused of SW_MODE_TWO_POINT_SMEARED / sw_apply_smearing
                 T_LAPH,         // k_laph_project of sw_perambulators; SW_KCLASS_LAPH reports it with T_LAPH_SRC
+                T_LAPH_CONTRACT,  // k_laph_elementals / k_laph_left / k_laph_right / k_laph_reduce (sw_distilled_two_point)
                 T_LAPH_SRC,     // k_laph_sources (internal: no kernel class of its own)
                 T_NCAT };
 // classes >= T_STENCIL are folded into the mvm / coarsest (two-point and three-point: other / dots; slice cdots,
 // meson fields, their contraction and the link dots: dots; smearing: other; distillation: the projection dots, the
-// sources other) buckets by
+// sources other, the contraction dots) buckets by
 // sw_timers and reported separately by sw_kernel_stats
 
 struct EllOp {
@@ -377,6 +378,12 @@ struct sw_engine {
   int lh_nev = 0, lh_Lp = 0, lh_ld = 0;
   cplx* lh_V = nullptr;
   int* lh_slicerow = nullptr;
+  // ... and its momenta (sw_set_distillation_momenta): the transposed, padded elementals Mt[momentum][t][ld][ld] of
+  // k_laph_elementals with the tables they were made from; dropped with the eigenvectors
+  std::vector<int32_t> lh_momenta;
+  int* lh_mom = nullptr;
+  cplx* lh_phase = nullptr;
+  cplx* lh_M = nullptr;
   // low-mode averaging (sw_set_low_mode_inverse, sw_meson_fields, SW_MODE_TWO_POINT_LMA): G [lm_k][lm_k] row-major
   // for the registered deflation vectors (lm_k = kd, 0: none), the tables of sw_meson_fields, the coefficients
   // c and c' [2][ld][columns], and the remainder R = T(z, z) - T(z_L, z_L) of the last batch with T(z_L, z_L)'s
@@ -2790,6 +2797,9 @@ int sw_hier_begin(sw_engine* h, int hid, int nlevels) {
     h->t3_momenta.clear();
     h->sm_sink.clear();
     h->lh_nev = 0;
+    h->lh_momenta.clear();
+    SWCHK(dev_free(h, h->lh_M));
+    h->lh_M = nullptr;
     for (auto r : kResults) (h->*r).drop();
   }
   return 0;
@@ -5999,8 +6009,17 @@ int sw_hutch_fetch_two_point_smeared(sw_engine* h, double* out) {
 }
 
 // ---- distillation: perambulators between the Laplacian eigenvectors of the timeslices -----------------------
+// the elementals belong to the eigenvectors they were made from
+static int drop_laph_momenta(sw_engine* h) {
+  h->lh_momenta.clear();
+  SWCHK(dev_free(h, h->lh_M));
+  h->lh_M = nullptr;
+  return 0;
+}
+
 int sw_set_distillation(sw_engine* h, int nev, const double* V) {
   SWCHK(check_hier(h, 0, 0, false));
+  SWCHK(drop_laph_momenta(h));
   if (nev == 0) {
     h->lh_nev = 0;
     return 0;
@@ -6059,6 +6078,40 @@ static int laph_project(sw_engine* h, Level& lv, const cplx* Z, int ncols, cplx*
   });
 }
 
+// One solve block of the perambulators: the global columns [c0, c0 + nvalid) of the sources d_t0, padded to ncols --
+// k_laph_sources -> solve_dev on hierarchy hid -> k_laph_project into proj [L][2][nev][ncols]; the blocks live in the
+// two-point workspace (ensure_two_point_ws by the caller).  iters (or NULL): the nvalid iteration counts.
+static int laph_block(sw_engine* h, int hid, Level& lv, const int* d_t0, int c0, int nvalid, int ncols, double tol,
+                      int maxiter, cplx* proj, int32_t* iters) {
+  SWCHK(laph_sources(h, lv, d_t0, c0, nvalid, ncols, h->tp_rhs));
+  int tot = 0;
+  SWCHK(solve_dev(h, hid, 0, h->tp_rhs, h->tp_z, tol, maxiter, ncols, &tot));
+  std::vector<int32_t> it;
+  SWCHK(record_level_iters(h, h->hier[hid], 0, tot, it, nvalid));
+  if (iters) std::copy(it.begin(), it.end(), iters);
+  return laph_project(h, lv, h->tp_z, ncols, proj);
+}
+// The global columns [c0, c0 + nvalid) between the block proj [L][2][nev][ncols] (its columns 0 ..) and the host
+// perambulators tau [nsrc][L][2][nev][nev][2]: the columns of one source timeslice are contiguous in tau, one strided
+// copy per timeslice the block touches.  to_host: proj -> tau, else tau -> proj.  The stream has drained.
+static int laph_copy_tau(sw_engine* h, cplx* tau, int c0, int nvalid, int ncols, cplx* proj, bool to_host) {
+  const int per = 2 * h->lh_nev;
+  const size_t rows = (size_t)h->hier[0].lv[0].L * per;
+  for (int c = c0; c < c0 + nvalid;) {
+    const int s = c / per, e = std::min(c0 + nvalid, (s + 1) * per);
+    cplx* host = tau + (size_t)s * rows * per + (c - s * per);
+    cplx* dev = proj + (c - c0);
+    if (to_host)
+      HIPCHK(hipMemcpy2D(host, sizeof(cplx) * per, dev, sizeof(cplx) * ncols, sizeof(cplx) * (e - c), rows,
+                         hipMemcpyDeviceToHost));
+    else
+      HIPCHK(hipMemcpy2D(dev, sizeof(cplx) * ncols, host, sizeof(cplx) * per, sizeof(cplx) * (e - c), rows,
+                         hipMemcpyHostToDevice));
+    c = e;
+  }
+  return 0;
+}
+
 // tau[s][t][c][m][n][a] = sum_x conj(v_m(x,t)) z^(s,n,a)[idx(c,x,t)], z = A^-1 eta for the eigenvector sources of the
 // nsrc source timeslices: the 2 nev nsrc columns in blocks of at most 256 (padded to 64 with zero columns), each block
 // k_laph_sources -> solve_dev on the hierarchy of solve_hier (no deflation, no permutation) -> k_laph_project -> the
@@ -6083,23 +6136,11 @@ int sw_perambulators(sw_engine* h, int nsrc, const int32_t* t0, double tol, int 
   SWCHK(upload(h, &d_t0.p, (const int*)t0, (size_t)nsrc));
   SWCHK(ensure_two_point_ws(h, (size_t)n * bmax));
   SWCHK(dev_realloc(h, &proj.p, rows * bmax));
-  std::vector<int32_t> it;
   for (int c0 = 0; c0 < total; c0 += 256) {
     const int nvalid = std::min(256, total - c0), ncols = pad64(nvalid);
-    SWCHK(laph_sources(h, lv, d_t0, c0, nvalid, ncols, h->tp_rhs));
-    int tot = 0;
-    SWCHK(solve_dev(h, hid, 0, h->tp_rhs, h->tp_z, tol, maxiter, ncols, &tot));
-    SWCHK(record_level_iters(h, h->hier[hid], 0, tot, it, nvalid));
-    if (iters) std::copy(it.begin(), it.end(), iters + c0);
-    SWCHK(laph_project(h, lv, h->tp_z, ncols, proj));
+    SWCHK(laph_block(h, hid, lv, d_t0, c0, nvalid, ncols, tol, maxiter, proj, iters ? iters + c0 : nullptr));
     SWCHK(stream_sync(h));
-    // the columns of one source timeslice are contiguous in `out`: one strided copy per timeslice the block touches
-    for (int c = c0; c < c0 + nvalid;) {
-      const int s = c / per, e = std::min(c0 + nvalid, (s + 1) * per);
-      HIPCHK(hipMemcpy2D((cplx*)out + (size_t)s * rows * per + (c - s * per), sizeof(cplx) * per, proj.p + (c - c0),
-                         sizeof(cplx) * ncols, sizeof(cplx) * (e - c), rows, hipMemcpyDeviceToHost));
-      c = e;
-    }
+    SWCHK(laph_copy_tau(h, (cplx*)out, c0, nvalid, ncols, proj, true));
   }
   return 0;
 }
@@ -6142,6 +6183,172 @@ int sw_apply_laph_project(sw_engine* h, int nb, const double* Z, double* out) {
   SWCHK(stream_sync(h));
   HIPCHK(hipMemcpy2D(out, sizeof(cplx) * nb, proj.p, sizeof(cplx) * nbp, sizeof(cplx) * nb, rows,
                      hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ---- distillation: the two-point functions contracted on the device ----------------------------------------
+// The momenta of sw_distilled_two_point with their elementals, computed here once and kept on the device:
+// Mt[j][t][ld][ld], transposed and padded (k_laph_elementals), nmom L ld^2 16 bytes.  Any sw_set_distillation and a
+// new definition of hierarchy 0 drop them.
+int sw_set_distillation_momenta(sw_engine* h, int nmom, const int32_t* p) {
+  SWCHK(check_hier(h, 0, 0, false));
+  if (nmom < 0 || nmom > SW_MAX_MOMENTA)
+    return sw_fail(h, "%d momenta: at most %d per registration", nmom, SW_MAX_MOMENTA);
+  if (nmom == 0) return drop_laph_momenta(h);
+  SWCHK(distillation_ready(h));
+  SWCHK(check_momenta(h, "distilled two-point functions", nmom, p));
+  HIPCHK(hipSetDevice(h->device));
+  SWCHK(stream_sync(h));
+  SWCHK(drop_laph_momenta(h));
+  SWCHK(upload_slice_tables(h, nmom, p, &h->lh_mom, &h->lh_phase, &h->lh_slicerow));
+  Level& lv = h->hier[0].lv[0];
+  const int L = lv.L, ld = h->lh_ld, Lp = h->lh_Lp;
+  const size_t per = (size_t)L * ld * ld;
+  SWCHK(dev_realloc(h, &h->lh_M, (size_t)nmom * per));
+  const dim3 grid(L, (ld / 16 + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK);
+  for (int j = 0; j < nmom; ++j) {
+    if (h->profiling) h->twork[T_LAPH_CONTRACT] += 8.0 * (double)L * (double)Lp * (double)ld * (double)ld;
+    if (p[j] == 0)
+      SWCHK(launch(h, T_LAPH_CONTRACT, swk::k_laph_elementals<false>, grid, dim3(SW_BLOCK), (const cplx*)h->lh_V, ld,
+                   Lp, h->lh_nev, (const cplx*)h->lh_phase, 0, L, h->lh_M + j * per));
+    else
+      SWCHK(launch(h, T_LAPH_CONTRACT, swk::k_laph_elementals<true>, grid, dim3(SW_BLOCK), (const cplx*)h->lh_V, ld,
+                   Lp, h->lh_nev, (const cplx*)h->lh_phase, (int)p[j], L, h->lh_M + j * per));
+  }
+  SWCHK(stream_sync(h));
+  h->lh_momenta.assign(p, p + nmom);
+  return 0;
+}
+
+static int laph_momenta_ready(sw_engine* h) {
+  if (h->lh_momenta.empty() || !h->lh_M)
+    return sw_fail(h, "no distillation momenta registered (sw_set_distillation_momenta)");
+  return 0;
+}
+
+// out complex128 [nmom][L][nev][nev]: the registered elementals M[j][t][m][m'], untransposed and dense.
+int sw_apply_laph_elementals(sw_engine* h, double* out) {
+  SWCHK(check_hier(h, 0, 0, false));
+  SWCHK(distillation_ready(h));
+  SWCHK(laph_momenta_ready(h));
+  if (!out) return sw_fail(h, "null output");
+  HIPCHK(hipSetDevice(h->device));
+  const int nev = h->lh_nev, nz = (int)h->lh_momenta.size() * h->hier[0].lv[0].L;
+  const size_t cnt = (size_t)nz * nev * nev;
+  DevBuf<cplx> dense(h);
+  SWCHK(dev_realloc(h, &dense.p, cnt));
+  SWCHK(launch(h, T_LAPH_CONTRACT, swk::k_laph_elementals_unpack, dim3((nev * nev + SW_BLOCK - 1) / SW_BLOCK, nz),
+               dim3(SW_BLOCK), (const cplx*)h->lh_M, h->lh_ld, nev, dense.p));
+  SWCHK(stream_sync(h));
+  HIPCHK(hipMemcpy(out, dense.p, cnt * sizeof(cplx), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The blocks of sw_distilled_two_point and sw_apply_laph_contract: whole sources, max(1, 256 / (2 nev)) per block
+static inline int laph_sources_per_block(int nev) { return std::max(1, 256 / (2 * nev)); }
+
+// The workspace of the contraction of one block: Y [2 L][ncols][ld], X [2 L][ns][2][nev][ld], T [ns][nmom][16][L],
+// loops [ns][nmom][4], sized for the largest block of the call and reused by every momentum and block.
+struct LaphContractWS {
+  DevBuf<cplx> Y, X, T, loops;
+  explicit LaphContractWS(sw_engine* h) : Y(h), X(h), T(h), loops(h) {}
+};
+static int laph_contract_ws(sw_engine* h, LaphContractWS& ws, int ns, int ncols) {
+  const int L = h->hier[0].lv[0].L, nev = h->lh_nev, ld = h->lh_ld, nmom = (int)h->lh_momenta.size();
+  SWCHK(dev_realloc(h, &ws.Y.p, (size_t)2 * L * ncols * ld));
+  SWCHK(dev_realloc(h, &ws.X.p, (size_t)2 * L * ns * 2 * nev * ld));
+  SWCHK(dev_realloc(h, &ws.T.p, (size_t)ns * nmom * 16 * L));
+  return dev_realloc(h, &ws.loops.p, (size_t)ns * nmom * 4);
+}
+// T [ns][nmom][2][2][2][2][L] and loops [ns][nmom][2][2] of the ns sources d_t0 whose columns are the first 2 nev ns of
+// the projection block proj [L][2][nev][ncols], into the host arrays: per registered momentum k_laph_left ->
+// k_laph_right -> k_laph_reduce (three launches of class SW_KCLASS_LAPH_CONTRACT), then two small copies.
+static int laph_contract(sw_engine* h, const cplx* proj, const int* d_t0, int ns, int ncols, LaphContractWS& ws,
+                         cplx* T, cplx* loops) {
+  const int L = h->hier[0].lv[0].L, nev = h->lh_nev, ld = h->lh_ld, nmom = (int)h->lh_momenta.size();
+  const int NTv = ld / 16, K4 = (nev + 3) / 4 * 4;
+  const size_t per = (size_t)L * ld * ld;
+  for (int j = 0; j < nmom; ++j) {
+    const cplx* Mt = h->lh_M + j * per;
+    if (h->profiling)
+      h->twork[T_LAPH_CONTRACT] += 8.0 * (2.0 * L * (double)ncols * ld * K4 + 4.0 * L * (double)ns * ld * ld * K4 +
+                                          16.0 * L * (double)ns * nev * nev + 4.0 * (double)ns * nev * nev);
+    SWCHK(pick<1, 2, 3, 4, 5, 6, 7, 8>(NTv, [&](auto NT) {
+      SWCHK(launch(h, T_LAPH_CONTRACT, swk::k_laph_left<decltype(NT)::value>, dim3(L, 2, ncols / 64), dim3(SW_BLOCK),
+                   proj, nev, ncols, Mt, ld, ws.Y.p));
+      return launch(h, T_LAPH_CONTRACT, swk::k_laph_right<decltype(NT)::value>,
+                    dim3(2 * L, 2 * ns, (NTv + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK), dim3(SW_BLOCK),
+                    (const cplx*)ws.Y.p, nev, ncols, Mt, ld, d_t0, ns, L, ws.X.p);
+    }));
+    SWCHK(launch(h, T_LAPH_CONTRACT, swk::k_laph_reduce, dim3(L, ns), dim3(SW_BLOCK), proj, nev, ncols,
+                 (const cplx*)ws.X.p, Mt, ld, d_t0, ns, L, j, nmom, ws.T.p, ws.loops.p));
+  }
+  SWCHK(stream_sync(h));
+  HIPCHK(hipMemcpy(T, ws.T.p, sizeof(cplx) * ns * nmom * 16 * L, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(loops, ws.loops.p, sizeof(cplx) * ns * nmom * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The distilled two-point functions of nsrc source timeslices, solved, projected and contracted on the device: per
+// block of whole sources laph_block (as sw_perambulators on that chunk) and laph_contract.  Stateless: no mode buffer,
+// no probe slot and no registration is touched; everything but the two-point workspace lives for this call only.
+int sw_distilled_two_point(sw_engine* h, int nsrc, const int32_t* t0, double tol, int maxiter, double* T,
+                           double* loops, double* tau, int32_t* iters) {
+  SWCHK(check_hier(h, 0, 0, true));
+  SWCHK(distillation_ready(h));
+  SWCHK(laph_momenta_ready(h));
+  SWCHK(check_source_timeslices(h, nsrc, t0));
+  if (maxiter < 1) return sw_fail(h, "maxiter must be >= 1");
+  if (!T || !loops) return sw_fail(h, "null output");
+  int hid;
+  SWCHK(solve_hier(h, 0, &hid));
+  HIPCHK(hipSetDevice(h->device));
+  Level& lv = h->hier[0].lv[0];
+  const int L = lv.L, nev = h->lh_nev, per = 2 * nev, nmom = (int)h->lh_momenta.size();
+  const int spb = laph_sources_per_block(nev), nsmax = std::min(spb, nsrc), bmax = pad64(nsmax * per);
+  DevBuf<int> d_t0(h);
+  DevBuf<cplx> proj(h);
+  LaphContractWS ws(h);
+  SWCHK(upload(h, &d_t0.p, (const int*)t0, (size_t)nsrc));
+  SWCHK(ensure_two_point_ws(h, (size_t)lv.n * bmax));
+  SWCHK(dev_realloc(h, &proj.p, (size_t)L * per * bmax));
+  SWCHK(laph_contract_ws(h, ws, nsmax, bmax));
+  for (int s0 = 0; s0 < nsrc; s0 += spb) {
+    const int ns = std::min(spb, nsrc - s0), nvalid = ns * per, ncols = pad64(nvalid);
+    SWCHK(laph_block(h, hid, lv, d_t0.p + s0, 0, nvalid, ncols, tol, maxiter, proj,
+                     iters ? iters + (size_t)s0 * per : nullptr));
+    SWCHK(laph_contract(h, proj, d_t0.p + s0, ns, ncols, ws, (cplx*)T + (size_t)s0 * nmom * 16 * L,
+                        (cplx*)loops + (size_t)s0 * nmom * 4));
+    if (tau) SWCHK(laph_copy_tau(h, (cplx*)tau + (size_t)s0 * L * per * per, 0, nvalid, ncols, proj, true));
+  }
+  return 0;
+}
+
+// The contraction alone on host perambulators tau [nsrc][L][2][nev][nev][2] (the layout of sw_perambulators), in the
+// blocks of sw_distilled_two_point; the pad columns of a block are zeros.
+int sw_apply_laph_contract(sw_engine* h, int nsrc, const int32_t* t0, const double* tau, double* T, double* loops) {
+  SWCHK(check_hier(h, 0, 0, false));
+  SWCHK(distillation_ready(h));
+  SWCHK(laph_momenta_ready(h));
+  SWCHK(check_source_timeslices(h, nsrc, t0));
+  if (!tau || !T || !loops) return sw_fail(h, "null argument");
+  HIPCHK(hipSetDevice(h->device));
+  const int L = h->hier[0].lv[0].L, nev = h->lh_nev, per = 2 * nev, nmom = (int)h->lh_momenta.size();
+  const int spb = laph_sources_per_block(nev), nsmax = std::min(spb, nsrc), bmax = pad64(nsmax * per);
+  DevBuf<int> d_t0(h);
+  DevBuf<cplx> proj(h);
+  LaphContractWS ws(h);
+  SWCHK(upload(h, &d_t0.p, (const int*)t0, (size_t)nsrc));
+  SWCHK(dev_realloc(h, &proj.p, (size_t)L * per * bmax));
+  SWCHK(laph_contract_ws(h, ws, nsmax, bmax));
+  for (int s0 = 0; s0 < nsrc; s0 += spb) {
+    const int ns = std::min(spb, nsrc - s0), nvalid = ns * per, ncols = pad64(nvalid);
+    SWCHK(stream_sync(h));
+    HIPCHK(hipMemset(proj.p, 0, sizeof(cplx) * L * per * ncols));
+    SWCHK(laph_copy_tau(h, (cplx*)tau + (size_t)s0 * L * per * per, 0, nvalid, ncols, proj, false));
+    SWCHK(laph_contract(h, proj, d_t0.p + s0, ns, ncols, ws, (cplx*)T + (size_t)s0 * nmom * 16 * L,
+                        (cplx*)loops + (size_t)s0 * nmom * 4));
+  }
   return 0;
 }
 
@@ -6808,7 +7015,7 @@ int sw_timers(sw_engine* h, double t[8]) {
   t[T_COARSEST] += h->tacc[T_MFMA_DENSE];
   t[T_OTHER] += h->tacc[T_TP_SOURCES] + h->tacc[T_3PT_SOURCES] + h->tacc[T_SMEAR] + h->tacc[T_LAPH_SRC];
   t[T_DOTS] += h->tacc[T_TP_DOTS] + h->tacc[T_SLICE_CDOTS] + h->tacc[T_MESON_FIELD] + h->tacc[T_LM_CONTRACT] +
-               h->tacc[T_LINK_DOTS] + h->tacc[T_3PT_DOTS] + h->tacc[T_LAPH];
+               h->tacc[T_LINK_DOTS] + h->tacc[T_3PT_DOTS] + h->tacc[T_LAPH] + h->tacc[T_LAPH_CONTRACT];
   return 0;
 }
 int sw_timers_reset(sw_engine* h) {

@@ -4510,4 +4510,247 @@ __global__ __launch_bounds__(SW_BLOCK) void k_laph_project(const cplx* __restric
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// The distilled two-point functions contracted on the device (sw_set_distillation_momenta, sw_distilled_two_point).
+// ------------------------------------------------------------------------------------------
+// Elementals of one momentum p, stored TRANSPOSED and padded, the layout every later stage takes as an MFMA operand:
+//   Mt[t][r][c] = M[t][c][r] = sum_x omega^(p x) conj(v_c(x,t)) v_r(x,t),   r, c < ld,
+// per timeslice an ld x Lp x ld product on v_mfma_f64_16x16x4_f64, K = x, operand lanes as k_meson_field: lane l holds
+// A[l&15][l>>4] = conj(a), a = Vc[t][x0 + (l>>4)][16 rt + (l&15)] (the packed conj(v_r), conjugated back by the signs
+// of the four real MFMAs), B[l>>4][l&15] = omega^(p x) Vc[t][x][16 ct + (l&15)], D[(l>>4) + 4 i][l&15].  Both operand
+// rows are the contiguous m of the packed eigenvectors; the rows x in [L, Lp) are packed zeros.  grid = (L,
+// ceil(NT / 4)): wave w owns the row tile rt = 4 blockIdx.y + w and walks the column tiles four at a time.  Every
+// entry is summed by one wave in the order x = 0, 4, 8, ..., written once; the padding rows and columns (>= nev) are
+// written as exact zeros.  PHASE = false: p = 0, no table, no multiply.  No LDS, no barrier.
+template <bool PHASE>
+__global__ __launch_bounds__(SW_BLOCK) void k_laph_elementals(const cplx* __restrict__ Vc, int ld, int Lp, int nev,
+                                                              const cplx* __restrict__ phase, int p, int L,
+                                                              cplx* __restrict__ out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int k = lane >> 4, c = lane & 15;
+  const int t = blockIdx.x, nt = ld / 16;
+  const int rt = blockIdx.y * SW_WAVES_PER_BLOCK + wave;
+  if (rt >= nt) return;
+  const cplx* __restrict__ v = Vc + (size_t)t * Lp * ld;
+  cplx* __restrict__ o = out + (size_t)t * ld * ld;
+  for (int g0 = 0; g0 < nt; g0 += 4) {
+    const int ng = min(4, nt - g0);
+    sw_double4 re[4], im[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) re[q] = im[q] = sw_double4{0.0, 0.0, 0.0, 0.0};
+    for (int x0 = 0; x0 < Lp; x0 += 4) {
+      const int x = x0 + k;                     // < Lp
+      const cplx* __restrict__ row = v + (size_t)x * ld;
+      const cplx a = row[rt * 16 + c];
+      cplx w = cmake(1.0, 0.0);
+      if constexpr (PHASE) w = phase[(p * x) % L];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (q < ng) {
+          cplx b = row[(g0 + q) * 16 + c];
+          if constexpr (PHASE) b = cmul(w, b);
+          // conj(a) b = (ar br + ai bi) + i (ar bi - ai br)
+          re[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, b.x, re[q], 0, 0, 0);
+          re[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, b.y, re[q], 0, 0, 0);
+          im[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, b.y, im[q], 0, 0, 0);
+          im[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(-a.y, b.x, im[q], 0, 0, 0);
+        }
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if (q < ng) {
+        const int mc = (g0 + q) * 16 + c;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int mr = rt * 16 + k + 4 * i;
+          o[(size_t)mr * ld + mc] = (mr < nev && mc < nev) ? cmake(re[q][i], im[q][i]) : cmake(0.0, 0.0);
+        }
+      }
+    }
+  }
+}
+
+// out[z][m][m'] = Mt[z][m'][m] for m, m' < nev: the elementals as sw_apply_laph_elementals returns them, dense and
+// untransposed.  grid = (ceil(nev^2 / SW_BLOCK), nmom L), one thread per entry.
+__global__ __launch_bounds__(SW_BLOCK) void k_laph_elementals_unpack(const cplx* __restrict__ Mt, int ld, int nev,
+                                                                     cplx* __restrict__ out) {
+  const int idx = blockIdx.x * SW_BLOCK + threadIdx.x;
+  if (idx >= nev * nev) return;
+  const int m = idx / nev, mp = idx - m * nev;
+  out[(size_t)blockIdx.y * nev * nev + idx] = Mt[((size_t)blockIdx.y * ld + mp) * ld + m];
+}
+
+// The product both matrix stages of the contraction are: for one wave, the 16 x ld tile
+//   D[i][j] = sum_{k < K} A[k sa + i] op(B[k ld + j]),   i < 16, j < ld = 16 NT,   op = conj where CONJB is set,
+// on v_mfma_f64_16x16x4_f64, four real MFMAs per complex product (re += ar br, re += -+ai bi, im += +-ar bi,
+// im += ai br).  The summed index k is the slow index of both operands, so a lane's operand elements lie in rows
+// contiguous over the lanes: lane l holds A[l&15][l>>4] = A[(k0 + (l>>4)) sa + (l&15)] and B[l>>4][l&15] =
+// B[(k0 + (l>>4)) ld + 16 q + (l&15)], D[(l>>4) + 4 r][l&15].  The A element is loaded once per K step and serves
+// all NT column tiles from a register (2 NT accumulators of four doubles; NT <= 8: 128 registers).  Summed in the
+// order k = 0, 4, 8, ...; k >= K (K not a multiple of 4) enters as an exact zero of A, never read, against rows of B
+// that exist (K <= ld).  D is written as out[i so + j], all 16 x ld entries.
+template <int NT, bool CONJB>
+__device__ __forceinline__ void laph_tile_product(const cplx* __restrict__ A, size_t sa, int K,
+                                                  const cplx* __restrict__ B, int ld, cplx* __restrict__ out,
+                                                  size_t so, int nrows) {
+  const int lane = threadIdx.x & 63;
+  const int k = lane >> 4, c = lane & 15;
+  sw_double4 re[NT], im[NT];
+#pragma unroll
+  for (int q = 0; q < NT; ++q) re[q] = im[q] = sw_double4{0.0, 0.0, 0.0, 0.0};
+  for (int k0 = 0; k0 < K; k0 += 4) {
+    const int kk = k0 + k;                      // < ld
+    cplx a = cmake(0.0, 0.0);
+    if (kk < K) a = A[(size_t)kk * sa + c];
+    const double are = CONJB ? a.y : -a.y;      // re += are bi
+    const double aim = CONJB ? -a.x : a.x;      // im += aim bi
+    const cplx* __restrict__ bp = B + (size_t)kk * ld + c;
+#pragma unroll
+    for (int q = 0; q < NT; ++q) {
+      const cplx b = bp[q * 16];
+      re[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, b.x, re[q], 0, 0, 0);
+      re[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(are, b.y, re[q], 0, 0, 0);
+      im[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(aim, b.y, im[q], 0, 0, 0);
+      im[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, b.x, im[q], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < NT; ++q) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = k + 4 * r;
+      if (i < nrows) out[(size_t)i * so + q * 16 + c] = cmake(re[q][r], im[q][r]);
+    }
+  }
+}
+
+// Stage 1, the left product, written with the eigenvector index contiguous:
+//   Y[(t,d)][col][m1] = sum_{m2 < nev} M_t[m1][m2] tau[(t,d)][m2][col],   [2 L][ncols][ld],
+// tau the projection block [L][2][nev][ncols] as k_laph_project leaves it, Mt the transposed elementals of the
+// momentum.  grid = (L, 2, ncols / 64) as k_laph_project: a wave owns 16 columns of one (t, d) and all NT tiles of
+// m1, A = the columns (rows of tau, contiguous), B = Mt[t].  A column's values depend on that column alone; the
+// entries m1 >= nev are exact zeros (the padding of Mt) unless tau is not finite.  No LDS, no barrier.
+template <int NT>
+__global__ __launch_bounds__(SW_BLOCK) void k_laph_left(const cplx* __restrict__ tau, int nev, int ncols,
+                                                        const cplx* __restrict__ Mt, int ld,
+                                                        cplx* __restrict__ Y) {
+  const int wave = threadIdx.x >> 6;
+  const int t = blockIdx.x;
+  const size_t td = (size_t)t * 2 + blockIdx.y;
+  const size_t col = (size_t)blockIdx.z * 64 + wave * 16;
+  laph_tile_product<NT, false>(tau + td * nev * ncols + col, (size_t)ncols, nev, Mt + (size_t)t * ld * ld, ld,
+                               Y + (td * ncols + col) * ld, (size_t)ld, 16);
+}
+
+// Stage 2, the right product with the elemental of every source's own timeslice:
+//   X[(t,d)][s][b][m1][n1] = sum_{n2 < nev} Y[(t,d)][(s,n2,b)][m1] conj(M_{t0(s)}[n1][n2]),   [2 L][ns][2][nev][ld],
+// grid = (2 L, 2 ns, ceil(NT / 4)): wave w owns the rows m1 of tile 4 blockIdx.z + w and all NT tiles of n1; A = the
+// rows of Y at the columns (s, n2, b), n2 with stride 2 ld, B = conj(Mt[t0s[s]]).  The rows m1 >= nev are not stored;
+// the columns n1 >= nev are exact zeros.  A source's values depend on its own columns alone.  No LDS, no barrier.
+template <int NT>
+__global__ __launch_bounds__(SW_BLOCK) void k_laph_right(const cplx* __restrict__ Y, int nev, int ncols,
+                                                         const cplx* __restrict__ Mt, int ld,
+                                                         const int* __restrict__ t0s, int ns, int L,
+                                                         cplx* __restrict__ X) {
+  const int wave = threadIdx.x >> 6;
+  const int mt = blockIdx.z * SW_WAVES_PER_BLOCK + wave;
+  if (mt >= NT) return;
+  const size_t td = blockIdx.x;
+  const int s = blockIdx.y >> 1, b = blockIdx.y & 1;
+  const int t0 = t0s[s];
+  laph_tile_product<NT, true>(Y + (td * ncols + (size_t)s * nev * 2 + b) * ld + mt * 16, (size_t)2 * ld, nev,
+                              Mt + (size_t)t0 * ld * ld, ld,
+                              X + (((td * ns + s) * 2 + b) * nev + mt * 16) * ld, (size_t)ld, nev - mt * 16);
+}
+
+// Stage 3, the reduction: for the timeslice t = blockIdx.x and the source s = blockIdx.y of the block
+//   T[s][a][b][c][d][t] = sum_{m1,n1 < nev} conj(tau[(t,c)][m1][(s,n1,a)]) X[(t,d)][s][b][m1][n1]
+//   loop[s][a][b]       = sum_{m,n < nev} M_{t0}[n][m] tau[(t0,b)][m][(s,n,a)]            (the workgroup with t = t0s[s])
+// on the VALU, every complex product in its four-real-product form.  Thread i takes the terms (m1, n1) = i, i + 256,
+// ... of the row-major nev x nev index (n1 fastest: contiguous in tau, X and Mt alike) into 20 complex sums of its own;
+// a wave adds its 64 lanes by the xor butterfly 32, 16, ..., 1, the four waves meet in LDS and are added in the order
+// w0 + w1 + w2 + w3.  The order is a function of nev alone: no atomics, two calls agree bit for bit, and a source's
+// values do not depend on the other sources of the block.  out_T [ns][nmom][16][L] at momentum j, out_l
+// [ns][nmom][4].
+__global__ __launch_bounds__(SW_BLOCK) void k_laph_reduce(const cplx* __restrict__ tau, int nev, int ncols,
+                                                          const cplx* __restrict__ X, const cplx* __restrict__ Mt,
+                                                          int ld, const int* __restrict__ t0s, int ns, int L, int j,
+                                                          int nmom, cplx* __restrict__ out_T,
+                                                          cplx* __restrict__ out_l) {
+  __shared__ double red[SW_WAVES_PER_BLOCK][40];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int t = blockIdx.x, s = blockIdx.y;
+  const int t0 = t0s[s];
+  const bool at_source = t == t0;
+  const cplx* __restrict__ tp = tau + (size_t)t * 2 * nev * ncols + (size_t)s * nev * 2;
+  const cplx* __restrict__ xp = X + ((size_t)t * 2 * ns + s) * 2 * nev * ld;
+  const size_t xd = (size_t)ns * 2 * nev * ld, xb = (size_t)nev * ld;        // strides of d and b in X
+  const cplx* __restrict__ mp = Mt + (size_t)t0 * ld * ld;
+  cplx acc[16], lp[4];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] = cmake(0.0, 0.0);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) lp[i] = cmake(0.0, 0.0);
+  const int terms = nev * nev;
+  for (int idx = threadIdx.x; idx < terms; idx += SW_BLOCK) {
+    const int m1 = idx / nev, n1 = idx - m1 * nev;
+    cplx u[2][2], x[2][2];                      // u[c][a], x[d][b]
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const cplx* __restrict__ r = tp + ((size_t)c * nev + m1) * ncols + 2 * n1;
+      u[c][0] = r[0];
+      u[c][1] = r[1];
+    }
+#pragma unroll
+    for (int d = 0; d < 2; ++d)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) x[d][b] = xp[d * xd + b * xb + (size_t)m1 * ld + n1];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+          for (int d = 0; d < 2; ++d) cfmac(acc[a * 8 + b * 4 + c * 2 + d], u[c][a], x[d][b]);
+    if (at_source) {
+      const cplx e = mp[(size_t)m1 * ld + n1];  // Mt[t0][m][n] = M[t0][n][m]
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) cfma(lp[a * 2 + b], e, u[b][a]);
+    }
+  }
+  double v[40];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    v[2 * i] = acc[i].x;
+    v[2 * i + 1] = acc[i].y;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    v[32 + 2 * i] = lp[i].x;
+    v[33 + 2 * i] = lp[i].y;
+  }
+#pragma unroll
+  for (int i = 0; i < 40; ++i) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v[i] += __shfl_xor(v[i], off, 64);
+    if (lane == 0) red[wave][i] = v[i];
+  }
+  __syncthreads();
+  const int i = threadIdx.x;
+  if (i < 40) {
+    const double sum = ((red[0][i] + red[1][i]) + red[2][i]) + red[3][i];
+    if (i < 32) {
+      double* o = (double*)(out_T + (((size_t)s * nmom + j) * 16 + (i >> 1)) * L + t);
+      o[i & 1] = sum;
+    } else if (at_source) {
+      double* o = (double*)(out_l + ((size_t)s * nmom + j) * 4 + ((i - 32) >> 1));
+      o[i & 1] = sum;
+    }
+  }
+}
+
 }  // namespace swk

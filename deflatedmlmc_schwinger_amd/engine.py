@@ -77,6 +77,7 @@ KCLASS_3PT_SOURCES = 23    # ... and of k_seq_sources / k_pair_slice_total and t
 KCLASS_3PT_DOTS = 24       # ... and of k_slice_seq_dots
 KCLASS_SMEAR = 25          # ... and of k_smear_step / k_smear_fused (smeared two-point functions)
 KCLASS_LAPH = 26           # ... and of k_laph_sources / k_laph_project (distillation)
+KCLASS_LAPH_CONTRACT = 27  # ... and of k_laph_elementals / k_laph_left / k_laph_right / k_laph_reduce
 MAX_LAPH = 128             # SW_MAX_LAPH
 MAX_SINK_LEVELS = 4        # SW_MAX_SINK_LEVELS, SW_MAX_SMEARING_STEPS
 MAX_SMEARING_STEPS = 1024
@@ -275,6 +276,10 @@ def load_library():
     sig("sw_perambulators", i32, vp, i32, vp, dbl, i32, vp, vp)
     sig("sw_apply_laph_sources", i32, vp, i32, vp, vp)
     sig("sw_apply_laph_project", i32, vp, i32, vp, vp)
+    sig("sw_set_distillation_momenta", i32, vp, i32, vp)
+    sig("sw_apply_laph_elementals", i32, vp, vp)
+    sig("sw_distilled_two_point", i32, vp, i32, vp, dbl, i32, vp, vp, vp, vp)
+    sig("sw_apply_laph_contract", i32, vp, i32, vp, vp, vp, vp)
     _lib = lib
     return lib
 
@@ -305,6 +310,7 @@ EXPORTED_SYMBOLS = (
     "sw_set_three_point", "sw_hutch_fetch_three_point", "sw_apply_seq_sources", "sw_apply_seq_dots",
     "sw_set_smearing", "sw_apply_smearing", "sw_hutch_fetch_two_point_smeared",
     "sw_set_distillation", "sw_perambulators", "sw_apply_laph_sources", "sw_apply_laph_project",
+    "sw_set_distillation_momenta", "sw_apply_laph_elementals", "sw_distilled_two_point", "sw_apply_laph_contract",
 )
 
 
@@ -375,6 +381,7 @@ class Engine:
             self._nmom = 0             # ... and its loop momenta
             self._t3_nmom = 0          # ... and its three-point registration
             self._lh_nev = 0           # ... and its distillation vectors
+            self._lh_nmom = 0          # ... with their momenta
 
     def set_lattice(self, hid, L, mass, U1, U2):
         U1, U2 = _c128(U1), _c128(U2)
@@ -1090,11 +1097,12 @@ class Engine:
         empty array clears).  Orthonormality is not checked: V defines the operator."""
         if V is None or np.size(V) == 0:
             self._chk(self._lib.sw_set_distillation(self._h, 0, None), "sw_set_distillation")
-            self._lh_nev = 0
+            self._lh_nev = self._lh_nmom = 0
             return
         V = _c128(V)
         if V.ndim != 3 or V.shape[0] != V.shape[2]:
             raise EngineError("set_distillation: V of shape %s, expected (L, nev, L)" % (V.shape,))
+        self._lh_nmom = 0              # every registration drops the momenta of set_distillation_momenta
         self._chk(self._lib.sw_set_distillation(self._h, V.shape[1], _ptr(V)), "sw_set_distillation")
         self._lh_nev = int(V.shape[1])
 
@@ -1132,6 +1140,61 @@ class Engine:
         self._chk(self._lib.sw_apply_laph_project(self._h, Z2.shape[0], _ptr(Z2), _ptr(out) if out.size else None),
                   "sw_apply_laph_project")
         return out
+
+    def set_distillation_momenta(self, momenta):
+        """The momenta of distilled_two_point(): at most MAX_MOMENTA different integers in [0, L) (None or an empty list
+        clears).  Needs set_distillation; the elementals are computed on the device here and stay there until the next
+        set_distillation."""
+        p = np.ascontiguousarray([] if momenta is None else momenta, dtype=np.int32).reshape(-1)
+        self._chk(self._lib.sw_set_distillation_momenta(self._h, p.size, _ptr(p) if p.size else None),
+                  "sw_set_distillation_momenta")
+        self._lh_nmom = int(p.size)
+
+    def _laph_shape(self):
+        return int(round((self._n(0, 0) // 2) ** 0.5)), getattr(self, "_lh_nev", 0), getattr(self, "_lh_nmom", 0)
+
+    def laph_elementals(self):
+        """M[nmom, L, nev, nev] = sum_x e^{-2 pi i p_j x / L} conj(v_m(x, t)) v_m'(x, t): the registered elementals as
+        the device computed them (utils.laph_elementals)."""
+        L, nev, nmom = self._laph_shape()
+        out = np.zeros((nmom, L, nev, nev), dtype=np.complex128)
+        self._chk(self._lib.sw_apply_laph_elementals(self._h, _ptr(out) if out.size else None),
+                  "sw_apply_laph_elementals")
+        return out
+
+    def distilled_two_point(self, t0s, tol, maxiter=1000, keep=True):
+        """(T[nsrc, nmom, 2, 2, 2, 2, L], loops[nsrc, nmom, 2, 2], tau or None, iters[nsrc, nev, 2]): the perambulators
+        of the timeslices t0s solved, projected and contracted on the device (utils.distilled_pair_sums and the
+        source-timeslice entries of utils.distilled_loops); tau as perambulators() returns it when keep is set,
+        otherwise nothing of its size leaves the device.  Stateless: no mode buffer is touched."""
+        t = self._t0s(t0s)
+        L, nev, nmom = self._laph_shape()
+        T = np.zeros((t.size, nmom, 2, 2, 2, 2, L), dtype=np.complex128)
+        loops = np.zeros((t.size, nmom, 2, 2), dtype=np.complex128)
+        tau = np.zeros((t.size, L, 2, nev, nev, 2), dtype=np.complex128) if keep else None
+        iters = np.zeros((t.size, nev, 2), dtype=np.int32)
+        self._chk(self._lib.sw_distilled_two_point(self._h, t.size, _ptr(t) if t.size else None, float(tol),
+                                                   int(maxiter), _ptr(T) if T.size else None,
+                                                   _ptr(loops) if loops.size else None,
+                                                   _ptr(tau) if keep and tau.size else None,
+                                                   _ptr(iters) if iters.size else None), "sw_distilled_two_point")
+        return T, loops, tau, iters
+
+    def apply_laph_contract(self, tau, t0s):
+        """The contraction kernels alone on perambulators tau[nsrc, L, 2, nev, nev, 2]: (T, loops) as
+        distilled_two_point() returns them."""
+        t = self._t0s(t0s)
+        L, nev, nmom = self._laph_shape()
+        tau = _c128(tau)
+        if tau.shape != (t.size, L, 2, nev, nev, 2):
+            raise EngineError("apply_laph_contract: tau of shape %s, expected %s"
+                              % (tau.shape, (t.size, L, 2, nev, nev, 2)))
+        T = np.zeros((t.size, nmom, 2, 2, 2, 2, L), dtype=np.complex128)
+        loops = np.zeros((t.size, nmom, 2, 2), dtype=np.complex128)
+        self._chk(self._lib.sw_apply_laph_contract(self._h, t.size, _ptr(t) if t.size else None,
+                                                   _ptr(tau) if tau.size else None, _ptr(T) if T.size else None,
+                                                   _ptr(loops) if loops.size else None), "sw_apply_laph_contract")
+        return T, loops
 
     def hutch_batch_two_point_smeared(self, level, probes, tol, maxiter=1000):
         """One MODE_TWO_POINT_SMEARED batch: (T[nb, nsink, nmom, 2, 2, 2, 2, L], iters_fine[nb], iters_coarse[nb])."""

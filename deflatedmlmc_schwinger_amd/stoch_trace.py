@@ -23,7 +23,7 @@ from .utils import (_engines, deflation_pre_computations, displacements_of, draw
                     register_low_modes, low_mode_contraction_of, link_loops_of, three_point_of,
                     register_three_point, refuse_three_point, register_smearing, refuse_smearing, smearing_of,
                     distillation_of, refuse_distillation, laplacian_eigenvectors, laph_elementals,
-                    distilled_pair_sums, distilled_loops, source_average)
+                    distilled_pair_sums, distilled_loops, source_average, distilled_contraction_of)
 
 DEFAULT_BATCH = 256
 NR_ROUGH_PROBES = 5
@@ -616,7 +616,8 @@ def distilled_two_point(A, params):
     of the gauge-covariant spatial Laplacian of every timeslice, box(t) = sum_m v_m v_m^H.  For every listed source
     timeslice the engine solves the 2 N eigenvector sources and projects the solutions on the device
     (Engine.perambulators); the perambulators tau(t, t0) are exact -- no noise, no stopping rule -- and every
-    connected correlator follows from them on the host:
+    connected correlator follows from them, on the host or (distilled_contraction = "device") by the
+    engine's contraction kernels with the perambulator blocks staying on the device (Engine.distilled_two_point):
 
         two_point[s][p][a][b][c][d][t]   utils.distilled_pair_sums: two_point()'s pair sums with box(t) A^-1 box(t0) in
                                          place of A^-1 (utils.meson_correlator applies unchanged)
@@ -624,7 +625,8 @@ def distilled_two_point(A, params):
         loops[p][a][b][t]                utils.distilled_loops on the source timeslices, NaN elsewhere
 
     Keys (utils.distillation_of): distillation_vectors, source_timeslices (a list, or "all"), two_point_momenta
-    (default [0]; need not contain 0), keep_perambulators (default True).  The sources go to the engine in chunks of
+    (default [0]; need not contain 0), keep_perambulators (default True), distilled_contraction ("host", the default,
+    or "device"; utils.distilled_contraction_of).  The sources go to the engine in chunks of
     max(1, 256 // (2 N)) timeslices, one 256-column solve block each, and are contracted chunk by chunk: with
     keep_perambulators false nothing of the size of all perambulators is retained.  One rank; the operator has to be the
     lattice stencil the engine detects.
@@ -635,6 +637,7 @@ def distilled_two_point(A, params):
     sel = distillation_of(params)
     if sel is None:
         raise Exception("distilled_two_point() needs the key distillation_vectors")
+    on_device = distilled_contraction_of(params) == "device"
     if _dist.default_comm().world > 1:
         raise Exception("distilled two-point functions run on one rank")
     # H pairs sites through the links: the operator has to be the lattice stencil the engine detects
@@ -651,7 +654,10 @@ def distilled_two_point(A, params):
     eng = engs[0]
     V, eigenvalues = laplacian_eigenvectors(lattice[2], L, nev)
     eng.set_distillation(V)
-    M = laph_elementals(V, L, momenta)
+    if on_device:
+        eng.set_distillation_momenta(momenta)
+    else:
+        M = laph_elementals(V, L, momenta)
     n = 2 * L * L
     tol, maxiter = params['function_params']['tol'], (n if n < 1000 else 1000)
 
@@ -668,12 +674,18 @@ def distilled_two_point(A, params):
     for first in range(0, len(t0s), chunk):
         part = t0s[first:first + chunk]
         t1 = time.time()
-        tau, it = eng.perambulators(part, tol, maxiter)
-        solve_s += time.time() - t1
+        if on_device:
+            Tp, lp, tau, it = eng.distilled_two_point(part, tol, maxiter, keep=sel['keep'])
+            solve_s += time.time() - t1
+            T[first:first + len(part)] = Tp
+            loops[..., part] = lp.transpose(1, 2, 3, 0)                    # [s][p][a][b] -> [p][a][b][t0s[s]]
+        else:
+            tau, it = eng.perambulators(part, tol, maxiter)
+            solve_s += time.time() - t1
+            T[first:first + len(part)] = distilled_pair_sums(tau, M, part)
+            lp = distilled_loops(tau, M, part)
+            loops[..., part] = lp[..., part]
         iters += int(np.sum(it))
-        T[first:first + len(part)] = distilled_pair_sums(tau, M, part)
-        lp = distilled_loops(tau, M, part)
-        loops[..., part] = lp[..., part]
         if kept is not None:
             kept.append(tau)
     print(" done. Time : " + str(solve_s) + " seconds")

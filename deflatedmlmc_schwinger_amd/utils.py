@@ -66,7 +66,7 @@ _BUILD_KEYS = ('batch', 'device', 'engines', 'cache_dir', 'report_path', 'probe_
                'timeslice_loops', 'source_timeslice', 'two_point_momenta', 'low_mode_contraction', 'link_loops',
                'sink_timeslice', 'sink_gamma', 'sink_momentum', 'three_point_momenta',
                'smearing_kappa', 'source_smearing_steps', 'sink_smearing_steps',
-               'distillation_vectors', 'source_timeslices', 'keep_perambulators')
+               'distillation_vectors', 'source_timeslices', 'keep_perambulators', 'distilled_contraction')
 # where the eigenpairs of the MLMC difference operators come from: host ARPACK (the reference's path) or
 # the block eigensolver on the GPU (setup_gpu.device_diff_eigenpairs)
 MLMC_DEFL_SETUPS = ("host", "device")
@@ -633,7 +633,10 @@ def refuse_smearing(params, who):
             raise Exception("%s belongs to two_point(), not to %s" % (key, who))
 
 
-DISTILLATION_KEYS = ('distillation_vectors', 'source_timeslices', 'keep_perambulators')
+DISTILLATION_KEYS = ('distillation_vectors', 'source_timeslices', 'keep_perambulators', 'distilled_contraction')
+# where distilled_two_point() contracts the perambulators: NumPy on the host from the read-back blocks, or the engine's
+# kernels with the blocks staying on the device (Engine.distilled_two_point)
+DISTILLED_CONTRACTIONS = ("host", "device")
 MAX_LAPH = 128                 # SW_MAX_LAPH of the engine
 LAPH_TIE = 1e-8                # moduli this close (relatively) to the largest are tied in the phase convention
 
@@ -830,6 +833,63 @@ def distillation_of(params):
     if not isinstance(keep, (bool, np.bool_)):
         raise Exception("keep_perambulators: %r is not a bool" % (keep,))
     return dict(nev=nev, t0s=t0s, momenta=momenta, keep=bool(keep))
+
+
+def distilled_contraction_of(params):
+    """The build-only key distilled_contraction of distilled_two_point(): "host" (also when absent) or "device"."""
+    where = params.get('distilled_contraction') if hasattr(params, "get") else None
+    where = "host" if where is None else where
+    if not isinstance(where, str) or where not in DISTILLED_CONTRACTIONS:
+        raise Exception("distilled_contraction: %r is none of %s" % (where, ", ".join(DISTILLED_CONTRACTIONS)))
+    return where
+
+
+def distilled_sums_wide(tau, M, t0s):
+    """(T, loops) of distilled_pair_sums and distilled_loops evaluated in np.clongdouble: T[s, j, a, b, c, d, t] and
+    loops[s, j, a, b] (per source, the entry of its own timeslice) -- the reference of the device contraction."""
+    tau, M, t0s = _check_tau(tau, M, t0s, "distilled_sums_wide")
+    return _distilled_sums(tau.astype(np.clongdouble), M.astype(np.clongdouble), t0s)
+
+
+def _distilled_sums(tau, M, t0s):
+    nsrc, L = tau.shape[:2]
+    T = np.zeros((nsrc, M.shape[0], 2, 2, 2, 2, L), dtype=tau.dtype)
+    loops = np.zeros((nsrc, M.shape[0], 2, 2), dtype=tau.dtype)
+    for s, t0 in enumerate(t0s):
+        ts = np.ascontiguousarray(tau[s].transpose(0, 1, 4, 2, 3))         # [t][c][a][m][n]
+        for j in range(M.shape[0]):
+            X = np.matmul(np.matmul(M[j][:, None, None], ts), M[j, t0].conj().T)       # [t][d][b][m1][n1]
+            T[s, j] = np.einsum('tcamn,tdbmn->abcdt', ts.conj(), X)
+        loops[s] = np.einsum('jnm,bmna->jab', M[:, t0], tau[s, t0])
+    return T, loops
+
+
+def distilled_contract_bounds(tau, M, t0s, wide=True):
+    """(bound_T, bound_loops), the rounding bounds of the device contraction, shaped as distilled_sums_wide:
+    |dT| <= (N^2 + 2 N + 16) 2^-52 W with W = sum_{m1,n1} |tau_ca| (|M_t| |tau_db| |M_t0|^T), and
+    |dloop| <= (N^2 + 8) 2^-52 sum_{m,n} |M_t0| |tau| -- the three stages are chains of N, N and N^2 complex
+    multiply-adds.  M: the elementals the device used.  The weights are sums of non-negative terms, evaluated in
+    np.longdouble, or (wide false, for large N) in float64, which is off by a relative N^2 2^-53 at most."""
+    tau, M, t0s = _check_tau(tau, M, t0s, "distilled_contract_bounds")
+    N = tau.shape[3]
+    rtype = np.longdouble if wide else np.float64
+    W, w = _distilled_sums(np.abs(tau).astype(rtype), np.abs(M).astype(rtype), t0s)
+    eps = rtype(2.0) ** -52
+    return (N * N + 2 * N + 16) * eps * W, (N * N + 8) * eps * w
+
+
+def laph_elemental_bounds(V, L):
+    """bound[t, m, m'] = (L + 8) 2^-52 sum_x |v_m(x, t)| |v_m'(x, t)|: the rounding bound of a device elemental of any
+    momentum (the three-factor chain of 4g)."""
+    a = np.abs(_check_laph(V, L, "laph_elemental_bounds")).astype(np.longdouble)
+    return (L + 8) * np.longdouble(2.0) ** -52 * np.einsum('tmx,tnx->tmn', a, a)
+
+
+def laph_elementals_wide(V, L, momenta):
+    """laph_elementals evaluated in np.clongdouble (the phases are the engine's table, as there)."""
+    V = _check_laph(V, L, "laph_elementals_wide").astype(np.clongdouble)
+    ph = _phase_table(L)[np.outer(np.asarray(momenta, dtype=np.int64), np.arange(L)) % L].astype(np.clongdouble)
+    return np.einsum('tmx,jtnx->jtmn', V.conj(), ph[:, None, None, :] * V[None])
 
 
 def refuse_distillation(params, who):

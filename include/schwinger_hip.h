@@ -387,6 +387,41 @@ int sw_apply_laph_sources(sw_engine* h, int nsrc, const int32_t* t0, double* out
 /* k_laph_project alone on nb host vectors Z complex128[nb][n] (reference ordering): out complex128[L][2][nev][nb],
  * out[t][c][m][k] = sum_x conj(v_m(x,t)) Z[k][idx(c,x,t)]. */
 int sw_apply_laph_project(sw_engine* h, int nb, const double* Z, double* out);
+/* The momenta of sw_distilled_two_point: 1 <= nmom <= SW_MAX_MOMENTA distinct p[j] in [0, L); nmom = 0 clears.  Needs
+ * the registration of sw_set_distillation.  The elementals
+ *   M[j][t][m][m'] = sum_x e^{-2 pi i p_j x / L} conj(v_m(x,t)) v_m'(x,t)
+ * are computed here on the fp64 matrix cores (k_laph_elementals: K = x, summed by one wave in the order x = 0, 4, 8,
+ * ...) from the packed eigenvectors and the engine's phase table and stay on the device, transposed and padded to
+ * ld = nev rounded up to 16 with exact zeros: nmom L ld^2 16 bytes.  Any call of sw_set_distillation and a new
+ * definition of hierarchy 0 drop them. */
+int sw_set_distillation_momenta(sw_engine* h, int nmom, const int32_t* p);
+/* out complex128[nmom][L][nev][nev]: the registered elementals M[j][t][m][m'] (one launch of class
+ * SW_KCLASS_LAPH_CONTRACT that counts no work, one copy). */
+int sw_apply_laph_elementals(sw_engine* h, double* out);
+/* The distilled two-point functions of the source timeslices t0[s] (as sw_perambulators), contracted on the device
+ * (build-only, stateless).  The sources go in blocks of max(1, 256 / (2 nev)) WHOLE timeslices, padded to 64 columns;
+ * per block k_laph_sources, the solve and k_laph_project exactly as sw_perambulators runs them on that chunk, then per
+ * registered momentum j three launches on the block tau = proj[(t,c,m)][(s,n,a)]:
+ *   k_laph_left    Y[(t,d)][col][m1]      = sum_m2 M[j][t][m1][m2] tau[(t,d)][m2][col]
+ *   k_laph_right   X[(t,d)][s][b][m1][n1] = sum_n2 Y[(t,d)][(s,n2,b)][m1] conj(M[j][t0[s]][n1][n2])
+ *   k_laph_reduce  T[s][j][a][b][c][d][t] = sum_{m1,n1} conj(tau[(t,c)][m1][(s,n1,a)]) X[(t,d)][s][b][m1][n1]
+ *                  loops[s][j][a][b]      = sum_{m,n} M[j][t0[s]][n][m] tau[(t0[s],b)][m][(s,n,a)]
+ * (the two products on v_mfma_f64_16x16x4_f64, the reduction on the VALU; every complex product in four real ones,
+ * every sum in an order fixed by L, nev and the source's own columns: no atomics, two calls agree bit for bit, and a
+ * source's values do not depend on the other sources of the call), and two small copies.
+ *   T      complex128[nsrc][nmom][2][2][2][2][L]
+ *   loops  complex128[nsrc][nmom][2][2]
+ *   tau    complex128[nsrc][L][2][nev][nev][2], the perambulators of sw_perambulators, or NULL: nothing of that size
+ *          leaves the device
+ *   iters  int32[nsrc][nev][2], or NULL
+ * Refused before anything is allocated or launched without a distillation registration, without momenta, without a
+ * finalised hierarchy, on a bad timeslice list, maxiter < 1 or a null T or loops.  No mode buffer, no probe slot and
+ * no registration is touched; the work buffers are released on return. */
+int sw_distilled_two_point(sw_engine* h, int nsrc, const int32_t* t0, double tol, int maxiter, double* T,
+                           double* loops, double* tau, int32_t* iters);
+/* The contraction of sw_distilled_two_point alone on host perambulators tau complex128[nsrc][L][2][nev][nev][2], in the
+ * same blocks (pad columns zero): T and loops as above. */
+int sw_apply_laph_contract(sw_engine* h, int nsrc, const int32_t* t0, const double* tau, double* T, double* loops);
 /* The sequential-source kernel of SW_MODE_THREE_POINT alone on host solutions: Z complex128[2][nb][n] (spin group a,
  * noise k, reference ordering), out complex128[2][nb][n], out[a][k][idx(e,x,t)] = delta_{t,tf} e^{+2 pi i pf x / L}
  * sum_c ((g3 Gf g3)^H)[e][c] Z[a][k][idx(c,x,tf)] for the registration of sw_set_three_point.  The refusals of the
@@ -722,6 +757,12 @@ int sw_timers_reset(sw_engine* h);
 #define SW_KCLASS_LAPH 26           /* k_laph_sources, k_laph_project (sw_perambulators, sw_apply_laph_*); in sw_timers
                                        the sources count as other, the projection as dots; sw_kernel_work counts
                                        8 * 2 L^2 * ld * ncols flops per projection launch, ld = nev rounded up to 16 */
+#define SW_KCLASS_LAPH_CONTRACT 27  /* k_laph_elementals, k_laph_left, k_laph_right, k_laph_reduce (and the unpack of
+                                       sw_apply_laph_elementals); in sw_timers: dots.  sw_kernel_work counts, with
+                                       K4 = nev rounded up to 4 and Lp = L rounded up to 4, 8 * L * Lp * ld^2 flops
+                                       per momentum of sw_set_distillation_momenta and, per momentum and block of
+                                       ns sources in ncols columns, 8 * (2L * ncols * ld * K4 + 4L * ns * ld^2 * K4
+                                       + 16 L * ns * nev^2 + 4 ns * nev^2) */
 int sw_kernel_stats(sw_engine* h, int which, double* total_ms, int64_t* launches);
 /* Floating-point operations issued by the launches of an MFMA kernel class since the last reset
  * (profiling on): 8 flops per complex multiply-add over every (row tile, k-step, probe). */
