@@ -72,11 +72,12 @@ enum TimerCat { T_MVM = 0, T_DEFL, T_P, T_R, T_AXPY, T_DOTS, T_COARSEST, T_OTHER
                 T_SMEAR,        // k_smear_step / k_smear_fused of SW_MODE_TWO_POINT_SMEARED / sw_apply_smearing
                 T_LAPH,         // k_laph_project of sw_perambulators; SW_KCLASS_LAPH reports it with T_LAPH_SRC
                 T_LAPH_CONTRACT,  // k_laph_elementals / k_laph_left / k_laph_right / k_laph_reduce (sw_distilled_two_point)
+                T_LAPH_GEN,     // k_laph_generalized (sw_generalized_perambulators, sw_apply_laph_generalized)
                 T_LAPH_SRC,     // k_laph_sources (internal: no kernel class of its own)
                 T_NCAT };
 // classes >= T_STENCIL are folded into the mvm / coarsest (two-point and three-point: other / dots; slice cdots,
 // meson fields, their contraction and the link dots: dots; smearing: other; distillation: the projection dots, the
-// sources other, the contraction dots) buckets by
+// sources other, the contraction and the generalized perambulators dots) buckets by
 // sw_timers and reported separately by sw_kernel_stats
 
 struct EllOp {
@@ -6352,6 +6353,168 @@ int sw_apply_laph_contract(sw_engine* h, int nsrc, const int32_t* t0, const doub
   return 0;
 }
 
+// ---- distillation: generalized perambulators, the distilled three-point functions ---------
+// What a k_laph_generalized call needs besides the fields: the insertion timeslices and momenta with their tables on
+// the device, for this call only.
+struct LaphGenTables {
+  DevBuf<int> tins, mom, sr;
+  DevBuf<cplx> phase;
+  int nt = 0, nmom = 0, jz = -1;
+  explicit LaphGenTables(sw_engine* h) : tins(h), mom(h), sr(h), phase(h) {}
+};
+// the argument checks both entry points share; nothing is allocated or launched here
+static int laph_generalized_args(sw_engine* h, int nt, const int32_t* tins, int nmom, const int32_t* q) {
+  Level& lv = h->hier[0].lv[0];
+  if (nmom < 1 || nmom > SW_MAX_MOMENTA)
+    return sw_fail(h, "%d momenta: between 1 and %d per call", nmom, SW_MAX_MOMENTA);
+  SWCHK(check_momenta(h, "generalized perambulators", nmom, q));
+  if (!lv.U1 || !lv.U2)
+    return sw_fail(h, "generalized perambulators need a lattice level 0 with links (sw_set_lattice)");
+  const int L = lv.L;
+  if (nt < 1 || nt > L) return sw_fail(h, "%d insertion timeslices outside [1,%d]", nt, L);
+  if (!tins) return sw_fail(h, "null insertion timeslice list");
+  std::vector<char> seen(L, 0);
+  for (int i = 0; i < nt; ++i) {
+    if (tins[i] < 0 || tins[i] >= L) return sw_fail(h, "insertion timeslice %d outside [0,%d)", (int)tins[i], L);
+    if (seen[tins[i]]) return sw_fail(h, "insertion timeslice %d listed twice", (int)tins[i]);
+    seen[tins[i]] = 1;
+  }
+  return 0;
+}
+static int laph_generalized_tables(sw_engine* h, LaphGenTables& tb, int nt, const int32_t* tins, int nmom,
+                                   const int32_t* q) {
+  SWCHK(upload(h, &tb.tins.p, (const int*)tins, (size_t)nt));
+  SWCHK(upload_slice_tables(h, nmom, q, &tb.mom.p, &tb.phase.p, &tb.sr.p));
+  tb.nt = nt;
+  tb.nmom = nmom;
+  tb.jz = -1;
+  for (int j = 0; j < nmom; ++j)
+    if (q[j] == 0) tb.jz = j;
+  return 0;
+}
+// column tiles of 16 per wave and column groups of a launch over nb0 source columns: at most 8 tiles per wave
+static inline void laph_generalized_tiles(int nb0, int* NT, int* ncg) {
+  const int ct = (nb0 + 15) / 16;
+  *ncg = (ct + 7) / 8;
+  *NT = (ct + *ncg - 1) / *ncg;
+}
+// bytes of G per insertion timeslice, and the timeslices of one chunk of the scoped device buffer (at most 256 MB)
+static inline size_t laph_generalized_chunk(int nt, int nmom, int nbf, int nb0) {
+  const size_t per_t = (size_t)nmom * 6 * nbf * nb0 * sizeof(cplx);
+  return std::min<size_t>((size_t)nt, std::max<size_t>(1, ((size_t)256 << 20) / per_t));
+}
+// G [nt][nmom][6][nbf][nb0] on the host from the columns [cf, cf + nbf) of Zf [n][ldf] and [c0, c0 + nb0) of Z0
+// [n][ld0]: per chunk of timeslices k_laph_generalized (the table-free instantiation for a momentum 0, the phased one
+// over the others) into the buffer `g`, then one copy.
+static int laph_generalized(sw_engine* h, Level& lv, const LaphGenTables& tb, const cplx* Zf, int ldf, int cf, int nbf,
+                            const cplx* Z0, int ld0, int c0, int nb0, DevBuf<cplx>& g, cplx* out) {
+  const int L = lv.L, M = tb.nmom, jz = tb.jz, nz = M - (jz >= 0 ? 1 : 0);
+  int NTv, ncg;
+  laph_generalized_tiles(nb0, &NTv, &ncg);
+  const int rgs = (nbf + 63) / 64, Lp = (L + 3) / 4 * 4;
+  const size_t per_t = (size_t)M * 6 * nbf * nb0, chunk = laph_generalized_chunk(tb.nt, M, nbf, nb0);
+  SWCHK(dev_realloc(h, &g.p, per_t * chunk));
+  for (size_t t0 = 0; t0 < (size_t)tb.nt; t0 += chunk) {
+    const int ntc = (int)std::min(chunk, (size_t)tb.nt - t0);
+    // eight complex products per timeslice and momentum, over the tiles the launch issues
+    if (h->profiling)
+      h->twork[T_LAPH_GEN] += 8.0 * 8.0 * (double)ntc * M * Lp * (16.0 * ((nbf + 15) / 16)) * (16.0 * NTv * ncg);
+    SWCHK(pick<1, 2, 3, 4, 5, 6, 7, 8>(NTv, [&](auto NT) {
+      if (jz >= 0)
+        SWCHK(launch(h, T_LAPH_GEN, swk::k_laph_generalized<false, decltype(NT)::value>,
+                     dim3(6 * ntc, 1, rgs * ncg), dim3(SW_BLOCK), Zf, ldf, cf, nbf, Z0, ld0, c0, nb0,
+                     (const int*)tb.sr.p, (const cplx*)tb.phase.p, (const int*)tb.mom.p,
+                     (const int*)tb.tins.p + t0, (const cplx*)lv.U1, (const cplx*)lv.U2, jz, M, L, ncg, g.p));
+      if (nz > 0)
+        SWCHK(launch(h, T_LAPH_GEN, swk::k_laph_generalized<true, decltype(NT)::value>,
+                     dim3(6 * ntc, nz, rgs * ncg), dim3(SW_BLOCK), Zf, ldf, cf, nbf, Z0, ld0, c0, nb0,
+                     (const int*)tb.sr.p, (const cplx*)tb.phase.p, (const int*)tb.mom.p,
+                     (const int*)tb.tins.p + t0, (const cplx*)lv.U1, (const cplx*)lv.U2, jz, M, L, ncg, g.p));
+      return 0;
+    }));
+    SWCHK(stream_sync(h));
+    HIPCHK(hipMemcpy(out + t0 * per_t, g.p, sizeof(cplx) * per_t * ntc, hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
+// k_laph_generalized alone on host fields Zf [nbf][n], Z0 [nb0][n] (reference ordering): out complex128
+// [nt][nmom][6][nbf][nb0].  Needs a lattice level 0 with links (the condition of sw_set_three_point), no distillation.
+int sw_apply_laph_generalized(sw_engine* h, int nbf, const double* Zf, int nb0, const double* Z0, int nt,
+                              const int32_t* tins, int nmom, const int32_t* q, double* out) {
+  SWCHK(check_hier(h, 0, 0, false));
+  SWCHK(laph_generalized_args(h, nt, tins, nmom, q));
+  if (nbf < 1 || nbf > 256 || nb0 < 1 || nb0 > 256)
+    return sw_fail(h, "%d x %d columns outside [1,256]", nbf, nb0);
+  if (!Zf || !Z0 || !out) return sw_fail(h, "null argument");
+  HIPCHK(hipSetDevice(h->device));
+  Level& lv = h->hier[0].lv[0];
+  const int ldf = pad64(nbf), ld0 = pad64(nb0);
+  LaphGenTables tb(h);
+  DevBuf<cplx> zf(h), z0(h), g(h);
+  SWCHK(laph_generalized_tables(h, tb, nt, tins, nmom, q));
+  SWCHK(dev_realloc(h, &zf.p, (size_t)lv.n * ldf));
+  SWCHK(dev_realloc(h, &z0.p, (size_t)lv.n * ld0));
+  SWCHK(pack_host(h, lv, nbf, Zf, zf, ldf));
+  SWCHK(stream_sync(h));   // the stage is free for the second block
+  SWCHK(pack_host(h, lv, nb0, Z0, z0, ld0));
+  return laph_generalized(h, lv, tb, zf, ldf, 0, nbf, z0, ld0, 0, nb0, g, (cplx*)out);
+}
+
+// The generalized perambulators between the source timeslice t0 and the sink timeslice tf:
+//   G [nt][nmom][6][2 nev][2 nev], row (m, e) = the solution of eigenvector m, spin e on tf, column (n, b) on t0,
+// from the solve blocks sw_perambulators(h, 2, {t0, tf}) makes (tau [2][L][2][nev][nev][2] and iters [2][nev][2],
+// either may be NULL, are what it returns, bit for bit).  One block (4 nev <= 256): the kernel reads both column
+// ranges from the solution block in the two-point workspace.  Two blocks: the columns of the first are copied into
+// scoped buffers before the second solve.  Stateless: no mode buffer, no probe slot and no registration is touched.
+int sw_generalized_perambulators(sw_engine* h, int t0, int tf, int nt, const int32_t* tins, int nmom, const int32_t* q,
+                                 double tol, int maxiter, double* G, double* tau, int32_t* iters) {
+  SWCHK(check_hier(h, 0, 0, true));
+  SWCHK(distillation_ready(h));
+  SWCHK(laph_generalized_args(h, nt, tins, nmom, q));
+  const int32_t ends[2] = {t0, tf};
+  SWCHK(check_source_timeslices(h, 2, ends));
+  if (maxiter < 1) return sw_fail(h, "maxiter must be >= 1");
+  if (!G) return sw_fail(h, "null output");
+  int hid;
+  SWCHK(solve_hier(h, 0, &hid));
+  HIPCHK(hipSetDevice(h->device));
+  Level& lv = h->hier[0].lv[0];
+  const int n = lv.n, L = lv.L, nev = h->lh_nev, per = 2 * nev, total = 2 * per;
+  const int bmax = std::min(256, pad64(total)), ldz = pad64(per);
+  const size_t rows = (size_t)L * 2 * nev;
+  LaphGenTables tb(h);
+  DevBuf<int> d_t0(h);
+  DevBuf<cplx> proj(h), z0(h), zf(h), g(h);
+  SWCHK(upload(h, &d_t0.p, (const int*)ends, (size_t)2));
+  SWCHK(laph_generalized_tables(h, tb, nt, tins, nmom, q));
+  SWCHK(ensure_two_point_ws(h, (size_t)n * bmax));
+  SWCHK(dev_realloc(h, &proj.p, rows * bmax));
+  const bool split = total > 256;
+  if (split) {
+    SWCHK(dev_realloc(h, &z0.p, (size_t)n * ldz));
+    SWCHK(dev_realloc(h, &zf.p, (size_t)n * ldz));   // the pad columns beyond 2 nev are never read
+  }
+  for (int c0 = 0; c0 < total; c0 += 256) {
+    const int nvalid = std::min(256, total - c0), ncols = pad64(nvalid);
+    SWCHK(laph_block(h, hid, lv, d_t0, c0, nvalid, ncols, tol, maxiter, proj, iters ? iters + c0 : nullptr));
+    if (split) {
+      // global columns [c0, c0 + nvalid): those below `per` belong to t0, the others to tf
+      const int n0 = std::max(0, std::min(c0 + nvalid, per) - c0), nf = nvalid - n0;
+      if (n0 > 0)
+        HIPCHK(hipMemcpy2DAsync(z0.p + c0, sizeof(cplx) * ldz, h->tp_z, sizeof(cplx) * ncols, sizeof(cplx) * n0, n,
+                                hipMemcpyDeviceToDevice, h->stream));
+      if (nf > 0)
+        HIPCHK(hipMemcpy2DAsync(zf.p + (c0 + n0 - per), sizeof(cplx) * ldz, h->tp_z + n0, sizeof(cplx) * ncols,
+                                sizeof(cplx) * nf, n, hipMemcpyDeviceToDevice, h->stream));
+    }
+    SWCHK(stream_sync(h));
+    if (tau) SWCHK(laph_copy_tau(h, (cplx*)tau, c0, nvalid, ncols, proj, true));
+  }
+  if (split) return laph_generalized(h, lv, tb, zf, ldz, 0, per, z0, ldz, 0, per, g, (cplx*)G);
+  return laph_generalized(h, lv, tb, h->tp_z, bmax, per, per, h->tp_z, bmax, 0, per, g, (cplx*)G);
+}
+
 // ---- three-point functions: sequential one-end-trick solves and a local or point-split insertion ---------
 // (g3 Gf g3)^H for Gf = 1, g3, s1, s2 as k_seq_sources takes it: bit 0 = the rows select the other spin, bits 1-2 /
 // 3-4 = the entry of row 0 / row 1 as a power of i:  1, diag(1,-1), -s1, -s2 = [[0, i], [-i, 0]]
@@ -7015,7 +7178,8 @@ int sw_timers(sw_engine* h, double t[8]) {
   t[T_COARSEST] += h->tacc[T_MFMA_DENSE];
   t[T_OTHER] += h->tacc[T_TP_SOURCES] + h->tacc[T_3PT_SOURCES] + h->tacc[T_SMEAR] + h->tacc[T_LAPH_SRC];
   t[T_DOTS] += h->tacc[T_TP_DOTS] + h->tacc[T_SLICE_CDOTS] + h->tacc[T_MESON_FIELD] + h->tacc[T_LM_CONTRACT] +
-               h->tacc[T_LINK_DOTS] + h->tacc[T_3PT_DOTS] + h->tacc[T_LAPH] + h->tacc[T_LAPH_CONTRACT];
+               h->tacc[T_LINK_DOTS] + h->tacc[T_3PT_DOTS] + h->tacc[T_LAPH] + h->tacc[T_LAPH_CONTRACT] +
+               h->tacc[T_LAPH_GEN];
   return 0;
 }
 int sw_timers_reset(sw_engine* h) {

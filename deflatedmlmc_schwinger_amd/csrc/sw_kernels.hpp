@@ -4753,4 +4753,137 @@ __global__ __launch_bounds__(SW_BLOCK) void k_laph_reduce(const cplx* __restrict
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// Distilled three-point functions (sw_generalized_perambulators): the generalized perambulators.
+// ------------------------------------------------------------------------------------------
+// i^e z for e in 0..3: a selection with a sign, no rounding
+__device__ __forceinline__ cplx laph_ipow(cplx z, int e) {
+  const cplx r = (e & 1) ? cmake(-z.y, z.x) : z;
+  return (e & 2) ? cmake(-r.x, -r.y) : r;
+}
+
+// out[ti][j][k][r][s] for the insertion timeslice t = tins[ti], the momentum q_j, the component k and the columns
+// r < nbf of Zf (the sink solutions z_f, columns cf + r of a block [n][ldf]) and s < nb0 of Z0 (the source solutions
+// z_0, columns c0 + s of a block [n][ld0]; the two may be one block):
+//   k = 2 f + c < 4:  sum_x omega^(q x) conj(Zf[row(f,x,t)][r]) Z0[row(c,x,t)][s]
+//   k = 4 (mu = x), 5 (mu = t), n = (x, t):
+//       sum_x omega^(q x) U_mu(n) conj(u+[n][r]) v+[n + mu][s]  -  sum_x omega^(q x) conj(U_mu(n)) conj(u-[n + mu][r]) v-[n][s]
+//     with the spin-projected fields u = Zf[spin 0] + conj(l_1) Zf[spin 1], v = Z0[spin 0] + r_1 Z0[spin 1] of the rank-one
+//     g3 H+-_mu = l r^T (l_0 = r_0 = 1; l_1, r_1 powers of i: the projection is one addition, formed here from the two
+//     spin rows as they are loaded).  The forward sum runs first, the backward one second, into the same accumulators.
+// Per branch a (16 rows) x L x (16 NT columns) complex product on v_mfma_f64_16x16x4_f64, K = x, four real MFMAs per
+// complex one, operand lanes as k_meson_field: lane l holds A[l&15][l>>4] = a = conj(w) u at the site x0 + (l>>4), row
+// 16 rt + (l&15), w = omega^(q x) times the link (conjugated and negated on the backward branch) -- applied once per K
+// step, on the left operand; conj(a) b comes from the signs of the MFMAs -- and B[l>>4][l&15] = v at column
+// 16 q + (l&15), D[(l>>4) + 4 i][l&15].  x is the slow index of both blocks (rows through slicerow): a lane's 16
+// columns are 256 contiguous bytes of a block row.  PHASE = false serves the momentum 0 (index jz): no table, the
+// local components multiply nothing.  PHASE = true runs over the other momenta (blockIdx.y skips jz when jz >= 0).
+// grid = (6 ntc, momenta of the launch, row groups x ncg column groups): wave w of a workgroup owns the row tile
+// 4 (row group) + w and the NT column tiles of its column group (2 NT accumulators of four doubles, NT <= 8: 128
+// registers).  Every entry is summed by one wave in the order x = 0, 4, 8, ... (L not a multiple of 4: the missing
+// sites enter with zero weight, rows and columns beyond nbf / nb0 as zeros, never read), written once: no atomics,
+// no LDS, no barrier; an entry depends on its own row and column, its own timeslice and momentum alone; two calls
+// agree bit for bit.  Only r < nbf, s < nb0 are stored.
+template <bool PHASE, int NT>
+__global__ __launch_bounds__(SW_BLOCK) void k_laph_generalized(const cplx* __restrict__ Zf, int ldf, int cf, int nbf,
+                                                               const cplx* __restrict__ Z0, int ld0, int c0, int nb0,
+                                                               const int* __restrict__ slicerow,
+                                                               const cplx* __restrict__ phase,
+                                                               const int* __restrict__ mom,
+                                                               const int* __restrict__ tins,
+                                                               const cplx* __restrict__ U1,
+                                                               const cplx* __restrict__ U2, int jz, int M, int L,
+                                                               int ncg, cplx* __restrict__ out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int kk = lane >> 4, c = lane & 15;
+  const int ti = (int)blockIdx.x / 6, comp = (int)blockIdx.x - 6 * ti;
+  const int jl = blockIdx.y;
+  const int j = PHASE ? jl + ((jz >= 0 && jl >= jz) ? 1 : 0) : jz;
+  const int rg = (int)blockIdx.z / ncg, cg = (int)blockIdx.z - rg * ncg;
+  const int row0 = (rg * SW_WAVES_PER_BLOCK + wave) * 16;
+  if (row0 >= nbf) return;
+  const int col0 = cg * NT * 16;
+  const int t = tins[ti];
+  const int p = PHASE ? mom[j] : 0;
+  const bool local = comp < 4, in_t = comp == 5;
+  const int arow = row0 + c;
+  const bool aok = arow < nbf;
+  const int tn = in_t ? (t + 1 == L ? 0 : t + 1) : t;          // timeslice of n + mu
+  const int dx = comp == 4 ? 1 : 0;
+  const int* __restrict__ sr_own = slicerow + (size_t)t * L * 2;
+  const int* __restrict__ sr_nb = slicerow + (size_t)tn * L * 2;
+  const cplx* __restrict__ U = (in_t ? U2 : U1) + (size_t)t * L;
+  sw_double4 re[NT], im[NT];
+#pragma unroll
+  for (int q = 0; q < NT; ++q) re[q] = im[q] = sw_double4{0.0, 0.0, 0.0, 0.0};
+  const int nbr = local ? 1 : 2;
+  for (int br = 0; br < nbr; ++br) {
+    const bool back = br == 1;
+    const int* __restrict__ sr_u = back ? sr_nb : sr_own;      // the left factor's site
+    const int* __restrict__ sr_v = back ? sr_own : sr_nb;      // the right factor's site
+    // local: the spins f, c of the component; current: spin 0 plus i^e times spin 1
+    const int fa = local ? comp >> 1 : 0, fb = local ? comp & 1 : 0;
+    const int ea = in_t ? (back ? 1 : 3) : (back ? 2 : 0);     // conj(l_1)
+    const int eb = in_t ? (back ? 3 : 1) : (back ? 0 : 2);     // r_1
+    for (int x0 = 0; x0 < L; x0 += 4) {
+      const int x = x0 + kk;
+      const bool in = x < L;
+      int xn = x + dx;
+      xn = xn >= L ? xn - L : xn;
+      const int xu = back ? xn : x, xv = back ? x : xn;
+      cplx a = cmake(0.0, 0.0);
+      const cplx* __restrict__ bp0 = Z0;
+      const cplx* __restrict__ bp1 = Z0;
+      if (in) {
+        bp0 = Z0 + (size_t)sr_v[2 * xv + fb] * ld0 + c0 + col0 + c;
+        if (!local) bp1 = Z0 + (size_t)sr_v[2 * xv + 1] * ld0 + c0 + col0 + c;
+        if (aok) {
+          a = Zf[(size_t)sr_u[2 * xu + fa] * ldf + cf + arow];
+          if (!local) {
+            const cplx a1 = laph_ipow(Zf[(size_t)sr_u[2 * xu + 1] * ldf + cf + arow], ea);
+            a = cmake(a.x + a1.x, a.y + a1.y);
+          }
+          cplx w = cmake(1.0, 0.0);
+          if (!local) {
+            const cplx lk = U[x];
+            w = back ? cmake(-lk.x, lk.y) : lk;
+          }
+          if constexpr (PHASE) {
+            const cplx e = phase[(p * x) % L];
+            w = local ? e : cmul(e, w);
+          }
+          // a <- conj(w) a
+          if (PHASE || !local) a = cmake(w.x * a.x + w.y * a.y, w.x * a.y - w.y * a.x);
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < NT; ++q) {
+        cplx b = cmake(0.0, 0.0);
+        if (in && col0 + q * 16 + c < nb0) {
+          b = bp0[q * 16];
+          if (!local) {
+            const cplx b1 = laph_ipow(bp1[q * 16], eb);
+            b = cmake(b.x + b1.x, b.y + b1.y);
+          }
+        }
+        // conj(a) b = (ar br + ai bi) + i (ar bi - ai br)
+        re[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, b.x, re[q], 0, 0, 0);
+        re[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, b.y, re[q], 0, 0, 0);
+        im[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, b.y, im[q], 0, 0, 0);
+        im[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(-a.y, b.x, im[q], 0, 0, 0);
+      }
+    }
+  }
+  cplx* __restrict__ o = out + (((size_t)ti * M + j) * 6 + comp) * nbf * nb0;
+#pragma unroll
+  for (int q = 0; q < NT; ++q) {
+    const int col = col0 + q * 16 + c;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int row = row0 + kk + 4 * i;
+      if (row < nbf && col < nb0) o[(size_t)row * nb0 + col] = cmake(re[q][i], im[q][i]);
+    }
+  }
+}
+
 }  // namespace swk

@@ -78,6 +78,7 @@ KCLASS_3PT_DOTS = 24       # ... and of k_slice_seq_dots
 KCLASS_SMEAR = 25          # ... and of k_smear_step / k_smear_fused (smeared two-point functions)
 KCLASS_LAPH = 26           # ... and of k_laph_sources / k_laph_project (distillation)
 KCLASS_LAPH_CONTRACT = 27  # ... and of k_laph_elementals / k_laph_left / k_laph_right / k_laph_reduce
+KCLASS_LAPH_GENERALIZED = 28   # ... and of k_laph_generalized (generalized perambulators)
 MAX_LAPH = 128             # SW_MAX_LAPH
 MAX_SINK_LEVELS = 4        # SW_MAX_SINK_LEVELS, SW_MAX_SMEARING_STEPS
 MAX_SMEARING_STEPS = 1024
@@ -280,6 +281,8 @@ def load_library():
     sig("sw_apply_laph_elementals", i32, vp, vp)
     sig("sw_distilled_two_point", i32, vp, i32, vp, dbl, i32, vp, vp, vp, vp)
     sig("sw_apply_laph_contract", i32, vp, i32, vp, vp, vp, vp)
+    sig("sw_generalized_perambulators", i32, vp, i32, i32, i32, vp, i32, vp, dbl, i32, vp, vp, vp)
+    sig("sw_apply_laph_generalized", i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp)
     _lib = lib
     return lib
 
@@ -311,6 +314,7 @@ EXPORTED_SYMBOLS = (
     "sw_set_smearing", "sw_apply_smearing", "sw_hutch_fetch_two_point_smeared",
     "sw_set_distillation", "sw_perambulators", "sw_apply_laph_sources", "sw_apply_laph_project",
     "sw_set_distillation_momenta", "sw_apply_laph_elementals", "sw_distilled_two_point", "sw_apply_laph_contract",
+    "sw_generalized_perambulators", "sw_apply_laph_generalized",
 )
 
 
@@ -1195,6 +1199,40 @@ class Engine:
                                                    _ptr(tau) if tau.size else None, _ptr(T) if T.size else None,
                                                    _ptr(loops) if loops.size else None), "sw_apply_laph_contract")
         return T, loops
+
+    def _insertions(self, timeslices, momenta):
+        return (np.ascontiguousarray(np.atleast_1d(timeslices), dtype=np.int32).reshape(-1),
+                np.ascontiguousarray(np.atleast_1d(momenta), dtype=np.int32).reshape(-1))
+
+    def generalized_perambulators(self, t0, tf, timeslices, momenta, tol, maxiter=1000, keep_tau=True):
+        """(G[nt, nmom, 6, 2 nev, 2 nev], tau[2, L, 2, nev, nev, 2] or None, iters[2, nev, 2]): the generalized
+        perambulators between the eigenvector solutions of the sink timeslice tf (rows (m, e) -> 2 m + e) and of the
+        source timeslice t0 (columns (n, b) -> 2 n + b) at the insertion timeslices and momenta
+        (utils.generalized_perambulators_from_solutions: components 2 f + c local, 4 = J_x, 5 = J_t), and, with
+        keep_tau, the perambulators of perambulators([t0, tf]), bit for bit.  Stateless: no mode buffer is touched."""
+        t, q = self._insertions(timeslices, momenta)
+        L, nev, _ = self._laph_shape()
+        G = np.zeros((t.size, q.size, 6, 2 * nev, 2 * nev), dtype=np.complex128)
+        tau = np.zeros((2, L, 2, nev, nev, 2), dtype=np.complex128) if keep_tau else None
+        iters = np.zeros((2, nev, 2), dtype=np.int32)
+        self._chk(self._lib.sw_generalized_perambulators(
+            self._h, int(t0), int(tf), t.size, _ptr(t) if t.size else None, q.size, _ptr(q) if q.size else None,
+            float(tol), int(maxiter), _ptr(G) if G.size else None, _ptr(tau) if keep_tau and tau.size else None,
+            _ptr(iters) if iters.size else None), "sw_generalized_perambulators")
+        return G, tau, iters
+
+    def apply_laph_generalized(self, Zf, Z0, timeslices, momenta):
+        """k_laph_generalized alone on Zf complex (nbf, n) and Z0 complex (nb0, n), reference ordering, in place of
+        the solutions: out[i, j, k, r, s], shape (nt, nmom, 6, nbf, nb0)
+        (utils.generalized_perambulators_from_solutions with the links of the lattice level)."""
+        Zf2, _ = self._io(Zf, self._n(0, 0))
+        Z02, _ = self._io(Z0, self._n(0, 0))
+        t, q = self._insertions(timeslices, momenta)
+        out = np.zeros((t.size, q.size, 6, Zf2.shape[0], Z02.shape[0]), dtype=np.complex128)
+        self._chk(self._lib.sw_apply_laph_generalized(
+            self._h, Zf2.shape[0], _ptr(Zf2), Z02.shape[0], _ptr(Z02), t.size, _ptr(t) if t.size else None, q.size,
+            _ptr(q) if q.size else None, _ptr(out) if out.size else None), "sw_apply_laph_generalized")
+        return out
 
     def hutch_batch_two_point_smeared(self, level, probes, tol, maxiter=1000):
         """One MODE_TWO_POINT_SMEARED batch: (T[nb, nsink, nmom, 2, 2, 2, 2, L], iters_fine[nb], iters_coarse[nb])."""

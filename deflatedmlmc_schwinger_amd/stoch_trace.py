@@ -22,7 +22,9 @@ from .utils import (_engines, deflation_pre_computations, displacements_of, draw
                     register_shifts, register_two_point, two_point_of, low_mode_inverse, low_mode_two_point,
                     register_low_modes, low_mode_contraction_of, link_loops_of, three_point_of,
                     register_three_point, refuse_three_point, register_smearing, refuse_smearing, smearing_of,
-                    distillation_of, refuse_distillation, laplacian_eigenvectors, laph_elementals,
+                    distillation_of, refuse_distillation, refuse_distilled_three_point,
+                    distilled_three_point_of, distilled_three_point_correlator, DISTILLED_INSERTIONS,
+                    laplacian_eigenvectors, laph_elementals,
                     distilled_pair_sums, distilled_loops, source_average, distilled_contraction_of)
 
 DEFAULT_BATCH = 256
@@ -469,6 +471,7 @@ def hutchinson(A, params):
     forms the conserved vector current) resolve the estimate, from one deflation projection and one
     solve per probe: the reference's result keys are then those of the control column, and the stopping rule runs on
     its series alone."""
+    refuse_distilled_three_point(params, "hutchinson()")
     refuse_three_point(params, "hutchinson()")
     refuse_smearing(params, "hutchinson()")
     refuse_distillation(params, "hutchinson()")
@@ -564,6 +567,7 @@ def two_point(A, params):
     Returns two_point (the mean, [p][a][b][c][d][t]), two_point_devs, two_point_ests (per noise), converged,
     momenta, source_timeslice, nr_ests, function_iters (a noise counts the largest iteration number among its
     2 M solves), ests (the control series), probe_loop_s and probes_solved."""
+    refuse_distilled_three_point(params, "two_point()")
     refuse_three_point(params, "two_point()")
     refuse_distillation(params, "two_point()")
     sel = two_point_of(params)
@@ -634,6 +638,7 @@ def distilled_two_point(A, params):
     Returns two_point, two_point_avg, loops, perambulators ([s][t][c][m][n][a], or None), eigenvalues ([t][m]),
     momenta, source_timeslices, distillation_vectors, function_iters (summed over all columns), solves and
     solve_s."""
+    refuse_distilled_three_point(params, "distilled_two_point()")
     sel = distillation_of(params)
     if sel is None:
         raise Exception("distilled_two_point() needs the key distillation_vectors")
@@ -709,6 +714,87 @@ def distilled_two_point(A, params):
     return result
 
 
+def distilled_three_point(A, params):
+    """Three-point functions in the distilled basis: both outer quark lines are eigenvector sources,
+    one on source_timeslice = t0 and one on sink_timeslice = tf, so no sequential solve is needed.  One engine call
+    (Engine.generalized_perambulators) solves the 2 x 2 N columns, keeps both solution blocks on the device and sums
+    them at every insertion timeslice and momentum into the generalized perambulators G; from G and the perambulator
+    tau(tf, t0) every source matrix, sink matrix and momentum is a small host contraction
+    (utils.distilled_three_point_correlator) -- nothing is solved again and there is no noise.
+
+    Keys (utils.distilled_three_point_of): distillation_vectors, source_timeslice, sink_timeslice, sink_gamma (default
+    'g3'), sink_momentum (default 0), three_point_momenta (default [0]), insertion_timeslices (a list, or "all", the
+    default) and source_momentum (default 0).  One rank; the operator has to be the lattice stencil the engine detects.
+
+    Returns three_point ([6 insertions '1', 'g3', 's1', 's2', 'Jx', 'Jt'][4 source matrices '1', 'g3', 's1',
+    's2'][momentum][insertion timeslice], for the given sink matrix and momenta), generalized_perambulators
+    ([t][q][6][(m,e)][(n,b)]), perambulators (the two tau of [t0, tf], [s][t][c][m][n][a]: utils.distilled_pair_sums
+    gives the two-point function of the ratio), eigenvalues, momenta, insertion_timeslices, source_timeslice,
+    sink_timeslice, sink_gamma, sink_momentum, source_momentum, distillation_vectors, function_iters, solves and
+    solve_s."""
+    sel = distilled_three_point_of(params)
+    if sel is None:
+        raise Exception("distilled_three_point() needs the keys distillation_vectors, source_timeslice and "
+                        "sink_timeslice")
+    if _dist.default_comm().world > 1:
+        raise Exception("distilled three-point functions run on one rank")
+    from .hierarchy import detect_lattice
+    lattice = A if isinstance(A, tuple) else (None if A is None else detect_lattice(A))
+    if lattice is None:
+        raise Exception("distilled_three_point() needs a lattice operator (a U(1) Wilson stencil with its links)")
+    nev, t0, tf, momenta, tins = sel['nev'], sel['t0'], sel['tf'], sel['momenta'], sel['tins']
+    L = int(params['latt_dims'][0])
+    mg_solver, nr_levels = _setup_solver(A, params, defer_coarse=True, lattice=lattice)
+    engs = _engines(mg_solver)
+    if not engs:
+        raise Exception("no GPU engine attached (run MG.setup first)")
+    eng = engs[0]
+    V, eigenvalues = laplacian_eigenvectors(lattice[2], L, nev)
+    eng.set_distillation(V)
+    ends = sorted({sel['pf'], sel['pi']})
+    M = laph_elementals(V, L, ends)
+    n = 2 * L * L
+    tol, maxiter = params['function_params']['tol'], (n if n < 1000 else 1000)
+
+    print("\nResetting timer to zero ...", end='')
+    mg_solver.timer.reset()
+    eng.timers_reset()
+    print(" done")
+    print("\nComputing the generalized perambulators ...", end='', flush=True)
+    t1 = time.time()
+    try:
+        G, tau, it = eng.generalized_perambulators(t0, tf, tins, momenta, tol, maxiter)
+        solve_s = time.time() - t1
+    finally:                               # the registration and the deferred set-up do not outlive a failed call
+        eng.set_distillation(None)
+        mg_solver.finish_setup()
+    print(" done. Time : " + str(solve_s) + " seconds")
+
+    sources = ('1', 'g3', 's1', 's2')
+    C3 = np.zeros((len(DISTILLED_INSERTIONS), len(sources), len(momenta), len(tins)), dtype=np.complex128)
+    Ms, Mi = M[ends.index(sel['pf']), tf], M[ends.index(sel['pi']), t0]
+    for i, insertion in enumerate(DISTILLED_INSERTIONS):
+        for s, source in enumerate(sources):
+            C3[i, s] = distilled_three_point_correlator(G, tau[0, tf], Ms, Mi, sel['sink'], insertion, source)
+
+    result = dict()
+    result['three_point'] = C3
+    result['generalized_perambulators'] = G
+    result['perambulators'] = tau
+    result['eigenvalues'] = eigenvalues
+    result['momenta'] = list(momenta)
+    result['insertion_timeslices'] = list(tins)
+    result['source_timeslice'], result['sink_timeslice'] = t0, tf
+    result['sink_gamma'], result['sink_momentum'], result['source_momentum'] = sel['sink'], sel['pf'], sel['pi']
+    result['distillation_vectors'] = nev
+    result['function_iters'] = int(np.sum(it))
+    result['solves'] = 4 * nev
+    result['solve_s'] = solve_s
+    mg_solver.sync_timer()
+    print(mg_solver.timer)
+    return result
+
+
 class _ThreePoint(_Observable):
     """three_point(): the sums S[d][j][a][b][f][c][t], flattened, plus one control column, c_k = the pion two-point value
     at the sink slice (real and positive) -- a batch's row as Engine.hutch_fetch_three_point_resolved returns it."""
@@ -745,6 +831,7 @@ def three_point(A, params):
     sink_gamma, sink_momentum, and the reference's keys from the control series: trace (= the mean of c_k), std_dev,
     nr_ests, function_iters (a noise counts its largest stage-1 plus its largest stage-2 iteration number), ests,
     rough_trace, level_tol, probe_loop_s and probes_solved."""
+    refuse_distilled_three_point(params, "three_point()")
     refuse_smearing(params, "three_point()")
     refuse_distillation(params, "three_point()")
     sel = three_point_of(params)
@@ -800,6 +887,7 @@ def lma_two_point(A, params):
     Returns two_point()'s keys with two_point = E_L(t0) + the remainder's mean, plus two_point_low (E_L, all t0),
     two_point_rest (the remainder's mean), two_point_rest_devs and nr_deflat_vctrs; two_point_ests are the per-noise
     remainders plus E_L(t0)."""
+    refuse_distilled_three_point(params, "lma_two_point()")
     refuse_three_point(params, "lma_two_point()")
     refuse_smearing(params, "lma_two_point()")
     refuse_distillation(params, "lma_two_point()")
@@ -937,6 +1025,7 @@ def _mlmc_work_model(output_params, mg_solver):
 
 # compute tr(A^{-1}) via multigrid multilevel Monte Carlo          stoch_trace.py:185-471
 def mlmc(A, params):
+    refuse_distilled_three_point(params, "mlmc()")
     refuse_three_point(params, "mlmc()")
     refuse_smearing(params, "mlmc()")
     refuse_distillation(params, "mlmc()")
@@ -1060,6 +1149,7 @@ def _mlmc_loops_checks(params, deflated=False):
     """The validation of mlmc_loops() (deflated: of deflated_mlmc_loops()), before any setup: (momenta, skip_level)."""
     who = "deflated_mlmc_loops" if deflated else "mlmc_loops"
     has = hasattr(params, "get")
+    refuse_distilled_three_point(params, who + "()")
     refuse_three_point(params, who + "()")
     refuse_distillation(params, who + "()")
     if has and params.get('source_timeslice') is not None:

@@ -66,7 +66,8 @@ _BUILD_KEYS = ('batch', 'device', 'engines', 'cache_dir', 'report_path', 'probe_
                'timeslice_loops', 'source_timeslice', 'two_point_momenta', 'low_mode_contraction', 'link_loops',
                'sink_timeslice', 'sink_gamma', 'sink_momentum', 'three_point_momenta',
                'smearing_kappa', 'source_smearing_steps', 'sink_smearing_steps',
-               'distillation_vectors', 'source_timeslices', 'keep_perambulators', 'distilled_contraction')
+               'distillation_vectors', 'source_timeslices', 'keep_perambulators', 'distilled_contraction',
+               'insertion_timeslices', 'source_momentum')
 # where the eigenpairs of the MLMC difference operators come from: host ARPACK (the reference's path) or
 # the block eigensolver on the GPU (setup_gpu.device_diff_eigenpairs)
 MLMC_DEFL_SETUPS = ("host", "device")
@@ -1057,6 +1058,208 @@ def three_point_current(S, mu, source=None):
     if source is None:
         return J
     return np.einsum('ba,...jabt->...jt', _source_weights(source, "three_point_current"), J)
+
+
+# ---- distilled three-point functions: generalized perambulators -------------------------------------
+DISTILLED_THREE_POINT_KEYS = ('insertion_timeslices', 'source_momentum')
+DISTILLED_INSERTIONS = ('1', 'g3', 's1', 's2', 'Jx', 'Jt')
+
+
+def refuse_distilled_three_point(params, who):
+    """insertion_timeslices and source_momentum belong to distilled_three_point(): every other flow raises on them."""
+    for key in DISTILLED_THREE_POINT_KEYS:
+        if hasattr(params, "get") and params.get(key) is not None:
+            raise Exception("%s belongs to distilled_three_point(), not to %s" % (key, who))
+
+
+def _hop_factors(mu):
+    """(l+, r+, l-, r-) with g3 H+-_mu = outer(l, r): the four hop matrices times g3 have rank one."""
+    from .hierarchy import _HOP
+    out = []
+    for key in (("+x", "-x") if mu == 0 else ("+y", "-y")):
+        h = _PAULI['g3'] @ _HOP[key]
+        l, r = h[:, 0] / h[0, 0], h[0, :]
+        if not np.array_equal(np.outer(l, r), h):
+            raise Exception("_hop_factors: g3 H%s is not of rank one" % key)
+        out += [l, r]
+    return out
+
+
+def _solution_fields(Z, L, who, ctype):
+    Z = np.asarray(Z)
+    if Z.ndim != 2 or Z.shape[1] != 2 * L * L:
+        raise Exception("%s: fields of shape %s, expected (nb, %d)" % (who, Z.shape, 2 * L * L))
+    return Z.astype(ctype).reshape(Z.shape[0], 2, L, L)                    # [k][c][t][x]
+
+
+def generalized_perambulators_from_solutions(Zf, Z0, U1, U2, L, timeslices, momenta, wide=False):
+    """G[i, j, k, r, s] for the insertion timeslices t = timeslices[i], the momenta q_j and the fields Zf (nbf, 2 L^2),
+    Z0 (nb0, 2 L^2) in the reference ordering, shape (nt, nmom, 6, nbf, nb0): the NumPy definition of what
+    Engine.apply_laph_generalized computes,
+
+        k = 2 f + c:   sum_x e^{-2 pi i q x / L} conj(Zf[r, idx(f,x,t)]) Z0[s, idx(c,x,t)]
+        k = 4 + mu:    sum_fc (g3 H+_mu)[f][c] F_mu[f][c] - (g3 H-_mu)[f][c] B_mu[f][c],        mu = 0 (x), 1 (t)
+            F_mu[f][c] = sum_x e^{-2 pi i q x / L}      U_mu(n)  conj(Zf[r, idx(f,n)])    Z0[s, idx(c,n+mu)]
+            B_mu[f][c] = sum_x e^{-2 pi i q x / L} conj(U_mu(n)) conj(Zf[r, idx(f,n+mu)]) Z0[s, idx(c,n)]
+
+    i.e. seq_dots followed by three_point_current(., mu, None) with the noise index replaced by the pair (r, s); links,
+    neighbours and hop matrices as there, phases from the engine's table.  The four g3 H+-_mu have rank one, so every
+    link branch is one product of spin-projected fields.  wide: evaluated in np.clongdouble."""
+    ctype = np.clongdouble if wide else np.complex128
+    who = "generalized_perambulators_from_solutions"
+    Zf, Z0 = _solution_fields(Zf, L, who, ctype), _solution_fields(Z0, L, who, ctype)
+    U = [np.asarray(u, dtype=np.complex128).reshape(-1) for u in (U1, U2)]
+    if any(u.size != L * L for u in U):
+        raise Exception("%s: links of %d and %d entries, expected %d each" % (who, U[0].size, U[1].size, L * L))
+    U = [u.reshape(L, L).astype(ctype) for u in U]                         # [t][x]
+    ts = [int(t) for t in np.atleast_1d(timeslices)]
+    qs = [int(q) for q in np.atleast_1d(momenta)]
+    ph = _phase_table(L)[np.outer(np.asarray(qs, dtype=np.int64), np.arange(L)) % L].astype(ctype)     # [j][x]
+    hops = [_hop_factors(mu) for mu in range(2)]
+    out = np.zeros((len(ts), len(qs), 6, Zf.shape[0], Z0.shape[0]), dtype=ctype)
+    for i, t in enumerate(ts):
+        zf, z0 = Zf[:, :, t, :], Z0[:, :, t, :]                            # [k][c][x]
+        tn = (t + 1) % L
+        # per current the (weight, left field, right field) of the F and the B branch, at the link's own x
+        branches = []
+        for mu in range(2):
+            lp, rp, lm, rm = [v.astype(ctype) for v in hops[mu]]
+            if mu == 0:
+                zfn, z0n = np.roll(zf, -1, axis=2), np.roll(z0, -1, axis=2)
+            else:
+                zfn, z0n = Zf[:, :, tn, :], Z0[:, :, tn, :]
+            u = U[mu][t]
+            branches.append(((u, np.einsum('f,kfx->kx', lp.conj(), zf), np.einsum('c,kcx->kx', rp, z0n)),
+                             (-u.conj(), np.einsum('f,kfx->kx', lm.conj(), zfn), np.einsum('c,kcx->kx', rm, z0))))
+        for j in range(len(qs)):
+            for f in range(2):
+                left = zf[:, f, :].conj() * ph[j]
+                for c in range(2):
+                    out[i, j, 2 * f + c] = left @ z0[:, c, :].T
+            for mu in range(2):
+                for w, a, b in branches[mu]:
+                    out[i, j, 4 + mu] += (a.conj() * (ph[j] * w)) @ b.T
+    return out
+
+
+def generalized_perambulator_bounds(Zf, Z0, L, timeslices):
+    """bound[i, k, r, s], the rounding bounds of the device's generalized perambulators at any momentum, in
+    np.longdouble:  (L + 12) 2^-52 sum_x |Zf_f| |Z0_c| for the local components k = 2 f + c -- a chain of 2 L
+    multiply-adds and one more multiply by the weight -- and (2 L + 16) 2^-52 sum_{branch,f,c} sum_x |Zf_f| |Z0_c| at
+    the branch's sites for the currents k = 4, 5: two branches of four spin terms with coefficients of modulus one
+    in one accumulator."""
+    who = "generalized_perambulator_bounds"
+    Af = np.abs(_solution_fields(Zf, L, who, np.complex128)).astype(np.longdouble)
+    A0 = np.abs(_solution_fields(Z0, L, who, np.complex128)).astype(np.longdouble)
+    ts = [int(t) for t in np.atleast_1d(timeslices)]
+    eps = np.longdouble(2.0) ** -52
+    out = np.zeros((len(ts), 6, Af.shape[0], A0.shape[0]), dtype=np.longdouble)
+    for i, t in enumerate(ts):
+        af, a0 = Af[:, :, t, :], A0[:, :, t, :]
+        tn = (t + 1) % L
+        for f in range(2):
+            for c in range(2):
+                out[i, 2 * f + c] = (L + 12) * eps * (af[:, f, :] @ a0[:, c, :].T)
+        sf, s0 = af.sum(axis=1), a0.sum(axis=1)                            # sum over the spins: [k][x]
+        sfx, s0x = np.roll(sf, -1, axis=1), np.roll(s0, -1, axis=1)
+        sft, s0t = Af[:, :, tn, :].sum(axis=1), A0[:, :, tn, :].sum(axis=1)
+        out[i, 4] = (2 * L + 16) * eps * (sf @ s0x.T + sfx @ s0.T)
+        out[i, 5] = (2 * L + 16) * eps * (sf @ s0t.T + sft @ s0.T)
+    return out
+
+
+def distilled_three_point_correlator(G, tau_f0, M_sink, M_source, sink, insertion, source):
+    """C3(t_i, q_j), shape (nmom, nt), from the generalized perambulators G[i, j, k, (m,e), (n',b)] of
+    Engine.generalized_perambulators, the perambulator tau_f0[e, m, n, a] = tau(tf, t0) (perambulators()[s, tf] of
+    the source t0), the sink elemental M_sink = M[pf][tf] and the source elemental M_source = M[pi][t0] (each
+    (nev, nev), laph_elementals):
+
+        R[(m,e)][(n,a)] = sum_{m',c} ((g3 Gf g3)^H)[e][c] conj(M_sink[m'][m]) tau_f0[c][m'][n][a]
+        C3 = sum (Gi g3)[b][a] X[f][c] conj(R[(m,e)][(n,a)]) M_source[n'][n] G[i][j][2 f + c][(m,e)][(n',b)]
+
+    with X = g3 Gamma for a local insertion Gamma out of '1', 'g3', 's1', 's2', and the component 4 / 5 of G in place
+    of the sum over f, c for the conserved current 'Jx' / 'Jt'; Gf = `sink`, Gi = `source`.  It equals
+    tr[(Gi x Phi(pi,t0)) A^-1(t0;tf) (Gf x Phi(pf,tf)) A^-1(tf;t) (Gamma x diag omega_q) A^-1(t;t0)] with
+    Phi(p,t) = box(t) diag(omega_p) box(t).  No fermion-loop sign, as in three_point_correlator."""
+    who = "distilled_three_point_correlator"
+    G = np.asarray(G, dtype=np.complex128)
+    tau_f0 = np.asarray(tau_f0, dtype=np.complex128)
+    if tau_f0.ndim != 4 or tau_f0.shape[0] != 2 or tau_f0.shape[3] != 2 or tau_f0.shape[1] != tau_f0.shape[2]:
+        raise Exception("%s: tau_f0 of shape %s, expected (2, nev, nev, 2)" % (who, tau_f0.shape))
+    N = tau_f0.shape[1]
+    if G.ndim != 5 or G.shape[2:] != (6, 2 * N, 2 * N):
+        raise Exception("%s: G of shape %s, expected (nt, nmom, 6, %d, %d)" % (who, G.shape, 2 * N, 2 * N))
+    Ms, Mi = np.asarray(M_sink, dtype=np.complex128), np.asarray(M_source, dtype=np.complex128)
+    if Ms.shape != (N, N) or Mi.shape != (N, N):
+        raise Exception("%s: elementals of shape %s and %s, expected (%d, %d)" % (who, Ms.shape, Mi.shape, N, N))
+    if sink not in _PAULI:
+        raise Exception("%s: unknown spin matrix %r (one of %s)" % (who, sink, sorted(_PAULI)))
+    if insertion not in DISTILLED_INSERTIONS:
+        raise Exception("%s: unknown insertion %r (one of %s)" % (who, insertion, list(DISTILLED_INSERTIONS)))
+    W = _source_weights(source, who)                                       # (Gi g3)[b][a]
+    g3 = _PAULI['g3']
+    Mx = (g3 @ _PAULI[sink] @ g3).conj().T
+    R = np.einsum('ec,pm,cpna->mena', Mx, Ms.conj(), tau_f0)
+    Y = np.einsum('mena,pn,ba->mepb', R.conj(), Mi, W).reshape(2 * N, 2 * N)
+    if insertion in _PAULI:
+        X = g3 @ _PAULI[insertion]
+        Gk = np.einsum('k,ijkrs->ijrs', X.reshape(4), G[:, :, :4])
+    else:
+        Gk = G[:, :, 4 if insertion == 'Jx' else 5]
+    return np.einsum('ijrs,rs->ji', Gk, Y)
+
+
+def distilled_three_point_of(params):
+    """The build-only keys of distilled_three_point(): None when distillation_vectors or sink_timeslice is absent, else
+    the validated dict(nev, t0, tf, sink, pf, pi, momenta, tins) -- distillation_vectors an integer in
+    [1, min(L, MAX_LAPH)]; source_timeslice, sink_timeslice, sink_gamma, sink_momentum and three_point_momenta as
+    three_point_of takes them; insertion_timeslices a non-empty list of different integers in [0, L) or "all" (the
+    default); source_momentum an integer in [0, L) (default 0).  The keys combine with none of source_timeslices,
+    keep_perambulators, distilled_contraction, two_point_momenta, x_displacements, timeslice_loops, link_loops and the
+    smearing keys."""
+    has = hasattr(params, "get")
+    if not has or params.get('distillation_vectors') is None or params.get('sink_timeslice') is None:
+        return None
+    for other in DISTILLATION_KEYS[1:] + SMEARING_KEYS:
+        if params.get(other) is not None:
+            raise Exception("distilled_three_point() does not combine with %s" % other)
+    got = three_point_of(params)           # refuses the loop and displacement keys and two_point_momenta
+    L = int(params['latt_dims'][0])
+    nev = params['distillation_vectors']
+    if isinstance(nev, (bool, str)) or int(nev) != nev:
+        raise Exception("distillation_vectors: %r is not an integer" % (nev,))
+    nev = int(nev)
+    if not 1 <= nev <= min(L, MAX_LAPH):
+        raise Exception("distillation_vectors: %d outside [1, %d]" % (nev, min(L, MAX_LAPH)))
+    pi = params.get('source_momentum')
+    pi = 0 if pi is None else pi
+    if isinstance(pi, (bool, str)) or int(pi) != pi:
+        raise Exception("source_momentum: %r is not an integer" % (pi,))
+    if not 0 <= int(pi) < L:
+        raise Exception("source_momentum: %d outside [0, %d)" % (int(pi), L))
+    given = params.get('insertion_timeslices')
+    given = "all" if given is None else given
+    if isinstance(given, str):
+        if given != "all":
+            raise Exception("insertion_timeslices: %r is neither a list nor \"all\"" % (given,))
+        tins = list(range(L))
+    else:
+        if isinstance(given, bytes) or not hasattr(given, '__len__'):
+            raise Exception("insertion_timeslices: %r is not a list" % (given,))
+        tins = []
+        for t in given:
+            if isinstance(t, (bool, str)) or int(t) != t:
+                raise Exception("insertion_timeslices: %r is not an integer" % (t,))
+            t = int(t)
+            if not 0 <= t < L:
+                raise Exception("insertion_timeslices: %d outside [0, %d)" % (t, L))
+            if t in tins:
+                raise Exception("insertion_timeslices: %d listed twice" % t)
+            tins.append(t)
+        if not tins:
+            raise Exception("insertion_timeslices: the list is empty")
+    return dict(nev=nev, t0=got['t0'], tf=got['tf'], sink=got['sink'], pf=got['pf'], pi=int(pi),
+                momenta=got['momenta'], tins=tins)
 
 
 def meson_fields(V, L, momenta):

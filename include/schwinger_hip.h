@@ -422,6 +422,29 @@ int sw_distilled_two_point(sw_engine* h, int nsrc, const int32_t* t0, double tol
 /* The contraction of sw_distilled_two_point alone on host perambulators tau complex128[nsrc][L][2][nev][nev][2], in the
  * same blocks (pad columns zero): T and loops as above. */
 int sw_apply_laph_contract(sw_engine* h, int nsrc, const int32_t* t0, const double* tau, double* T, double* loops);
+/* The generalized perambulators of the distilled three-point functions (build-only, stateless in the style of
+ * sw_perambulators): z_0^(n,b) and z_f^(m,e) the solutions of the eigenvector sources on the timeslices
+ * t0 and tf (different, in [0, L)), in exactly the solve blocks of sw_perambulators(h, 2, {t0, tf}, ...).  For the nt
+ * insertion timeslices tins[i] (distinct, in [0, L)) and the nmom momenta q[j] (1 <= nmom <= SW_MAX_MOMENTA, distinct,
+ * in [0, L)), with row (m, e) -> 2 m + e and column (n, b) -> 2 n + b,
+ *   G[i][j][2 f + c][row][col] = sum_x e^{-2 pi i q x / L} conj(z_f[idx(f,x,t)]) z_0[idx(c,x,t)]
+ *   G[i][j][4 + mu][row][col]  = the sums of sw_apply_seq_dots over the link mu = 0 (x), 1 (t) contracted as the
+ *                                conserved current, the noise index replaced by the pair of columns
+ * by k_laph_generalized on v_mfma_f64_16x16x4_f64: every entry summed by one wave in the order x = 0, 4, 8, ..., two
+ * calls agree bit for bit, an entry depends on its own two columns, timeslice and momentum alone.
+ *   G      complex128[nt][nmom][6][2 nev][2 nev], through a device buffer of at most 256 MB, chunk by chunk
+ *   tau    complex128[2][L][2][nev][nev][2] and iters int32[2][nev][2]: what sw_perambulators returns for {t0, tf},
+ *          bit for bit; either may be NULL
+ * Refused before anything is allocated or launched without a registration of sw_set_distillation, without a finalised
+ * hierarchy or links on level 0, on bad end timeslices (tf == t0 included), a bad insertion list or momenta,
+ * maxiter < 1 or a null G.  No mode buffer, no probe slot and no registration is touched. */
+int sw_generalized_perambulators(sw_engine* h, int t0, int tf, int nt, const int32_t* tins, int nmom, const int32_t* q,
+                                 double tol, int maxiter, double* G, double* tau, int32_t* iters);
+/* k_laph_generalized alone on host fields Zf complex128[nbf][n] and Z0 complex128[nb0][n] (reference ordering,
+ * 1 <= nbf, nb0 <= 256) in place of the solutions: out complex128[nt][nmom][6][nbf][nb0].  Needs a lattice level 0
+ * with links (the condition of sw_set_three_point) and no distillation. */
+int sw_apply_laph_generalized(sw_engine* h, int nbf, const double* Zf, int nb0, const double* Z0, int nt,
+                              const int32_t* tins, int nmom, const int32_t* q, double* out);
 /* The sequential-source kernel of SW_MODE_THREE_POINT alone on host solutions: Z complex128[2][nb][n] (spin group a,
  * noise k, reference ordering), out complex128[2][nb][n], out[a][k][idx(e,x,t)] = delta_{t,tf} e^{+2 pi i pf x / L}
  * sum_c ((g3 Gf g3)^H)[e][c] Z[a][k][idx(c,x,tf)] for the registration of sw_set_three_point.  The refusals of the
@@ -763,6 +786,12 @@ int sw_timers_reset(sw_engine* h);
                                        per momentum of sw_set_distillation_momenta and, per momentum and block of
                                        ns sources in ncols columns, 8 * (2L * ncols * ld * K4 + 4L * ns * ld^2 * K4
                                        + 16 L * ns * nev^2 + 4 ns * nev^2) */
+#define SW_KCLASS_LAPH_GENERALIZED 28  /* k_laph_generalized (sw_generalized_perambulators,
+                                       sw_apply_laph_generalized); in sw_timers: dots.  sw_kernel_work counts, per
+                                       insertion timeslice and momentum, the eight complex products of the tiles
+                                       issued: 8 * 8 * Lp * (16 RT) * (16 NT ncg), Lp = L rounded up to 4, RT =
+                                       ceil(rows / 16), ncg = ceil(ceil(columns / 16) / 8) column groups of NT =
+                                       ceil(ceil(columns / 16) / ncg) tiles */
 int sw_kernel_stats(sw_engine* h, int which, double* total_ms, int64_t* launches);
 /* Floating-point operations issued by the launches of an MFMA kernel class since the last reset
  * (profiling on): 8 flops per complex multiply-add over every (row tile, k-step, probe). */
