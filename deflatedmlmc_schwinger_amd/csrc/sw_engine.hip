@@ -73,11 +73,13 @@ enum TimerCat { T_MVM = 0, T_DEFL, T_P, T_R, T_AXPY, T_DOTS, T_COARSEST, T_OTHER
                 T_LAPH,         // k_laph_project of sw_perambulators; SW_KCLASS_LAPH reports it with T_LAPH_SRC
                 T_LAPH_CONTRACT,  // k_laph_elementals / k_laph_left / k_laph_right / k_laph_reduce (sw_distilled_two_point)
                 T_LAPH_GEN,     // k_laph_generalized (sw_generalized_perambulators, sw_apply_laph_generalized)
-                T_LAPH_SRC,     // k_laph_sources (internal: no kernel class of its own)
+                T_LAPH_SRC,     // k_laph_sources (internal: number 29 is no kernel class and stays refused)
+                T_LAPH_2M,      // k_laph_sink / k_laph_sandwich / k_laph_source / k_laph_trace1 / k_laph_trace2
+                                // (sw_distilled_two_meson, sw_apply_laph_two_meson): SW_KCLASS_LAPH_TWO_MESON = 30
                 T_NCAT };
 // classes >= T_STENCIL are folded into the mvm / coarsest (two-point and three-point: other / dots; slice cdots,
 // meson fields, their contraction and the link dots: dots; smearing: other; distillation: the projection dots, the
-// sources other, the contraction and the generalized perambulators dots) buckets by
+// sources other, the contraction, the generalized perambulators and the two-meson blocks dots) buckets by
 // sw_timers and reported separately by sw_kernel_stats
 
 struct EllOp {
@@ -6353,6 +6355,180 @@ int sw_apply_laph_contract(sw_engine* h, int nsrc, const int32_t* t0, const doub
   return 0;
 }
 
+// ---- distillation: two-meson correlators from the perambulators ---------------------------
+// The operators of one side of a two-meson call: the folded spin matrices and momentum indices as the kernels take
+// them, and the number of non-zero spin entries (the work counted).
+struct LaphMesonSide {
+  swk::LaphMesonOps ops;
+  int n = 0, nnz[SW_MAX_MESON_OPS] = {0, 0, 0, 0};
+};
+static int laph_meson_side(sw_engine* h, const char* what, int n, const double* spin, const int32_t* mom,
+                           LaphMesonSide& side) {
+  if (n < 1 || n > SW_MAX_MESON_OPS) return sw_fail(h, "%d %s operators outside [1,%d]", n, what, SW_MAX_MESON_OPS);
+  if (!spin || !mom) return sw_fail(h, "null %s operators", what);
+  const int nmom = (int)h->lh_momenta.size();
+  std::memset(&side.ops, 0, sizeof(side.ops));
+  side.n = n;
+  for (int k = 0; k < n; ++k) {
+    if (mom[k] < 0 || mom[k] >= nmom)
+      return sw_fail(h, "%s operator %d: momentum index %d outside the %d registered", what, k, (int)mom[k], nmom);
+    side.ops.mom[k] = mom[k];
+    side.nnz[k] = 0;
+    for (int e = 0; e < 4; ++e) {
+      side.ops.w[k][2 * e] = spin[8 * k + 2 * e];
+      side.ops.w[k][2 * e + 1] = spin[8 * k + 2 * e + 1];
+      if (spin[8 * k + 2 * e] != 0.0 || spin[8 * k + 2 * e + 1] != 0.0) side.nnz[k]++;
+    }
+  }
+  return 0;
+}
+
+// The tiling of the sandwich: RT = ceil(2 nev / 16) row tiles, the column tiles in `halves` passes of NT
+static inline void laph_sandwich_tiles(int nev, int* RT, int* halves, int* NT) {
+  *RT = (2 * nev + 15) / 16;
+  *halves = (*RT + 7) / 8;
+  *NT = (*RT + *halves - 1) / *halves;
+}
+
+// The workspace of one block: W [L][2][nev][ncols], Qt [nk][ns][L][P][P], R [nk][nkp][ns][L][P][P] (P = 2 ld), the
+// results C1 [ns][nk][nkp][L] and C2 [ns][nk][nk][nkp][nkp][L] and, when the sandwich is asked for, Q dense
+// [ns][nk][L][2 nev][2 nev]; sized for the largest block of the call.
+struct LaphTwoMesonWS {
+  DevBuf<cplx> W, Qt, R, C1, C2, Q;
+  explicit LaphTwoMesonWS(sw_engine* h) : W(h), Qt(h), R(h), C1(h), C2(h), Q(h) {}
+};
+static int laph_two_meson_ws(sw_engine* h, LaphTwoMesonWS& ws, int ns, int ncols, int nk, int nkp, bool want_Q) {
+  const int L = h->hier[0].lv[0].L, nev = h->lh_nev, P = 2 * h->lh_ld;
+  const size_t mat = (size_t)ns * L * P * P;
+  SWCHK(dev_realloc(h, &ws.W.p, (size_t)L * 2 * nev * ncols));
+  SWCHK(dev_realloc(h, &ws.Qt.p, (size_t)nk * mat));
+  SWCHK(dev_realloc(h, &ws.R.p, (size_t)nk * nkp * mat));
+  SWCHK(dev_realloc(h, &ws.C1.p, (size_t)ns * nk * nkp * L));
+  SWCHK(dev_realloc(h, &ws.C2.p, (size_t)ns * nk * nk * nkp * nkp * L));
+  if (want_Q) SWCHK(dev_realloc(h, &ws.Q.p, (size_t)ns * nk * L * 4 * nev * nev));
+  return 0;
+}
+// C1 [ns][nk][nkp][L] and C2 [ns][nk][nk][nkp][nkp][L] (and Q, or NULL) of the ns sources d_t0 whose columns are the
+// first 2 nev ns of the projection block proj [L][2][nev][ncols], into the host arrays: per sink operator k_laph_sink
+// -> k_laph_sandwich, then k_laph_source, k_laph_trace1 and k_laph_trace2 once each (2 nk + 3 launches of class
+// SW_KCLASS_LAPH_TWO_MESON, one more for Q), then the small copies.
+static int laph_two_meson(sw_engine* h, const cplx* proj, const int* d_t0, int ns, int ncols, const LaphMesonSide& snk,
+                          const LaphMesonSide& src, LaphTwoMesonWS& ws, cplx* C1, cplx* C2, cplx* Q) {
+  const int L = h->hier[0].lv[0].L, nev = h->lh_nev, ld = h->lh_ld, P = 2 * ld, per = 2 * nev;
+  const int nk = snk.n, nkp = src.n, K4 = (nev + 3) / 4 * 4, K4p = (per + 3) / 4 * 4;
+  int RT, halves, NTq;
+  laph_sandwich_tiles(nev, &RT, &halves, &NTq);
+  const int groups = (RT + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK;
+  const int mgroups = (ld / 16 + SW_WAVES_PER_BLOCK - 1) / SW_WAVES_PER_BLOCK;
+  const size_t mat = (size_t)ns * L * P * P;
+  const cplx* Mt = h->lh_M;
+  if (h->profiling) {
+    double w = 0.0;
+    for (int k = 0; k < nk; ++k)
+      w += (double)snk.nnz[k] * L * ld * ncols * K4 + (double)L * ns * (16.0 * RT) * (16.0 * NTq * halves) * K4p;
+    for (int kp = 0; kp < nkp; ++kp) w += (double)nk * src.nnz[kp] * L * ns * (16.0 * RT) * ld * K4;
+    w += (double)nk * nkp * L * ns * 5.0 * nev * nev + (double)nk * nk * nkp * nkp * L * ns * (double)per * per;
+    h->twork[T_LAPH_2M] += 8.0 * w;
+  }
+  for (int k = 0; k < nk; ++k) {
+    SWCHK(launch(h, T_LAPH_2M, swk::k_laph_sink<4>, dim3(L, 2, mgroups * (ncols / 64)), dim3(SW_BLOCK), proj, nev,
+                 ncols, Mt, ld, snk.ops, k, ws.W.p));
+    SWCHK(pick<1, 2, 3, 4, 5, 6, 7, 8>(NTq, [&](auto NT) {
+      return launch(h, T_LAPH_2M, swk::k_laph_sandwich<decltype(NT)::value>, dim3(L, ns, groups * halves),
+                    dim3(SW_BLOCK), (const cplx*)ws.W.p, proj, nev, ncols, halves, P, ws.Qt.p + k * mat);
+    }));
+  }
+  SWCHK(pick<1, 2, 3, 4, 5, 6, 7, 8>(ld / 16, [&](auto NT) {
+    return launch(h, T_LAPH_2M, swk::k_laph_source<decltype(NT)::value>, dim3(L, 2 * ns, nk * nkp * groups),
+                  dim3(SW_BLOCK), (const cplx*)ws.Qt.p, nev, P, Mt, ld, d_t0, ns, nkp, src.ops, groups, ws.R.p);
+  }));
+  SWCHK(launch(h, T_LAPH_2M, swk::k_laph_trace1, dim3(nk * nkp, L, ns), dim3(SW_BLOCK), (const cplx*)ws.Qt.p, nev, P,
+               Mt, ld, d_t0, nkp, src.ops, ws.C1.p));
+  SWCHK(launch(h, T_LAPH_2M, swk::k_laph_trace2, dim3(nk * nk * nkp * nkp, L, ns), dim3(SW_BLOCK),
+               (const cplx*)ws.R.p, nev, P, nk, nkp, ws.C2.p));
+  if (Q)
+    SWCHK(launch(h, T_LAPH_2M, swk::k_laph_sandwich_unpack, dim3((per * per + SW_BLOCK - 1) / SW_BLOCK, L, nk * ns),
+                 dim3(SW_BLOCK), (const cplx*)ws.Qt.p, nev, P, nk, ws.Q.p));
+  SWCHK(stream_sync(h));
+  HIPCHK(hipMemcpy(C1, ws.C1.p, sizeof(cplx) * ns * nk * nkp * L, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(C2, ws.C2.p, sizeof(cplx) * ns * nk * nk * nkp * nkp * L, hipMemcpyDeviceToHost));
+  if (Q) HIPCHK(hipMemcpy(Q, ws.Q.p, sizeof(cplx) * ns * nk * L * per * per, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The two-meson building blocks of nsrc source timeslices, solved, projected and contracted on the device: per block
+// of whole sources laph_block (as sw_perambulators on that chunk) and laph_two_meson.  Stateless: no mode buffer, no
+// probe slot and no registration is touched; everything but the two-point workspace lives for this call only.
+int sw_distilled_two_meson(sw_engine* h, int nsrc, const int32_t* t0, int nk, const double* sink_spin,
+                           const int32_t* sink_mom, int nkp, const double* source_spin, const int32_t* source_mom,
+                           double tol, int maxiter, double* C1, double* C2, int32_t* iters) {
+  SWCHK(check_hier(h, 0, 0, true));
+  SWCHK(distillation_ready(h));
+  SWCHK(laph_momenta_ready(h));
+  SWCHK(check_source_timeslices(h, nsrc, t0));
+  LaphMesonSide snk, src;
+  SWCHK(laph_meson_side(h, "sink", nk, sink_spin, sink_mom, snk));
+  SWCHK(laph_meson_side(h, "source", nkp, source_spin, source_mom, src));
+  if (maxiter < 1) return sw_fail(h, "maxiter must be >= 1");
+  if (!C1 || !C2) return sw_fail(h, "null output");
+  int hid;
+  SWCHK(solve_hier(h, 0, &hid));
+  HIPCHK(hipSetDevice(h->device));
+  Level& lv = h->hier[0].lv[0];
+  const int L = lv.L, nev = h->lh_nev, per = 2 * nev;
+  const int spb = laph_sources_per_block(nev), nsmax = std::min(spb, nsrc), bmax = pad64(nsmax * per);
+  const size_t c1 = (size_t)nk * nkp * L, c2 = (size_t)nk * nk * nkp * nkp * L;
+  DevBuf<int> d_t0(h);
+  DevBuf<cplx> proj(h);
+  LaphTwoMesonWS ws(h);
+  SWCHK(upload(h, &d_t0.p, (const int*)t0, (size_t)nsrc));
+  SWCHK(ensure_two_point_ws(h, (size_t)lv.n * bmax));
+  SWCHK(dev_realloc(h, &proj.p, (size_t)L * per * bmax));
+  SWCHK(laph_two_meson_ws(h, ws, nsmax, bmax, nk, nkp, false));
+  for (int s0 = 0; s0 < nsrc; s0 += spb) {
+    const int ns = std::min(spb, nsrc - s0), nvalid = ns * per, ncols = pad64(nvalid);
+    SWCHK(laph_block(h, hid, lv, d_t0.p + s0, 0, nvalid, ncols, tol, maxiter, proj,
+                     iters ? iters + (size_t)s0 * per : nullptr));
+    SWCHK(laph_two_meson(h, proj, d_t0.p + s0, ns, ncols, snk, src, ws, (cplx*)C1 + s0 * c1, (cplx*)C2 + s0 * c2,
+                         nullptr));
+  }
+  return 0;
+}
+
+// The contraction alone on host perambulators tau [nsrc][L][2][nev][nev][2] (the layout of sw_perambulators), in the
+// blocks of sw_distilled_two_meson; the pad columns of a block are zeros.  Q (or NULL): the sandwich, dense.
+int sw_apply_laph_two_meson(sw_engine* h, int nsrc, const int32_t* t0, const double* tau, int nk,
+                            const double* sink_spin, const int32_t* sink_mom, int nkp, const double* source_spin,
+                            const int32_t* source_mom, double* C1, double* C2, double* Q) {
+  SWCHK(check_hier(h, 0, 0, false));
+  SWCHK(distillation_ready(h));
+  SWCHK(laph_momenta_ready(h));
+  SWCHK(check_source_timeslices(h, nsrc, t0));
+  LaphMesonSide snk, src;
+  SWCHK(laph_meson_side(h, "sink", nk, sink_spin, sink_mom, snk));
+  SWCHK(laph_meson_side(h, "source", nkp, source_spin, source_mom, src));
+  if (!tau || !C1 || !C2) return sw_fail(h, "null argument");
+  HIPCHK(hipSetDevice(h->device));
+  const int L = h->hier[0].lv[0].L, nev = h->lh_nev, per = 2 * nev;
+  const int spb = laph_sources_per_block(nev), nsmax = std::min(spb, nsrc), bmax = pad64(nsmax * per);
+  const size_t c1 = (size_t)nk * nkp * L, c2 = (size_t)nk * nk * nkp * nkp * L, q = (size_t)nk * L * per * per;
+  DevBuf<int> d_t0(h);
+  DevBuf<cplx> proj(h);
+  LaphTwoMesonWS ws(h);
+  SWCHK(upload(h, &d_t0.p, (const int*)t0, (size_t)nsrc));
+  SWCHK(dev_realloc(h, &proj.p, (size_t)L * per * bmax));
+  SWCHK(laph_two_meson_ws(h, ws, nsmax, bmax, nk, nkp, Q != nullptr));
+  for (int s0 = 0; s0 < nsrc; s0 += spb) {
+    const int ns = std::min(spb, nsrc - s0), nvalid = ns * per, ncols = pad64(nvalid);
+    SWCHK(stream_sync(h));
+    HIPCHK(hipMemset(proj.p, 0, sizeof(cplx) * L * per * ncols));
+    SWCHK(laph_copy_tau(h, (cplx*)tau + (size_t)s0 * L * per * per, 0, nvalid, ncols, proj, false));
+    SWCHK(laph_two_meson(h, proj, d_t0.p + s0, ns, ncols, snk, src, ws, (cplx*)C1 + s0 * c1, (cplx*)C2 + s0 * c2,
+                         Q ? (cplx*)Q + s0 * q : nullptr));
+  }
+  return 0;
+}
+
 // ---- distillation: generalized perambulators, the distilled three-point functions ---------
 // What a k_laph_generalized call needs besides the fields: the insertion timeslices and momenta with their tables on
 // the device, for this call only.
@@ -7179,7 +7355,7 @@ int sw_timers(sw_engine* h, double t[8]) {
   t[T_OTHER] += h->tacc[T_TP_SOURCES] + h->tacc[T_3PT_SOURCES] + h->tacc[T_SMEAR] + h->tacc[T_LAPH_SRC];
   t[T_DOTS] += h->tacc[T_TP_DOTS] + h->tacc[T_SLICE_CDOTS] + h->tacc[T_MESON_FIELD] + h->tacc[T_LM_CONTRACT] +
                h->tacc[T_LINK_DOTS] + h->tacc[T_3PT_DOTS] + h->tacc[T_LAPH] + h->tacc[T_LAPH_CONTRACT] +
-               h->tacc[T_LAPH_GEN];
+               h->tacc[T_LAPH_GEN] + h->tacc[T_LAPH_2M];
   return 0;
 }
 int sw_timers_reset(sw_engine* h) {
@@ -7195,7 +7371,7 @@ int sw_timers_reset(sw_engine* h) {
 }
 int sw_kernel_stats(sw_engine* h, int which, double* total_ms, int64_t* launches) {
   if (!h || !total_ms || !launches) return 1;
-  if (which < 0 || which >= T_LAPH_SRC) return sw_fail(h, "kernel class %d out of range", which);
+  if (which < 0 || which >= T_NCAT || which == T_LAPH_SRC) return sw_fail(h, "kernel class %d out of range", which);
   SWCHK(stream_sync(h));
   *total_ms = h->tacc[which];
   *launches = h->tcount[which];
@@ -7207,7 +7383,7 @@ int sw_kernel_stats(sw_engine* h, int which, double* total_ms, int64_t* launches
 }
 int sw_kernel_work(sw_engine* h, int which, double* work) {
   if (!h || !work) return 1;
-  if (which < 0 || which >= T_LAPH_SRC) return sw_fail(h, "kernel class %d out of range", which);
+  if (which < 0 || which >= T_NCAT || which == T_LAPH_SRC) return sw_fail(h, "kernel class %d out of range", which);
   *work = h->twork[which];
   return 0;
 }

@@ -4886,4 +4886,249 @@ __global__ __launch_bounds__(SW_BLOCK) void k_laph_generalized(const cplx* __res
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// Two-meson correlators from the perambulators (sw_distilled_two_meson).  rho = 2 n + a is the
+// column of a source inside its block, per = 2 nev of them; P = 2 ld is the leading dimension of the per-(source,
+// operator, timeslice) matrices Qt and R.
+// ------------------------------------------------------------------------------------------
+// The folded 2 x 2 spin matrices and momentum indices of up to SW_MAX_MESON_OPS operators, passed by value:
+// w[k][2 (2 r + c)], w[k][2 (2 r + c) + 1] = re, im of the entry [r][c].
+struct LaphMesonOps {
+  double w[SW_MAX_MESON_OPS][8];
+  int mom[SW_MAX_MESON_OPS];
+};
+__device__ __forceinline__ cplx laph_op_weight(const LaphMesonOps& ops, int k, int r, int c) {
+  return cmake(ops.w[k][2 * (2 * r + c)], ops.w[k][2 * (2 * r + c) + 1]);
+}
+
+// The sibling of laph_tile_product that only accumulates, with separate operand strides, a weight on A and guards on
+// both operands: for one wave
+//   D[i][j] += sum_{k < K} (w A[k sa + i]) op(B[k sb + j]),   i < 16, j < 16 NT,   op = conj where CONJB is set,
+// A read for i < na only and B for j < nb only (the rest enter as exact zeros and are never read), k >= K likewise.
+// Operand lanes and the four real MFMAs as laph_tile_product; summed in the order k = 0, 4, 8, ...  The weight is one
+// complex multiply on the VALU per A element; w = 1 multiplies exactly.
+template <int NT, bool CONJB>
+__device__ __forceinline__ void laph_tile_accumulate(const cplx* __restrict__ A, size_t sa, int na, cplx w,
+                                                     const cplx* __restrict__ B, size_t sb, int nb, int K,
+                                                     sw_double4 (&re)[NT], sw_double4 (&im)[NT]) {
+  const int lane = threadIdx.x & 63;
+  const int k = lane >> 4, c = lane & 15;
+  for (int k0 = 0; k0 < K; k0 += 4) {
+    const int kk = k0 + k;
+    const bool live = kk < K;
+    cplx a = cmake(0.0, 0.0);
+    if (live && c < na) a = cmul(w, A[(size_t)kk * sa + c]);
+    const double are = CONJB ? a.y : -a.y;      // re += are bi
+    const double aim = CONJB ? -a.x : a.x;      // im += aim bi
+    const cplx* __restrict__ bp = B + (size_t)kk * sb + c;
+#pragma unroll
+    for (int q = 0; q < NT; ++q) {
+      cplx b = cmake(0.0, 0.0);
+      if (live && q * 16 + c < nb) b = bp[q * 16];
+      re[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, b.x, re[q], 0, 0, 0);
+      re[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(are, b.y, re[q], 0, 0, 0);
+      im[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(aim, b.y, im[q], 0, 0, 0);
+      im[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, b.x, im[q], 0, 0, 0);
+    }
+  }
+}
+
+// Stage 1a, the sink operator applied to the perambulator block, in the layout of the block itself:
+//   W[(t,c)][m1][col] = sum_d G[c][d] sum_{m2 < nev} M_t[m1][m2] tau[(t,d)][m2][col],   [L][2][nev][ncols],
+// A = Mt[t] (the rows m2 of the transposed elementals, m1 contiguous) weighted by G[c][d], B = the rows m2 of
+// tau[(t,d)]: one chain over (d, m2) with the terms of an exactly zero G[c][d] left out.  grid = (L, 2,
+// ceil(ld / 64) * (ncols / (16 NT))): wave w owns the 16 rows m1 of tile 4 g + w and NT column tiles (the engine
+// launches NT = 4, a 64-column pad unit: 108 registers, four waves per SIMD).  A column's values depend on that column alone; the rows m1 >= nev are not
+// stored.  No LDS, no barrier.
+template <int NT>
+__global__ __launch_bounds__(SW_BLOCK) void k_laph_sink(const cplx* __restrict__ tau, int nev, int ncols,
+                                                        const cplx* __restrict__ Mt, int ld, LaphMesonOps ops,
+                                                        int k, cplx* __restrict__ W) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int t = blockIdx.x, c = blockIdx.y;
+  const int nchunk = ncols / (16 * NT);
+  const int mt = (blockIdx.z / nchunk) * SW_WAVES_PER_BLOCK + wave;
+  const int col0 = (blockIdx.z % nchunk) * 16 * NT;
+  if (mt * 16 >= nev) return;
+  sw_double4 re[NT], im[NT];
+#pragma unroll
+  for (int q = 0; q < NT; ++q) re[q] = im[q] = sw_double4{0.0, 0.0, 0.0, 0.0};
+  const cplx* __restrict__ A = Mt + ((size_t)ops.mom[k] * gridDim.x + t) * ld * ld + mt * 16;
+#pragma nounroll
+  for (int d = 0; d < 2; ++d) {
+    const cplx w = laph_op_weight(ops, k, c, d);
+    if (w.x == 0.0 && w.y == 0.0) continue;
+    laph_tile_accumulate<NT, false>(A, (size_t)ld, 16, w, tau + ((size_t)t * 2 + d) * nev * ncols + col0,
+                                    (size_t)ncols, 16 * NT, nev, re, im);
+  }
+  cplx* __restrict__ o = W + (((size_t)t * 2 + c) * nev + mt * 16) * ncols + col0 + (lane & 15);
+#pragma unroll
+  for (int q = 0; q < NT; ++q) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = (lane >> 4) + 4 * r;
+      if (mt * 16 + i < nev) o[(size_t)i * ncols + q * 16] = cmake(re[q][r], im[q][r]);
+    }
+  }
+}
+
+// Stage 1b, the sandwich, stored transposed:
+//   Qt[s][t][rho2][rho1] = Q[rho1][rho2] = sum_{(c,m1) < 2 nev} W[(t,c)][m1][(s,rho2)] conj(tau[(t,c)][m1][(s,rho1)]),
+// A = the rows (c, m1) of W at the source's columns, B = the same rows of tau, conjugated; the 2 nev rows of a
+// timeslice are contiguous in both, so the chain runs over k = c nev + m1 = 0, 4, 8, ...  grid = (L, ns,
+// ceil(RT / 4) * halves), RT = ceil(per / 16): wave w owns the 16 rows rho2 of tile 4 g + w and the NT column tiles
+// of its half (RT <= 8: one half of RT tiles; above: two halves of ceil(RT / 2)).  Only the columns of source s are
+// read, only rho1, rho2 < per are stored: a source's values do not depend on the other sources of the block, and its
+// pad columns never enter.  No LDS, no barrier.
+template <int NT>
+__global__ __launch_bounds__(SW_BLOCK) void k_laph_sandwich(const cplx* __restrict__ W,
+                                                            const cplx* __restrict__ tau, int nev, int ncols,
+                                                            int halves, int P, cplx* __restrict__ Qt) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int t = blockIdx.x, s = blockIdx.y, per = 2 * nev;
+  const int rt = (blockIdx.z / halves) * SW_WAVES_PER_BLOCK + wave;
+  const int col0 = (blockIdx.z % halves) * 16 * NT;
+  if (rt * 16 >= per) return;
+  sw_double4 re[NT], im[NT];
+#pragma unroll
+  for (int q = 0; q < NT; ++q) re[q] = im[q] = sw_double4{0.0, 0.0, 0.0, 0.0};
+  const size_t base = (size_t)t * per * ncols + (size_t)s * per;
+  laph_tile_accumulate<NT, true>(W + base + rt * 16, (size_t)ncols, per - rt * 16, cmake(1.0, 0.0),
+                                 tau + base + col0, (size_t)ncols, per - col0, per, re, im);
+  cplx* __restrict__ o = Qt + ((size_t)s * gridDim.x + t) * P * P + (size_t)rt * 16 * P + col0 + (lane & 15);
+#pragma unroll
+  for (int q = 0; q < NT; ++q) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = (lane >> 4) + 4 * r;
+      if (rt * 16 + i < per && col0 + q * 16 + (lane & 15) < per) o[(size_t)i * P + q * 16] = cmake(re[q][r], im[q][r]);
+    }
+  }
+}
+
+// Stage 2, the right product of every sink operator k with every source operator kp:
+//   R[k][kp][s][t][rho][2 n1 + a] = sum_b H[b][a] sum_{n2 < nev} Q[rho][(n2,b)] conj(M_{t0(s)}[n1][n2]),
+// A = the rows (n2, b) of Qt (stride 2 P, rho contiguous) weighted by H[b][a], B = conj(Mt[t0s[s]]): one chain over
+// (b, n2), the terms of an exactly zero H[b][a] left out.  grid = (L, 2 ns, nk nkp ceil(RT / 4)): wave w owns the 16
+// rows rho of tile 4 g + w and all NT = ld / 16 tiles of n1.  Only rho < per and n1 < nev are stored.  No LDS, no
+// barrier.
+template <int NT>
+__global__ __launch_bounds__(SW_BLOCK) void k_laph_source(const cplx* __restrict__ Qt, int nev, int P,
+                                                          const cplx* __restrict__ Mt, int ld,
+                                                          const int* __restrict__ t0s, int ns, int nkp,
+                                                          LaphMesonOps src, int groups, cplx* __restrict__ R) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int t = blockIdx.x, L = gridDim.x, s = blockIdx.y >> 1, a = blockIdx.y & 1, per = 2 * nev;
+  const int kk = blockIdx.z / groups, kp = kk % nkp, k = kk / nkp;
+  const int rt = (blockIdx.z % groups) * SW_WAVES_PER_BLOCK + wave;
+  if (rt * 16 >= per) return;
+  sw_double4 re[NT], im[NT];
+#pragma unroll
+  for (int q = 0; q < NT; ++q) re[q] = im[q] = sw_double4{0.0, 0.0, 0.0, 0.0};
+  const cplx* __restrict__ q0 = Qt + (((size_t)k * ns + s) * L + t) * P * P + rt * 16;
+  const cplx* __restrict__ B = Mt + ((size_t)src.mom[kp] * L + t0s[s]) * ld * ld;
+#pragma nounroll
+  for (int b = 0; b < 2; ++b) {
+    const cplx w = laph_op_weight(src, kp, b, a);
+    if (w.x == 0.0 && w.y == 0.0) continue;
+    laph_tile_accumulate<NT, true>(q0 + (size_t)b * P, (size_t)2 * P, per - rt * 16, w, B, (size_t)ld, ld, nev, re,
+                                   im);
+  }
+  cplx* __restrict__ o = R + ((((size_t)k * nkp + kp) * ns + s) * L + t) * P * P + (size_t)rt * 16 * P + a;
+#pragma unroll
+  for (int q = 0; q < NT; ++q) {
+    const int n1 = q * 16 + (lane & 15);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = (lane >> 4) + 4 * r;
+      if (rt * 16 + i < per && n1 < nev) o[(size_t)i * P + 2 * n1] = cmake(re[q][r], im[q][r]);
+    }
+  }
+}
+
+// The end of both traces: a wave adds its 64 lanes by the xor butterfly 32, 16, ..., 1, the four waves meet in LDS and
+// thread 0 returns w0 + w1 + w2 + w3 (the other threads return garbage).
+__device__ __forceinline__ cplx laph_block_sum(cplx v, double (*red)[2]) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    v.x += __shfl_xor(v.x, off, 64);
+    v.y += __shfl_xor(v.y, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6][0] = v.x;
+    red[threadIdx.x >> 6][1] = v.y;
+  }
+  __syncthreads();
+  return cmake(((red[0][0] + red[1][0]) + red[2][0]) + red[3][0], ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1]);
+}
+
+// Stage 3a: C1[s][k][kp][t] = tr[Q S] = sum_{n1,n2 < nev} (sum_{a,b} H[b][a] Q[(n1,a)][(n2,b)]) conj(M_t0[n1][n2]) on
+// the VALU, grid = (nk nkp, L, ns).  Thread i takes the terms idx = n2 nev + n1 = i, i + 256, ... (n1 fastest:
+// contiguous in Qt and Mt alike), then laph_block_sum: the order is a function of nev alone.
+__global__ __launch_bounds__(SW_BLOCK) void k_laph_trace1(const cplx* __restrict__ Qt, int nev, int P,
+                                                          const cplx* __restrict__ Mt, int ld,
+                                                          const int* __restrict__ t0s, int nkp, LaphMesonOps src,
+                                                          cplx* __restrict__ C1) {
+  __shared__ double red[SW_WAVES_PER_BLOCK][2];
+  const int k = blockIdx.x / nkp, kp = blockIdx.x % nkp, nk = gridDim.x / nkp;
+  const int t = blockIdx.y, L = gridDim.y, s = blockIdx.z, ns = gridDim.z;
+  const cplx* __restrict__ q = Qt + (((size_t)k * ns + s) * L + t) * P * P;
+  const cplx* __restrict__ m = Mt + ((size_t)src.mom[kp] * L + t0s[s]) * ld * ld;
+  cplx h[2][2];                                 // h[b][a]
+#pragma unroll
+  for (int b = 0; b < 2; ++b)
+#pragma unroll
+    for (int a = 0; a < 2; ++a) h[b][a] = laph_op_weight(src, kp, b, a);
+  cplx acc = cmake(0.0, 0.0);
+  const int terms = nev * nev;
+  for (int idx = threadIdx.x; idx < terms; idx += SW_BLOCK) {
+    const int n2 = idx / nev, n1 = idx - n2 * nev;
+    cplx x = cmake(0.0, 0.0);
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int a = 0; a < 2; ++a) cfma(x, h[b][a], q[(size_t)(2 * n2 + b) * P + 2 * n1 + a]);
+    cfmac(acc, m[(size_t)n2 * ld + n1], x);     // conj(Mt[t0][n2][n1]) x = conj(M_t0[n1][n2]) x
+  }
+  const cplx sum = laph_block_sum(acc, red);
+  if (threadIdx.x == 0) C1[(((size_t)s * nk + k) * nkp + kp) * L + t] = sum;
+}
+
+// Stage 3b: C2[s][k][l][kp][lp][t] = sum_{rho,sigma < per} R_{k,kp}[rho][sigma] R_{l,lp}[sigma][rho] on the VALU, grid =
+// (nk nk nkp nkp, L, ns).  The per x per index is walked in 8 x 8 tiles, row-major over the tiles and inside them, so
+// that a wave reads eight 128-byte rows of either factor: thread i takes the terms i, i + 256, ... of that order
+// (entries past per are skipped), then laph_block_sum: the order is a function of nev alone.
+__global__ __launch_bounds__(SW_BLOCK) void k_laph_trace2(const cplx* __restrict__ R, int nev, int P, int nk,
+                                                          int nkp, cplx* __restrict__ C2) {
+  __shared__ double red[SW_WAVES_PER_BLOCK][2];
+  int z = blockIdx.x;
+  const int lp = z % nkp; z /= nkp;
+  const int kp = z % nkp; z /= nkp;
+  const int l = z % nk, k = z / nk;
+  const int t = blockIdx.y, L = gridDim.y, s = blockIdx.z, ns = gridDim.z, per = 2 * nev;
+  const cplx* __restrict__ r1 = R + ((((size_t)k * nkp + kp) * ns + s) * L + t) * P * P;
+  const cplx* __restrict__ r2 = R + ((((size_t)l * nkp + lp) * ns + s) * L + t) * P * P;
+  const int T8 = (per + 7) / 8, terms = T8 * T8 * 64;
+  cplx acc = cmake(0.0, 0.0);
+  for (int idx = threadIdx.x; idx < terms; idx += SW_BLOCK) {
+    const int tile = idx >> 6, in = idx & 63;
+    const int rho = (tile / T8) * 8 + (in >> 3), sig = (tile % T8) * 8 + (in & 7);
+    if (rho < per && sig < per) cfma(acc, r1[(size_t)rho * P + sig], r2[(size_t)sig * P + rho]);
+  }
+  const cplx sum = laph_block_sum(acc, red);
+  if (threadIdx.x == 0) C2[((((((size_t)s * nk + k) * nk + l) * nkp + kp) * nkp + lp)) * L + t] = sum;
+}
+
+// out[s][k][t][rho1][rho2] = Qt[k][s][t][rho2][rho1] for rho1, rho2 < per: the sandwich as sw_apply_laph_two_meson
+// returns it, dense and untransposed.  grid = (ceil(per^2 / SW_BLOCK), L, nk ns), one thread per entry.
+__global__ __launch_bounds__(SW_BLOCK) void k_laph_sandwich_unpack(const cplx* __restrict__ Qt, int nev, int P,
+                                                                   int nk, cplx* __restrict__ out) {
+  const int per = 2 * nev, idx = blockIdx.x * SW_BLOCK + threadIdx.x;
+  if (idx >= per * per) return;
+  const int r1 = idx / per, r2 = idx - r1 * per;
+  const int t = blockIdx.y, L = gridDim.y, k = blockIdx.z % nk, s = blockIdx.z / nk, ns = gridDim.z / nk;
+  out[((((size_t)s * nk + k) * L + t) * per) * per + idx] =
+      Qt[(((size_t)k * ns + s) * L + t) * P * P + (size_t)r2 * P + r1];
+}
+
 }  // namespace swk

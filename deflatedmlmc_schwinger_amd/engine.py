@@ -79,6 +79,8 @@ KCLASS_SMEAR = 25          # ... and of k_smear_step / k_smear_fused (smeared tw
 KCLASS_LAPH = 26           # ... and of k_laph_sources / k_laph_project (distillation)
 KCLASS_LAPH_CONTRACT = 27  # ... and of k_laph_elementals / k_laph_left / k_laph_right / k_laph_reduce
 KCLASS_LAPH_GENERALIZED = 28   # ... and of k_laph_generalized (generalized perambulators)
+KCLASS_LAPH_TWO_MESON = 30     # (29 is no class: kernel_stats(29) stays out of range) ... and of k_laph_sink / k_laph_sandwich / k_laph_source / k_laph_trace1 / k_laph_trace2
+MAX_MESON_OPS = 4              # SW_MAX_MESON_OPS: sink operators, and source operators, of one two-meson call
 MAX_LAPH = 128             # SW_MAX_LAPH
 MAX_SINK_LEVELS = 4        # SW_MAX_SINK_LEVELS, SW_MAX_SMEARING_STEPS
 MAX_SMEARING_STEPS = 1024
@@ -281,6 +283,8 @@ def load_library():
     sig("sw_apply_laph_elementals", i32, vp, vp)
     sig("sw_distilled_two_point", i32, vp, i32, vp, dbl, i32, vp, vp, vp, vp)
     sig("sw_apply_laph_contract", i32, vp, i32, vp, vp, vp, vp)
+    sig("sw_distilled_two_meson", i32, vp, i32, vp, i32, vp, vp, i32, vp, vp, dbl, i32, vp, vp, vp)
+    sig("sw_apply_laph_two_meson", i32, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp)
     sig("sw_generalized_perambulators", i32, vp, i32, i32, i32, vp, i32, vp, dbl, i32, vp, vp, vp)
     sig("sw_apply_laph_generalized", i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp)
     _lib = lib
@@ -315,6 +319,7 @@ EXPORTED_SYMBOLS = (
     "sw_set_distillation", "sw_perambulators", "sw_apply_laph_sources", "sw_apply_laph_project",
     "sw_set_distillation_momenta", "sw_apply_laph_elementals", "sw_distilled_two_point", "sw_apply_laph_contract",
     "sw_generalized_perambulators", "sw_apply_laph_generalized",
+    "sw_distilled_two_meson", "sw_apply_laph_two_meson",
 )
 
 
@@ -1199,6 +1204,62 @@ class Engine:
                                                    _ptr(tau) if tau.size else None, _ptr(T) if T.size else None,
                                                    _ptr(loops) if loops.size else None), "sw_apply_laph_contract")
         return T, loops
+
+    @staticmethod
+    def _meson_ops(ops, what):
+        """(spin complex128[n, 2, 2], mom int32[n]) from a list of (2 x 2 matrix, momentum index) pairs."""
+        ops = list(ops)
+        spin = np.zeros((len(ops), 2, 2), dtype=np.complex128)
+        mom = np.zeros(len(ops), dtype=np.int32)
+        for k, op in enumerate(ops):
+            g = np.asarray(op[0], dtype=np.complex128)
+            if g.shape != (2, 2):
+                raise EngineError("%s operator %d: spin matrix of shape %s, expected (2, 2)" % (what, k, g.shape))
+            spin[k], mom[k] = g, int(op[1])
+        return spin, mom
+
+    def distilled_two_meson(self, t0s, sink_ops, source_ops, tol, maxiter=1000):
+        """(C1[nsrc, nk, nkp, L], C2[nsrc, nk, nk, nkp, nkp, L], iters[nsrc, nev, 2]): the perambulators of the
+        timeslices t0s solved, projected and contracted into the two-meson building blocks on the device
+        (utils.two_meson_sums).  sink_ops: 1 to MAX_MESON_OPS pairs (G, j) of the folded 2 x 2 matrix G = g3 Gamma and
+        the index j into the momenta of set_distillation_momenta; source_ops: pairs (H, j), H = Gamma' g3
+        (utils.two_meson_folded makes both).  Stateless: no mode buffer is touched."""
+        t = self._t0s(t0s)
+        L, nev, _ = self._laph_shape()
+        G, jk = self._meson_ops(sink_ops, "sink")
+        H, jkp = self._meson_ops(source_ops, "source")
+        nk, nkp = jk.size, jkp.size
+        C1 = np.zeros((t.size, nk, nkp, L), dtype=np.complex128)
+        C2 = np.zeros((t.size, nk, nk, nkp, nkp, L), dtype=np.complex128)
+        iters = np.zeros((t.size, nev, 2), dtype=np.int32)
+        self._chk(self._lib.sw_distilled_two_meson(
+            self._h, t.size, _ptr(t) if t.size else None, nk, _ptr(G) if nk else None, _ptr(jk) if nk else None,
+            nkp, _ptr(H) if nkp else None, _ptr(jkp) if nkp else None, float(tol), int(maxiter),
+            _ptr(C1) if C1.size else None, _ptr(C2) if C2.size else None, _ptr(iters) if iters.size else None),
+            "sw_distilled_two_meson")
+        return C1, C2, iters
+
+    def apply_laph_two_meson(self, tau, t0s, sink_ops, source_ops, want_Q=False):
+        """The two-meson kernels alone on perambulators tau[nsrc, L, 2, nev, nev, 2]: (C1, C2) as
+        distilled_two_meson() returns them and, with want_Q, the sandwich Q[nsrc, nk, L, 2 nev, 2 nev] (else None)."""
+        t = self._t0s(t0s)
+        L, nev, _ = self._laph_shape()
+        tau = _c128(tau)
+        if tau.shape != (t.size, L, 2, nev, nev, 2):
+            raise EngineError("apply_laph_two_meson: tau of shape %s, expected %s"
+                              % (tau.shape, (t.size, L, 2, nev, nev, 2)))
+        G, jk = self._meson_ops(sink_ops, "sink")
+        H, jkp = self._meson_ops(source_ops, "source")
+        nk, nkp = jk.size, jkp.size
+        C1 = np.zeros((t.size, nk, nkp, L), dtype=np.complex128)
+        C2 = np.zeros((t.size, nk, nk, nkp, nkp, L), dtype=np.complex128)
+        Q = np.zeros((t.size, nk, L, 2 * nev, 2 * nev), dtype=np.complex128) if want_Q else None
+        self._chk(self._lib.sw_apply_laph_two_meson(
+            self._h, t.size, _ptr(t) if t.size else None, _ptr(tau) if tau.size else None, nk,
+            _ptr(G) if nk else None, _ptr(jk) if nk else None, nkp, _ptr(H) if nkp else None,
+            _ptr(jkp) if nkp else None, _ptr(C1) if C1.size else None, _ptr(C2) if C2.size else None,
+            _ptr(Q) if want_Q and Q.size else None), "sw_apply_laph_two_meson")
+        return C1, C2, Q
 
     def _insertions(self, timeslices, momenta):
         return (np.ascontiguousarray(np.atleast_1d(timeslices), dtype=np.int32).reshape(-1),

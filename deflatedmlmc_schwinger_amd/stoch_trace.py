@@ -23,6 +23,7 @@ from .utils import (_engines, deflation_pre_computations, displacements_of, draw
                     register_low_modes, low_mode_contraction_of, link_loops_of, three_point_of,
                     register_three_point, refuse_three_point, register_smearing, refuse_smearing, smearing_of,
                     distillation_of, refuse_distillation, refuse_distilled_three_point,
+                    refuse_two_meson, two_meson_ops_of, two_meson_sums, two_meson_folded,
                     distilled_three_point_of, distilled_three_point_correlator, DISTILLED_INSERTIONS,
                     laplacian_eigenvectors, laph_elementals,
                     distilled_pair_sums, distilled_loops, source_average, distilled_contraction_of)
@@ -472,6 +473,7 @@ def hutchinson(A, params):
     solve per probe: the reference's result keys are then those of the control column, and the stopping rule runs on
     its series alone."""
     refuse_distilled_three_point(params, "hutchinson()")
+    refuse_two_meson(params, "hutchinson()")
     refuse_three_point(params, "hutchinson()")
     refuse_smearing(params, "hutchinson()")
     refuse_distillation(params, "hutchinson()")
@@ -568,6 +570,7 @@ def two_point(A, params):
     momenta, source_timeslice, nr_ests, function_iters (a noise counts the largest iteration number among its
     2 M solves), ests (the control series), probe_loop_s and probes_solved."""
     refuse_distilled_three_point(params, "two_point()")
+    refuse_two_meson(params, "two_point()")
     refuse_three_point(params, "two_point()")
     refuse_distillation(params, "two_point()")
     sel = two_point_of(params)
@@ -639,6 +642,7 @@ def distilled_two_point(A, params):
     momenta, source_timeslices, distillation_vectors, function_iters (summed over all columns), solves and
     solve_s."""
     refuse_distilled_three_point(params, "distilled_two_point()")
+    refuse_two_meson(params, "distilled_two_point()")
     sel = distillation_of(params)
     if sel is None:
         raise Exception("distilled_two_point() needs the key distillation_vectors")
@@ -714,6 +718,99 @@ def distilled_two_point(A, params):
     return result
 
 
+def distilled_two_meson(A, params):
+    """Two-meson correlators in the distilled basis: two mesons at the source timeslice and two at the
+    sink (the pi-pi type, isospin-2 channel) need only the source-to-sink perambulators of distilled_two_point() --
+    nothing more is solved.  For the sink operators k = (Gamma_k, p_k) and the source operators k' = (Gamma'_k', p_k')
+
+        C1[s][k][k'][t]           tr[Q_k S_k']            the single-meson correlator (utils.two_meson_sums)
+        C2[s][k][l][k'][l'][t]    tr[Q_k S_k' Q_l S_l']   the chain of four perambulators
+        C1_avg, C2_avg            their utils.source_average over the sources at t = t0 + dt mod L
+
+    from which utils.two_meson_correlator forms the direct and crossed diagrams and their isospin-2 combination.
+
+    Keys (utils.two_meson_ops_of): distillation_vectors, source_timeslices, two_point_momenta and distilled_contraction
+    as distilled_two_point() takes them; meson_operators, a list of 1 to 4 pairs (spin matrix out of '1', 'g3', 's1',
+    's2', momentum out of two_point_momenta); source_operators, the same form (default: meson_operators).  With
+    distilled_contraction = "host" (the default) the perambulators come back chunk by chunk (Engine.perambulators) and
+    NumPy contracts them; with "device" the engine's kernels do and no perambulator leaves the device
+    (Engine.distilled_two_meson).  One rank; the operator has to be the lattice stencil the engine detects.
+
+    Returns C1, C2, C1_avg, C2_avg, operators, source_operators, momenta, source_timeslices, distillation_vectors,
+    eigenvalues, function_iters, solves and solve_s."""
+    refuse_distilled_three_point(params, "distilled_two_meson()")
+    sel = two_meson_ops_of(params)
+    if sel is None:
+        raise Exception("distilled_two_meson() needs the keys distillation_vectors and meson_operators")
+    on_device = distilled_contraction_of(params) == "device"
+    if _dist.default_comm().world > 1:
+        raise Exception("distilled two-meson correlators run on one rank")
+    from .hierarchy import detect_lattice
+    lattice = A if isinstance(A, tuple) else (None if A is None else detect_lattice(A))
+    if lattice is None:
+        raise Exception("distilled_two_meson() needs a lattice operator (a U(1) Wilson stencil with its links)")
+    nev, t0s, momenta = sel['nev'], sel['t0s'], sel['momenta']
+    sink_ops, source_ops = sel['sink_ops'], sel['source_ops']
+    nk, nkp = len(sink_ops), len(source_ops)
+    L = int(params['latt_dims'][0])
+    mg_solver, nr_levels = _setup_solver(A, params, defer_coarse=True, lattice=lattice)
+    engs = _engines(mg_solver)
+    if not engs:
+        raise Exception("no GPU engine attached (run MG.setup first)")
+    eng = engs[0]
+    V, eigenvalues = laplacian_eigenvectors(lattice[2], L, nev)
+    n = 2 * L * L
+    tol, maxiter = params['function_params']['tol'], (n if n < 1000 else 1000)
+    C1 = np.zeros((len(t0s), nk, nkp, L), dtype=np.complex128)
+    C2 = np.zeros((len(t0s), nk, nk, nkp, nkp, L), dtype=np.complex128)
+    iters, solve_s = 0, 0.0
+    try:                                   # the registrations and the deferred set-up do not outlive a failed call
+        eng.set_distillation(V)
+        if on_device:
+            eng.set_distillation_momenta(momenta)
+            G, H = two_meson_folded(sink_ops, source_ops, len(momenta), "distilled_two_meson()")
+        else:
+            M = laph_elementals(V, L, momenta)
+
+        print("\nResetting timer to zero ...", end='')
+        mg_solver.timer.reset()
+        eng.timers_reset()
+        print(" done")
+        print("\nComputing the two-meson building blocks ...", end='', flush=True)
+        chunk = max(1, 256 // (2 * nev))
+        for first in range(0, len(t0s), chunk):
+            part = t0s[first:first + chunk]
+            t1 = time.time()
+            if on_device:
+                c1, c2, it = eng.distilled_two_meson(part, G, H, tol, maxiter)
+            else:
+                tau, it = eng.perambulators(part, tol, maxiter)
+                c1, c2 = two_meson_sums(tau, M, part, sink_ops, source_ops)
+            solve_s += time.time() - t1
+            C1[first:first + len(part)], C2[first:first + len(part)] = c1, c2
+            iters += int(np.sum(it))
+        print(" done. Time : " + str(solve_s) + " seconds")
+    finally:
+        eng.set_distillation(None)
+        mg_solver.finish_setup()
+
+    result = dict()
+    result['C1'], result['C2'] = C1, C2
+    result['C1_avg'], result['C2_avg'] = source_average(C1, t0s), source_average(C2, t0s)
+    result['operators'] = list(sel['operators'])
+    result['source_operators'] = list(sel['source_operators'])
+    result['momenta'] = list(momenta)
+    result['source_timeslices'] = list(t0s)
+    result['distillation_vectors'] = nev
+    result['eigenvalues'] = eigenvalues
+    result['function_iters'] = iters
+    result['solves'] = 2 * nev * len(t0s)
+    result['solve_s'] = solve_s
+    mg_solver.sync_timer()
+    print(mg_solver.timer)
+    return result
+
+
 def distilled_three_point(A, params):
     """Three-point functions in the distilled basis: both outer quark lines are eigenvector sources,
     one on source_timeslice = t0 and one on sink_timeslice = tf, so no sequential solve is needed.  One engine call
@@ -732,6 +829,7 @@ def distilled_three_point(A, params):
     gives the two-point function of the ratio), eigenvalues, momenta, insertion_timeslices, source_timeslice,
     sink_timeslice, sink_gamma, sink_momentum, source_momentum, distillation_vectors, function_iters, solves and
     solve_s."""
+    refuse_two_meson(params, "distilled_three_point()")
     sel = distilled_three_point_of(params)
     if sel is None:
         raise Exception("distilled_three_point() needs the keys distillation_vectors, source_timeslice and "
@@ -832,6 +930,7 @@ def three_point(A, params):
     nr_ests, function_iters (a noise counts its largest stage-1 plus its largest stage-2 iteration number), ests,
     rough_trace, level_tol, probe_loop_s and probes_solved."""
     refuse_distilled_three_point(params, "three_point()")
+    refuse_two_meson(params, "three_point()")
     refuse_smearing(params, "three_point()")
     refuse_distillation(params, "three_point()")
     sel = three_point_of(params)
@@ -888,6 +987,7 @@ def lma_two_point(A, params):
     two_point_rest (the remainder's mean), two_point_rest_devs and nr_deflat_vctrs; two_point_ests are the per-noise
     remainders plus E_L(t0)."""
     refuse_distilled_three_point(params, "lma_two_point()")
+    refuse_two_meson(params, "lma_two_point()")
     refuse_three_point(params, "lma_two_point()")
     refuse_smearing(params, "lma_two_point()")
     refuse_distillation(params, "lma_two_point()")
@@ -1026,6 +1126,7 @@ def _mlmc_work_model(output_params, mg_solver):
 # compute tr(A^{-1}) via multigrid multilevel Monte Carlo          stoch_trace.py:185-471
 def mlmc(A, params):
     refuse_distilled_three_point(params, "mlmc()")
+    refuse_two_meson(params, "mlmc()")
     refuse_three_point(params, "mlmc()")
     refuse_smearing(params, "mlmc()")
     refuse_distillation(params, "mlmc()")
@@ -1150,6 +1251,7 @@ def _mlmc_loops_checks(params, deflated=False):
     who = "deflated_mlmc_loops" if deflated else "mlmc_loops"
     has = hasattr(params, "get")
     refuse_distilled_three_point(params, who + "()")
+    refuse_two_meson(params, who + "()")
     refuse_three_point(params, who + "()")
     refuse_distillation(params, who + "()")
     if has and params.get('source_timeslice') is not None:

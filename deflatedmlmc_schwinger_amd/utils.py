@@ -67,7 +67,7 @@ _BUILD_KEYS = ('batch', 'device', 'engines', 'cache_dir', 'report_path', 'probe_
                'sink_timeslice', 'sink_gamma', 'sink_momentum', 'three_point_momenta',
                'smearing_kappa', 'source_smearing_steps', 'sink_smearing_steps',
                'distillation_vectors', 'source_timeslices', 'keep_perambulators', 'distilled_contraction',
-               'insertion_timeslices', 'source_momentum')
+               'insertion_timeslices', 'source_momentum', 'meson_operators', 'source_operators')
 # where the eigenpairs of the MLMC difference operators come from: host ARPACK (the reference's path) or
 # the block eigensolver on the GPU (setup_gpu.device_diff_eigenpairs)
 MLMC_DEFL_SETUPS = ("host", "device")
@@ -1260,6 +1260,198 @@ def distilled_three_point_of(params):
             raise Exception("insertion_timeslices: the list is empty")
     return dict(nev=nev, t0=got['t0'], tf=got['tf'], sink=got['sink'], pf=got['pf'], pi=int(pi),
                 momenta=got['momenta'], tins=tins)
+
+
+# ---- two-meson correlators from the perambulators ---------------------------------------------------
+TWO_MESON_KEYS = ('meson_operators', 'source_operators')
+MAX_MESON_OPS = 4              # SW_MAX_MESON_OPS of the engine
+
+
+def refuse_two_meson(params, who):
+    """meson_operators and source_operators belong to distilled_two_meson(): every other flow raises on them."""
+    for key in TWO_MESON_KEYS:
+        if hasattr(params, "get") and params.get(key) is not None:
+            raise Exception("%s belongs to distilled_two_meson(), not to %s" % (key, who))
+
+
+def _meson_operator_list(key, given, momenta):
+    if isinstance(given, (str, bytes)) or not hasattr(given, '__len__'):
+        raise Exception("%s: %r is not a list of (spin matrix, momentum) pairs" % (key, given))
+    if not 1 <= len(given) <= MAX_MESON_OPS:
+        raise Exception("%s: %d operators, between 1 and %d" % (key, len(given), MAX_MESON_OPS))
+    ops = []
+    for op in given:
+        if isinstance(op, (str, bytes)) or not hasattr(op, '__len__') or len(op) != 2:
+            raise Exception("%s: %r is not a (spin matrix, momentum) pair" % (key, op))
+        which, p = op
+        if not isinstance(which, str) or which not in _PAULI:
+            raise Exception("%s: unknown spin matrix %r (one of %s)" % (key, which, sorted(_PAULI)))
+        if isinstance(p, (bool, str)) or int(p) != p:
+            raise Exception("%s: momentum %r is not an integer" % (key, p))
+        if int(p) not in momenta:
+            raise Exception("%s: momentum %d is not in two_point_momenta %s" % (key, int(p), list(momenta)))
+        ops.append((which, int(p)))
+    return ops
+
+
+def two_meson_ops_of(params):
+    """The build-only keys of distilled_two_meson(): None when meson_operators is absent, else the validated
+    dict(nev, t0s, momenta, operators, source_operators, sink_ops, source_ops) -- distillation_vectors,
+    source_timeslices and two_point_momenta as distillation_of takes them (keep_perambulators is refused: the flow keeps
+    no perambulators); meson_operators a list of 1 to MAX_MESON_OPS pairs (spin matrix out of '1', 'g3', 's1', 's2',
+    momentum), every momentum one of two_point_momenta; source_operators the same form, meson_operators when absent.
+    sink_ops / source_ops: the pairs with the momentum replaced by its index in `momenta`, as two_meson_sums and the
+    engine take them."""
+    has = hasattr(params, "get")
+    if not has or params.get('meson_operators') is None:
+        if has and params.get('source_operators') is not None:
+            raise Exception("source_operators needs meson_operators")
+        return None
+    if params.get('keep_perambulators') is not None:
+        raise Exception("distilled_two_meson() does not combine with keep_perambulators")
+    for key in DISTILLED_THREE_POINT_KEYS:
+        if params.get(key) is not None:
+            raise Exception("distilled_two_meson() does not combine with %s" % key)
+    sel = distillation_of(params)
+    if sel is None:
+        raise Exception("meson_operators needs distillation_vectors")
+    momenta = sel['momenta']
+    operators = _meson_operator_list('meson_operators', params['meson_operators'], momenta)
+    given = params.get('source_operators')
+    source_operators = list(operators) if given is None else _meson_operator_list('source_operators', given, momenta)
+    return dict(nev=sel['nev'], t0s=sel['t0s'], momenta=momenta, operators=operators,
+                source_operators=source_operators,
+                sink_ops=[(g, momenta.index(p)) for g, p in operators],
+                source_ops=[(g, momenta.index(p)) for g, p in source_operators])
+
+
+def _meson_spin(which, who):
+    if isinstance(which, str):
+        if which not in _PAULI:
+            raise Exception("%s: unknown spin matrix %r (one of %s)" % (who, which, sorted(_PAULI)))
+        return _PAULI[which]
+    g = np.asarray(which, dtype=np.complex128)
+    if g.shape != (2, 2):
+        raise Exception("%s: spin matrix of shape %s, expected (2, 2)" % (who, g.shape))
+    return g
+
+
+def two_meson_folded(sink_ops, source_ops, nmom=None, who="two_meson_folded"):
+    """([(G_k, j_k)], [(H_k', j_k')]) with G = g3 Gamma and H = Gamma' g3: the operators as the engine takes them, from
+    pairs (Gamma, momentum index), Gamma a name out of '1', 'g3', 's1', 's2' or a 2 x 2 matrix."""
+    g3 = _PAULI['g3']
+    out = []
+    for ops, sink in ((sink_ops, True), (source_ops, False)):
+        ops = list(ops)
+        if not 1 <= len(ops) <= MAX_MESON_OPS:
+            raise Exception("%s: %d operators, between 1 and %d" % (who, len(ops), MAX_MESON_OPS))
+        side = []
+        for which, j in ops:
+            if isinstance(j, bool) or int(j) != j or int(j) < 0 or (nmom is not None and int(j) >= nmom):
+                raise Exception("%s: momentum index %r outside the %s momenta" % (who, j, nmom))
+            g = _meson_spin(which, who)
+            side.append((g3 @ g if sink else g @ g3, int(j)))
+        out.append(side)
+    return out[0], out[1]
+
+
+def _two_meson_sums(tau, M, t0s, G, H, want_Q):
+    """C1, C2 (and Q) in the dtype of tau from the folded operators G = [(G_k, j_k)], H = [(H_k', j_k')]: batched
+    matrix products over the timeslices on the 2 N x 2 N matrices of one source."""
+    nsrc, L, N = tau.shape[0], tau.shape[1], tau.shape[3]
+    nk, nkp = len(G), len(H)
+    C1 = np.zeros((nsrc, nk, nkp, L), dtype=tau.dtype)
+    C2 = np.zeros((nsrc, nk, nk, nkp, nkp, L), dtype=tau.dtype)
+    Q = np.zeros((nsrc, nk, L, 2 * N, 2 * N), dtype=tau.dtype) if want_Q else None
+    for s, t0 in enumerate(t0s):
+        X = tau[s].reshape(L, 2 * N, 2 * N)                                # [t][(c,m)][(n,a)]
+        Xh = X.conj().transpose(0, 2, 1)
+        R = np.zeros((nk, nkp, L, 2 * N, 2 * N), dtype=tau.dtype)
+        for k, (g, j) in enumerate(G):
+            Phi = (g.astype(tau.dtype)[None, :, None, :, None] * M[j][:, None, :, None, :]).reshape(L, 2 * N, 2 * N)
+            Qk = np.matmul(Xh, np.matmul(Phi, X))                          # [t][rho1][rho2]
+            if want_Q:
+                Q[s, k] = Qk
+            for kp, (hm, jp) in enumerate(H):
+                # S[(n2,b)][(n1,a)] = H[b][a] conj(M_t0[n1][n2])
+                S = (M[jp, t0].conj().T[:, None, :, None] * hm.astype(tau.dtype)[None, :, None, :]).reshape(2 * N, 2 * N)
+                C1[s, k, kp] = np.sum(Qk * S.T[None], axis=(1, 2))
+                R[k, kp] = np.matmul(Qk, S)
+        for k in range(nk):
+            for l in range(nk):
+                for kp in range(nkp):
+                    for lp in range(nkp):
+                        C2[s, k, l, kp, lp] = np.sum(R[k, kp] * R[l, lp].transpose(0, 2, 1), axis=(1, 2))
+    return C1, C2, Q
+
+
+def two_meson_sums(tau, M, t0s, sink_ops, source_ops):
+    """(C1[s, k, k', t], C2[s, k, l, k', l', t]), the two-meson building blocks from the perambulators tau[s, t, c, m, n,
+    a] and the elementals M of laph_elementals, for the sink operators (Gamma_k, j_k) and the source operators
+    (Gamma'_k', j_k') -- spin matrix (a name or 2 x 2) and index into M's momenta: with G = g3 Gamma, H = Gamma' g3 and
+    rho = 2 n + a,
+
+        Q[s, k, t][rho1, rho2] = sum conj(tau[s, t, c, m1, n1, a]) G[c, d] M[j_k, t, m1, m2] tau[s, t, d, m2, n2, b]
+        S[s, k'][rho2, rho1]   = H[b, a] conj(M[j_k', t0s[s], n1, n2])
+        C1 = tr[Q_k S_k'],     C2 = tr[Q_k S_k' Q_l S_l'].
+
+    C1[s, k, k'] is meson_correlator(distilled_pair_sums(...)[s, j], Gamma_k, Gamma'_k') when both momenta are j; C2 is
+    the crossed quark-line diagram of two mesons at the sink and two at the source.  No fermion-loop sign."""
+    tau, M, t0s = _check_tau(tau, M, t0s, "two_meson_sums")
+    G, H = two_meson_folded(sink_ops, source_ops, M.shape[0], "two_meson_sums")
+    return _two_meson_sums(tau, M, t0s, G, H, False)[:2]
+
+
+def two_meson_sums_wide(tau, M, t0s, sink_ops, source_ops):
+    """(C1, C2, Q) of two_meson_sums evaluated in np.clongdouble, with the sandwich Q[s, k, t, rho1, rho2] -- the
+    reference of the device kernels."""
+    tau, M, t0s = _check_tau(tau, M, t0s, "two_meson_sums_wide")
+    G, H = two_meson_folded(sink_ops, source_ops, M.shape[0], "two_meson_sums_wide")
+    return _two_meson_sums(tau.astype(np.clongdouble), M.astype(np.clongdouble), t0s, G, H, True)
+
+
+def two_meson_bounds(tau, M, t0s, sink_ops, source_ops, wide=True):
+    """(bound_Q, bound_C1, bound_C2), the rounding bounds of the device's two-meson kernels, shaped as
+    two_meson_sums_wide's Q, C1, C2: the same formulas on absolute values,
+
+        |dQ|  <= (4 N + 16) 2^-52 |tau|^H (|G| x |M_t|) |tau|
+        |dC1| <= (4 N^2 + 4 N + 32) 2^-52 tr[Qabs Sabs]
+        |dC2| <= (4 N^2 + 12 N + 64) 2^-52 tr[Qabs_k Sabs_k' Qabs_l Sabs_l']
+
+    -- chains of 2 N (W), 2 N (Q), 2 N (R) and 4 N^2 (the traces) complex multiply-adds plus the spin weights.  M: the
+    elementals the device used.  Sums of non-negative terms in np.longdouble, or (wide false, for large N) float64."""
+    tau, M, t0s = _check_tau(tau, M, t0s, "two_meson_bounds")
+    G, H = two_meson_folded(sink_ops, source_ops, M.shape[0], "two_meson_bounds")
+    N = tau.shape[3]
+    rtype = np.longdouble if wide else np.float64
+    Ga = [(np.abs(g).astype(rtype), j) for g, j in G]
+    Ha = [(np.abs(hm).astype(rtype), j) for hm, j in H]
+    C1, C2, Q = _two_meson_sums(np.abs(tau).astype(rtype), np.abs(M).astype(rtype), t0s, Ga, Ha, True)
+    eps = rtype(2.0) ** -52
+    return (4 * N + 16) * eps * Q, (4 * N * N + 4 * N + 32) * eps * C1, (4 * N * N + 12 * N + 64) * eps * C2
+
+
+def two_meson_correlator(C1, C2, k, l, kp, lp):
+    """dict(direct, crossed, isospin2), each of the shape of C1[..., 0, 0, :]: for the sink operators k, l and the source
+    operators kp, lp of two_meson_sums' C1[..., k, k', t] and C2[..., k, l, k', l', t],
+
+        direct   = C1[k, kp] C1[l, lp] + C1[k, lp] C1[l, kp]
+        crossed  = C2[k, l, kp, lp] + C2[k, l, lp, kp]
+        isospin2 = direct - crossed.
+
+    No fermion-loop sign is applied anywhere, as in meson_correlator."""
+    C1, C2 = np.asarray(C1), np.asarray(C2)
+    if C1.ndim < 3 or C2.ndim != C1.ndim + 2 or C2.shape[-5:-3] != (C1.shape[-3],) * 2 \
+            or C2.shape[-3:-1] != (C1.shape[-2],) * 2 or C2.shape[-1] != C1.shape[-1]:
+        raise Exception("two_meson_correlator: C1 of shape %s and C2 of shape %s, expected (..., nk, nkp, L) and "
+                        "(..., nk, nk, nkp, nkp, L)" % (C1.shape, C2.shape))
+    for name, v, n in (('k', k, C1.shape[-3]), ('l', l, C1.shape[-3]), ('kp', kp, C1.shape[-2]),
+                       ('lp', lp, C1.shape[-2])):
+        if isinstance(v, bool) or int(v) != v or not 0 <= int(v) < n:
+            raise Exception("two_meson_correlator: %s = %r outside [0, %d)" % (name, v, n))
+    direct = C1[..., k, kp, :] * C1[..., l, lp, :] + C1[..., k, lp, :] * C1[..., l, kp, :]
+    crossed = C2[..., k, l, kp, lp, :] + C2[..., k, l, lp, kp, :]
+    return dict(direct=direct, crossed=crossed, isospin2=direct - crossed)
 
 
 def meson_fields(V, L, momenta):

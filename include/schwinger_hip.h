@@ -37,6 +37,7 @@ extern "C" {
 #define SW_MAX_SINK_LEVELS 4
 #define SW_MAX_SMEARING_STEPS 1024
 #define SW_MAX_LAPH 128
+#define SW_MAX_MESON_OPS 4 /* sink operators, and source operators, of one sw_distilled_two_meson call */
 
 typedef struct sw_engine sw_engine;
 
@@ -422,6 +423,39 @@ int sw_distilled_two_point(sw_engine* h, int nsrc, const int32_t* t0, double tol
 /* The contraction of sw_distilled_two_point alone on host perambulators tau complex128[nsrc][L][2][nev][nev][2], in the
  * same blocks (pad columns zero): T and loops as above. */
 int sw_apply_laph_contract(sw_engine* h, int nsrc, const int32_t* t0, const double* tau, double* T, double* loops);
+/* The two-meson building blocks of the source timeslices t0[s] (build-only, stateless): the sink
+ * operators k = (G_k, sink_mom[k]), 1 <= nk <= SW_MAX_MESON_OPS, and the source operators kp = (H_kp, source_mom[kp]),
+ * 1 <= nkp <= SW_MAX_MESON_OPS -- G = gamma_3 Gamma and H = Gamma' gamma_3 folded by the caller, complex128[n][2][2],
+ * the momenta as indices into the list of sw_set_distillation_momenta.  With rho = 2 n + a the column of a source,
+ *   Q[s][k][t][rho1][rho2] = sum conj(tau[s][t][c][m1][n1][a]) G_k[c][d] M[j_k][t][m1][m2] tau[s][t][d][m2][n2][b]
+ *   S[s][kp][rho2][rho1]   = H_kp[b][a] conj(M[j_kp][t0[s]][n1][n2])
+ *   C1[s][k][kp][t]        = tr[Q[s][k][t] S[s][kp]]
+ *   C2[s][k][l][kp][lp][t] = tr[Q[s][k][t] S[s][kp] Q[s][l][t] S[s][lp]]
+ * in the blocks of sw_distilled_two_point (k_laph_sources, the solve and k_laph_project exactly as sw_perambulators
+ * runs them on that chunk), then per block 2 nk + 3 launches:
+ *   k_laph_sink      W[(t,c)][m1][col]  = sum_d G[c][d] sum_m2 M[t][m1][m2] tau[(t,d)][m2][col]            per k
+ *   k_laph_sandwich  Q^T[rho2][rho1]    = sum_(c,m1) W[(t,c)][m1][(s,rho2)] conj(tau[(t,c)][m1][(s,rho1)])  per k
+ *   k_laph_source    R[rho][(n1,a)]     = sum_b H[b][a] sum_n2 Q[rho][(n2,b)] conj(M[t0][n1][n2])          all (k, kp)
+ *   k_laph_trace1    C1 from Q and S;   k_laph_trace2    C2 = sum R_{k,kp}[rho][sigma] R_{l,lp}[sigma][rho]
+ * (the products on v_mfma_f64_16x16x4_f64, the traces on the VALU; every complex product in four real ones, every sum
+ * in an order fixed by nev: no atomics, two calls agree bit for bit, and a source's values do not depend on the other
+ * sources of the call), and two small copies.
+ *   C1     complex128[nsrc][nk][nkp][L]
+ *   C2     complex128[nsrc][nk][nk][nkp][nkp][L]
+ *   iters  int32[nsrc][nev][2] as sw_perambulators, or NULL
+ * Refused before anything is allocated or launched without a distillation registration, without momenta, without a
+ * finalised hierarchy, on a bad timeslice list, nk or nkp outside [1, SW_MAX_MESON_OPS], a momentum index outside the
+ * registered list, maxiter < 1 or a null output.  No mode buffer, no probe slot and no registration is touched; the
+ * work buffers, (nk + nk nkp + 1) ns L (2 ld)^2 16 bytes for a block of ns sources, are released on return. */
+int sw_distilled_two_meson(sw_engine* h, int nsrc, const int32_t* t0, int nk, const double* sink_spin,
+                           const int32_t* sink_mom, int nkp, const double* source_spin, const int32_t* source_mom,
+                           double tol, int maxiter, double* C1, double* C2, int32_t* iters);
+/* The contraction of sw_distilled_two_meson alone on host perambulators tau complex128[nsrc][L][2][nev][nev][2], in
+ * the same blocks (pad columns zero): C1 and C2 as above; Q (or NULL) the sandwich, complex128[nsrc][nk][L][2 nev]
+ * [2 nev], dense (one more launch per block). */
+int sw_apply_laph_two_meson(sw_engine* h, int nsrc, const int32_t* t0, const double* tau, int nk,
+                            const double* sink_spin, const int32_t* sink_mom, int nkp, const double* source_spin,
+                            const int32_t* source_mom, double* C1, double* C2, double* Q);
 /* The generalized perambulators of the distilled three-point functions (build-only, stateless in the style of
  * sw_perambulators): z_0^(n,b) and z_f^(m,e) the solutions of the eigenvector sources on the timeslices
  * t0 and tf (different, in [0, L)), in exactly the solve blocks of sw_perambulators(h, 2, {t0, tf}, ...).  For the nt
@@ -792,6 +826,15 @@ int sw_timers_reset(sw_engine* h);
                                        issued: 8 * 8 * Lp * (16 RT) * (16 NT ncg), Lp = L rounded up to 4, RT =
                                        ceil(rows / 16), ncg = ceil(ceil(columns / 16) / 8) column groups of NT =
                                        ceil(ceil(columns / 16) / ncg) tiles */
+#define SW_KCLASS_LAPH_TWO_MESON 30  /* (29 is the engine's internal bucket of k_laph_sources, reported with class
+                                       26, and stays out of range)  k_laph_sink, k_laph_sandwich, k_laph_source, k_laph_trace1, k_laph_trace2 (and
+                                       the unpack of Q); in sw_timers: dots.  sw_kernel_work counts, per block of ns
+                                       sources in ncols columns, with K4 = nev and K4' = 2 nev rounded up to 4, RT =
+                                       ceil(2 nev / 16) row tiles whose columns go in h = ceil(RT / 8) passes of NT =
+                                       ceil(RT / h) tiles, z(.) the non-zero entries of a folded spin matrix:
+                                       8 * (sum_k [z(G_k) L ld ncols K4 + L ns (16 RT) (16 NT h) K4']
+                                       + sum_kp nk z(H_kp) L ns (16 RT) ld K4 + nk nkp L ns 5 nev^2
+                                       + nk^2 nkp^2 L ns (2 nev)^2) */
 int sw_kernel_stats(sw_engine* h, int which, double* total_ms, int64_t* launches);
 /* Floating-point operations issued by the launches of an MFMA kernel class since the last reset
  * (profiling on): 8 flops per complex multiply-add over every (row tile, k-step, probe). */
